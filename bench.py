@@ -2,6 +2,13 @@
 """bench.py — quantized tokens/s of the VQ codebook-lookup hot path on MI355X.
 
     python bench.py [--gpus N] [--steps K] [--warmup W] [--images B] [--workload vqgan|cvq|vqkd|tokenize]
+                    [--dump-outputs DIR] [--full]
+
+A plain run sets up, runs W warm-up steps, times EXACTLY K steps, writes the last step's outputs if --dump-outputs is
+given, and prints the result line (`metric`, `value`, `unit`, `higher_is_better`, `dtype`, `ms_per_step`, the config).
+Everything else the benchmark measures or checks — the repeated blocks of --min-seconds, the roofline and its event-timed
+kernel, the parity self-check, the side steps, the multi-rank cvq blocks, the CVQ exchange accounting and graph replay, the
+CPU baseline — runs only with --full.
 
 `--gpus N` with N > 1 from a bare invocation (no WORLD_SIZE in the environment) starts the N ranks itself: the parent —
 which makes NO GPU call — checks that N devices exist, runs `python -m torch.distributed.run --nproc-per-node N bench.py
@@ -29,12 +36,19 @@ Workloads (BASELINE.json configs; each "step" is one pass of the hot path over o
   tokenize (configs[4]) LlamaGen bulk tokenization: 2048 images per step IN TOTAL, sharded over the ranks
            (`encode` only, D=8 + NormalizeCallback + L2: configs/llamagen/vqgan.py:10-20).  Strong scaling, no collective.
 
-Timing: W warm-up steps, then blocks of EXACTLY K steps, each bracketed by barrier + synchronize on both sides and
-reduced with MAX over the ranks; blocks repeat until --min-seconds of timed GPU work have accumulated (the GPU is then
-visible to an external sampler and box-to-box variance shows); `value` / `ms_per_step` are those of the MEDIAN block, all
-blocks are listed in `repeats`.
+Timing: untimed steps for --settle-seconds (vqgan, tokenize: the GPU's clock is still ramping up over the first few
+hundred milliseconds of back-to-back steps, and a short timed block would price the ramp), W warm-up steps, then ONE block
+of EXACTLY K steps, bracketed by barrier + synchronize on both sides and reduced
+with MAX over the ranks.  With --full, blocks of K steps repeat until --min-seconds (default 8 there) of timed GPU work have
+accumulated (the GPU is then visible to an external sampler and box-to-box variance shows); `value` / `ms_per_step` are
+then those of the MEDIAN block, all blocks are listed in `repeats`.
 
-Prints ONE JSON line (rank 0) with the driver's contract fields plus
+--dump-outputs DIR: after the timed steps, rank 0 writes what its last timed step returned as DIR/<name>.npy (float32;
+indices as float64): the straight-through output (a fixed, seeded row sample when it is large, the rows in
+DIR/<name>_rows.npy), the loss, the token indices; for the training workloads also the input gradient and the codebook
+after the step.  Inputs are seeded, so two builds run with the same arguments can be compared output for output.
+
+Prints ONE JSON line (rank 0) with the driver's contract fields; with --full also
   roofline     — the dominant kernel (fp16-MFMA proposal pass) against the dense MFMA peak, timed live with HIP events
                  recorded on the launch stream (libvqhip's vqhip_profile_* hooks)
   parity       — the timed batch's indices checked, outside the timed region, against the all-fp32 route on every row and
@@ -75,8 +89,16 @@ def parse():
                     help='images per GPU per step (256 tokens each; vqkd: 196); default 2048 (vqgan), 12 (cvq), 64 (vqkd); '
                          'tokenize: images per step over ALL ranks, default 2048')
     ap.add_argument('--workload', choices=('vqgan', 'cvq', 'vqkd', 'tokenize'), default='vqgan')
-    ap.add_argument('--min-seconds', type=float, default=8.0,
-                    help='repeat the K-step block until this much timed GPU work has accumulated (0: one block)')
+    ap.add_argument('--min-seconds', type=float, default=None,
+                    help='--full only: repeat the K-step block until this much timed GPU work has accumulated (default 8; 0: one block)')
+    ap.add_argument('--settle-seconds', type=float, default=None,
+                    help='vqgan / tokenize: untimed steps for this long before the warm-up steps (default 4; 0 with --full, whose '
+                         'median block is past the ramp)')
+    ap.add_argument('--full', action='store_true',
+                    help='also run everything beyond the headline figure: repeated blocks, roofline, parity self-check, side steps, '
+                         'multi-rank cvq blocks, exchange accounting, graph replay, CPU baseline')
+    ap.add_argument('--dump-outputs', metavar='DIR', default=None,
+                    help='after the timed steps, write the last step\'s outputs as DIR/<name>.npy (rank 0)')
     ap.add_argument('--no-cpu-baseline', action='store_true')
     ap.add_argument('--bind', choices=('auto', 'on', 'off'), default='auto',
                     help='pin the rank to one L3 slice of its GPU\'s NUMA node (vector_quantization_amd/affinity.py). auto: on for the '
@@ -84,7 +106,55 @@ def parse():
                          'take successive slices), off for the single-GPU GPU-bound ones')
     ap.add_argument('--no-verify', action='store_true', help='skip the parity self-check after the timed region')
     ap.add_argument('--no-cvq', action='store_true', help='world > 1, vqgan workload: skip the communicating cvq block')
-    return ap.parse_args()
+    args = ap.parse_args()
+    if args.steps < 1:
+        ap.error('--steps must be at least 1')
+    if args.min_seconds is None:
+        args.min_seconds = 8.0 if args.full else 0.0
+    elif not args.full:
+        args.min_seconds = 0.0             # a plain run times exactly --steps steps
+    if args.settle_seconds is None:
+        args.settle_seconds = 0.0 if args.full else 4.0
+    return args
+
+
+# ------------------------------------------------------------------------------------------------------------------
+# --dump-outputs
+# ------------------------------------------------------------------------------------------------------------------
+
+DUMP_MAX_ELEMENTS = 1 << 22               # per array: larger outputs are written as a seeded row sample (16 MB of float32)
+DUMP_MAX_BYTES = 64 << 20
+
+
+def host_outputs(named):
+    """{name: tensor} -> {name: numpy array} on the host: integers as float64 (exact), floating point as float32; an array of
+    more than DUMP_MAX_ELEMENTS elements is cut to a fixed, seeded sample of its rows (sorted), whose indices come along as
+    `<name>_rows`."""
+    import numpy as np
+    import torch
+    arrays = {}
+    for name, t in named.items():
+        if t is None:
+            continue
+        t = t.detach()
+        if t.dim() > 1 and t.numel() > DUMP_MAX_ELEMENTS:
+            t = t.reshape(t.shape[0], -1)
+            n = max(1, DUMP_MAX_ELEMENTS // t.shape[1])
+            rows = np.sort(np.random.default_rng(3407).choice(t.shape[0], size=n, replace=False))
+            arrays[name + '_rows'] = rows.astype(np.float64)
+            t = t[torch.from_numpy(rows).to(t.device)]
+        dt = torch.float32 if t.is_floating_point() else torch.float64
+        arrays[name] = t.to(dt).cpu().numpy()
+    return arrays
+
+
+def write_outputs(out_dir, arrays):
+    import numpy as np
+    total = sum(a.nbytes for a in arrays.values())
+    assert total <= DUMP_MAX_BYTES, f'--dump-outputs: {total} bytes > {DUMP_MAX_BYTES}'
+    os.makedirs(out_dir, exist_ok=True)
+    for name, a in arrays.items():
+        np.save(os.path.join(out_dir, name + '.npy'), a)
 
 
 # ------------------------------------------------------------------------------------------------------------------
@@ -318,10 +388,18 @@ class Bench:
             self.dist.all_reduce(el, op=self.dist.ReduceOp.MAX)
         return float(el.item()), out, prof
 
-    def timed_blocks(self, fn, steps, warmup, min_seconds, max_blocks=200):
-        """Blocks of exactly `steps` steps until `min_seconds` of timed work; the proposal kernel is event-timed in the
-        first block.  Returns (per-block seconds, last output, (kernel ms sum, launches))."""
-        el, out, prof = self.timed(fn, steps, warmup, profile=True)
+    def settle(self, fn, seconds):
+        """Untimed steps until `seconds` have passed (only for steps without a collective: ranks may run different counts)."""
+        t0 = time.perf_counter()
+        while time.perf_counter() - t0 < seconds:
+            for _ in range(8):
+                fn()
+            self.torch.cuda.synchronize()
+
+    def timed_blocks(self, fn, steps, warmup, min_seconds, max_blocks=200, profile=True):
+        """Blocks of exactly `steps` steps until `min_seconds` of timed work; with `profile` the proposal kernel is event-timed
+        in the first block.  Returns (per-block seconds, last output, (kernel ms sum, launches) or None)."""
+        el, out, prof = self.timed(fn, steps, warmup, profile=profile)
         blocks = [el]
         self.block_rank_seconds = [self.last_rank_seconds]
         while sum(blocks) < min_seconds and len(blocks) < max_blocks:
@@ -380,9 +458,11 @@ def build_train_module(kind, cfg, dev, w):
     return q
 
 
-def run_cvq(B: Bench, tokens: int, steps: int, warmup: int, min_seconds: float, graphs: bool = True, settle: int = 150, kind: str = 'cvq'):
+def run_cvq(B: Bench, tokens: int, steps: int, warmup: int, min_seconds: float, graphs: bool = True, settle: int = 150, kind: str = 'cvq',
+            full: bool = True, want_outputs: bool = False):
     """The CVQ-VAE (or, kind='vqkd', the VQ-KD) training step at `tokens` per rank (module + callbacks, forward + backward
-    from a given upstream gradient), eager and replayed from HIP graphs; exchange accounting; codebook-in-sync check."""
+    from a given upstream gradient); with `full` also replayed from HIP graphs, exchange accounting, codebook-in-sync check.
+    Returns (record, kernel profile or None, the last timed step's outputs on the host or None)."""
     torch, dist = B.torch, B.dist
     from vector_quantization_amd.utils import exchange_log
     K, D, cfg = train_cfg(kind)
@@ -423,13 +503,21 @@ def run_cvq(B: Bench, tokens: int, steps: int, warmup: int, min_seconds: float, 
         step()
         if i == 0:
             rows_first = getattr(cvq_cb, 'last_exchange_rows', None)
-    blocks, out, prof = B.timed_blocks(step, steps, warmup, min_seconds)
+    blocks, out, prof = B.timed_blocks(step, steps, warmup, min_seconds, profile=full)
+    outputs = None
+    if want_outputs:                      # before anything else moves the codebook
+        memo = out[2] if isinstance(out[2], dict) else {}
+        outputs = host_outputs({'z': out[0], 'loss': out[1], 'quant': memo.get('quant'),
+                                'x_grad': pool[(turn[0] - 1) % len(pool)].grad, 'codebook': q.embedding.weight})
     el = _median_block(blocks)
     rec = {'tokens_per_rank': tokens, 'ms_per_step': el / steps * 1e3, 'tokens_per_s': tokens * B.world * steps / el,
            'per_rank_ms_per_step': [round(v / steps * 1e3, 5) for v in B.block_rank_seconds[blocks.index(el)]],
            'blocks': len(blocks), 'ms_per_step_min': min(blocks) / steps * 1e3, 'ms_per_step_max': max(blocks) / steps * 1e3,
-           'settle_steps': settle, 'exchange_rows_first_step': rows_first, 'exchange_rows': getattr(cvq_cb, 'last_exchange_rows', None),
-           'one_call_forward': bool(q._one_call_step(x) is not None)}
+           'settle_steps': settle}
+    if not full:
+        return rec, prof, outputs
+    rec.update({'exchange_rows_first_step': rows_first, 'exchange_rows': getattr(cvq_cb, 'last_exchange_rows', None),
+                'one_call_forward': bool(q._one_call_step(x) is not None)})
     # exchange accounting on a few extra steps (events around the collective: not part of the timed blocks)
     exchange_log.start(timing=B.distributed and not B.share_gpu)
     n_acc = 10
@@ -481,7 +569,7 @@ def run_cvq(B: Bench, tokens: int, steps: int, warmup: int, min_seconds: float, 
         assert rec['codebook_in_sync'], 'codebooks diverged across ranks'
     used = out[2].get('encode', {}).get('hist') if isinstance(out[2], dict) else None
     rec['used_codes'] = int((used > 0).sum().item()) if used is not None else None
-    return rec, prof
+    return rec, prof, outputs
 
 
 def direct_route_subblock(B: Bench, tokens: int, timeout_s: float = 240.0):
@@ -500,7 +588,7 @@ def direct_route_subblock(B: Bench, tokens: int, timeout_s: float = 240.0):
     env.update(VQHIP_ALLREDUCE=route, MASTER_ADDR='127.0.0.1', MASTER_PORT=str(int(port.item())), VQ_BENCH_CHILD='1',
                RANK=str(B.rank), WORLD_SIZE=str(B.world), LOCAL_RANK=os.environ.get('LOCAL_RANK', str(B.rank)))
     cmd = [sys.executable, os.path.abspath(__file__), '--gpus', str(B.world), '--workload', 'cvq', '--images', str(tokens // TOK_PER_IMAGE),
-           '--steps', '20', '--warmup', '5', '--min-seconds', '0.5', '--no-cpu-baseline', '--bind', 'off']      # (the child inherits this rank's CPUs)
+           '--steps', '20', '--warmup', '5', '--min-seconds', '0.5', '--no-cpu-baseline', '--bind', 'off', '--full']      # (the child inherits this rank's CPUs)
     t0 = time.perf_counter()
     rec = {'route_requested': route, 'tokens_per_rank': tokens, 'timeout_s': timeout_s,
            'what': 'the cvq step in a child process per rank with VQHIP_ALLREDUCE=' + route + ' (own ncclComm on the compute stream when direct)'}
@@ -616,8 +704,12 @@ def main():
     if 'VQHIP_TUNE_SLICES' in os.environ:                   # A/B knob (results unchanged): codebook slices
         L.vqhip_set_tuning(2, int(os.environ['VQHIP_TUNE_SLICES']))
 
+    full = args.full
+    dump = args.dump_outputs is not None and rank == 0
+    outputs = None                     # the last timed step's outputs on the host (--dump-outputs)
     parity = None
     main_rank_seconds = None
+    loss = used_codes = None
     if wl == 'vqgan':
         images = args.images or 2048
         N, K, D = images * TOK_PER_IMAGE, K_CODES, DIM
@@ -634,56 +726,60 @@ def main():
             idx = ops.argmin(x, cb)
             return ops.gather_ste_loss(x, w, idx, need_z=False)
 
-        qt = build_module(quantizer_cfg(K, D, 'L2'), dev, w, train=True)
-        xt = x.clone().requires_grad_(True)
-        qt_params = list(qt.parameters())
-
-        def train_step():
-            for p_ in qt_params:                 # what an optimizer's zero_grad(set_to_none=True) does with its parameter list
-                p_.grad = None
-            xt.grad = None
-            z, loss, _ = qt(xt, {})
-            (loss + z.float().mean()).backward()
-
-        blocks, out, prof = B.timed_blocks(step, args.steps, args.warmup, args.min_seconds)
+        B.settle(step, args.settle_seconds)
+        blocks, out, prof = B.timed_blocks(step, args.steps, args.warmup, args.min_seconds, profile=full)
         main_rank_seconds = B.block_rank_seconds
-        loss = float(out[1].item())
-        hist = ops.hist(out[2]['quant'], K)                   # code-usage statistics outside the timed region
-        used_codes = int((hist > 0).sum().item())
-        if not args.no_verify:
-            parity = verify_vqgan(B, q, x, w, out, N, K, D)
-        side_steps = max(5, args.steps // 5)
-        e_ops, _, _ = B.timed(ops_step, side_steps, 2)
-        e_tr, _, _ = B.timed(train_step, side_steps, 2)
-        extra['ops_step'] = {'ms_per_step': e_ops / side_steps * 1e3, 'tokens_per_s': N * world * side_steps / e_ops,
-                             'what': 'the same forward through the tensor-level ops layer (round-1 bench step)'}
-        extra['module_train'] = {'ms_per_step': e_tr / side_steps * 1e3, 'tokens_per_s': N * world * side_steps / e_tr,
-                                 'what': 'VQGANQuantizer.forward in train mode + backward (fused HIP backward, codebook gradient)'}
-        # VQ_BENCH_FORCE_CVQ=1: the multi-rank blocks at ANY world size — with `torch.distributed.run --nproc-per-node=1` and
-        # VQ_FORCE_EXCHANGE=1 the closest rehearsal of the multi-GPU line a one-GPU box allows ON RCCL: the per-rank gathers, the
-        # communicating step through the whole exchange flow, the direct-route children beside the parent's communicator
-        if (world > 1 or (B.distributed and os.environ.get('VQ_BENCH_FORCE_CVQ') == '1')) and not args.no_cvq:
-            # the communicating workload of the path, so that a scaling run is interpretable
-            extra['cvq'] = {}
-            # The eager step is ONE library call per forward (vqhip_cvq_forward) and GPU-bound at both sizes; it is what is
-            # timed by default.  VQ_BENCH_CVQ_GRAPHS=1 adds the graph-replayed step: capture and replay of a step that contains
-            # the collective have executed at world size 1 on RCCL, both routes (tests/test_gpu_rccl.py), never with more ranks
-            # (one-GPU builder boxes) — a capture that goes wrong there would cost the whole scaling run.
-            cvq_graphs = os.environ.get('VQ_BENCH_CVQ_GRAPHS') == '1'
-            for toks in (12 * TOK_PER_IMAGE, 256 * TOK_PER_IMAGE):
-                rec, _ = run_cvq(B, toks, max(20, args.steps), 5, min(1.0, args.min_seconds), graphs=cvq_graphs, settle=int(os.environ.get('VQ_BENCH_CVQ_SETTLE', '120')))
-                if not cvq_graphs:
-                    rec['graphed_note'] = 'not run: set VQ_BENCH_CVQ_GRAPHS=1 (graph replay of an RCCL collective has run at world size 1 only)'
-                extra['cvq'][str(toks)] = rec
-            # the cluster config's step (configs/cluster/model.py:28: NearestAnchor(sync=True), 6 272 x 8192 x 768 per rank): the key
-            # exchange of DESIGN.md §4.5 — a MIN all-reduce of 8-byte keys in front of the packed SUM, no latent gathered
-            rec, _ = run_cvq(B, 6272, max(20, args.steps), 5, min(1.0, args.min_seconds), graphs=False,
-                             settle=int(os.environ.get('VQ_BENCH_CVQ_SETTLE', '120')), kind='cluster')
-            rec['what'] = 'VQGANQuantizer + CVQVAECallback(NearestAnchor(sync=True)) + CodebookLoss, cosine, K=8192 D=768 (configs/cluster/model.py)'
-            extra['cvq']['cluster_sync_6272'] = rec
-            if os.environ.get('VQ_BENCH_DIRECT', '1') != '0' and os.environ.get('VQ_BENCH_CHILD') != '1':
-                extra['cvq']['direct_route'] = direct_route_subblock(B, 12 * TOK_PER_IMAGE,
-                                                                     timeout_s=float(os.environ.get('VQ_BENCH_DIRECT_TIMEOUT', '240')))
+        if dump:
+            outputs = host_outputs({'z': out[0], 'loss': out[1], 'quant': out[2]['quant']})
+        if full:
+            qt = build_module(quantizer_cfg(K, D, 'L2'), dev, w, train=True)
+            xt = x.clone().requires_grad_(True)
+            qt_params = list(qt.parameters())
+
+            def train_step():
+                for p_ in qt_params:                 # what an optimizer's zero_grad(set_to_none=True) does with its parameter list
+                    p_.grad = None
+                xt.grad = None
+                z, loss, _ = qt(xt, {})
+                (loss + z.float().mean()).backward()
+
+            loss = float(out[1].item())
+            hist = ops.hist(out[2]['quant'], K)                   # code-usage statistics outside the timed region
+            used_codes = int((hist > 0).sum().item())
+            if not args.no_verify:
+                parity = verify_vqgan(B, q, x, w, out, N, K, D)
+            side_steps = max(5, args.steps // 5)
+            e_ops, _, _ = B.timed(ops_step, side_steps, 2)
+            e_tr, _, _ = B.timed(train_step, side_steps, 2)
+            extra['ops_step'] = {'ms_per_step': e_ops / side_steps * 1e3, 'tokens_per_s': N * world * side_steps / e_ops,
+                                 'what': 'the same forward through the tensor-level ops layer (round-1 bench step)'}
+            extra['module_train'] = {'ms_per_step': e_tr / side_steps * 1e3, 'tokens_per_s': N * world * side_steps / e_tr,
+                                     'what': 'VQGANQuantizer.forward in train mode + backward (fused HIP backward, codebook gradient)'}
+            # VQ_BENCH_FORCE_CVQ=1: the multi-rank blocks at ANY world size — with `torch.distributed.run --nproc-per-node=1` and
+            # VQ_FORCE_EXCHANGE=1 the closest rehearsal of the multi-GPU line a one-GPU box allows ON RCCL: the per-rank gathers, the
+            # communicating step through the whole exchange flow, the direct-route children beside the parent's communicator
+            if (world > 1 or (B.distributed and os.environ.get('VQ_BENCH_FORCE_CVQ') == '1')) and not args.no_cvq:
+                # the communicating workload of the path, so that a scaling run is interpretable
+                extra['cvq'] = {}
+                # The eager step is ONE library call per forward (vqhip_cvq_forward) and GPU-bound at both sizes; it is what is
+                # timed by default.  VQ_BENCH_CVQ_GRAPHS=1 adds the graph-replayed step: capture and replay of a step that contains
+                # the collective have executed at world size 1 on RCCL, both routes (tests/test_gpu_rccl.py), never with more ranks
+                # (one-GPU builder boxes) — a capture that goes wrong there would cost the whole scaling run.
+                cvq_graphs = os.environ.get('VQ_BENCH_CVQ_GRAPHS') == '1'
+                for toks in (12 * TOK_PER_IMAGE, 256 * TOK_PER_IMAGE):
+                    rec, _, _ = run_cvq(B, toks, max(20, args.steps), 5, min(1.0, args.min_seconds), graphs=cvq_graphs, settle=int(os.environ.get('VQ_BENCH_CVQ_SETTLE', '120')))
+                    if not cvq_graphs:
+                        rec['graphed_note'] = 'not run: set VQ_BENCH_CVQ_GRAPHS=1 (graph replay of an RCCL collective has run at world size 1 only)'
+                    extra['cvq'][str(toks)] = rec
+                # the cluster config's step (configs/cluster/model.py:28: NearestAnchor(sync=True), 6 272 x 8192 x 768 per rank): the key
+                # exchange of DESIGN.md §4.5 — a MIN all-reduce of 8-byte keys in front of the packed SUM, no latent gathered
+                rec, _, _ = run_cvq(B, 6272, max(20, args.steps), 5, min(1.0, args.min_seconds), graphs=False,
+                                    settle=int(os.environ.get('VQ_BENCH_CVQ_SETTLE', '120')), kind='cluster')
+                rec['what'] = 'VQGANQuantizer + CVQVAECallback(NearestAnchor(sync=True)) + CodebookLoss, cosine, K=8192 D=768 (configs/cluster/model.py)'
+                extra['cvq']['cluster_sync_6272'] = rec
+                if os.environ.get('VQ_BENCH_DIRECT', '1') != '0' and os.environ.get('VQ_BENCH_CHILD') != '1':
+                    extra['cvq']['direct_route'] = direct_route_subblock(B, 12 * TOK_PER_IMAGE,
+                                                                         timeout_s=float(os.environ.get('VQ_BENCH_DIRECT_TIMEOUT', '240')))
         tokens_per_step_global = N * world
         scaling = 'weak'
         workload = ('VQGAN K=16384 D=256, 256x256 images -> 16x16 tokens, bf16 latents, VQGANQuantizer.forward of the '
@@ -694,11 +790,12 @@ def main():
         images = args.images or 64
         K, D, _ = train_cfg('vqkd')
         N = images * 196
-        rec, prof = run_cvq(B, N, args.steps, args.warmup, args.min_seconds,
-                            graphs=(world == 1 or os.environ.get('VQ_BENCH_CVQ_GRAPHS') == '1'), kind='vqkd')
+        rec, prof, outputs = run_cvq(B, N, args.steps, args.warmup, args.min_seconds,
+                                     graphs=(world == 1 or os.environ.get('VQ_BENCH_CVQ_GRAPHS') == '1'), kind='vqkd',
+                                     full=full, want_outputs=dump)
         blocks = [rec['ms_per_step'] * args.steps / 1e3]
         extra['vqkd'] = rec
-        loss, used_codes = rec['loss'], rec['used_codes']
+        loss, used_codes = rec.get('loss'), rec.get('used_codes')
         tokens_per_step_global = N * world
         scaling = 'weak'
         workload = ('VQ-KD training step K=8192 D=32 cosine, VQKDQuantizer + VQKDCallback(ema) + CommitmentLoss(norm=True), 64 images x '
@@ -710,11 +807,12 @@ def main():
     elif wl == 'cvq':
         images = args.images or 12
         N, K, D = images * TOK_PER_IMAGE, K_CODES, DIM
-        rec, prof = run_cvq(B, N, args.steps, args.warmup, args.min_seconds,
-                            graphs=(world == 1 or os.environ.get('VQ_BENCH_CVQ_GRAPHS') == '1'))
+        rec, prof, outputs = run_cvq(B, N, args.steps, args.warmup, args.min_seconds,
+                                     graphs=(world == 1 or os.environ.get('VQ_BENCH_CVQ_GRAPHS') == '1'),
+                                     full=full, want_outputs=dump)
         blocks = [rec['ms_per_step'] * args.steps / 1e3]
         extra['cvq'] = rec
-        loss, used_codes = rec['loss'], rec['used_codes']
+        loss, used_codes = rec.get('loss'), rec.get('used_codes')
         tokens_per_step_global = N * world
         scaling = 'weak'
         workload = ('CVQ-VAE training step K=16384 D=256 cosine, VQGANQuantizer + CVQVAECallback(NearestAnchor): forward '
@@ -736,11 +834,14 @@ def main():
             with torch.no_grad():
                 return q.encode(x, {})
 
-        blocks, out, prof = B.timed_blocks(step, args.steps, args.warmup, args.min_seconds)
+        B.settle(step, args.settle_seconds)
+        blocks, out, prof = B.timed_blocks(step, args.steps, args.warmup, args.min_seconds, profile=full)
         main_rank_seconds = B.block_rank_seconds
-        loss = None
-        used_codes = int((ops.hist(out[1], K) > 0).sum().item())
-        if not args.no_verify:                                   # tokens of the timed batch against the all-fp32 route
+        if dump:
+            outputs = host_outputs({'x_normalized': out[0], 'quant': out[1]})
+        if full:
+            used_codes = int((ops.hist(out[1], K) > 0).sum().item())
+        if full and not args.no_verify:                          # tokens of the timed batch against the all-fp32 route
             xn, wn = ops.normalize_rows(x), ops.normalize_rows(w)
             mism = int((out[1].reshape(-1) != ops.argmin_exact(xn, wn, 'L2')).sum().item())
             parity = {'parity_checked_rows': N, 'mismatches': mism, 'ok': mism == 0,
@@ -761,10 +862,46 @@ def main():
         parity['ranks_failed'] = [i for i, b in enumerate(bad) if b]
         parity['mismatches_all_ranks'] = int(sum(mism_all))
         parity_ok = not parity['ranks_failed']
-    kern_ms_ranks = B.gather_floats(prof[0] / max(1, prof[1]))     # the dominant kernel's average launch on each rank
+    if full:
+        kern_ms_ranks = B.gather_floats(prof[0] / max(1, prof[1]))     # the dominant kernel's average launch on each rank
+    if dump:
+        write_outputs(args.dump_outputs, outputs)
     if rank == 0:
         elapsed = _median_block(blocks)
         tokens = tokens_per_step_global * args.steps
+        per_step = sorted(b / args.steps * 1e3 for b in blocks)
+        per_rank_ms = None
+        if main_rank_seconds is not None:                          # each rank's own clock around the median block's K steps
+            per_rank_ms = [round(v / args.steps * 1e3, 5) for v in main_rank_seconds[blocks.index(elapsed)]]
+        elif wl in ('cvq', 'vqkd'):
+            per_rank_ms = extra[wl].get('per_rank_ms_per_step')
+        out_line = {
+            'metric': metric,
+            'value': tokens / elapsed, 'unit': 'tokens/s', 'n_gpus': world, 'steps': args.steps,
+            'warmup': args.warmup, 'ms_per_step': elapsed / args.steps * 1e3, 'higher_is_better': True,
+            'scaling': scaling, 'vs_baseline': None, 'dtype': 'f16+f32',
+            'dtype_note': 'f16 MFMA (f32 accumulate) proposes candidates under a rigorous bound; the decision is exact f32',
+            'data': 'synthetic', 'rccl_ranks': B.rccl_ranks, 'collective_backend': B.backend,
+            'per_rank_ms_per_step': per_rank_ms,
+            'config': {'workload': workload, 'images_per_gpu': images, 'tokens_per_gpu_per_step': N, 'codebook': [K, D],
+                       'parallelism': parallelism},
+            'timing_note': (f'value / ms_per_step: the median of {len(blocks)} timed blocks of exactly {args.steps} steps each '
+                            if len(blocks) > 1 else f'value / ms_per_step: one timed block of exactly {args.steps} steps '
+                            f'(after {args.settle_seconds:g} s of untimed steps and {args.warmup} warm-up steps) ')
+                           + '(barrier + synchronize on both sides, MAX over ranks); all blocks in `repeats`',
+            'repeats': {'blocks': len(blocks), 'timed_seconds': sum(blocks), 'ms_per_step_median': elapsed / args.steps * 1e3,
+                        'ms_per_step_min': per_step[0], 'ms_per_step_max': per_step[-1],
+                        'ms_per_step_all': [round(v, 5) for v in (b / args.steps * 1e3 for b in blocks)][:64]},
+        }
+        if B.binding is not None:
+            out_line['host_binding'] = {k: B.binding.get(k) for k in ('cpus', 'numa_local', 'slice', 'slices_on_node', 'position_on_node', 'ranks_on_node')}
+            from vector_quantization_amd import affinity
+            affinity.restore(B.binding['previous'])              # the CPU baseline below gets every core back
+    if rank == 0 and not full:
+        if wl in ('cvq', 'vqkd'):
+            out_line[wl] = extra[wl]
+        emit(json.dumps(out_line))
+    if rank == 0 and full:
         kern_ms = max(kern_ms_ranks)                               # the SLOWEST rank's kernel prices the roofline
         launches_per_step = prof[1] / max(1, args.steps)
         flops = 2.0 * N * K * D                                          # 2*K*D per token, per launch
@@ -819,38 +956,10 @@ def main():
         if wl in ('cvq', 'vqkd'):
             roofline['kernel_ms_note'] = ('average over the proposal launches of a step: the row pass (N x K) and, when codes are listed, '
                                           'the role-swapped column pass (listed codes x N) — `achieved` prices the row pass only')
-        per_step = sorted(b / args.steps * 1e3 for b in blocks)
-        per_rank_ms = None
-        if main_rank_seconds is not None:                          # each rank's own clock around the median block's K steps
-            per_rank_ms = [round(v / args.steps * 1e3, 5) for v in main_rank_seconds[blocks.index(elapsed)]]
-        elif wl in ('cvq', 'vqkd'):
-            per_rank_ms = extra[wl].get('per_rank_ms_per_step')
-        out_line = {
-            'metric': metric,
-            'value': tokens / elapsed, 'unit': 'tokens/s', 'n_gpus': world, 'steps': args.steps,
-            'warmup': args.warmup, 'ms_per_step': elapsed / args.steps * 1e3, 'higher_is_better': True,
-            'scaling': scaling, 'vs_baseline': None, 'dtype': 'f16+f32',
-            'dtype_note': 'f16 MFMA (f32 accumulate) proposes candidates under a rigorous bound; the decision is exact f32',
-            'data': 'synthetic', 'rccl_ranks': B.rccl_ranks, 'collective_backend': B.backend,
-            'per_rank_ms_per_step': per_rank_ms,
-            'config': {'workload': workload, 'images_per_gpu': images, 'tokens_per_gpu_per_step': N, 'codebook': [K, D],
-                       'parallelism': parallelism},
-            'timing_note': f'value / ms_per_step: the median of {len(blocks)} timed blocks of exactly {args.steps} steps each '
-                           f'(barrier + synchronize on both sides, MAX over ranks); all blocks in `repeats`',
-            'repeats': {'blocks': len(blocks), 'timed_seconds': sum(blocks), 'ms_per_step_median': elapsed / args.steps * 1e3,
-                        'ms_per_step_min': per_step[0], 'ms_per_step_max': per_step[-1],
-                        'ms_per_step_all': [round(v, 5) for v in (b / args.steps * 1e3 for b in blocks)][:64]},
-            'roofline': roofline,
-            'lib_sha256': sha,
-            'loss': loss, 'used_codes': used_codes,
-        }
+        out_line.update({'roofline': roofline, 'lib_sha256': sha, 'loss': loss, 'used_codes': used_codes})
         if parity is not None:
             out_line['parity'] = parity
         out_line.update(extra)
-        if B.binding is not None:
-            out_line['host_binding'] = {k: B.binding.get(k) for k in ('cpus', 'numa_local', 'slice', 'slices_on_node', 'position_on_node', 'ranks_on_node')}
-            from vector_quantization_amd import affinity
-            affinity.restore(B.binding['previous'])              # the CPU baseline below gets every core back
         if not args.no_cpu_baseline and world == 1:          # reported once, at N=1 (rank 0's host cores)
             out_line['cpu_baseline'] = cpu_baseline()
         emit(json.dumps(out_line))

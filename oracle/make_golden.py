@@ -647,15 +647,49 @@ def runner_cases():
                                         'tools/tokenize_llamagen.py:65-103'])))
 
 
+# The last bit of a float sum follows how the CPU libraries split and vectorise it: by the thread count, and by the kernels
+# ATen and MKL pick for the host's processor.  The fixtures are written, and regenerated to be compared byte for byte, under
+# ONE configuration: 8 threads (MKL_DYNAMIC off: exactly those), ATen's AVX-512 kernels and MKL's AVX512 conditional
+# numerical reproducibility branch, which gives the same bits on every processor that supports it.  The libraries read
+# these at load time: a fresh process gets them (pinned_env()), and main() refuses to write fixtures without them.
+FIXTURE_THREADS = 8
+PINNED_ENV = {'ATEN_CPU_CAPABILITY': 'avx512', 'MKL_CBWR': 'AVX512', 'MKL_DYNAMIC': 'FALSE',
+              'OMP_NUM_THREADS': str(FIXTURE_THREADS), 'MKL_NUM_THREADS': str(FIXTURE_THREADS)}
+AVX512_FLAGS = ('avx512f', 'avx512bw', 'avx512vl', 'avx512dq')      # what ATen's AVX-512 kernels need
+
+
+def host_has_avx512() -> bool:
+    try:
+        flags = next(ln for ln in open('/proc/cpuinfo') if ln.startswith('flags')).split()
+    except (OSError, StopIteration):
+        return False
+    return all(f in flags for f in AVX512_FLAGS)
+
+
+def pinned_env(base=None) -> dict:
+    """The environment of a process that generates fixtures: `base` (default: this process's) with PINNED_ENV."""
+    env = dict(os.environ if base is None else base)
+    env.update(PINNED_ENV)
+    return env
+
+
+def check_pinned() -> None:
+    off = {k: os.environ.get(k) for k, v in PINNED_ENV.items() if os.environ.get(k) != v}
+    if off or torch.backends.cpu.get_cpu_capability() != 'AVX512':
+        raise RuntimeError(f'fixtures are generated only under PINNED_ENV (run `python -m oracle.make_golden`): '
+                           f'differs in {off}, ATen CPU capability {torch.backends.cpu.get_cpu_capability()}')
+
+
 def main(only=(), out_dir=None, quiet=False):
     global OUT
     if not ref_import.available():
         sys.exit('oracle/make_golden.py needs /root/reference (build container only)')
+    check_pinned()
     if out_dir is not None:
         OUT = out_dir
     os.makedirs(OUT, exist_ok=True)
     torch.manual_seed(0)
-    torch.set_num_threads(os.cpu_count() or 1)
+    torch.set_num_threads(FIXTURE_THREADS)
     only = set(only)
     print_ = (lambda *a, **k: None) if quiet else print
     for c in ENCODE_CASES:
@@ -686,4 +720,7 @@ def main(only=(), out_dir=None, quiet=False):
 
 
 if __name__ == '__main__':
+    if any(os.environ.get(k) != v for k, v in PINNED_ENV.items()):      # a fresh child process with the pinned numerics
+        import subprocess
+        sys.exit(subprocess.run([sys.executable, '-m', 'oracle.make_golden'] + sys.argv[1:], env=pinned_env()).returncode)
     main(sys.argv[1:])

@@ -746,3 +746,34 @@ def test_full_size_tokenizer_shape():
     rows = torch.linspace(0, N - 1, 256, device='cuda').long()
     xo, wo = co.normalize_rows(x[rows].float().cpu().numpy()), co.normalize_rows(w.cpu().numpy())
     np.testing.assert_array_equal(quant[rows].cpu().numpy(), co.l2_argmin(xo, wo))
+
+
+def test_plain_bench_run_times_its_steps_and_dumps_its_outputs(tmp_path):
+    """`bench.py --steps K --warmup W --dump-outputs DIR` without --full: exactly one block of K timed steps, the headline fields
+    only, and the last step's outputs (indices, loss, a seeded row sample of the straight-through output) as .npy files —
+    identical from run to run with the same arguments."""
+    import subprocess
+    import sys
+    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+    recs = []
+    for run in ('a', 'b'):
+        res = subprocess.run([sys.executable, os.path.join(root, 'bench.py'), '--gpus', '1', '--steps', '3', '--warmup', '1',
+                              '--images', '64', '--dump-outputs', str(tmp_path / run)], capture_output=True, text=True, timeout=600, cwd=root)
+        assert res.returncode == 0, res.stderr[-3000:]
+        lines = [ln for ln in res.stdout.splitlines() if ln.startswith('{')]
+        assert len(lines) == 1, res.stdout[-2000:]
+        recs.append(json.loads(lines[0]))
+    for rec in recs:
+        assert rec['steps'] == 3 and rec['warmup'] == 1 and rec['repeats']['blocks'] == 1 and rec['ms_per_step'] > 0
+        assert rec['unit'] == 'tokens/s' and rec['higher_is_better'] is True and rec['dtype'] == 'f16+f32'
+        assert abs(rec['value'] - 64 * 256 * 1e3 / rec['ms_per_step']) <= 1e-6 * rec['value']
+        for key in ('roofline', 'parity', 'cpu_baseline', 'ops_step', 'module_train'):
+            assert key not in rec, key
+    names = sorted(os.listdir(tmp_path / 'a'))
+    assert names == sorted(os.listdir(tmp_path / 'b')) and {'quant.npy', 'loss.npy', 'z.npy'} <= set(names)
+    for name in names:
+        a, b = np.load(tmp_path / 'a' / name), np.load(tmp_path / 'b' / name)
+        assert a.dtype in (np.float32, np.float64) and a.tobytes() == b.tobytes(), name
+    quant = np.load(tmp_path / 'a' / 'quant.npy')
+    assert quant.shape == (64 * 256,) and quant.min() >= 0 and quant.max() < 16384 and np.array_equal(quant, np.round(quant))
+    assert np.load(tmp_path / 'a' / 'z.npy').shape == (64 * 256, 256) and np.load(tmp_path / 'a' / 'loss.npy').shape == ()

@@ -85,7 +85,7 @@ def test_fsdp_use_orig_params_smoke(ws1):
 
 
 def test_bench_multi_rank_blocks_on_rccl_at_world_size_one(tmp_path):
-    """The part of `bench.py --gpus N` that only runs with more than one rank — each rank's own clock and kernel time gathered, parity
+    """The part of `bench.py --gpus N --full` that only runs with more than one rank — each rank's own clock and kernel time gathered, parity
     gathered, the communicating cvq blocks, and the direct-route sub-block in a child process with its own rendezvous — on the REAL
     backend: one rank under `torch.distributed.run` with VQ_BENCH_FORCE_CVQ=1 and VQ_FORCE_EXCHANGE=1.  The child creates the library's
     own RCCL communicator (VQHIP_ALLREDUCE=direct) on the GPU whose parent process holds torch's: what the first multi-GPU lease will
@@ -95,7 +95,7 @@ def test_bench_multi_rank_blocks_on_rccl_at_world_size_one(tmp_path):
     env.pop('VQHIP_ALLREDUCE', None)
     cmd = [sys.executable, '-m', 'torch.distributed.run', '--nnodes=1', '--nproc-per-node=1', '--master-addr', '127.0.0.1',
            '--master-port', str(_free_port()), os.path.join(ROOT, 'bench.py'), '--gpus', '1', '--steps', '3', '--warmup', '1', '--images', '64',
-           '--min-seconds', '0', '--no-cpu-baseline']
+           '--min-seconds', '0', '--no-cpu-baseline', '--full']
     res = subprocess.run(cmd, env=env, capture_output=True, text=True, timeout=900, cwd=ROOT)
     assert res.returncode == 0, f'{res.stdout[-2000:]}\n{res.stderr[-3000:]}'
     lines = [ln for ln in res.stdout.splitlines() if ln.startswith('{') and '"metric"' in ln]

@@ -187,15 +187,17 @@ def test_callbacks_at_world_size_eight(tmp_path):
 
 
 def test_bench_eight_ranks_on_a_shared_gpu(tmp_path):
-    """`python bench.py --gpus 8` to completion with every rank on cuda:0 over gloo (VQ_BENCH_SHARE_GPU=1): the only rehearsal
+    """`python bench.py --gpus 8 --full` to completion with every rank on cuda:0 over gloo (VQ_BENCH_SHARE_GPU=1): the only rehearsal
     of the driver's 8-GPU command a one-GPU box allows — the launcher, the rendezvous, the barriers and max-reduction of the
-    timing, the communicating cvq block with its exchange accounting and the codebook-in-sync check."""
+    timing, the communicating cvq block with its exchange accounting and the codebook-in-sync check.  The direct-route sub-block
+    (a child process per rank, beside its rank) is rehearsed at four ranks below: eight ranks and eight children would hold the
+    one GPU from seventeen processes, this one included."""
     import subprocess
     import sys
     root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-    env = dict(os.environ, VQ_BENCH_SHARE_GPU='1', VQ_BENCH_CVQ_SETTLE='30')
+    env = dict(os.environ, VQ_BENCH_SHARE_GPU='1', VQ_BENCH_CVQ_SETTLE='30', VQ_BENCH_DIRECT='0')
     res = subprocess.run([sys.executable, os.path.join(root, 'bench.py'), '--gpus', '8', '--steps', '3', '--warmup', '1', '--images', '16',
-                          '--min-seconds', '0', '--no-cpu-baseline'], env=env, capture_output=True, text=True, timeout=1500, cwd=root)
+                          '--min-seconds', '0', '--no-cpu-baseline', '--full'], env=env, capture_output=True, text=True, timeout=1500, cwd=root)
     assert res.returncode == 0, res.stderr[-3000:]
     lines = [ln for ln in res.stdout.splitlines() if ln.startswith('{')]
     assert len(lines) == 1, res.stdout[-2000:]
@@ -206,7 +208,7 @@ def test_bench_eight_ranks_on_a_shared_gpu(tmp_path):
     # what the first real multi-GPU run must show (round-5 review item 4): every rank's own clock and kernel time, the slowest one priced
     assert len(rec['per_rank_ms_per_step']) == 8 and max(rec['per_rank_ms_per_step']) <= rec['ms_per_step'] * 1.0001
     assert len(rec['roofline']['kernel_ms_per_rank']) == 8 and abs(rec['roofline']['kernel_ms'] - max(rec['roofline']['kernel_ms_per_rank'])) < 1e-4
-    direct = rec['cvq'].pop('direct_route')
+    assert 'direct_route' not in rec['cvq']
     cluster = rec['cvq'].pop('cluster_sync_6272')
     for toks, blk in rec['cvq'].items():
         assert blk['codebook_in_sync'] is True and blk['collectives_per_step'] == 1.0, (toks, blk)
@@ -217,9 +219,26 @@ def test_bench_eight_ranks_on_a_shared_gpu(tmp_path):
     assert cluster['codebook_in_sync'] is True and cluster['one_call_forward'] is True and cluster['collectives_per_step'] in (1.0, 2.0)
     assert abs(cluster['exchange_bytes_per_step'] - (8 * m + 4 * (2 * 8192 + 4 + m * 768))) < 1e-6 or cluster['collectives_per_step'] < 2.0
     assert cluster['exchange_bytes_per_step'] < cluster['dense_exchange_bytes_per_step'] / 100
-    # the second sub-block: the same step in a child process per rank under a timeout (on RCCL: VQHIP_ALLREDUCE=direct; the shared-GPU
-    # rehearsal runs gloo, where only the plumbing — rendezvous of the children, their JSON, the agreement — can be exercised)
-    assert direct['ok'] is True and direct['route_requested'] == 'torch' and direct['rccl_ranks'] == 8, direct
+
+
+def test_bench_direct_route_on_a_shared_gpu(tmp_path):
+    """The second sub-block of the multi-rank line: the same step in a child process per rank under a timeout (on RCCL:
+    VQHIP_ALLREDUCE=direct; the shared-GPU rehearsal runs gloo, where only the plumbing — rendezvous of the children, their JSON,
+    the agreement — can be exercised).  Four ranks and their four children on cuda:0."""
+    import subprocess
+    import sys
+    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+    env = dict(os.environ, VQ_BENCH_SHARE_GPU='1', VQ_BENCH_CVQ_SETTLE='30')
+    res = subprocess.run([sys.executable, os.path.join(root, 'bench.py'), '--gpus', '4', '--steps', '3', '--warmup', '1', '--images', '16',
+                          '--min-seconds', '0', '--no-cpu-baseline', '--full'], env=env, capture_output=True, text=True, timeout=1500, cwd=root)
+    assert res.returncode == 0, res.stderr[-3000:]
+    lines = [ln for ln in res.stdout.splitlines() if ln.startswith('{')]
+    assert len(lines) == 1, res.stdout[-2000:]
+    rec = json.loads(lines[0])
+    assert rec['n_gpus'] == 4 and rec['rccl_ranks'] == 4 and rec['collective_backend'] == 'gloo'
+    assert rec['parity']['mismatches_all_ranks'] == 0 and rec['parity']['ranks_checked'] == 4
+    direct = rec['cvq']['direct_route']
+    assert direct['ok'] is True and direct['route_requested'] == 'torch' and direct['rccl_ranks'] == 4, direct
     assert direct['codebook_in_sync'] is True and direct['collectives_per_step'] == 1.0 and direct['ms_per_step'] > 0, direct
 
 
@@ -231,7 +250,7 @@ def test_bench_direct_route_timeout_is_a_reported_failure(tmp_path):
     root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
     env = dict(os.environ, VQ_BENCH_SHARE_GPU='1', VQ_BENCH_DIRECT_TIMEOUT='0.5', VQ_BENCH_CVQ_SETTLE='30')
     res = subprocess.run([sys.executable, os.path.join(root, 'bench.py'), '--gpus', '2', '--steps', '3', '--warmup', '1', '--images', '16',
-                          '--min-seconds', '0', '--no-cpu-baseline'], env=env, capture_output=True, text=True, timeout=900, cwd=root)
+                          '--min-seconds', '0', '--no-cpu-baseline', '--full'], env=env, capture_output=True, text=True, timeout=900, cwd=root)
     assert res.returncode == 0, res.stderr[-3000:]
     lines = [ln for ln in res.stdout.splitlines() if ln.startswith('{')]
     assert len(lines) == 1, res.stdout[-2000:]

@@ -145,21 +145,32 @@ def test_committed_bench_line_has_the_contract_fields():
     assert abs(tokens - line['value']) / line['value'] < 1e-6
 
 
-def test_bench_gpus_n_self_launch_fails_loudly_without_gpus():
+def test_bench_gpus_n_self_launch_fails_loudly_without_gpus(monkeypatch):
     """`python bench.py --gpus 2` with no launcher environment starts the ranks itself (torch.distributed.run child
     process); here there is no GPU, so the ranks fail and the parent must exit non-zero without printing a JSON line
-    (never a silent 1-rank number)."""
+    (never a silent 1-rank number).  At most one device is made visible (HIP_VISIBLE_DEVICES=0), so that a host with GPUs
+    sees the same refusal."""
+    import importlib.util
     import subprocess
     import sys
     env = {k: v for k, v in os.environ.items() if k not in ('RANK', 'WORLD_SIZE', 'LOCAL_RANK')}
+    env['HIP_VISIBLE_DEVICES'] = '0'
     root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+    spec = importlib.util.spec_from_file_location('bench_mod', os.path.join(root, 'bench.py'))
+    bench = importlib.util.module_from_spec(spec)
+    spec.loader.exec_module(bench)
+    monkeypatch.setenv('HIP_VISIBLE_DEVICES', '0')
+    have = bench.count_gpus_sysfs()                # what the launching parent will see: 0 or 1, None if the topology is unreadable
     p = subprocess.run([sys.executable, os.path.join(root, 'bench.py'), '--gpus', '2', '--steps', '1', '--warmup', '0'],
                        env=env, capture_output=True, text=True, timeout=300)
     assert p.returncode != 0
     assert '"metric"' not in p.stdout
     assert '2-rank launch failed' in p.stderr
+    if have is None:                               # no topology to count from: the ranks find out for themselves and fail
+        assert 'has no device 1' in p.stderr, p.stderr[-2000:]
+        return
     # ... and it is refused BEFORE anything is spawned: more ranks than devices is never turned into a smaller run
-    assert 'this node has 0 GPU(s); refusing to start' in p.stderr and 'torch.distributed' not in p.stderr
+    assert f'this node has {have} GPU(s); refusing to start' in p.stderr and 'torch.distributed' not in p.stderr
 
 
 def test_bench_counts_gpus_from_sysfs_without_touching_a_device(tmp_path, monkeypatch):

@@ -5,16 +5,16 @@ tag=$1
 cd /root/repo
 o=gpurun_out
 sha256sum vector_quantization_amd/libvqhip.so > $o/${tag}_lib_sha256.txt
-python bench.py > $o/${tag}_bench.json 2> $o/${tag}_bench.err; echo "bench rc=$?"
-bash tools/prof_bench.sh ${tag}_bench_profiled --no-cpu-baseline --min-seconds 0 > $o/${tag}_bench_profiled.txt 2>&1; tail -3 $o/${tag}_bench_profiled.txt
+python bench.py --full > $o/${tag}_bench.json 2> $o/${tag}_bench.err; echo "bench rc=$?"
+VQ_OUT="$PWD/$o" bash tools/prof_bench.sh ${tag}_bench_profiled --no-cpu-baseline --min-seconds 0 > $o/${tag}_bench_profiled.txt 2>&1; tail -3 $o/${tag}_bench_profiled.txt
 bash tools/pmc_passes.sh ${tag}_pmc > $o/${tag}_pmc.txt 2>&1; tail -3 $o/${tag}_pmc.txt | cut -c1-300
-python bench.py --workload cvq --no-cpu-baseline --min-seconds 3 > $o/${tag}_cvq.json 2>> $o/${tag}_bench.err; echo "cvq rc=$?"
-python bench.py --workload cvq --images 256 --no-cpu-baseline --min-seconds 3 > $o/${tag}_cvq256.json 2>> $o/${tag}_bench.err; echo "cvq256 rc=$?"
-python bench.py --workload vqkd --no-cpu-baseline --min-seconds 3 > $o/${tag}_vqkd.json 2>> $o/${tag}_bench.err; echo "vqkd rc=$?"
-python bench.py --workload tokenize --no-cpu-baseline > $o/${tag}_tokenize.json 2>> $o/${tag}_bench.err; echo "tokenize rc=$?"
-python bench.py --images 32 --no-cpu-baseline --min-seconds 3 > $o/${tag}_bench_32img.json 2>> $o/${tag}_bench.err; echo "32img rc=$?"
-python bench.py --images 256 --no-cpu-baseline --min-seconds 3 > $o/${tag}_bench_256img.json 2>> $o/${tag}_bench.err; echo "256img rc=$?"
-VQ_BENCH_SHARE_GPU=1 python bench.py --gpus 2 --steps 10 --warmup 3 --images 256 --min-seconds 0.3 --no-cpu-baseline > $o/${tag}_gpus2_shared.json 2>> $o/${tag}_bench.err; echo "gpus2 rc=$?"
+python bench.py --full --workload cvq --no-cpu-baseline --min-seconds 3 > $o/${tag}_cvq.json 2>> $o/${tag}_bench.err; echo "cvq rc=$?"
+python bench.py --full --workload cvq --images 256 --no-cpu-baseline --min-seconds 3 > $o/${tag}_cvq256.json 2>> $o/${tag}_bench.err; echo "cvq256 rc=$?"
+python bench.py --full --workload vqkd --no-cpu-baseline --min-seconds 3 > $o/${tag}_vqkd.json 2>> $o/${tag}_bench.err; echo "vqkd rc=$?"
+python bench.py --full --workload tokenize --no-cpu-baseline > $o/${tag}_tokenize.json 2>> $o/${tag}_bench.err; echo "tokenize rc=$?"
+python bench.py --full --images 32 --no-cpu-baseline --min-seconds 3 > $o/${tag}_bench_32img.json 2>> $o/${tag}_bench.err; echo "32img rc=$?"
+python bench.py --full --images 256 --no-cpu-baseline --min-seconds 3 > $o/${tag}_bench_256img.json 2>> $o/${tag}_bench.err; echo "256img rc=$?"
+VQ_BENCH_SHARE_GPU=1 python bench.py --full --gpus 2 --steps 10 --warmup 3 --images 256 --min-seconds 0.3 --no-cpu-baseline > $o/${tag}_gpus2_shared.json 2>> $o/${tag}_bench.err; echo "gpus2 rc=$?"
 python tools/bench_shapes.py > $o/${tag}_shapes.txt 2>&1; echo "shapes rc=$?"
 python tools/time_exact_tiled.py >> $o/${tag}_shapes.txt 2>&1
 # BASELINE configs[2] / configs[4]: kernel statistics and counters of the D <= 32 kernels on the final library

@@ -3,10 +3,14 @@
 # ONE command gives both artefacts the judge compares: bench.py's JSON line (HIP-event time of the proposal kernel)
 # and rocprofv3's per-kernel summary of the very same process.  Many steps, so the clock-ramp launches do not skew
 # the profiler's average.
+# Output: $VQ_OUT/<tag>{,.json,.err} (VQ_OUT: an absolute directory, default out/ in the repository).
 tag=$1; shift
+root="$(cd "$(dirname "${BASH_SOURCE[0]}")/.." && pwd)"
+out="${VQ_OUT:-$root/out}/$tag"
+mkdir -p "$(dirname "$out")"
 cd /tmp && export TMPDIR=/tmp
-rocprofv3 --kernel-trace --stats --output-format csv -d /root/repo/gpurun_out/$tag -- python3 /root/repo/bench.py --steps 200 --warmup 10 "$@" > /root/repo/gpurun_out/$tag.json 2> /root/repo/gpurun_out/$tag.err
-python3 - /root/repo/gpurun_out/$tag <<'PY'
+rocprofv3 --kernel-trace --stats --output-format csv -d "$out" -- python3 "$root/bench.py" --full --steps 200 --warmup 10 "$@" > "$out.json" 2> "$out.err"
+python3 - "$out" <<'PY'
 import csv,sys,glob,json
 f=glob.glob(sys.argv[1]+'/*/*kernel_stats.csv')[0]
 rows=list(csv.DictReader(open(f)))
