@@ -520,19 +520,13 @@ int vqhip_debug_proposal_scores(const void *x, int x_dtype, const void *cb, int6
  * around that launch (bench.py's roofline leg).  enable(1) starts collecting, collect() synchronises on the
  * recorded events, returns the summed kernel milliseconds and launch count (HOST pointers) and resets. */
 int vqhip_profile_enable(int on);
-/* Knobs for A/B measurements (results never change): key 2 = number of codebook slices (1,2,4,8,16; 0 = automatic);
- * key 3 = workgroup cap of the gather kernel (0 = automatic); key 4 = its streaming mode (1 on, 2 off, 0 = automatic:
- * on when the outputs exceed 192 MiB); key 5 = filtered epilogue of the D <= 128 proposal kernels (default 1); key 6 = decision
- * stage inside the proposal kernel (0 never, 1 always, 2 = where one slice covers the codebook: default); key 8 = no aux reads
- * for cosine / dot codebooks at D <= 32 (1); key 9 = group records at D <= 32, identified by identify32_kernel (32x32x16 form: K <= 131 072, N < 2^30) or by an in-kernel replay (16x16x32 form) (1); key 10 = balanced
- * tiles per workgroup (1); key 11 = the 32x32x16 proposal kernel at D <= 16 (1); key 13 = whole-image tiles in vqhip_gather_ste_map
- * for maps of 256-position images (1); key 15 = the direct fp32 form of vqhip_col_argmin_rows for short lists (1); key 17 = D = 256 batches of
- * more than 16 384 bf16 rows make their token fragments in the proposal kernel's prologue instead of writing and reading a token
- * image (1; 2 = fp32 rows too, a measurement aid); key 18 = the streamed form of the whole-batch fp32 pass (vqhip_argmin_exact,
- * vqhip_distance, the column fallback: exact_stream_kernel) where D % 4 == 0 (bf16 rows: D % 8 == 0) (1; 0 = the register form).
- * Key 12 is a verification aid, not an A/B knob: value V > 0 sends rows 0 .. min(V, N, 1024) - 1 of every vqhip_argmin batch
- * through the last-resort whole-codebook fp32 pass as well (its indices replace the ones the earlier stages wrote — the same
- * ones; a histogram requested from the call counts those rows twice); 0 = off (default).  Any other key: VQHIP_EINVAL. */
+/* Verification aids (results never change; process-wide host state): key 2 = number of codebook slices of the proposal
+ * pass (1,2,4,8,16; 0 = automatic); key 18 = the streamed form of the whole-batch fp32 pass (vqhip_argmin_exact,
+ * vqhip_distance, the column fallback: exact_stream_kernel) where D % 4 == 0 (bf16 rows: D % 8 == 0) (1, default; 0 = the
+ * register form, which D % 4 != 0 takes anyway).  Key 12: value V > 0 sends rows 0 .. min(V, N, 1024) - 1 of every
+ * vqhip_argmin batch through the last-resort whole-codebook fp32 pass as well (its indices replace the ones the earlier stages
+ * wrote — the same ones; a histogram requested from the call counts those rows twice); 0 = off (default).
+ * Any other key: VQHIP_EINVAL. */
 int vqhip_set_tuning(int key, int value);
 int vqhip_profile_collect(double *ms_sum, int64_t *launches);
 

@@ -52,13 +52,14 @@ def test_bad_arguments_are_rejected_without_a_gpu(lib):
     assert rc == -22
 
 
-def test_tuning_knobs_are_host_state_and_unknown_keys_are_refused(lib):
-    """vqhip_set_tuning touches no device: every documented A/B key is accepted (and restored), any other key is VQHIP_EINVAL;
-    VQHIP_TUNING applies the same knobs at load (vector_quantization_amd/_lib.py)."""
-    for key, default in ((2, 0), (5, 1), (6, 2), (8, 1), (9, 1), (10, 1), (11, 1), (13, 1), (15, 1), (17, 1), (18, 1), (12, 0)):
+def test_tuning_aids_are_host_state_and_retired_keys_are_refused(lib):
+    """vqhip_set_tuning touches no device: the three verification aids (keys 2, 12, 18) are accepted (and restored), any
+    other key — the retired A/B keys 3-6, 8-11, 13, 15 and 17 among them — is VQHIP_EINVAL; VQHIP_TUNING applies the same
+    knobs at load (vector_quantization_amd/_lib.py)."""
+    for key, default in ((2, 0), (18, 1), (12, 0)):
         assert lib.vqhip_set_tuning(key, 0) == 0
         assert lib.vqhip_set_tuning(key, default) == 0
-    for key in (-1, 1, 7, 14, 16, 19, 1000):
+    for key in (-1, 0, 1, 3, 4, 5, 6, 7, 8, 9, 10, 11, 13, 14, 15, 16, 17, 19, 1000):
         assert lib.vqhip_set_tuning(key, 1) == -22
         assert b'vqhip_set_tuning' in lib.vqhip_last_error()
 

@@ -435,22 +435,30 @@ def test_d1024_one_wave_per_simd_form(ops, metric):
 
 
 def test_large_batch_many_slices_and_single_slice(ops):
-    """Slice counts 1..16 give identical indices (tuning knob 2 forces the split)."""
+    """Slice counts 1..16 give identical indices (tuning knob 2 forces the split).  The D = 256 bf16 batch is one whose token
+    fragments the proposal kernel makes itself (coarse_kernel<..., XD = 1>) at the default slice count: two and four forced
+    slices keep that form, a forced single slice keeps the token image (one slice decides inside the proposal kernel)."""
     from vector_quantization_amd import _lib
     L = _lib.lib()
     N, K, D = 3000, 4096, 64
     x, w = synth.make_inputs('normal', 55, N, K, D)
     ref = co.l2_argmin(x, w)
     cb = ops.prepare_codebook(dev(w), 'L2')
+    g = torch.Generator(device='cuda').manual_seed(256)
+    w2 = torch.randn(16384, 256, device='cuda', generator=g)
+    x2 = (w2[torch.randint(0, 16384, (20000,), device='cuda', generator=g)]
+          + 0.05 * torch.randn(20000, 256, device='cuda', generator=g)).bfloat16()
+    ref2 = ops.argmin_exact(x2, w2, 'L2')
+    cb2 = ops.prepare_codebook(w2, 'L2')
     try:
         for ns in (1, 2, 4, 8, 16):
-            L.vqhip_set_tuning(2, ns)
-            for pipe in (0, 1):
-                L.vqhip_set_tuning(0, pipe)
-                np.testing.assert_array_equal(ops.argmin(dev(x), cb).cpu().numpy(), ref)
+            assert L.vqhip_set_tuning(2, ns) == 0
+            np.testing.assert_array_equal(ops.argmin(dev(x), cb).cpu().numpy(), ref)
+        for ns in (1, 2, 4):
+            assert L.vqhip_set_tuning(2, ns) == 0
+            assert torch.equal(ops.argmin(x2, cb2), ref2), ns
     finally:
         L.vqhip_set_tuning(2, 0)
-        L.vqhip_set_tuning(0, 1)
 
 
 @pytest.mark.parametrize('metric', ['L2', 'Cosine'])
@@ -604,14 +612,16 @@ def test_randomised_shapes_sweep(ops):
 
 
 @pytest.mark.parametrize('N,K,D,metric', [(20000, 8192, 32, 'Cosine'), (16500, 1000, 32, 'Cosine'), (40000, 777, 24, 'L2'),
-                                          (70001, 4099, 8, 'L2'), (33333, 300, 16, 'Cosine')])
+                                          (70001, 4099, 8, 'L2'), (33333, 300, 16, 'Cosine'),
+                                          (6000, 8192, 32, 'Cosine'), (12000, 4096, 32, 'L2'), (5000, 8192, 16, 'L2'),
+                                          (7000, 2000, 8, 'Cosine')])
 def test_small_d_kernel_forms_agree(ops, N, K, D, metric):
     """D <= 32 at >= 16 384 tokens runs the group-record form (identification requests served by identify32_kernel, or the
     in-kernel replay of the 16x16x32 form), without aux reads for cosine
-    (a codebook that does not fill its last stage reads them there) and with balanced workgroup sizes: every
-    combination of the three knobs (8, 9, 10) returns the indices of the all-fp32 route, on the CPU oracle's definition."""
-    from vector_quantization_amd import _lib
-    L = _lib.lib()
+    (a codebook that does not fill its last stage reads them there) and with balanced workgroup sizes.  Below 16 384 tokens
+    (VQ_GROUPS_MIN_N) the filtered form without group records runs, and below 8192 (VQ_W32_MIN_N) for D <= 16 and cosine
+    D = 32 too; L2 codebooks take the forms that read the aux chunk.  Every form returns the indices of the all-fp32 route,
+    on the CPU oracle's definition."""
     g = torch.Generator(device='cuda').manual_seed(N + K + D)
     w = torch.randn(K, D, device='cuda', generator=g)
     x = torch.randn(N, D, device='cuda', generator=g)
@@ -625,16 +635,8 @@ def test_small_d_kernel_forms_agree(ops, N, K, D, metric):
     sample = slice(0, 600)
     oracle = (co.cos_argmin if metric == 'Cosine' else co.l2_argmin)(x[sample].cpu().numpy(), w.cpu().numpy())
     np.testing.assert_array_equal(ref[sample].cpu().numpy(), oracle)
-    try:
-        for noaux in (0, 1):
-            for groups in (0, 1):
-                for balance in (0, 1):
-                    L.vqhip_set_tuning(8, noaux); L.vqhip_set_tuning(9, groups); L.vqhip_set_tuning(10, balance)
-                    got = ops.argmin(xq, ops.prepare_codebook(w, metric))
-                    assert torch.equal(got, ref), (noaux, groups, balance)
-    finally:
-        for key in (8, 9, 10):
-            L.vqhip_set_tuning(key, 1)
+    got = ops.argmin(xq, ops.prepare_codebook(w, metric))
+    assert torch.equal(got, ref)
 
 
 @pytest.mark.parametrize('N,K,D,metric,hot', [(40000, 8192, 32, 'Cosine', 1), (50000, 16384, 8, 'L2', 1), (60000, 8192, 16, 'Cosine', 40)])

@@ -1,7 +1,7 @@
 #!/usr/bin/env python3
 """BASELINE configs[1] at small batches (VQGANQuantizer.forward, eval, K = 16384, D = 256, bf16 latents): ms per step for the
 tuning states given as key=value pairs on the command line, in one process, alternating.
-usage: ab_small_batch.py images  [6=1] [2=8] ..."""
+usage: ab_small_batch.py images  [2=1] [2=8] ..."""
 import os, sys, time
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 import torch
@@ -15,7 +15,7 @@ g = torch.Generator(device=dev).manual_seed(3407)
 w = torch.randn(K, D, device=dev, generator=g)
 x = torch.randn(images * 256, D, device=dev, generator=g).bfloat16()
 q = bench.build_module(bench.quantizer_cfg(K, D, 'L2'), dev, w, train=False)
-DEFAULTS = {6: 2, 2: 0}
+DEFAULTS = {2: 0}
 def run(n):
     with torch.no_grad():
         for _ in range(n):
@@ -26,9 +26,9 @@ ref = None
 for rnd in range(5):
     for s in states:
         for k, v in DEFAULTS.items():
-            L.vqhip_set_tuning(k, v)
+            assert L.vqhip_set_tuning(k, v) == 0
         if s is not None:
-            L.vqhip_set_tuning(*s)
+            assert L.vqhip_set_tuning(*s) == 0, f'tuning {s} refused'
         run(20); torch.cuda.synchronize()
         t0 = time.perf_counter(); out = run(200); torch.cuda.synchronize()
         res[s].append((time.perf_counter() - t0) / 200 * 1e3)

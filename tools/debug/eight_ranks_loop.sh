@@ -1,6 +1,6 @@
 #!/bin/bash
 # The shared-GPU rehearsal of `bench.py --gpus 8` (tests/test_gpu_two_ranks.py) in a loop: the stderr of a failing run.
-# usage: tools/debug/eight_ranks_loop.sh <runs> [extra env, e.g. VQ_TUNE18=0]
+# usage: [VQHIP_TUNING=18=0] tools/debug/eight_ranks_loop.sh <runs>
 n=${1:-4}
 out=${VQ_OUT:-out}; mkdir -p "$out"      # output directory (default out/ in the repository)
 for i in $(seq 1 $n); do

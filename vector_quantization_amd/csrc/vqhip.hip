@@ -94,32 +94,22 @@ static inline int waves_grid(int64_t rows, int waves_per_block) {
 }
 
 // ---- proposal-pass dispatch ------------------------------------------------------------------------
-static std::atomic<int> g_tune_slices{0};   // proposal-kernel knob for A/B measurements (vqhip_set_tuning key 2)
-// key 6: 1 = the proposal kernel runs the decision stage itself (last workgroup of a token block, arrival tickets).
-// Measured neutral (tools/ab_key.py 6: -1.6 % .. +1.4 % over seven shapes; the release/acquire fences cost what the
-// launch saves), so the stand-alone launch stays the default; results are identical either way.
-// (2 = only where ONE slice covers the codebook: the workgroup then decides its own tokens, no ticket and no fence involved)
-static std::atomic<int> g_tune_fused_decide{2};
-// mode 2: the proposal kernel runs the decision stage itself where one slice covers the codebook, and for small batches
-// whatever the slice count (a launch less on a chain of ~5 us launches: 12 images -2.6 %, 32 images -0.5 %, tools/ab_small_batch.py;
-// at 256 images and more the last-arriving workgroup's merge is the longer tail)
+// Verification aids (vqhip_set_tuning; results unchanged): they let the tests reach paths the defaults take only for some shapes
+static std::atomic<int> g_tune_slices{0};        // key 2: force the slice count of the proposal pass (1, 2, 4, 8 or 16)
+static std::atomic<int> g_tune_force_exact{0};   // key 12: the first V rows of a batch also take the whole-codebook fp32 pass
+static std::atomic<int> g_tune_stream{1};        // key 18: 0 = the whole-batch fp32 pass keeps its register form (exact_tiled_kernel)
+// The proposal kernel runs the decision stage itself where one slice covers the codebook (the workgroup then decides its own
+// tokens, no ticket involved), and for small batches whatever the slice count: the workgroup that draws a token block's last
+// arrival ticket merges its slices (a launch less on a chain of ~5 us launches: 12 images -2.6 %, 32 images -0.5 %,
+// tools/ab_small_batch.py; at 256 images and more the last-arriving workgroup's merge is the longer tail).  Deciding in-kernel
+// at every slice count was measured neutral (the fences cost what the launch saves: profiles/r02_ab_fused_decide.txt).
 #define VQ_FUSED_DECIDE_MAX_N 16384
-static std::atomic<int> g_tune_col_direct{1};   // key 15: 0 = a short list of codes takes the proposal pipeline like a long one (A/B; results unchanged)
-static std::atomic<int> g_tune_map256{1};   // key 13: 0 = maps of 256-position images keep the 64-token tiles of gather_ste_map_kernel (A/B; results unchanged)
-static std::atomic<int> g_tune_force_exact{0};   // key 12 (verification aid): the first V rows of a batch also take the whole-codebook fp32 pass
-static std::atomic<int> g_tune_w32{1};      // key 11: 0 = D <= 16 keeps the 16x16x32 proposal kernel (A/B; results unchanged)
-static std::atomic<int> g_tune_groups{1};   // key 9: 0 = per-element update inside the stream of the D <= 32 kernels (A/B; results unchanged)
-static std::atomic<int> g_tune_noaux{1};    // key 8: 0 = cosine / dot codebooks read the (all-zero) aux chunk like L2 ones (A/B; results unchanged)
-static std::atomic<int> g_tune_filter{1};   // key 5: 0 = unfiltered epilogue on the small-D instantiations too (A/B; results unchanged)
-static std::atomic<int> g_tune_gather_grid{0}, g_tune_gather_nt{0};   // gather kernel knobs (keys 3, 4)
-static std::atomic<int> g_tune_stream{1};   // key 18: 0 = the whole-batch fp32 pass keeps its register form (exact_tiled_kernel) (A/B; results unchanged)
-static std::atomic<int> g_tune_xdirect{1};  // key 17: 0 = D = 256 batches keep the fp16 token image (x_prep / pre_kernel token side) (A/B; results unchanged)
 
 template <int NSTEP, int TT, int WAVES, int TPS, int NBUF = 2, bool FILTER = false, bool NOAUX = false, bool GROUPS = false, int XD = 0>
 static int launch_coarse_cfg(const char *ximg, int64_t N, const char *frag, int64_t nstages, int nslices, float *rec,
                              int64_t Np, const VqCbStats *cbst, const float *xh2, const float *rho2, int Dp, int metric,
                              const VqDecideOut &dec, int pad_stage, int tpb, hipStream_t s) {
-    constexpr int LDS = NBUF * (TPS * NSTEP + VQ_AUX_CHUNKS(TPS)) * VQ_CHUNK_BYTES + VQ_STAGE_LDS_EXTRA;
+    constexpr int LDS = NBUF * (TPS * NSTEP + VQ_AUX_CHUNKS(TPS)) * VQ_CHUNK_BYTES;
     auto kern = coarse_kernel<NSTEP, TT, WAVES, TPS, NBUF, FILTER, NOAUX, GROUPS, XD>;
     static LdsCache lds_set;
     if (int rc = ensure_dyn_lds((const void *)kern, LDS, lds_set)) return rc;
@@ -139,7 +129,7 @@ template <int TT, int WAVES, int TPS, int NBUF, bool NOAUX, int KS>
 static int launch_coarse32_cfg(const char *ximg, int64_t N, const char *frag, int64_t nstages, int nslices, float *rec,
                                int64_t Np, const VqCbStats *cbst, const float *xh2, const float *rho2, int Dp, int metric,
                                const int *n_dev, const VqGroupLists &grp, int pad_stage, int tpb, hipStream_t s) {
-    constexpr int LDS = NBUF * (TPS * 2 + VQ_AUX_CHUNKS(TPS)) * VQ_CHUNK_BYTES + VQ_STAGE_LDS_EXTRA;
+    constexpr int LDS = NBUF * (TPS * 2 + VQ_AUX_CHUNKS(TPS)) * VQ_CHUNK_BYTES;
     auto kern = coarse32_kernel<TT, WAVES, TPS, NBUF, NOAUX, KS, VQ_GROUP_TILES>;
     static LdsCache lds_set;
     if (int rc = ensure_dyn_lds((const void *)kern, LDS, lds_set)) return rc;
@@ -183,9 +173,8 @@ static int launch_rescan_cfg(const char *ximg, const char *frag, int64_t nstages
 // (BASELINE configs[2]) make 392 workgroups of 16 tiles, two on 136 CUs and one on the other 120 (32 tiles at worst);
 // 13 tiles per workgroup make 483, two per CU at worst (26 tiles).  Ties keep the larger workgroup; at least half the
 // waves stay busy (and a workgroup covers >= 128 tokens: the arrival counters of the workspace are laid out for that).
-static std::atomic<int> g_tune_balance{1};  // key 10: 0 = always full workgroups (A/B; results unchanged)
 static int balanced_tiles_per_block(int64_t N, int full) {
-    if (!g_tune_balance.load() || full < 16) return full;
+    if (full < 16) return full;
     const int64_t ntiles = (N + 15) / 16;
     int best = full;
     int64_t best_cost = ((ntiles + full - 1) / full + 255) / 256 * full;
@@ -199,15 +188,15 @@ static int balanced_tiles_per_block(int64_t N, int full) {
 // The token side made inside the proposal kernel's prologue instead of a token image (coarse_kernel<..., XD>):
 // the D = 256 form with 64 tokens per wave, rows as the caller holds them, the decision stage in its own launch.  One predicate
 // for the front (which then skips its token side), the proposal launch and the second pass (which reads the rows instead).
+// The form never decides in-kernel: it needs at least two slices (one slice, forced by key 2 included, decides in-kernel).
 static bool vq_xdirect(int64_t N, int64_t K, int D, int x_dtype, int metric, const int *n_dev) {
-    if (!g_tune_xdirect.load() || D != 256 || n_dev != nullptr || vq_cb_layout(K, D).nstages < 2) return false;   // (one slice would decide in-kernel)
-    // bf16 rows only: a piece of 8 latents has the fragment's own 16 bytes and is converted in place.  fp32 rows (XD = 2: twice the
+    if (D != 256 || n_dev != nullptr || vq_cb_layout(K, D).nstages < 2 || g_tune_slices.load() == 1) return false;
+    // bf16 rows only: a piece of 8 latents has the fragment's own 16 bytes and is converted in place.  fp32 rows (twice the
     // bytes per piece, a round trip per token tile, 58 spilled registers) cost a workgroup +44 us of prologue at 20 000 x 16384 x 256
     // against +3 us for bf16 (profiles/r06_xdirect.txt): they keep the token image
-    if (x_dtype != VQHIP_DTYPE_BF16 && g_tune_xdirect.load() != 2) return false;
+    if (x_dtype != VQHIP_DTYPE_BF16) return false;
     if (metric != VQHIP_METRIC_L2 && metric != VQHIP_METRIC_COS && metric != VQHIP_METRIC_COS_BF16) return false;   // (not the role-swapped column pass)
     if (N <= VQ_FUSED_DECIDE_MAX_N) return false;                                     // small batches decide inside the proposal kernel
-    if (g_tune_fused_decide.load() == 1) return false;
     return !(N <= 4096 || (N <= 256 * 64 && K <= 4096));                               // the 64-tokens-per-wave form (launch_coarse: !small16)
 }
 
@@ -233,7 +222,7 @@ struct VqGroupRun { int used, ks, noaux, pad_stage; };
 static int launch_coarse(const char *ximg, int64_t N, const VqCbLayout &L, const char *frag, float *rec, int64_t Np,
                          const VqCbStats *cbst, const float *xh2, const float *rho2, int metric, const VqDecideOut &dec,
                          int *nslices_out, int *fused_decide_out, hipStream_t s, VqGroupLists grp = VqGroupLists{nullptr, nullptr, nullptr, nullptr, 0, 1, 0},
-                         VqGroupRun *grun = nullptr, int xd = 0) {
+                         VqGroupRun *grun = nullptr, bool xd = false) {
     const int nstep = L.nstep;
     // small batches use fewer tokens per wave so that more workgroups exist
     const bool small = N <= 256 * 64;
@@ -247,7 +236,7 @@ static int launch_coarse(const char *ximg, int64_t N, const VqCbLayout &L, const
     // 64-token form is the faster one)
     const bool small32 = N < 512 * 512;
     // cosine / dot product: every real code's aux value is 0 (cb_stats_kernel), only padding codes need the aux chunk
-    const bool noaux = !VQ_IS_L2(metric) && g_tune_noaux.load();
+    const bool noaux = !VQ_IS_L2(metric);
     const int pad_stage = (L.K % ((int64_t)L.tps * VQ_TILE_CODES)) ? (int)(L.nstages - 1) : -1;
 #define VQ_CFG(NS, TT, W, ...)                                                                      \
     {                                                                                               \
@@ -255,26 +244,20 @@ static int launch_coarse(const char *ximg, int64_t N, const VqCbLayout &L, const
         int ns = pick_slices(ntb, L.nstages, (NS) <= 8 ? VQ_MIN_SLICES_FILTER : 2);                 \
         *nslices_out = ns;                                                                          \
         const int tpb = (ns == 1) ? balanced_tiles_per_block(N, (W) * (TT)) : (W) * (TT);           \
-        const int fmode = g_tune_fused_decide.load();                                               \
         VqDecideOut dsel = dec;                                                                     \
-        if (!(fmode == 1 || (fmode == 2 && (ns == 1 || N <= VQ_FUSED_DECIDE_MAX_N)))) dsel.idx = nullptr;                            \
+        if (!(ns == 1 || N <= VQ_FUSED_DECIDE_MAX_N)) dsel.idx = nullptr;                           \
         *fused_decide_out = dsel.idx != nullptr ? 1 : 0;                                            \
         return launch_coarse_cfg<NS, TT, W, __VA_ARGS__>(ximg, N, frag, L.nstages, ns, rec, Np, cbst, xh2, rho2, L.Dp, metric, dsel, pad_stage, tpb, s); \
     }
     switch (nstep) {
         // D <= 128: VALU-issue-bound with the plain epilogue -> filtered epilogue (see coarse_kernel)
-        // D <= 16 always; 16 < D <= 32 (two instructions per tile) only without aux reads — measured (tools/ab_w32.py,
-        // profiles/r03_w32_ab.txt): D = 32 cosine +2.5..5 %, D = 32 L2 -4..-14 % (the form is LDS-bound once the four 16-byte aux
+        // D <= 16 always; 16 < D <= 32 (two instructions per tile) only without aux reads — measured
+        // (profiles/r03_w32_ab.txt): D = 32 cosine +2.5..5 %, D = 32 L2 -4..-14 % (the form is LDS-bound once the four 16-byte aux
         // reads per lane and tile come on top of 2 KiB of fragments)
-        case 2: if ((L.D <= 16 || (L.D <= VQ_W32_MAX_D && noaux)) && N >= VQ_W32_MIN_N && g_tune_w32.load() && g_tune_filter.load() && g_tune_groups.load() &&
-                    grp.bcnt != nullptr && grun != nullptr) {
+        case 2: if ((L.D <= 16 || (L.D <= VQ_W32_MAX_D && noaux)) && N >= VQ_W32_MIN_N && grp.bcnt != nullptr && grun != nullptr) {
                     // one 32x32x16 instruction covers the whole inner dimension: a quarter of the MFMA issue, group update per
                     // 16 scores.  Wide token tiles of 32 tokens: 1 (below 262 144 tokens) or 2 per wave.
-#ifdef VQ_W32_TT
-                    const int tt = VQ_W32_TT;
-#else
                     const int tt = small32 ? 1 : 2;
-#endif
                     const int full = 8 * tt * 2;                                    // 16-token tiles per workgroup
                     const int64_t ntb0 = (N + full * 16 - 1) / (full * 16);
                     int ns = pick_slices(ntb0, L.nstages, VQ_MIN_SLICES_FILTER);
@@ -298,38 +281,22 @@ static int launch_coarse(const char *ximg, int64_t N, const VqCbLayout &L, const
                     }
 #undef VQ_CFG32
                 }
-                if (!g_tune_filter.load()) { if (small32) VQ_CFG(2, 2, 8, VQ_TPS_D32, VQ_NBUF_D32) else VQ_CFG(2, 4, 8, VQ_TPS_D32, VQ_NBUF_D32) }
                 // (N >= 262 144: at least 1024 workgroups of 64 tokens per wave — balance no longer matters and that form is the faster one)
                 // group records from VQ_GROUPS_MIN_N tokens on: below, the identification replay at the end of a
                 // workgroup (a few L2 round trips) costs more than the stream saves
-                if (N >= VQ_GROUPS_MIN_N && g_tune_groups.load()) {
+                if (N >= VQ_GROUPS_MIN_N) {
                     if (noaux) { if (small32) VQ_CFG(2, VQ_D32_SMALL_TT, VQ_D32_SMALL_W, VQ_TPS_D32, VQ_NBUF_D32, true, true, true) else VQ_CFG(2, 4, 8, VQ_TPS_D32, VQ_NBUF_D32, true, true, true) }
                     if (small32) VQ_CFG(2, VQ_D32_SMALL_TT, VQ_D32_SMALL_W, VQ_TPS_D32, VQ_NBUF_D32, true, false, true) else VQ_CFG(2, 4, 8, VQ_TPS_D32, VQ_NBUF_D32, true, false, true)
                 }
                 if (noaux) { if (small32) VQ_CFG(2, VQ_D32_SMALL_TT, VQ_D32_SMALL_W, VQ_TPS_D32, VQ_NBUF_D32, true, true) else VQ_CFG(2, 4, 8, VQ_TPS_D32, VQ_NBUF_D32, true, true) }
                 if (small32) VQ_CFG(2, VQ_D32_SMALL_TT, VQ_D32_SMALL_W, VQ_TPS_D32, VQ_NBUF_D32, true) else VQ_CFG(2, 4, 8, VQ_TPS_D32, VQ_NBUF_D32, true)
-        case 4: if (!g_tune_filter.load()) { if (small) VQ_CFG(4, 2, 8, 4, 4) else VQ_CFG(4, 4, 8, 4, 4) }
-                if (small) VQ_CFG(4, 2, 8, 4, 4, true) else VQ_CFG(4, 4, 8, 4, 4, true)
-        case 8: if (!g_tune_filter.load()) { if (small) VQ_CFG(8, 2, 8, 4, 4) else VQ_CFG(8, 4, 8, 4, 4) }
-                if (small) VQ_CFG(8, 2, 8, 4, 4, true) else VQ_CFG(8, 4, 8, 4, 4, true)
-#if defined(VQ_D256_GROUPS)
-        case 16: if (small16) VQ_CFG(16, 2, 8, VQ_TPS16, 4) else VQ_CFG(16, 4, 8, VQ_TPS16, 4, true, false, true)
-#elif defined(VQ_D256_FILTER)
-        case 16: if (small16) VQ_CFG(16, 2, 8, VQ_TPS16, 4, true) else VQ_CFG(16, 4, 8, VQ_TPS16, 4, true)
-#else
-        case 16: if (xd == 1 && !small16) VQ_CFG(16, 4, 8, VQ_TPS16, 4, false, false, false, 1)
-                 if (xd == 2 && !small16) VQ_CFG(16, 4, 8, VQ_TPS16, 4, false, false, false, 2)
+        case 4: if (small) VQ_CFG(4, 2, 8, 4, 4, true) else VQ_CFG(4, 4, 8, 4, 4, true)
+        case 8: if (small) VQ_CFG(8, 2, 8, 4, 4, true) else VQ_CFG(8, 4, 8, 4, 4, true)
+        case 16: if (xd && !small16) VQ_CFG(16, 4, 8, VQ_TPS16, 4, false, false, false, 1)
                  if (small16) VQ_CFG(16, 2, 8, VQ_TPS16, 4) else VQ_CFG(16, 4, 8, VQ_TPS16, 4)
-#endif
         // large D: the token fragments of a wave must stay in registers for the whole stream
-#ifndef VQ_CFG_D512
-#define VQ_CFG_D512 VQ_CFG(32, 2, 8, 2)
-#endif
-#ifndef VQ_CFG_D768
-#define VQ_CFG_D768 VQ_CFG(48, 2, 8, 1)
-#endif
-        case 32: VQ_CFG_D512
-        case 48: VQ_CFG_D768
+        case 32: VQ_CFG(32, 2, 8, 2)
+        case 48: VQ_CFG(48, 2, 8, 1)
         case 64: {
             // D = 1024, two forms: eight waves x 16 tokens (two waves per SIMD; one 1 KiB LDS read per MFMA), or four waves x 48
             // tokens (one wave per SIMD with the whole register file: coarse_kernel, PIPE_H; a third of the LDS bytes per flop).
@@ -586,7 +553,7 @@ static int argmin_pipeline(const void *x, int x_dtype, const float *e_exact, con
     const int narrive = (int)W.narrive;          // arrival counters + the group path's bucket counters (one zeroed range)
     int xgrid = (int)((N + 31) / 32);
     // no token image: the proposal kernel converts the rows it loads (coarse_kernel<..., XD>); the front only does the housekeeping
-    const int xd = vq_xdirect(N, K, D, x_dtype, metric, n_dev) ? (x_dtype == VQHIP_DTYPE_BF16 ? 1 : 2) : 0;
+    const bool xd = vq_xdirect(N, K, D, x_dtype, metric, n_dev);
     if (!x_prepared) {
         if (xd) xgrid = xgrid < 64 ? xgrid : 64;
         if (x_dtype == VQHIP_DTYPE_F32) x_prep_kernel<0><<<xgrid, 256, 0, s>>>(x, N, D, L.nstep, ximg, xh2, rho2, (float *)(w + W.off_xn), counters, (char *)cb, L, arrive, narrive, xd);
@@ -596,7 +563,7 @@ static int argmin_pipeline(const void *x, int x_dtype, const float *e_exact, con
     // the proposal kernel also runs the decision stage (the workgroup that completes a token block merges its slices)
     VqDecideOut dec{idx, hist, rescan_list, multi_list, exact_list, counters, keys, thr, rescan_cnt, arrive, n_dev,
                     x, xh2, rho2, (float *)(w + W.off_xn)};
-    VqDecideOut dec_arg = dec;                   // launch_coarse decides (knob 6, slice count) whether the proposal kernel runs the
+    VqDecideOut dec_arg = dec;                   // launch_coarse decides (slice count, batch size) whether the proposal kernel runs the
     int fused_done = 0;                          // decision stage itself and reports it here
     // D <= 32 group path: request lists of the proposal kernel (cap = an equal share of the pool per code tile, whole batches of 32)
     VqGroupLists grp{nullptr, nullptr, nullptr, nullptr, 0, 1, 0};
@@ -636,8 +603,7 @@ static int argmin_pipeline(const void *x, int x_dtype, const float *e_exact, con
     {
         const char *frag = c + L.off_frag;
         int rrc = VQHIP_OK;
-        if (xd == 1) rrc = launch_rescan_cfg<16, 2, 8, VQ_TPS16, 4, 1>(ximg, frag, L.nstages, rescan_list, counters, thr, rescan_cnt, cand_list, s, x);
-        else if (xd == 2) rrc = launch_rescan_cfg<16, 2, 8, VQ_TPS16, 4, 2>(ximg, frag, L.nstages, rescan_list, counters, thr, rescan_cnt, cand_list, s, x);
+        if (xd) rrc = launch_rescan_cfg<16, 2, 8, VQ_TPS16, 4, 1>(ximg, frag, L.nstages, rescan_list, counters, thr, rescan_cnt, cand_list, s, x);
         else switch (L.nstep) {
 #define VQ_RESCAN(NS, TT, ...) case NS: rrc = launch_rescan_cfg<NS, TT, 8, __VA_ARGS__>(ximg, frag, L.nstages, rescan_list, counters, thr, rescan_cnt, cand_list, s); break;
             VQ_RESCAN(2, 2, VQ_TPS_D32, 4) VQ_RESCAN(4, 2, 4, 4) VQ_RESCAN(8, 2, 4, 4) VQ_RESCAN(16, 2, VQ_TPS16, 4) VQ_RESCAN(32, 2, 2) VQ_RESCAN(48, 2, 1) VQ_RESCAN(64, 1, 1)
@@ -917,7 +883,7 @@ static inline int64_t col_direct_bytes(int64_t N, int64_t cap, int D, int64_t K)
     return (K * 8 + 1023) / 1024 * 1024 + 1024 + (N * 4 + 1023) / 1024 * 1024 + (K * 4 + 1023) / 1024 * 1024;
 }
 static bool col_direct_ok(int x_dtype, int metric, int64_t cap, int64_t N, int64_t K, int D, int64_t ws_bytes) {
-    if (!g_tune_col_direct.load() || cap <= 0 || (D % 4) != 0) return false;
+    if (cap <= 0 || (D % 4) != 0) return false;
     if (x_dtype != VQHIP_DTYPE_F32) return false;        // the pass reads the tokens as fp32 rows, whatever the metric
     if (((cap + 31) / 32) * ((N + 127) / 128) * (int64_t)D > VQ_COL_DIRECT_MAX_WORK) return false;
     return ws_bytes >= col_direct_bytes(N, cap, D, K);
@@ -1054,7 +1020,7 @@ int vqhip_gather_ste_map(const void *x_rows, int x_dtype, const float *e, const 
     hipStream_t s = (hipStream_t)stream;
     double *sse = x_rows ? (double *)scratch16 : nullptr;
     if (x_rows && x_dtype != VQHIP_DTYPE_F32 && x_dtype != VQHIP_DTYPE_BF16) return fail(VQHIP_EINVAL, "vqhip_gather_ste_map: x_dtype");
-    if (HW % 256 == 0 && D % 32 == 0 && g_tune_map256.load()) {
+    if (HW % 256 == 0 && D % 32 == 0) {
         // images of a multiple of 256 positions: whole 1 KiB channel rows per wave-store (gather_ste_map256_kernel)
         const int64_t nt = N / 256;
         int csplit = 1;                                     // share the channels while that still leaves whole chunks and the grid is short
@@ -1085,9 +1051,8 @@ static int gather_ste_impl(const void *x, int x_dtype, const float *e, const int
     hipStream_t s = (hipStream_t)stream;
     // outputs beyond the Infinity Cache (256 MiB) are streamed: non-temporal accesses and twice the waves in flight
     const int64_t out_bytes = (int64_t)N * D * 4 * ((z ? 1 : 0) + (z_ste ? 1 : 0));
-    const int tune_nt = g_tune_gather_nt.load(), tune_grid = g_tune_gather_grid.load();
-    const bool streamed = tune_nt ? tune_nt == 1 : out_bytes > (192ll << 20);
-    int cap = tune_grid > 0 ? tune_grid : (streamed ? 512 : 256);      // blocks of 16 waves
+    const bool streamed = out_bytes > (192ll << 20);
+    int cap = streamed ? 512 : 256;                                    // blocks of 16 waves
     int grid = (int)((N + 15) / 16);
     grid = grid > cap ? cap : grid;
 #define VQ_GATHER(DT, NT) gather_ste_loss_kernel<DT, NT><<<grid, 1024, 0, s>>>(x, e, idx, N, D, z, z_ste, sse, mse, beta)
@@ -1727,49 +1692,8 @@ int vqhip_debug_proposal_scores(const void *x, int x_dtype, const void *cb, int6
     return VQHIP_OK;
 }
 
-#ifdef VQ_CLOCK_STAMPS
-// diagnostic builds only (not declared in include/vqhip.h): the (delta s_memtime, delta s_memrealtime) pairs the proposal kernel's
-// waves stamped around their stage loop, copied to the HOST buffer out[2 * n], n <= VQ_CLOCK_SLOTS
-int vqhip_debug_clock_stamps(unsigned long long *out_host, int n) {
-    if (!out_host || n <= 0 || n > VQ_CLOCK_SLOTS) return fail(VQHIP_EINVAL, "vqhip_debug_clock_stamps: bad argument");
-    VQ_HIP(hipDeviceSynchronize());
-    VQ_HIP(hipMemcpyFromSymbol(out_host, HIP_SYMBOL(vq_clock_dbg), (size_t)n * 16, 0, hipMemcpyDeviceToHost));
-    return VQHIP_OK;
-}
-#endif
-
-#ifdef VQ_STAGE_STAMPS
-// diagnostic builds only (tools/stage_stamps.py): the per-iteration stamps of the first workgroups of the last coarse_kernel launch
-int vqhip_debug_stage_stamps(unsigned long long *out_host, int wgs) {
-    if (!out_host || wgs <= 0 || wgs > VQ_STAGE_WGS) return fail(VQHIP_EINVAL, "vqhip_debug_stage_stamps: bad argument");
-    VQ_HIP(hipDeviceSynchronize());
-    VQ_HIP(hipMemcpyFromSymbol(out_host, HIP_SYMBOL(vq_stage_dbg), (size_t)wgs * 8 * VQ_STAGE_ITERS * 5 * 8, 0, hipMemcpyDeviceToHost));
-    return VQHIP_OK;
-}
-#endif
-#ifdef VQ_PHASE_STAMPS
-// diagnostic builds only (tools/phase_stamps.py): the per-workgroup phase stamps of the last coarse_kernel launch
-int vqhip_debug_phase_stamps(unsigned long long *out_host, int n) {
-    if (!out_host || n <= 0 || n > VQ_PHASE_SLOTS) return fail(VQHIP_EINVAL, "vqhip_debug_phase_stamps: bad argument");
-    VQ_HIP(hipDeviceSynchronize());
-    VQ_HIP(hipMemcpyFromSymbol(out_host, HIP_SYMBOL(vq_phase_dbg), (size_t)n * 64, 0, hipMemcpyDeviceToHost));
-    return VQHIP_OK;
-}
-#endif
-
 int vqhip_set_tuning(int key, int value) {
     if (key == 2) g_tune_slices = (value == 1 || value == 2 || value == 4 || value == 8 || value == 16) ? value : 0;
-    else if (key == 3) g_tune_gather_grid = value > 0 ? value : 0;
-    else if (key == 4) g_tune_gather_nt = (value == 1 || value == 2) ? value : 0;
-    else if (key == 5) g_tune_filter = value != 0;
-    else if (key == 6) g_tune_fused_decide = (value >= 0 && value <= 2) ? value : 0;
-    else if (key == 8) g_tune_noaux = value != 0;
-    else if (key == 9) g_tune_groups = value != 0;
-    else if (key == 10) g_tune_balance = value != 0;
-    else if (key == 11) g_tune_w32 = value != 0;
-    else if (key == 13) g_tune_map256 = value != 0;
-    else if (key == 15) g_tune_col_direct = value != 0;
-    else if (key == 17) g_tune_xdirect = (value == 0 || value == 1 || value == 2) ? value : 1;       // 2: fp32 rows too (measurement)
     else if (key == 18) g_tune_stream = value != 0;
     else if (key == 12) g_tune_force_exact = value > 0 ? (value < 1024 ? value : 1024) : 0;
     else return fail(VQHIP_EINVAL, "vqhip_set_tuning: unknown key");

@@ -115,9 +115,7 @@ __device__ __forceinline__ void exact_rows_mfma(const void *__restrict__ x, cons
         }
         u64 o = __shfl_xor(best, 32, 64);
         best = o < best ? o : best;
-#ifndef VQ_EXACT_NO_ATOMIC       // (timing-only diagnostic build, tools/micro/exact_rows.hip)
         if (h == 0 && rvalid && best != ~0ull) atomicMin(&keys[row], best);
-#endif
     }
 }
 
@@ -137,7 +135,7 @@ __device__ __forceinline__ void exact_rows_mfma(const void *__restrict__ x, cons
 // (i & 7) ^ j.  Lane l reads piece p of its code l = 8 a + b at slot 64 b + 8 a + (p ^ b): within each of ds_read_b128's four
 // 16-lane groups the 16 slots are distinct mod 16 (conflict-free).  One barrier per block.  Then the epilogue of the MFMA form
 // per (code, row), the wave's smallest key and ONE atomicMin per (wave, row).
-// Where a launch's time goes (tools/micro/exact_rows.hip, 12 rows, K = 16384, D = 256, us after the first workgroup starts,
+// Where a launch's time goes (a stamp build of this kernel, 12 rows, K = 16384, D = 256, us after the first workgroup starts,
 // median over workgroups; profiles/r04_exact_rows_stamps.txt): x tile staged 2.3 (row ids -> x rows: two dependent memory
 // latencies; the e tile lands meanwhile), blocks done 8.3 (one wave per SIMD: 1600 cycles per block for 40 LDS reads and 64
 // v_pk_fma_f32), keys sent 10.0, atomics drained 11.1, last workgroup done 11.6 — 17.7 us by HIP events against 29.1 for the
@@ -185,14 +183,6 @@ __device__ __forceinline__ void exact_few_block(const float4 *__restrict__ et, c
         }
     }
 }
-
-#ifdef VQ_EXACT_STAMPS      // tools/micro/exact_rows.hip: where a workgroup's time goes (100 MHz counter, wave 0)
-__device__ unsigned long long vq_exact_stamps[1024 * 8];
-__device__ unsigned long long vq_exact_cycles[1024 * 8];
-#define VQ_STAMP(i) do { if (threadIdx.x == 0) { vq_exact_stamps[(blockIdx.x & 1023) * 8 + (i)] = wall_clock64(); vq_exact_cycles[(blockIdx.x & 1023) * 8 + (i)] = clock64(); } } while (0)
-#else
-#define VQ_STAMP(i) do {} while (0)
-#endif
 
 __device__ __forceinline__ void wait_vm_pairs(int n) {       // s_waitcnt vmcnt(2 n), n = 0 .. 6 (the count is an immediate)
     switch (n) {
@@ -268,7 +258,6 @@ __device__ __forceinline__ void exact_rows_few(const void *__restrict__ x, const
         // epilogue, the x tile — and behind those requests the e tiles of the first VQ_FEW_RING - 1 blocks; the x tile is
         // written (scaled, widened) while the e tiles are on their way.  Wave w stages rows w, w + 4, w + 8, w + 12, a lane
         // pieces lane, lane + 64, ... (4 x 4 requests cover D <= VQ_FEW_MAX_D).
-        VQ_STAMP(0);
         const int rid_v = row_list[rt * RT + ((lane & 15) < nr ? (lane & 15) : 0)];
         const int64_t k = k0 + lane;
         const float enk = (VQ_IS_L2(metric) && k < K) ? en_in[k] : 0.0f;
@@ -318,14 +307,12 @@ __device__ __forceinline__ void exact_rows_few(const void *__restrict__ x, const
             }
         }
 
-        VQ_STAMP(1);
         vq_f32x2 acc[2] = {vq_f32x2{0.0f, 0.0f}, vq_f32x2{0.0f, 0.0f}};
         for (int b = 0; b < nb; ++b) {
             // block b landed once the DMAs of the blocks requested after it (b + 1 .. b + RING - 2) are all that is pending
             const int after = nb - 1 - b < VQ_FEW_RING - 2 ? nb - 1 - b : VQ_FEW_RING - 2;
             wait_vm_pairs(after);
             __syncthreads();                                       // ... for every wave's part; everybody is done with block b - 1
-            if (b == 0) VQ_STAMP(2);
             if (b + VQ_FEW_RING - 1 < nb) issue_e(b + VQ_FEW_RING - 1);   // into the buffer of block b - 1
             const int np = (D - 32 * b) >= 32 ? 8 : (D - 32 * b) >> 2;
             const float4 *et = ering + (b % VQ_FEW_RING) * 512, *xt = (const float4 *)xtile + (p_lo * npcp + b * 8) * 2;
@@ -337,7 +324,6 @@ __device__ __forceinline__ void exact_rows_few(const void *__restrict__ x, const
                 else if (myn == 1) exact_few_block<1, 7>(et, xt, npcp, eslot, lane & 7, np, acc);
             }
         }
-        VQ_STAMP(3);
         __syncthreads();                                           // the next item refills the ring and the x tile
 
         // keys of the wave's (up to) 4 rows and their wave-wide minima.  A run-time loop on purpose: this code runs once per
@@ -391,13 +377,10 @@ __global__ __launch_bounds__(256) void exact_kernel(const void *__restrict__ x, 
         // complete at the memory side once vmcnt has counted it down — is a property of gfx950's memory system this gfx950-only
         // library relies on, not of the HIP memory model (which would ask for the release fence)
         __shared__ int is_last;
-        VQ_STAMP(4);
         asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
         __syncthreads();
-        VQ_STAMP(5);
         if (threadIdx.x == 0) is_last = (atomicAdd(ticket, 1) == (int)gridDim.x - 1) ? 1 : 0;
         __syncthreads();
-        VQ_STAMP(6);
         if (is_last) {
             for (int64_t i = threadIdx.x; i < nrows; i += blockDim.x) {
                 const int64_t r = (int64_t)row_list[i];
@@ -407,7 +390,6 @@ __global__ __launch_bounds__(256) void exact_kernel(const void *__restrict__ x, 
                 if (fin_hist) atomicAdd(&fin_hist[kk], 1);
             }
         }
-        VQ_STAMP(7);
     }
 }
 

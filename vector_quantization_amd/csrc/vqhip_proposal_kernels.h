@@ -15,7 +15,7 @@ struct VqDecideOut {
     int *arrive;            // one arrival counter per token block of the proposal kernel (zeroed by x_prep_kernel)
     const int *n_dev;       // nullable DEVICE row count: only rows [0, min(N, *n_dev)) are live (vqhip_col_argmin_rows:
                             // the launch is sized for a capacity, the actual number of listed codes stays on the device)
-    // coarse_kernel<..., XD != 0> (the token side made in the proposal prologue, no token image): the rows as the caller holds
+    // coarse_kernel<..., XD = 1> (the token side made in the proposal prologue, no token image): the rows as the caller holds
     // them (row-major, D elements) and where slice 0 writes the per-row statistics x_prep_kernel would have written
     const void *xrows; float *xh2_w, *rho2_w, *xn_w;
 };
@@ -70,38 +70,10 @@ __device__ __forceinline__ int tile_row16(int e, int lane) { return 16 * (e >> 2
 // stream loop; two (256 registers) compile without a spill, and at these sizes there are at most two workgroups per CU to
 // co-schedule anyway: 4096 x 8192 x 32 cosine 0.0705 -> 0.0538 ms per encode, 4096 x 16384 x 8 0.0768 -> 0.0592
 // (profiles/r05_ab_small_d.txt; 12 544 rows: level).
-#ifdef VQ_CLOCK_STAMPS
-#define VQ_CLOCK_SLOTS 16384
-__device__ unsigned long long vq_clock_dbg[2 * VQ_CLOCK_SLOTS];
-#endif
-#ifdef VQ_PHASE_STAMPS
-// diagnostic build only (tools/phase_stamps.py): eight absolute s_memrealtime stamps (100 MHz) per workgroup, taken by its first
-// lane — entry, first stages requested, first barrier passed, stream done, records stored, ticket drawn, end
-#define VQ_PHASE_SLOTS 4096
-__device__ unsigned long long vq_phase_dbg[8 * VQ_PHASE_SLOTS];
-#define VQ_PHASE(i) do { if (threadIdx.x == 0 && blockIdx.x < VQ_PHASE_SLOTS) vq_phase_dbg[8 * blockIdx.x + (i)] = __builtin_amdgcn_s_memrealtime(); } while (0)
-#else
-#define VQ_PHASE(i) do { } while (0)
-#endif
-#ifdef VQ_STAGE_STAMPS
-// diagnostic build only (tools/stage_stamps.py): s_memtime (shader clock) at five points of every iteration of the stage loop, kept in
-// LDS behind the ring and dumped after the loop: [workgroup < 64][wave < 8][iteration < 24][5]
-#define VQ_STAGE_WGS 64
-#define VQ_STAGE_ITERS 24
-__device__ unsigned long long vq_stage_dbg[VQ_STAGE_WGS * 8 * VQ_STAGE_ITERS * 5];
-#define VQ_STAGE_LDS_EXTRA (8 * VQ_STAGE_ITERS * 5 * 8)
-#define VQ_STAMP(k) do { if (lane == 0 && stamp_it < VQ_STAGE_ITERS) stamp_lds[(wave * VQ_STAGE_ITERS + stamp_it) * 5 + (k)] = __builtin_amdgcn_s_memtime(); } while (0)
-#else
-#define VQ_STAGE_LDS_EXTRA 0
-#define VQ_STAMP(k) do { } while (0)
-#endif
-#ifndef VQ_TICKET_NOFENCE
-#define VQ_TICKET_NOFENCE 1
-#endif
 #ifndef VQ_D32_PLAIN_OCC
 #define VQ_D32_PLAIN_OCC 2
 #endif
-// XD != 0 (1: bf16 rows, 2: fp32 rows; D == the padded dimension): the workgroup makes its token fragments itself, from the
+// XD == 1 (bf16 rows; D == the padded dimension): the workgroup makes its token fragments itself, from the
 // row-major latents — fp16 conversion with flush-to-zero, |xh|^2, |x - xh|^2 and the oracle-order |x|^2 exactly as x_prep_body
 // computes them (same fma chains, same folding order: bit-identical statistics) — and slice 0 writes the statistics.  The
 // 268 MB fp16 token image of the headline batch is then neither written nor read: pre_kernel's token side (85 us of HBM time
@@ -113,7 +85,6 @@ __global__ __launch_bounds__(WAVES * 64, (FILTER && NSTEP <= 2) ? (GROUPS ? 4 : 
     float *__restrict__ rec, int64_t Np, const VqCbStats *__restrict__ cbst, const float *__restrict__ xh2,
     const float *__restrict__ rho2, int Dp, int metric, VqDecideOut dec, int pad_stage, int tpb) {
     extern __shared__ __attribute__((aligned(16))) char lds[];
-    VQ_PHASE(0);
     static_assert(NSTEP % 2 == 0, "16x16x32 layout: 32-dim k-steps");
     static_assert(!GROUPS || FILTER, "group records are a form of the filtered epilogue");
     constexpr bool GBRANCH = TT >= VQ_GROUP_BRANCH_MIN_TT;
@@ -170,48 +141,43 @@ __global__ __launch_bounds__(WAVES * 64, (FILTER && NSTEP <= 2) ? (GROUPS ? 4 : 
             for (int s = 0; s < NS32; ++s) xf[t][s] = *(const half8 *)(src + s * VQ_CHUNK_BYTES);
         }
     } else {
-        static_assert(XD == 0 || (!FILTER && !GROUPS && !NOAUX && (NSTEP % 4) == 0), "token side in the prologue: plain D % 64 == 0 forms");
+        static_assert(XD == 1 && !FILTER && !GROUPS && !NOAUX && (NSTEP % 4) == 0, "token side in the prologue: bf16 rows, plain D % 64 == 0 forms");
         const int q4 = lane >> 4, r16 = lane & 15;           // the fragment's own layout: token r16 of the tile, dims 32 s + 8 q4 .. + 8
         constexpr int Dr = NS32 * 32;
         // bf16 rows: a piece of 8 latents is 16 bytes, exactly the fragment's size — ALL the wave's pieces are requested into the
         // fragment registers themselves, then converted in place (one round trip to HBM for the whole prologue, as with the image:
         // a first form loaded into temporaries and hipcc, short of 128 more registers, made 32 round trips of it: +160 us per launch)
-        if constexpr (XD == 1) {
-            // Requested as whole rows — two 512-byte rows per wave-instruction, 1 KiB contiguous — and turned into the fragment
-            // layout through a wave-private LDS tile (16 rows x 528 bytes: the 16-byte pad makes the fragment reads conflict-free)
-            // in the ring's stages 2 and 3, which nothing writes before the first barrier of the stream.  (Requested in the fragment
-            // layout itself a wave-instruction is 16 rows x 64 bytes: twice the requests for the same bytes, +5 us per workgroup.)
-            static_assert(NS32 == 8 && NBUF >= 4 && 2 * STAGE_BYTES >= WAVES * 16 * 528, "row tile: D = 256, staged behind stage 1");
-            char *stg = lds + 2 * STAGE_BYTES + wave * (16 * 528);
-            const int hr = lane >> 5, c32 = lane & 31;
+        // Requested as whole rows — two 512-byte rows per wave-instruction, 1 KiB contiguous — and turned into the fragment
+        // layout through a wave-private LDS tile (16 rows x 528 bytes: the 16-byte pad makes the fragment reads conflict-free)
+        // in the ring's stages 2 and 3, which nothing writes before the first barrier of the stream.  (Requested in the fragment
+        // layout itself a wave-instruction is 16 rows x 64 bytes: twice the requests for the same bytes, +5 us per workgroup.)
+        static_assert(NS32 == 8 && NBUF >= 4 && 2 * STAGE_BYTES >= WAVES * 16 * 528, "row tile: D = 256, staged behind stage 1");
+        char *stg = lds + 2 * STAGE_BYTES + wave * (16 * 528);
+        const int hr = lane >> 5, c32 = lane & 31;
 #pragma unroll
-            for (int t = 0; t < TT; ++t) {
-                const int64_t tok0 = (tb * tpb + wave * TT + t) * 16;
+        for (int t = 0; t < TT; ++t) {
+            const int64_t tok0 = (tb * tpb + wave * TT + t) * 16;
 #pragma unroll
-                for (int i = 0; i < 8; ++i) {
-                    const int64_t tok = tok0 + 2 * i + hr;
-                    const int64_t trow = tok < N ? tok : N - 1;  // rows past the end repeat the last one and are never written
-                    xf[t][i] = *(const half8 *)((const uint16_t *)dec.xrows + trow * Dr + 8 * c32);
-                }
+            for (int i = 0; i < 8; ++i) {
+                const int64_t tok = tok0 + 2 * i + hr;
+                const int64_t trow = tok < N ? tok : N - 1;  // rows past the end repeat the last one and are never written
+                xf[t][i] = *(const half8 *)((const uint16_t *)dec.xrows + trow * Dr + 8 * c32);
             }
-            __builtin_amdgcn_sched_barrier(0);
+        }
+        __builtin_amdgcn_sched_barrier(0);
 #pragma unroll
-            for (int t = 0; t < TT; ++t) {
+        for (int t = 0; t < TT; ++t) {
 #pragma unroll
-                for (int i = 0; i < 8; ++i) *(half8 *)(stg + (2 * i + hr) * 528 + 16 * c32) = xf[t][i];
+            for (int i = 0; i < 8; ++i) *(half8 *)(stg + (2 * i + hr) * 528 + 16 * c32) = xf[t][i];
 #pragma unroll
-                for (int s = 0; s < NS32; ++s) xf[t][s] = *(const half8 *)(stg + r16 * 528 + 64 * s + 16 * q4);
-            }
+            for (int s = 0; s < NS32; ++s) xf[t][s] = *(const half8 *)(stg + r16 * 528 + 64 * s + 16 * q4);
         }
 #pragma unroll
         for (int t = 0; t < TT; ++t) {
             const int64_t tok = (tb * tpb + wave * TT + t) * 16 + r16;
-            const int64_t trow = tok < N ? tok : N - 1;
-            float raw32[XD == 2 ? NS32 : 1][8];              // fp32 rows: one token tile's pieces at a time (a round trip per tile)
-            if constexpr (XD == 2) {
-#pragma unroll
-                for (int s = 0; s < NS32; ++s) load8<0>(dec.xrows, trow * Dr + 32 * s + 8 * q4, raw32[s]);
-            }
+            // (unused since the fp32-row form left; kept because hipcc schedules and allocates this kernel differently without it:
+            //  the device code stays the measured one)
+            [[maybe_unused]] const int64_t trow = tok < N ? tok : N - 1;
             // x_prep_body's thread g = 4 (s & 1) + q4 owns the pieces of this lane with that parity: two running sums each.
             // The statistics are slice 0's business alone (wave-uniform branch): the other slices only convert.
             const bool stats = sl == 0;
@@ -222,27 +188,22 @@ __global__ __launch_bounds__(WAVES * 64, (FILTER && NSTEP <= 2) ? (GROUPS ? 4 : 
             for (int s = 0; s < NS32; ++s) {
                 float v[8];
                 half8 f;
-                if constexpr (XD == 1) {
-                    // bf16 -> fp16 two at a time (v_cvt_pk_f16_f32).  A bf16 value below 2^-14 converts to an fp16 subnormal or
-                    // zero and never rounds up to 2^-14 (8 significant bits against 11), so flushing the INPUT where |v| < 2^-14
-                    // is to_f16_ftz's flush of the result; everything else converts as (_Float16)v does (RNE, overflow to inf)
-                    typedef uint32_t u32x4 __attribute__((ext_vector_type(4)));
-                    typedef _Float16 half2v __attribute__((ext_vector_type(2)));
-                    typedef float float2v __attribute__((ext_vector_type(2)));
-                    const u32x4 bits = __builtin_bit_cast(u32x4, xf[t][s]);
+                // bf16 -> fp16 two at a time (v_cvt_pk_f16_f32).  A bf16 value below 2^-14 converts to an fp16 subnormal or
+                // zero and never rounds up to 2^-14 (8 significant bits against 11), so flushing the INPUT where |v| < 2^-14
+                // is to_f16_ftz's flush of the result; everything else converts as (_Float16)v does (RNE, overflow to inf)
+                typedef uint32_t u32x4 __attribute__((ext_vector_type(4)));
+                typedef _Float16 half2v __attribute__((ext_vector_type(2)));
+                typedef float float2v __attribute__((ext_vector_type(2)));
+                const u32x4 bits = __builtin_bit_cast(u32x4, xf[t][s]);
 #pragma unroll
-                    for (int j = 0; j < 4; ++j) {
-                        const uint32_t lo = bits[j] << 16, hi = bits[j] & 0xFFFF0000u;
-                        v[2 * j] = __uint_as_float(lo); v[2 * j + 1] = __uint_as_float(hi);
-                        float2v c;
-                        c[0] = (lo & 0x7FFFFFFFu) < 0x38800000u ? 0.0f : v[2 * j];
-                        c[1] = (hi & 0x7FFFFFFFu) < 0x38800000u ? 0.0f : v[2 * j + 1];
-                        const half2v h = __builtin_convertvector(c, half2v);
-                        f[2 * j] = h[0]; f[2 * j + 1] = h[1];
-                    }
-                } else {
-#pragma unroll
-                    for (int j = 0; j < 8; ++j) { v[j] = raw32[s][j]; f[j] = to_f16_ftz(v[j]); }
+                for (int j = 0; j < 4; ++j) {
+                    const uint32_t lo = bits[j] << 16, hi = bits[j] & 0xFFFF0000u;
+                    v[2 * j] = __uint_as_float(lo); v[2 * j + 1] = __uint_as_float(hi);
+                    float2v c;
+                    c[0] = (lo & 0x7FFFFFFFu) < 0x38800000u ? 0.0f : v[2 * j];
+                    c[1] = (hi & 0x7FFFFFFFu) < 0x38800000u ? 0.0f : v[2 * j + 1];
+                    const half2v h = __builtin_convertvector(c, half2v);
+                    f[2 * j] = h[0]; f[2 * j + 1] = h[1];
                 }
                 if (stats) {
 #pragma unroll
@@ -329,9 +290,7 @@ __global__ __launch_bounds__(WAVES * 64, (FILTER && NSTEP <= 2) ? (GROUPS ? 4 : 
     const int lag = (NBUF >= 4 && wave >= WAVES / 2 && st1 - st0 >= VQ_LAG_MIN_STAGES) ? 1 : 0;
     if (st0 < st1) issue_stage(st0, 0);
     if (AHEAD >= 2 && st0 + 1 < st1) issue_stage(st0 + 1, 1);
-    VQ_PHASE(1);
     vq_dma_barrier();  // drains the LDS-DMA (vmcnt(0)) and makes it visible to every wave
-    VQ_PHASE(2);
 
     f32x4 accA[2][TT], accB[2][TT];
 #pragma unroll
@@ -346,24 +305,8 @@ __global__ __launch_bounds__(WAVES * 64, (FILTER && NSTEP <= 2) ? (GROUPS ? 4 : 
         for (int t = 0; t < TT; ++t) accA[1][t] = f32x4{-3.0e38f, -3.0e38f, -3.0e38f, -3.0e38f};
     }
 
-#ifdef VQ_CLOCK_STAMPS
-    // diagnostic build only (tools/inkernel_clock.py; MI355X guide, DVFS item 6): the shader clock this wave's stage loop ran at =
-    // delta s_memtime / delta s_memrealtime x 100 MHz.  The stamps go to a buffer of their own that nothing else reads.
-    const unsigned long long clk_t0 = __builtin_amdgcn_s_memtime(), clk_r0 = __builtin_amdgcn_s_memrealtime();
-#endif
-#ifdef VQ_STAGE_STAMPS
-    unsigned long long *stamp_lds = (unsigned long long *)(lds + NBUF * STAGE_BYTES);
-    for (int i = threadIdx.x; i < 8 * VQ_STAGE_ITERS * 5; i += WAVES * 64) stamp_lds[i] = 0;
-#endif
     for (int64_t it = st0; it < st1 + ((NBUF >= 4 && st1 - st0 >= VQ_LAG_MIN_STAGES) ? 1 : 0); ++it) {
-#ifdef VQ_STAGE_STAMPS
-        const int stamp_it = (int)(it - st0);
-#endif
-        VQ_STAMP(0);
-#ifndef VQ_EXP_NO_DMA            // (timing-only diagnostic build: the ring is never refilled inside the loop)
         if (it + AHEAD < st1) issue_stage(it + AHEAD, (int)((it + AHEAD - st0) % NBUF));
-#endif
-        VQ_STAMP(1);
         const int64_t st = it - lag;
         if (st < st0 || st >= st1 || !wave_active) { vq_dma_barrier(); continue; }
         const int buf = (int)((st - st0) % NBUF);
@@ -455,12 +398,8 @@ __global__ __launch_bounds__(WAVES * 64, (FILTER && NSTEP <= 2) ? (GROUPS ? 4 : 
             }
 #pragma unroll
             for (int ch = 0; ch < NSTEP; ++ch) {
-#ifdef VQ_EXP_NO_LDS_READS      // timing-only diagnostic build: the A fragment of every chunk is the register set loaded first (opaque to the compiler)
-                if (ch + PF < NSTEP) { af[(ch + PF) % RING] = af[0]; asm volatile("" : "+v"(af[(ch + PF) % RING])); }
-#else
                 if (ch + PF < NSTEP || (STAGE_PF && ti + 1 < TPS))
                     af[(g0 + ch + PF) % RING] = *(const half8 *)(base + (ti * NSTEP + ch + PF) * VQ_CHUNK_BYTES + lane * 16);
-#endif
 #pragma unroll
                 for (int t = 0; t < TT; ++t) {
                     if constexpr (!WITH_AUX) {
@@ -509,15 +448,7 @@ __global__ __launch_bounds__(WAVES * 64, (FILTER && NSTEP <= 2) ? (GROUPS ? 4 : 
                 }
                 // retire NE*TT/NSTEP accumulator elements of the previous tile per chunk step
                 constexpr int TOTAL = NE * TT;
-#ifdef VQ_EXP_NO_EPILOGUE       // timing-only diagnostic build: the scores are never looked at.  Every accumulator of the previous tile is
-                constexpr bool RETIRE = false;      // named as an asm input once per tile, so that not one MFMA is dead code (a first form that
-                if (ch == 0) {                      // read ONE element per chunk let hipcc drop a quarter of the MFMAs: 96 of 128 per stage)
-#pragma unroll
-                    for (int u = 0; u < TT; ++u) asm volatile("" :: "v"(prv[0][u]), "v"(prv[1][u]));
-                }
-#else
                 constexpr bool RETIRE = PIPE && !FILTER;
-#endif
 #pragma unroll
                 for (int i = 0; RETIRE && i < (TOTAL + NSTEP - 1) / NSTEP; ++i) {
                     constexpr int EVERY = (NSTEP / TOTAL) > 0 ? NSTEP / TOTAL : 1;   // TOTAL < NSTEP: one element every EVERY chunks
@@ -553,15 +484,11 @@ __global__ __launch_bounds__(WAVES * 64, (FILTER && NSTEP <= 2) ? (GROUPS ? 4 : 
         }
         }
       };   // run_stage
-#ifdef VQ_EXP_NO_COMPUTE         // timing-only diagnostic build: the ring, its requests and the barriers alone
-        asm volatile("" :: "v"(xf[0][0]));
-#else
         if constexpr (NOAUX) {
             if (st == (int64_t)pad_stage) run_stage(std::true_type{}); else run_stage(std::false_type{});
         } else {
             run_stage(std::true_type{});
         }
-#endif
         if constexpr (FILTER && (!GROUPS || GBRANCH)) {   // refresh the skip thresholds: best score among the token's four lanes, less the margin
 #pragma unroll
             for (int t = 0; t < TT; ++t) th[t] = quad_rows_max(b1[t]) - mg[t];
@@ -569,35 +496,8 @@ __global__ __launch_bounds__(WAVES * 64, (FILTER && NSTEP <= 2) ? (GROUPS ? 4 : 
         // next stage landed (vmcnt(0)) and everybody is done reading this one.  (A barrier that keeps the pieces of the
         // stage requested in this iteration in flight — s_waitcnt vmcnt(pieces) instead of 0 — was measured: 1-3 %
         // slower at D <= 128 and 2x slower at D = 256, profiles/r02_ring_partial_wait.txt; the full drain stays.)
-#ifdef VQ_STAGE_STAMPS
-        VQ_STAMP(2);
-        asm volatile("s_waitcnt vmcnt(0) lgkmcnt(0)" ::: "memory");
-        VQ_STAMP(3);
-        __syncthreads();
-        VQ_STAMP(4);
-#elif defined(VQ_EXP_NO_BARRIER)    // timing-only diagnostic build
-        asm volatile("" ::: "memory");
-#else
         vq_dma_barrier();
-#endif
     }
-#ifdef VQ_STAGE_STAMPS
-    __syncthreads();
-    if (blockIdx.x < VQ_STAGE_WGS)
-        for (int i = threadIdx.x; i < 8 * VQ_STAGE_ITERS * 5; i += WAVES * 64) vq_stage_dbg[(size_t)blockIdx.x * 8 * VQ_STAGE_ITERS * 5 + i] = stamp_lds[i];
-    __syncthreads();
-#endif
-#ifdef VQ_CLOCK_STAMPS
-    {
-        const unsigned long long clk_t1 = __builtin_amdgcn_s_memtime(), clk_r1 = __builtin_amdgcn_s_memrealtime();
-        if (lane == 0 && wave_active) {
-            const unsigned slot = ((unsigned)blockIdx.x * WAVES + (unsigned)wave) & (VQ_CLOCK_SLOTS - 1);
-            vq_clock_dbg[2 * slot] = clk_t1 - clk_t0;
-            vq_clock_dbg[2 * slot + 1] = clk_r1 - clk_r0;
-        }
-    }
-#endif
-    VQ_PHASE(3);
     if (PIPE_H && st1 > st0) {   // drain: second half of the last tile
 #pragma unroll
         for (int t = 0; t < TT; ++t) {
@@ -724,7 +624,7 @@ __global__ __launch_bounds__(WAVES * 64, (FILTER && NSTEP <= 2) ? (GROUPS ? 4 : 
         const int64_t tokn = (tb * tpb + wave * TT + t) * 16 + (lane & 15);
         if (lane < 16 && tokn < N && wave * TT + t < tpb) {
             float *rp = rec + (int64_t)sl * VQ_REC_FIELDS * Np + tokn;
-            if (VQ_TICKET_NOFENCE && dec.idx != nullptr && nslices > 1) {
+            if (dec.idx != nullptr && nslices > 1) {
                 // read by ANOTHER workgroup of this launch (the one that draws the block's last ticket): agent-scope stores, which go
                 // past this XCD's L2 on their own — no write-back of the whole L2 (the release fence) in front of the ticket
                 __hip_atomic_store(rp, r.v1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
@@ -747,27 +647,17 @@ __global__ __launch_bounds__(WAVES * 64, (FILTER && NSTEP <= 2) ? (GROUPS ? 4 : 
         int *flags = (int *)lds;                         // the stage ring is free now (first barrier below)
         asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
         __syncthreads();
-        VQ_PHASE(4);
         if (threadIdx.x == 0) {
             int last = 1;
             if (nslices > 1) {
                 // (every wave drained its record stores before the barrier above; the records are read back with agent-scope loads)
-                if (!VQ_TICKET_NOFENCE) { __builtin_amdgcn_fence(__ATOMIC_RELEASE, "agent"); asm volatile("s_waitcnt vmcnt(0)" ::: "memory"); }
                 last = (atomicAdd(&dec.arrive[tb], 1) == nslices - 1) ? 1 : 0;
-                if (last && !VQ_TICKET_NOFENCE) {
-                    __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "agent");
-                    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-                }
             }
             flags[0] = last;
         }
         __syncthreads();
         const bool last = flags[0] != 0;
         __syncthreads();                                 // everybody has read the flag before the LDS words are reused
-        VQ_PHASE(5);
-#ifdef VQ_PHASE_STAMPS
-        if (threadIdx.x == 0 && blockIdx.x < VQ_PHASE_SLOTS) vq_phase_dbg[8 * blockIdx.x + 7] = last ? 1 : 0;
-#endif
         if (last) {
             int *wcount = (int *)lds, *wbase = wcount + 3 * 16;
             int64_t n = tb * (int64_t)(tpb * 16) + threadIdx.x;      // tpb*16 <= BM <= WAVES*64 threads: one token per thread
@@ -776,6 +666,5 @@ __global__ __launch_bounds__(WAVES * 64, (FILTER && NSTEP <= 2) ? (GROUPS ? 4 : 
             decide_rows<true>(n, oob, cbst, Dp, metric, nslices, rec, xh2, rho2, Np, dec, wcount, wbase);
         }
     }
-    VQ_PHASE(6);
   }
 }

@@ -247,8 +247,8 @@ __global__ void refine_decide_kernel(const char *cb, VqCbLayout L, int64_t N, in
 // codebook stages arrive by LDS-DMA through the same ring and are shared by the 8 waves — as a persistent grid over
 // (block of WAVES*TT*16 queued rows, slice of stages) items, the slice count chosen on the device from the queue
 // length so that every workgroup gets an item.
-// XD != 0 (1: bf16 rows, 2: fp32 rows): there is no token image (coarse_kernel<..., XD>) — the queued rows' fragments come from
-// the row-major latents `xrows` (D == the padded dimension): 4 or 8 whole cache lines per row instead of 32 pieces in 32 lines,
+// XD == 1 (bf16 rows): there is no token image (coarse_kernel<..., XD>) — the queued rows' fragments come from
+// the row-major latents `xrows` (D == the padded dimension): 4 whole cache lines per row instead of 32 pieces in 32 lines,
 // converted as the prologue of the proposal kernel converts them (the same fp16 values: the scores stay bitwise the stream's)
 template <int NSTEP, int TT, int WAVES, int TPS, int NBUF = 2, int XD = 0>
 __global__ __launch_bounds__(WAVES * 64) void rescan_kernel(const char *__restrict__ ximg, const char *__restrict__ frag,
@@ -314,7 +314,7 @@ __global__ __launch_bounds__(WAVES * 64) void rescan_kernel(const char *__restri
 #pragma unroll
                 for (int s = 0; s < NS32; ++s) {
                     float v[8];
-                    load8<(XD == 1 ? 1 : 0)>(xrows, tk * (int64_t)(NS32 * 32) + 32 * s + 8 * (lane >> 4), v);
+                    load8<1>(xrows, tk * (int64_t)(NS32 * 32) + 32 * s + 8 * (lane >> 4), v);
                     half8 f;
 #pragma unroll
                     for (int j = 0; j < 8; ++j) f[j] = to_f16_ftz(v[j]);

@@ -207,10 +207,7 @@ __global__ __launch_bounds__(256, 2) void exact_stream_kernel(const void *__rest
         // the next stage's code tiles — and at a block's first stage the next block's rows — are requested
         auto stage_top = [&](int db, int cs) {
             const bool lastb = db + 1 == nb;
-#ifndef VQ_XS_NO_BAR         // (timing-only diagnostic builds: VQ_XS_NO_BAR / _NO_DMA / _NO_EPI / _NO_ATOMIC)
             vq_dma_barrier();    // (the drain written out: __syncthreads() alone does not promise it — vqhip_kernels.h)
-#endif
-#ifndef VQ_XS_NO_DMA
             if (cs + 1 < NS) issue_e(kbase, cs + 1, db, eb ^ 1);
             else if (!lastb) issue_e(kbase, 0, db + 1, eb ^ 1);
             else if (has_next) issue_e(kbase2, 0, 0, eb ^ 1);
@@ -219,10 +216,6 @@ __global__ __launch_bounds__(256, 2) void exact_stream_kernel(const void *__rest
                 if (!lastb) issue_x(rb, db + 1, xb ^ 1);
                 else if (has_next) issue_x(rb2, 0, xb ^ 1);
             }
-#endif
-#ifdef VQ_XS_SYNC_DMA       // (diagnostic: nothing in flight while a stage computes)
-            __syncthreads();
-#endif
         };
         for (int db = 0; db < nbf; ++db) {
 #pragma unroll
@@ -243,17 +236,6 @@ __global__ __launch_bounds__(256, 2) void exact_stream_kernel(const void *__rest
             xb ^= 1;
         }
 
-#ifdef VQ_XS_NO_EPI
-        {
-            float sacc = 0.0f;
-#pragma unroll
-            for (int c = 0; c < CT; ++c)
-#pragma unroll
-                for (int q = 0; q < 16; q += 4) sacc += acc[c][q];
-            if (sacc == 123.456f) keys[row] = 0;
-            continue;
-        }
-#endif
         // ---- epilogue (tiled_epilogue, vqhip_exact_kernels.h: shared with the register form) ----
         // (distances leave through the wave's own 32 rows of the row block just consumed: the other one receives the next item's)
         const u64 best = tiled_epilogue<MODE, (MODE == 2 ? (DT ? 16 : 32) : 0)>(acc, en_lds, xn, kbase, K, metric, h, j, rvalid, row, keys, dout,
@@ -263,9 +245,7 @@ __global__ __launch_bounds__(256, 2) void exact_stream_kernel(const void *__rest
             if (!has_next || rb2 != rb) {                            // last chunk of the row block in this span (wave-uniform)
                 u64 o = __shfl_xor(run_best, 32, 64);
                 run_best = o < run_best ? o : run_best;
-#ifndef VQ_XS_NO_ATOMIC
                 if (h == 0 && rvalid && run_best != ~0ull) atomicMin(&keys[row], run_best);
-#endif
                 run_best = ~0ull;
             }
         }
