@@ -179,6 +179,46 @@ int vqhip_gather_ste_map(const void *x_rows, int x_dtype, const float *e, const 
 /* hist[K] int32 += bincount(idx) (utils.py:42; runners/metrics.py:40-44) */
 int vqhip_hist(const int64_t *idx, int64_t N, int64_t K, int32_t *hist, void *stream);
 
+/* vqhip_hist for int32 tokens (FiniteScalarQuantizer's, vq/algorithms/fsq/quantizers.py:61-64): the same rule, only
+ * 0 <= idx < K is counted. */
+int vqhip_hist_i32(const int32_t *idx, int64_t N, int64_t K, int32_t *hist, void *stream);
+
+/* ---- FiniteScalarQuantizer (vq/algorithms/fsq/quantizers.py:74-150) ------------------------------------------------------
+ * Element-wise, one launch per call.  The per-channel constants are computed by the caller with the reference's own torch
+ * expressions (M = (L - 1) * (1 - eps), shift = atanh(((L - 1) % 2) / M), both fp32) and never recomputed on the device; the
+ * library derives the integers odd = (L - 1) % 2, h = L // 2 and cumprod from `levels`.
+ *   encode   t = (tanh(x + shift) * M - odd) / 2;  r = round-half-even(t);  z = (t + (r - t)) / h                (fp32)
+ *            quant = int32(sum_i (r_i + h_i) * cumprod_i)  (fp32 sum of exact integers; a NaN latent gives INT32_MIN)
+ *   backward grad_x = (((g / h) / 2) * M) * (1 - y * y),  y = tanh(x + shift), cast to x's dtype (round to nearest even)
+ *   decode   z = ((quant // cumprod) % L) / h - 1  for any int32 / int64 token (floor division, non-negative remainder)
+ * Layouts: VQHIP_LAYOUT_ROWS = token-major [N, C]; VQHIP_LAYOUT_MAP = the NCHW-contiguous map [B, C, HW] with N = B * HW.
+ * LIMITS (VQHIP_EINVAL, checked before any HIP call): 1 <= C <= 16, every level >= 3 (2 makes atanh's argument > 1, the
+ * reference's NaN), prod(levels) <= 2^24 (the fp32 digit sum stays exact), 0 <= N < 2^31, for the map HW >= 1 and N % HW == 0. */
+#define VQHIP_FSQ_MAX_C 16
+#define VQHIP_LAYOUT_ROWS 0
+#define VQHIP_LAYOUT_MAP 1
+#define VQHIP_DTYPE_I32 2     /* token dtypes of vqhip_fsq_decode */
+#define VQHIP_DTYPE_I64 3
+
+typedef struct {
+    int64_t struct_bytes;                 /* sizeof(vqhip_fsq_t) */
+    int32_t C;                            /* channels = number of levels */
+    int32_t levels[VQHIP_FSQ_MAX_C];      /* L_i (num_scalars_per_channel) */
+    float shift[VQHIP_FSQ_MAX_C];         /* atanh(odd_i / M_i) */
+    float scale[VQHIP_FSQ_MAX_C];         /* M_i */
+} vqhip_fsq_t;
+
+/* quant int32 [N] (required); z fp32 (nullable) in x's layout — or token-major [N, C] when z_rows != 0; x_rows (nullable, MAP
+ * only) = the token-major copy of x in x's dtype; hist int32 [prod(levels)] (nullable) += the tokens (not zeroed here). */
+int vqhip_fsq_encode(const vqhip_fsq_t *q, const void *x, int x_dtype, int layout, int64_t N, int64_t HW, int32_t *quant,
+                     float *z, int z_rows, void *x_rows, int32_t *hist, void *stream);
+/* grad_x (x's dtype and layout) of the encode's z from g = dL/dz (fp32, x's layout) */
+int vqhip_fsq_backward(const vqhip_fsq_t *q, const void *x, int x_dtype, int layout, int64_t N, int64_t HW, const float *g,
+                       void *grad_x, void *stream);
+/* z fp32 [N, C] (ROWS) or [B, C, HW] (MAP) of tokens quant (quant_dtype VQHIP_DTYPE_I32 or VQHIP_DTYPE_I64) */
+int vqhip_fsq_decode(const vqhip_fsq_t *q, const void *quant, int quant_dtype, int layout, int64_t N, int64_t HW, float *z,
+                     void *stream);
+
 /* dst[idx[n], :] += src[n, :]  (centroids.scatter_add_, vqkd/quantizers/callbacks.py:60-62; also the
  * dense embedding backward).  fp32 atomics. */
 int vqhip_scatter_add_rows(const float *src, const int64_t *idx, int64_t N, int64_t K, int D, float *dst,

@@ -15,6 +15,9 @@ LIB_PATH = os.environ.get('VQHIP_LIB') or os.path.join(_HERE, 'libvqhip.so')   #
 ABI_VERSION = 600          # VQHIP_VERSION of include/vqhip.h this binding was written against
 METRIC_L2, METRIC_COS, METRIC_COS_BF16 = 0, 1, 5
 DTYPE_F32, DTYPE_BF16 = 0, 1
+DTYPE_I32, DTYPE_I64 = 2, 3                # token dtypes of vqhip_fsq_decode
+LAYOUT_ROWS, LAYOUT_MAP = 0, 1             # [N, C] token-major / NCHW-contiguous map [B, C, H*W]
+FSQ_MAX_C = 16
 
 _vp, _i64, _i32, _f32 = ctypes.c_void_p, ctypes.c_int64, ctypes.c_int, ctypes.c_float
 
@@ -61,6 +64,12 @@ class VqForwardArgs(ctypes.Structure):
                 ('ws', _vp), ('ws_bytes', _i64)]
 
 
+class FsqConstants(ctypes.Structure):
+    """vqhip_fsq_t of include/vqhip.h, field for field."""
+    _fields_ = [('struct_bytes', _i64), ('C', _i32), ('levels', _i32 * FSQ_MAX_C),
+                ('shift', _f32 * FSQ_MAX_C), ('scale', _f32 * FSQ_MAX_C)]
+
+
 STEP_BEFORE_EXCHANGE, STEP_AFTER_EXCHANGE, STEP_ALL, STEP_PACK_SYNC = 1, 2, 3, 4
 
 # name -> (restype, argtypes); mirrors include/vqhip.h one to one
@@ -85,6 +94,10 @@ SIGNATURES = {
     'vqhip_gather_ste_loss': (_i32, [_vp, _i32, _vp, _vp, _i64, _i32, _vp, _vp, _vp, _vp]),
     'vqhip_gather_ste_mse': (_i32, [_vp, _i32, _vp, _vp, _i64, _i32, _vp, _vp, _vp, _f32, _vp, _vp]),
     'vqhip_hist': (_i32, [_vp, _i64, _i64, _vp, _vp]),
+    'vqhip_hist_i32': (_i32, [_vp, _i64, _i64, _vp, _vp]),
+    'vqhip_fsq_encode': (_i32, [ctypes.POINTER(FsqConstants), _vp, _i32, _i32, _i64, _i64, _vp, _vp, _i32, _vp, _vp, _vp]),
+    'vqhip_fsq_backward': (_i32, [ctypes.POINTER(FsqConstants), _vp, _i32, _i32, _i64, _i64, _vp, _vp, _vp]),
+    'vqhip_fsq_decode': (_i32, [ctypes.POINTER(FsqConstants), _vp, _i32, _i32, _i64, _i64, _vp, _vp]),
     'vqhip_scatter_add_rows': (_i32, [_vp, _vp, _i64, _i64, _i32, _vp, _vp]),
     'vqhip_vqkd_update': (_i32, [_vp, _vp, _vp, _i64, _i32, _f32, _i32, _vp]),
     'vqhip_cvq_update': (_i32, [_vp, _vp, _vp, _i64, _vp, _vp, _i64, _i32, _f32, _f32, _i32, _vp]),

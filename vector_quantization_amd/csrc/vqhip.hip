@@ -6,6 +6,7 @@
 #include <string.h>
 
 #include "vqhip_kernels.h"
+#include "vqhip_fsq_kernels.h"
 
 static thread_local char g_err[256] = "";
 
@@ -1078,6 +1079,125 @@ int vqhip_hist(const int64_t *idx, int64_t N, int64_t K, int32_t *hist, void *st
         hist_kernel<<<grid, 256, 0, (hipStream_t)stream>>>(idx, N, K, hist);
     }
     VQ_CHECK_LAUNCH("hist_kernel");
+    return VQHIP_OK;
+}
+
+int vqhip_hist_i32(const int32_t *idx, int64_t N, int64_t K, int32_t *hist, void *stream) {
+    if (!idx || !hist || N < 0 || K <= 0) return fail(VQHIP_EINVAL, "vqhip_hist_i32: bad argument");
+    if (N == 0) return VQHIP_OK;
+    if (K <= 32768 && N >= 16384) {
+        static LdsCache lds_set;
+        if (int rc = ensure_dyn_lds((const void *)hist_i32_lds_kernel, (size_t)K * 4, lds_set)) return rc;
+        int grid = (int)((N + 2047) / 2048); grid = grid > 256 ? 256 : grid;
+        hist_i32_lds_kernel<<<grid, 1024, (size_t)K * 4, (hipStream_t)stream>>>(idx, N, (int)K, hist);
+    } else {
+        int grid = (int)((N + 255) / 256); grid = grid > 2048 ? 2048 : grid;
+        hist_i32_kernel<<<grid, 256, 0, (hipStream_t)stream>>>(idx, N, K, hist);
+    }
+    VQ_CHECK_LAUNCH("hist_i32_kernel");
+    return VQHIP_OK;
+}
+
+// ---- FiniteScalarQuantizer ----------------------------------------------------------------------------------------------
+// Validates the caller's constants and the shape, and turns them into the kernels' by-value argument.  Every refusal names
+// the entry point (`what`).
+static int fsq_setup(const char *what, const vqhip_fsq_t *q, int layout, int64_t N, int64_t HW, VqFsqConsts *k, int *grid) {
+    char msg[160];
+    if (!q) return fail(VQHIP_EINVAL, what, "null constants");
+    if (q->struct_bytes != (int64_t)sizeof(vqhip_fsq_t)) return fail(VQHIP_EINVAL, what, "struct_bytes != sizeof(vqhip_fsq_t)");
+    if (q->C < 1 || q->C > VQHIP_FSQ_MAX_C) {
+        snprintf(msg, sizeof(msg), "C = %d outside 1..%d", q->C, VQHIP_FSQ_MAX_C);
+        return fail(VQHIP_EINVAL, what, msg);
+    }
+    if (layout != VQHIP_LAYOUT_ROWS && layout != VQHIP_LAYOUT_MAP) return fail(VQHIP_EINVAL, what, "unknown layout");
+    if (N < 0 || N >= (1ll << 31)) return fail(VQHIP_EINVAL, what, "N outside 0 .. 2^31 - 1");
+    if (layout == VQHIP_LAYOUT_MAP && (HW < 1 || HW >= (1ll << 31) || N % HW != 0))
+        return fail(VQHIP_EINVAL, what, "the map needs HW >= 1 and N % HW == 0");
+    memset(k, 0, sizeof(*k));
+    k->C = q->C;
+    int64_t cum = 1;
+    for (int i = 0; i < q->C; ++i) {
+        const int L = q->levels[i];
+        if (L < 3) {
+            snprintf(msg, sizeof(msg), "level %d of channel %d < 3 (2 gives NaN, 1 divides by zero)", L, i);
+            return fail(VQHIP_EINVAL, what, msg);
+        }
+        if (cum * L > (1ll << 24)) return fail(VQHIP_EINVAL, what, "prod(levels) > 2^24 (the fp32 digit sum would not be exact)");
+        k->level[i] = L;
+        k->cum[i] = (int)cum;
+        k->cumf[i] = (float)cum;
+        k->half[i] = (float)(L / 2);
+        k->rhalf[i] = ((L / 2) & (L / 2 - 1)) == 0 ? 1.0f / (float)(L / 2) : 0.f;
+        k->odd[i] = (float)((L - 1) % 2);
+        k->shift[i] = q->shift[i];
+        k->scale[i] = q->scale[i];
+        cum *= L;
+    }
+    k->K = (int)cum;
+    *grid = (int)((N + VQ_FSQ_TILE - 1) / VQ_FSQ_TILE);
+    return VQHIP_OK;
+}
+
+static inline int fsq_aligned(const void *p, int flag) { return ((uintptr_t)p % 16 == 0) ? flag : 0; }
+
+int vqhip_fsq_encode(const vqhip_fsq_t *q, const void *x, int x_dtype, int layout, int64_t N, int64_t HW, int32_t *quant,
+                     float *z, int z_rows, void *x_rows, int32_t *hist, void *stream) {
+    const char *what = "vqhip_fsq_encode";
+    VqFsqConsts k;
+    int grid = 0;
+    if (int rc = fsq_setup(what, q, layout, N, HW, &k, &grid)) return rc;
+    if (!x || !quant) return fail(VQHIP_EINVAL, what, "x and quant are required");
+    if (x_dtype != VQHIP_DTYPE_F32 && x_dtype != VQHIP_DTYPE_BF16) return fail(VQHIP_EINVAL, what, "x_dtype");
+    if (x_rows && layout != VQHIP_LAYOUT_MAP) return fail(VQHIP_EINVAL, what, "x_rows is a by-product of the map layout");
+    if (N == 0) return VQHIP_OK;
+    const int vec = fsq_aligned(x, VQ_FSQ_VEC_X) | fsq_aligned(z, VQ_FSQ_VEC_Z) | fsq_aligned(x_rows, VQ_FSQ_VEC_ROWS);
+    hipStream_t s = (hipStream_t)stream;
+    const int n = (int)N, hw = (int)(layout == VQHIP_LAYOUT_MAP ? HW : 0);
+#define VQ_FSQ_ENC(DT, MAP) fsq_encode_kernel<DT, MAP><<<grid, VQ_FSQ_TILE, 0, s>>>(k, x, n, hw, quant, z, z_rows, x_rows, hist, vec)
+    if (layout == VQHIP_LAYOUT_ROWS) { if (x_dtype == VQHIP_DTYPE_F32) VQ_FSQ_ENC(0, false); else VQ_FSQ_ENC(1, false); }
+    else { if (x_dtype == VQHIP_DTYPE_F32) VQ_FSQ_ENC(0, true); else VQ_FSQ_ENC(1, true); }
+#undef VQ_FSQ_ENC
+    VQ_CHECK_LAUNCH("fsq_encode_kernel");
+    return VQHIP_OK;
+}
+
+int vqhip_fsq_backward(const vqhip_fsq_t *q, const void *x, int x_dtype, int layout, int64_t N, int64_t HW, const float *g,
+                       void *grad_x, void *stream) {
+    const char *what = "vqhip_fsq_backward";
+    VqFsqConsts k;
+    int grid = 0;
+    if (int rc = fsq_setup(what, q, layout, N, HW, &k, &grid)) return rc;
+    if (!x || !g || !grad_x) return fail(VQHIP_EINVAL, what, "x, g and grad_x are required");
+    if (x_dtype != VQHIP_DTYPE_F32 && x_dtype != VQHIP_DTYPE_BF16) return fail(VQHIP_EINVAL, what, "x_dtype");
+    if (N == 0) return VQHIP_OK;
+    const int vec = fsq_aligned(x, VQ_FSQ_VEC_X) | fsq_aligned(grad_x, VQ_FSQ_VEC_Z) | fsq_aligned(g, VQ_FSQ_VEC_G);
+    hipStream_t s = (hipStream_t)stream;
+    const int n = (int)N, hw = (int)(layout == VQHIP_LAYOUT_MAP ? HW : 0);
+#define VQ_FSQ_BWD(DT, MAP) fsq_backward_kernel<DT, MAP><<<grid, VQ_FSQ_TILE, 0, s>>>(k, x, g, n, hw, grad_x, vec)
+    if (layout == VQHIP_LAYOUT_ROWS) { if (x_dtype == VQHIP_DTYPE_F32) VQ_FSQ_BWD(0, false); else VQ_FSQ_BWD(1, false); }
+    else { if (x_dtype == VQHIP_DTYPE_F32) VQ_FSQ_BWD(0, true); else VQ_FSQ_BWD(1, true); }
+#undef VQ_FSQ_BWD
+    VQ_CHECK_LAUNCH("fsq_backward_kernel");
+    return VQHIP_OK;
+}
+
+int vqhip_fsq_decode(const vqhip_fsq_t *q, const void *quant, int quant_dtype, int layout, int64_t N, int64_t HW, float *z,
+                     void *stream) {
+    const char *what = "vqhip_fsq_decode";
+    VqFsqConsts k;
+    int grid = 0;
+    if (int rc = fsq_setup(what, q, layout, N, HW, &k, &grid)) return rc;
+    if (!quant || !z) return fail(VQHIP_EINVAL, what, "quant and z are required");
+    if (quant_dtype != VQHIP_DTYPE_I32 && quant_dtype != VQHIP_DTYPE_I64) return fail(VQHIP_EINVAL, what, "quant_dtype");
+    if (N == 0) return VQHIP_OK;
+    const int vec = fsq_aligned(z, VQ_FSQ_VEC_Z);
+    hipStream_t s = (hipStream_t)stream;
+    const int n = (int)N, hw = (int)(layout == VQHIP_LAYOUT_MAP ? HW : 0);
+#define VQ_FSQ_DEC(I64, MAP) fsq_decode_kernel<I64, MAP><<<grid, VQ_FSQ_TILE, 0, s>>>(k, quant, n, hw, z, vec)
+    if (layout == VQHIP_LAYOUT_ROWS) { if (quant_dtype == VQHIP_DTYPE_I64) VQ_FSQ_DEC(true, false); else VQ_FSQ_DEC(false, false); }
+    else { if (quant_dtype == VQHIP_DTYPE_I64) VQ_FSQ_DEC(true, true); else VQ_FSQ_DEC(false, true); }
+#undef VQ_FSQ_DEC
+    VQ_CHECK_LAUNCH("fsq_decode_kernel");
     return VQHIP_OK;
 }
 

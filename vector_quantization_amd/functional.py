@@ -98,6 +98,32 @@ def ste(z: torch.Tensor, x: torch.Tensor) -> torch.Tensor:
     return _STE.apply(z, x)
 
 
+class _FSQ(Function):
+    """FiniteScalarQuantizer's encode (vq/algorithms/fsq/quantizers.py:110-125): x -> (z, quant) with z = ste(round(t), t) / h
+    and t = (tanh(x + shift) * M - odd) / 2, one launch; the backward (one launch) recomputes tanh from x.  ``x`` is [N, C]
+    rows or the NCHW-contiguous map [B, C, H, W]; z has x's layout (fp32), quant is int32 [N] (not differentiable)."""
+
+    @staticmethod
+    def forward(ctx, x: torch.Tensor, q, hist: Optional[torch.Tensor] = None):
+        quant, z, _ = ops.fsq_encode(x, q, hist=hist)
+        ctx.save_for_backward(x)
+        ctx.q = q
+        ctx.mark_non_differentiable(quant)
+        return z, quant
+
+    @staticmethod
+    def backward(ctx, g, g_quant):
+        (x,) = ctx.saved_tensors
+        if g is None or not ctx.needs_input_grad[0]:
+            return None, None, None
+        return ops.fsq_backward(x, g, ctx.q), None, None
+
+
+def fsq(x: torch.Tensor, q, hist: Optional[torch.Tensor] = None):
+    """(z fp32 with gradient to x, quant int32 [N]) of FiniteScalarQuantizer's encode; ``q`` = ops.fsq_constants(levels, eps)."""
+    return _FSQ.apply(x, q, hist)
+
+
 class _FusedDecodeLoss(Function):
     """decode + straight-through + both MSE terms in one pass:
         z = W[idx];  z_ste = x + sg(z - x);  m_cb = mse(z, sg x);  m_cm = mse(sg z, x)   (same value, two graph nodes)

@@ -9,7 +9,7 @@ behind a structure-only stand-in for the un-vendored todd).
 from __future__ import annotations
 
 REPLACED = {
-    'VQITQuantizerRegistry': ('VectorQuantizer', 'VQGANQuantizer', 'VQKDQuantizer'),
+    'VQITQuantizerRegistry': ('VectorQuantizer', 'VQGANQuantizer', 'VQKDQuantizer', 'ScalarQuantizer', 'FiniteScalarQuantizer'),
     'VQITQuantizerDistanceRegistry': ('L2Distance', 'CosineDistance'),
     'VQITQuantizerLossRegistry': ('CodebookLoss', 'CommitmentLoss', 'VQGANLoss', 'EntropyLoss'),
     'VQITQuantizerCallbackRegistry': ('ComposedCallback', 'NormalizeCallback', 'VQKDCallback', 'CVQVAECallback'),

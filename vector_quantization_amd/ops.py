@@ -381,13 +381,135 @@ def gather_ste_mse(x: torch.Tensor, e: torch.Tensor, idx: torch.Tensor, need_z: 
 
 @_on_tensor_device
 def hist(idx: torch.Tensor, K: int, out: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """hist[K] int32 (+)= bincount(idx) of int64 tokens, or of int32 ones (FiniteScalarQuantizer's); only 0 <= k < K counts."""
     _require_cuda(idx)
     idx = idx.reshape(-1).contiguous()
-    assert idx.dtype == torch.int64
     if out is None:
         out = torch.zeros(K, dtype=torch.int32, device=idx.device)
+    if idx.dtype == torch.int32:
+        check(_lib.lib().vqhip_hist_i32(_ptr(idx), idx.numel(), K, _ptr(out), _stream()), 'vqhip_hist_i32')
+        return out
+    assert idx.dtype == torch.int64
     check(_lib.lib().vqhip_hist(_ptr(idx), idx.numel(), K, _ptr(out), _stream()), 'vqhip_hist')
     return out
+
+
+# ---- FiniteScalarQuantizer (vq/algorithms/fsq/quantizers.py:74-150) --------------------------------------------------------
+
+FSQ_MAX_K = 1 << 24          # the reference's fp32 digit sum is exact up to here
+
+
+def fsq_check_levels(levels) -> tuple:
+    """The levels FiniteScalarQuantizer accepts: 1 <= C <= 16 channels, each level >= 3, product <= 2^24."""
+    levels = tuple(int(v) for v in levels)
+    if not 1 <= len(levels) <= _lib.FSQ_MAX_C:
+        raise ValueError(f'FiniteScalarQuantizer: {len(levels)} channels, expected 1..{_lib.FSQ_MAX_C}')
+    bad = [v for v in levels if v < 3]
+    if bad:
+        raise ValueError(f'FiniteScalarQuantizer: levels {bad} < 3 (the reference divides by zero at 1 and gives NaN at 2)')
+    K = 1
+    for v in levels:
+        K *= v
+    if K > FSQ_MAX_K:
+        raise ValueError(f'FiniteScalarQuantizer: prod(levels) = {K} > 2^24 (the reference\'s fp32 token sum is no longer exact)')
+    return levels
+
+
+def fsq_constants(levels, eps: float = 1e-3) -> _lib.FsqConstants:
+    """vqhip_fsq_t of ``levels``: M and shift = atanh(odd / M) evaluated by the reference's own torch expressions on the host
+    (quantizers.py:116-121, max_ = (L - 1) * (1 - eps), odd = (L - 1) % 2, both from the int32 levels tensor)."""
+    levels = fsq_check_levels(levels)
+    max_per_digit = torch.tensor(levels, dtype=torch.int)
+    max_ = (max_per_digit - 1) * (1 - eps)
+    odd = (max_per_digit - 1) % 2
+    shift = torch.atanh(odd / max_)
+    q = _lib.FsqConstants()
+    q.struct_bytes = ctypes.sizeof(_lib.FsqConstants)
+    q.C = len(levels)
+    for i, v in enumerate(levels):
+        q.levels[i] = v
+        q.shift[i] = float(shift[i])
+        q.scale[i] = float(max_[i])
+    return q
+
+
+def _fsq_layout(t: torch.Tensor, C: int, what: str):
+    """(layout, N, HW) of fp32 / bf16 latents: [..., C] token-major, or the NCHW-contiguous map [B, C, H, W]."""
+    if t.dim() == 4 and t.shape[1] == C and t.is_contiguous():
+        b, _, h, w = t.shape
+        return _lib.LAYOUT_MAP, b * h * w, max(h * w, 1)
+    if t.shape[-1] != C or not t.is_contiguous():
+        raise ValueError(f'{what}: expected contiguous [..., {C}] rows or an NCHW-contiguous [B, {C}, H, W] map, got '
+                         f'{tuple(t.shape)}')
+    return _lib.LAYOUT_ROWS, t.numel() // C, 0
+
+
+def _float_dtype(t: torch.Tensor) -> int:
+    if t.dtype == torch.float32:
+        return _lib.DTYPE_F32
+    if t.dtype == torch.bfloat16:
+        return _lib.DTYPE_BF16
+    raise ValueError(f'FiniteScalarQuantizer latents must be fp32 or bf16, got {t.dtype}')
+
+
+@_on_tensor_device
+def fsq_encode(x: torch.Tensor, q: _lib.FsqConstants, need_z: bool = True, z_rows: bool = False, want_rows: bool = False,
+               hist: Optional[torch.Tensor] = None):
+    """One launch: (quant int32 [N], z fp32 or None, x_rows or None).  ``x`` is [..., C] rows or an NCHW-contiguous map
+    [B, C, H, W]; z comes in x's layout (``z_rows``: token-major [N, C] also for a map); ``want_rows`` (map only) adds the
+    token-major copy of x in x's dtype; ``hist`` (int32 [K]) is added to."""
+    _require_cuda(x)
+    C = q.C
+    layout, N, HW = _fsq_layout(x, C, 'fsq_encode')
+    dt = _float_dtype(x)
+    quant = torch.empty(N, dtype=torch.int32, device=x.device)
+    z = None
+    if need_z:
+        z = torch.empty((N, C) if (z_rows or layout == _lib.LAYOUT_ROWS) else x.shape, dtype=torch.float32, device=x.device)
+    rows = torch.empty(N, C, dtype=x.dtype, device=x.device) if (want_rows and layout == _lib.LAYOUT_MAP) else None
+    if hist is not None:
+        assert hist.dtype == torch.int32 and hist.is_contiguous() and hist.is_cuda
+    check(_lib.lib().vqhip_fsq_encode(ctypes.byref(q), _ptr(x), dt, layout, N, HW, _ptr(quant), _ptr(z), int(z_rows), _ptr(rows),
+                                      _ptr(hist), _stream()), 'vqhip_fsq_encode')
+    if z is not None and layout == _lib.LAYOUT_ROWS:
+        z = z.view(x.shape)
+    return quant, z, rows
+
+
+@_on_tensor_device
+def fsq_backward(x: torch.Tensor, g: torch.Tensor, q: _lib.FsqConstants) -> torch.Tensor:
+    """dL/dx (x's dtype and layout) of the encode's z, from g = dL/dz (x's shape; read as fp32)."""
+    _require_cuda(x, g)
+    layout, N, HW = _fsq_layout(x, q.C, 'fsq_backward')
+    dt = _float_dtype(x)
+    g = g.float().contiguous()
+    assert g.shape == x.shape
+    gx = torch.empty_like(x)
+    check(_lib.lib().vqhip_fsq_backward(ctypes.byref(q), _ptr(x), dt, layout, N, HW, _ptr(g), _ptr(gx), _stream()),
+          'vqhip_fsq_backward')
+    return gx
+
+
+@_on_tensor_device
+def fsq_decode(quant: torch.Tensor, q: _lib.FsqConstants, map_shape: Optional[tuple] = None) -> torch.Tensor:
+    """z fp32 of int32 / int64 tokens: [*quant.shape, C], or (``map_shape`` = (B, H, W)) the NCHW map [B, C, H, W]."""
+    _require_cuda(quant)
+    if quant.dtype not in (torch.int32, torch.int64):
+        raise ValueError(f'fsq_decode: tokens must be int32 or int64, got {quant.dtype}')
+    flat = quant.reshape(-1).contiguous()
+    N = flat.numel()
+    C = q.C
+    qdt = _lib.DTYPE_I32 if quant.dtype == torch.int32 else _lib.DTYPE_I64
+    if map_shape is not None:
+        B, H, W = map_shape
+        assert B * H * W == N
+        z = torch.empty(B, C, H, W, dtype=torch.float32, device=quant.device)
+        layout, HW = _lib.LAYOUT_MAP, H * W
+    else:
+        z = torch.empty(*quant.shape, C, dtype=torch.float32, device=quant.device)
+        layout, HW = _lib.LAYOUT_ROWS, 0
+    check(_lib.lib().vqhip_fsq_decode(ctypes.byref(q), _ptr(flat), qdt, layout, N, HW, _ptr(z), _stream()), 'vqhip_fsq_decode')
+    return z
 
 
 ORDERED_MAX_K = 32768     # the ordered (deterministic) route keeps one code histogram per 1024-token chunk in LDS

@@ -5,6 +5,7 @@ from .callbacks import (BaseCallback, ComposedCallback, CVQVAECallback, LazyInit
                         QuantizerHolderMixin, UpdateMixin, VQKDCallback)
 from .distances import BaseDistance, CosineDistance, L2Distance, LazyDistance, as_distance_tensor
 from .losses import BaseLoss, CodebookLoss, CommitmentLoss, EntropyLoss, VQGANLoss
+from .scalar_quantizer import FiniteScalarQuantizer, ScalarQuantizer
 from .statistics import QuantStatistics
 from .vector_quantizer import VectorQuantizer, VQGANQuantizer, VQKDQuantizer
 
@@ -13,5 +14,6 @@ __all__ = [
     'build_module_dict', 'get_memo', 'BaseCallback', 'ComposedCallback', 'CVQVAECallback', 'LazyInitWeightsMixin',
     'NormalizeCallback', 'QuantizerHolderMixin', 'UpdateMixin', 'VQKDCallback', 'BaseDistance', 'CosineDistance',
     'L2Distance', 'LazyDistance', 'as_distance_tensor', 'BaseLoss', 'CodebookLoss', 'CommitmentLoss', 'EntropyLoss',
-    'VQGANLoss', 'QuantStatistics', 'VectorQuantizer', 'VQGANQuantizer', 'VQKDQuantizer',
+    'VQGANLoss', 'QuantStatistics', 'VectorQuantizer', 'VQGANQuantizer', 'VQKDQuantizer', 'ScalarQuantizer',
+    'FiniteScalarQuantizer',
 ]

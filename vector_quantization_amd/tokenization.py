@@ -124,6 +124,10 @@ def decode_from_quant(quantizer, quant: torch.Tensor, memo: dict, token_major: b
             and getattr(quantizer, '_fused', True) and type(quantizer)._decode is VectorQuantizer._decode
             and not quantizer._callbacks.overrides_decode_or_loss()):
         return quantizer.decode_map(quant, get_memo(memo, 'quantizer'))[0], memo     # rows gathered straight into the NCHW map
+    from .quantizers.scalar_quantizer import FiniteScalarQuantizer
+    if (not token_major and isinstance(quantizer, FiniteScalarQuantizer) and quant.is_cuda and quantizer._fusable()
+            and 'z' not in get_memo(get_memo(memo, 'quantizer'), 'encode')):
+        return quantizer.decode_map(quant, get_memo(memo, 'quantizer'))[0], memo     # tokens decoded straight into the NCHW map
     z, memo['quantizer'] = quantizer.decode(quant.reshape(-1), get_memo(memo, 'quantizer'))
     return to_map(z, b, h, w, token_major), memo
 
