@@ -61,6 +61,8 @@ def test_vqgan_forward_backward(fused):
     quant = memo['quant'].cpu().numpy()
     np.testing.assert_array_equal(quant, co.l2_argmin(x, w))
     assert memo['x'] is xd and set(memo['loss']) == {'vqgan_loss'}
+    # NOT a check of the loss gradient: `up` ~ N(0,1) is 2^17 times the commitment term 2/(N D) (z - x), which rtol hides.
+    # tests/test_gpu_backward.py checks the loss term alone and at the scale of `up` against float64 under a derived bound.
     up = synth.normal(5, N, D)
     (loss + (z * torch.from_numpy(up).cuda()).sum()).backward()
     rl, rz, rgx, rgw = ref_grads(x, w, quant, upstream=torch.from_numpy(up))
