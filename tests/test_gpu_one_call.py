@@ -297,7 +297,7 @@ def test_graphed_cvq_replays_interleaved_with_eager_steps():
     """Round-5 advisor: an eager train step between two replays (a ragged last batch the graph refuses by shape) rewrites the
     device-side list in place without touching the early word or ``p._version`` — the next replay used to trust a stale
     length and could pick a capacity SMALLER than the list (anchors of the codes beyond it read from unwritten slots), and an
-    eager step after a replay read a count the replay had not produced.  `CvqStepState.writer` names the last writer: both
+    eager step after a replay read a count the replay had not produced.  `CvqStepState` records the last writer: both
     directions recount.  A second, smaller eager batch makes the list GROW between replays (codes fall out of use), which is
     exactly the case where the stale length is too small.  Compared with the all-eager module step by step."""
     from vector_quantization_amd.graphs import GraphedQuantizer
@@ -337,6 +337,39 @@ def test_graphed_cvq_replays_interleaved_with_eager_steps():
         assert abs(la - lb) <= 1e-6 * max(1.0, abs(la))
     for i, kind in enumerate(plan):                              # a replay never ran below the length of its list
         assert used[i] >= counts[i], (i, kind, counts, used)
+
+
+@pytest.mark.parametrize('dist,inplace', [('Cosine', False), ('L2', False), ('Cosine', True)])
+def test_cvq_routes_alternating_on_one_module(dist, inplace):
+    """The hand-over between the two eager flows: ONE module whose ``one_call_steps`` flips every step (and in a second
+    pattern every other step) against modules that stay on one route.  Both flows keep the listed codes, the pinned count
+    and its event in the same `CvqStepState`, so the list a hook-by-hook step prefetched is the one the next one-call step
+    starts from, and the reverse — tokens, outputs, codebook and probabilities bit for bit at every step, the same
+    ``last_exchange_rows`` at every step."""
+    N, K, D = 3000, 2048, 64
+    w0 = synth.unit_rows(synth.rng(5).standard_normal((K, D), dtype=np.float32))
+    xs = batches(N, K, D, w0, 8, 38)
+    gz = torch.randn(N, D, device='cuda', generator=torch.Generator(device='cuda').manual_seed(7)) / (N * D)
+
+    def run(routes):
+        q = build(cvq_cfg(K, D, dist), w0)
+        q.inplace_updates = inplace
+        rec, rows, probs = [], [], []
+        for x, one_call in zip(xs, routes):
+            rec += run_steps(q, [x], gz, one_call)
+            rows.append(q._callbacks.callbacks[0].last_exchange_rows)
+            probs.append(q.get_buffer('_probability').clone())
+        return rec, rows, probs
+
+    n = len(xs)
+    fixed = [run([False] * n), run([True] * n)]
+    for routes in ([i % 2 == 1 for i in range(n)], [i % 2 == 0 for i in range(n)], [(i // 2) % 2 == 1 for i in range(n)]):
+        rec, rows, probs = run(routes)
+        for ref_rec, ref_rows, ref_probs in fixed:
+            assert_same(ref_rec, rec)
+            assert rows == ref_rows, (routes, rows, ref_rows)
+            for i, (pa, pb) in enumerate(zip(ref_probs, probs)):
+                assert torch.equal(pa, pb), (routes, i)
 
 
 @pytest.mark.parametrize('kind,dist,D,bf16,train', [('plain', 'L2', 256, True, True), ('plain', 'L2', 256, True, False), ('plain', 'Cosine', 32, False, True),

@@ -11,7 +11,7 @@ from . import ops
 
 
 def _as2d(t: torch.Tensor) -> torch.Tensor:
-    return t.reshape(-1, t.shape[-1])
+    return t if t.dim() == 2 else t.reshape(-1, t.shape[-1])
 
 
 class _Embedding(Function):
@@ -124,44 +124,8 @@ def fsq(x: torch.Tensor, q, hist: Optional[torch.Tensor] = None):
     return _FSQ.apply(x, q, hist)
 
 
-class _FusedDecodeLoss(Function):
-    """decode + straight-through + both MSE terms in one pass:
-        z = W[idx];  z_ste = x + sg(z - x);  m_cb = mse(z, sg x);  m_cm = mse(sg z, x)   (same value, two graph nodes)
-        combined = m_cb + beta * m_cm   (VQGANLoss, losses.py:119-127 — finished inside the kernel)
-    Backward is one fused kernel (vqhip_vq_backward_ex): m_cb's gradient flows to W, m_cm's and z_ste's to x, the combined
-    value's to both; gradients of unused outputs are not materialised."""
-
-    @staticmethod
-    def forward(ctx, x: torch.Tensor, weight: torch.Tensor, idx: torch.Tensor, beta: float = 0.0):
-        ctx.set_materialize_grads(False)
-        ctx.beta = float(beta)
-        if x.numel() == 0:
-            _, z_ste, sse = ops.gather_ste_loss(x, weight, idx, need_z=False, need_ste=True, need_sse=True)
-            ctx.save_for_backward(x, weight, idx)
-            m = (sse / x.numel()).float().reshape(())                  # nan, as mse_loss of an empty tensor
-            return z_ste.view(x.shape), m, m.clone(), m + beta * m
-        _, z_ste, mse = ops.gather_ste_mse(x, weight, idx, beta=beta)   # means and their combination finished inside the kernel
-        ctx.save_for_backward(x, weight, idx)
-        return z_ste.view(x.shape), mse[0], mse[1], mse[2]
-
-    @staticmethod
-    def backward(ctx, g_zste, g_cb, g_cm, g_comb):
-        x, weight, idx = ctx.saved_tensors
-        need_x, need_w = ctx.needs_input_grad[0], ctx.needs_input_grad[1]
-        gx, gw = ops.vq_backward(x, weight, idx, g_zste, g_cb, g_cm, need_x, need_w, g_comb=g_comb, beta=ctx.beta)
-        if gx is not None:
-            gx = gx.view(x.shape).to(x.dtype)
-        return gx, gw, None, None
-
-
-def fused_decode_loss(x: torch.Tensor, weight: torch.Tensor, idx: torch.Tensor, beta: float = 0.0):
-    """Returns (z_ste, m_cb, m_cm, m_cb + beta*m_cm): the straight-through output, the codebook / commitment MSE values and
-    their VQGAN combination."""
-    return _FusedDecodeLoss.apply(x, weight, idx, beta)
-
-
 class _FusedMapDecodeLoss(Function):
-    """``_FusedDecodeLoss`` for a quantizer call on the NCHW feature map (tokenization.quantize): the straight-through
+    """``fused_decode_loss`` for a quantizer call on the NCHW feature map (tokenization.quantize): the straight-through
     output is written directly as the map [B, D, H, W], the loss values are those of the token form.  ``x_rows`` are the
     token-major rows the map encode produced (``ops.encode_map``); gradients flow to ``x_map`` and the codebook."""
 
@@ -208,33 +172,6 @@ class _Computed:
         self.__dict__.update(tensors)
 
 
-class _PrecomputedDecodeLoss(Function):
-    """``_FusedDecodeLoss`` whose forward values were computed by vqhip_cvq_forward in the same library call as the encode and
-    the codebook update: the node only ties them into the graph.  Backward is the same fused kernel."""
-
-    @staticmethod
-    def forward(ctx, x: torch.Tensor, weight: torch.Tensor, done: _Computed, beta: float):
-        ctx.set_materialize_grads(False)
-        ctx.beta = float(beta)
-        ctx.save_for_backward(x, weight, done.idx)
-        mse = done.mse
-        return done.z_ste.view(x.shape), mse[0], mse[1], mse[2]
-
-    @staticmethod
-    def backward(ctx, g_zste, g_cb, g_cm, g_comb):
-        x, weight, idx = ctx.saved_tensors
-        need_x, need_w = ctx.needs_input_grad[0], ctx.needs_input_grad[1]
-        gx, gw = ops.vq_backward(x, weight, idx, g_zste, g_cb, g_cm, need_x, need_w, g_comb=g_comb, beta=ctx.beta)
-        if gx is not None:
-            gx = gx.view(x.shape).to(x.dtype)
-        return gx, gw, None, None
-
-
-def precomputed_decode_loss(x: torch.Tensor, weight: torch.Tensor, done: _Computed, beta: float = 0.0):
-    """(z_ste, m_cb, m_cm, m_cb + beta*m_cm) of ``fused_decode_loss`` from values a one-call forward already holds."""
-    return _PrecomputedDecodeLoss.apply(x, weight, done, beta)
-
-
 class _VqkdStep(Function):
     """Autograd node of the VQ-KD one-call forward: outputs xn = F.normalize(x) (what memo['x'] holds), the straight-through
     output xn + sg(z - xn) and the commitment loss mean((F.normalize(sg z) - F.normalize(xn))^2) (CommitmentLoss with
@@ -269,10 +206,14 @@ def vqkd_step(x: torch.Tensor, weight: torch.Tensor, done: _Computed):
 
 
 class _VqStep(Function):
-    """Autograd node of the one-call forward of a quantizer without an update callback, or with NormalizeCallback alone
-    (vqhip_vq_forward): outputs (xn = F.normalize(x) when normalised, else x itself is what memo['x'] holds), the straight-through
-    output, both MSE values and their VQGAN combination.  Backward: the fused kernel of ``_FusedDecodeLoss`` on the rows the
-    forward quantized, then F.normalize's backward when the rows were normalised."""
+    """The one autograd node of the decode / straight-through / MSE-loss tail:
+        z = W[idx];  z_ste = r + sg(z - r);  m_cb = mse(z, sg r);  m_cm = mse(sg z, r)   (same value, two graph nodes)
+        combined = m_cb + beta * m_cm   (VQGANLoss, losses.py:119-127 — finished inside the kernel)
+    on rows r = x, or r = xn = F.normalize(x) when ``done.xn`` is given (NormalizeCallback; xn is then the first output: what
+    memo['x'] holds).  The forward values come from ``done`` — a one-call forward (vqhip_vq_forward, vqhip_cvq_forward) or
+    ``fused_decode_loss`` has produced them — and the node only ties them into the graph.  Backward is one fused kernel
+    (vqhip_vq_backward_ex): m_cb's gradient flows to W, m_cm's and z_ste's to the rows, the combined value's to both; gradients of
+    unused outputs are not materialised; then F.normalize's backward when the rows were normalised."""
 
     @staticmethod
     def forward(ctx, x: torch.Tensor, weight: torch.Tensor, done: _Computed, beta: float):
@@ -306,7 +247,7 @@ class _VqStep(Function):
                 if g_xn is not None:                             # a consumer of memo['x'] other than the decode / loss tail
                     gr = _as2d(g_xn).float() if gr is None else gr + _as2d(g_xn)
                 gx = ops.normalize_rows_bwd(_as2d(x), gr, 1e-12).view(x.shape).to(x.dtype)
-            else:
+            elif gr is not None:
                 gx = gr.view(x.shape).to(x.dtype)
         return gx, gw, None, None
 
@@ -314,3 +255,16 @@ class _VqStep(Function):
 def vq_step(x: torch.Tensor, weight: torch.Tensor, done: _Computed, beta: float = 0.0):
     """(xn or None, z_ste, m_cb, m_cm, m_cb + beta*m_cm) of a one-call forward, tied into the autograd graph."""
     return _VqStep.apply(x, weight, done, beta)
+
+
+def fused_decode_loss(x: torch.Tensor, weight: torch.Tensor, idx: torch.Tensor, beta: float = 0.0):
+    """Returns (z_ste, m_cb, m_cm, m_cb + beta*m_cm): the straight-through output, the codebook / commitment MSE values and
+    their VQGAN combination, from one gather kernel, tied into the graph by ``vq_step``."""
+    xd = x.detach()
+    if x.numel() == 0:
+        _, z_ste, sse = ops.gather_ste_loss(xd, weight.detach(), idx, need_z=False, need_ste=True, need_sse=True)
+        m = (sse / x.numel()).float().reshape(())                      # nan, as mse_loss of an empty tensor
+        mse = (m, m.clone(), m + beta * m)
+    else:
+        _, z_ste, mse = ops.gather_ste_mse(xd, weight.detach(), idx, beta=beta)   # means and their combination finished inside the kernel
+    return vq_step(x, weight, _Computed(xn=None, z_ste=z_ste, mse=mse, idx=idx), beta)[1:]

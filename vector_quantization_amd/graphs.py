@@ -154,8 +154,6 @@ class GraphedQuantizer(nn.Module):
                         self._steps.append(st)
                 finally:
                     self._cvq.capture_plan = None
-                self._list_version = None            # the chained list is (re)built before the first replay
-                self._seq = None                     # sequence number the last launched replay will publish (set at the first one)
             elif self._train:
                 sample = sample_x.detach().clone().requires_grad_(True)
                 # (allow_unused_input: a VQ-KD step gives the codebook no gradient — the commitment term and the straight-through
@@ -182,54 +180,27 @@ class GraphedQuantizer(nn.Module):
         step = getattr(quantizer, '_one_call_step', None)
         if step is None or sample_x.dim() != 2:
             return None
-        bound = step(sample_x)
-        if bound is None or getattr(bound, '__name__', '') != '_forward_cvq':
+        from .quantizers.vector_quantizer import VectorQuantizer
+        if getattr(step(sample_x), '__func__', None) is not VectorQuantizer._forward_cvq:
             return None
         return quantizer._callbacks.callbacks[0]
 
     def _replay_chained(self, x: torch.Tensor):
         cb = self._cvq
         p = cb.probability
-        st = cb._step_state
-        me = ('replay', id(self))
-        # The chain trusts rows / slot / count / the early word to describe the probabilities the replay starts from.  That holds
-        # only while the LAST writer of that state was a replay of this object: an eager train step in between (a ragged last
-        # batch, say) rewrites the list in place without touching the early word or `p._version`, and so does another
-        # GraphedQuantizer on the same module — `writer` (train_step.CvqStepState) names the last one
-        if st is None or self._seq is None or st.writer != me or self._list_version != (p._version, p.data_ptr()):
-            count = self._resync()
-            st = cb._step_state
-        else:
-            # the previous replay publishes {its sequence number, the length of THIS step's list} as soon as its histogram is final:
-            # usually long since there — the rest of that replay (column pass, update, decode, backward) is what the GPU is running now
-            word = int(st.early_host[0])
-            if (word >> 32) != self._seq:
-                deadline = time.monotonic() + self.poll_timeout_s
-                while (word >> 32) != self._seq and time.monotonic() < deadline:
-                    word = int(st.early_host[0])
-            if (word >> 32) == self._seq:
-                count = word & 0xFFFFFFFF
-            else:                                                 # never published (a failed replay, a non-coherent pinned pool): count on the spot
-                count = self._resync()
-                st = cb._step_state
+        st, me = cb._state(p), ('replay', id(self))
+        # The previous replay of this object has published the length of the list this one starts from (usually long since: the
+        # rest of that replay — column pass, update, decode, backward — is what the GPU is running now).  None: the chain is
+        # broken (the first replay, an eager step or another GraphedQuantizer in between, probabilities changed from outside, a
+        # word that never arrived): list and count on the spot, one synchronisation (train_step.CvqStepState)
+        count = st.published_count(me, p, self.poll_timeout_s)
+        if count is None:
+            count = st.resync(p)
         which = next(i for i, cap in enumerate(self._caps) if cap >= count)
         self.last_capacity = self._caps[which]
         z, loss = self._calls[which](x)
-        self._seq += 1                                            # every replay advances the device counter by one
-        st.writer = me
-        st.list_of = None                                         # (an eager step after this one rebuilds the list: the host knows no count)
+        st.claim_by_replay(me, p)
         return z, loss, self._steps[which].last_quant
-
-    def _resync(self) -> int:
-        """Rebuild the list for the current probabilities and re-read the device's sequence number (one synchronisation): the first
-        replay, probabilities changed from outside, or another writer since the last replay."""
-        cb = self._cvq
-        cb.refresh_list()
-        st = cb._step_state
-        p = cb.probability
-        self._list_version = (p._version, p.data_ptr())
-        self._seq = int(st.seq_dev.item())
-        return int(st.count_host[0])
 
     def forward(self, x: torch.Tensor):
         if tuple(x.shape) != self._shape or x.dtype != self._dtype:

@@ -13,13 +13,13 @@ from typing import TYPE_CHECKING, Iterable, Mapping
 import torch
 import torch.distributed as dist
 
-from .. import exchange, ops
+from .. import exchange, functional as VF, ops, train_step, utils
 from ..config import BuildPreHookMixin, Config, Item, RegistryMeta
 from ..registries import AnchorRegistry, VQITQuantizerCallbackRegistry
 from ..utils import (EMA, PriorityQueue, Store, all_reduce_statistics, broadcast_, exchange_log, exchanging, gather_to_rank0,
                      get_rank, get_world_size, is_sync)
 from .anchors import NearestAnchor
-from .distances import LazyDistance
+from .distances import CosineDistance, L2Distance, LazyDistance
 from .memo import Memo, get_memo
 from .quantizer_api import BaseQuantizer
 from .statistics import QuantStatistics
@@ -194,15 +194,30 @@ class UpdateMixin(BuildPreHookMixin, BaseCallback):
         #  a non-leaf tensor: rebinding ITS .data, as callbacks/update.py:56 does, changes nothing that outlives the forward)
         return bool(self.quantizer.inplace_updates or getattr(weight, '_fsdp_flattened', False) or not weight.is_leaf or weight._is_view())
 
-    def _update_embedding(self, e: torch.Tensor) -> None:
+    def _publish_weight(self, weight: torch.Tensor, e: torch.Tensor) -> None:
+        """``e`` holds the updated codebook: a fresh tensor, which becomes the parameter's storage, or the parameter's own
+        storage, which a kernel has already written in place."""
         if Store.DRY_RUN:
             assert is_sync(e)
-        weight = self.vector_quantizer.embedding.weight
-        if self._writes_in_place(weight):                    # same values into the existing storage (graph replay, FSDP)
-            weight.data.copy_(e)
-        else:
+        if e.data_ptr() != weight.data_ptr():
             weight.data = e                                  # rebinds the storage, like callbacks/update.py:56
-        self.vector_quantizer.invalidate_codebook()          # neither form bumps weight._version
+        self.quantizer.invalidate_codebook()                 # neither form bumps weight._version
+
+    def _update_embedding(self, e: torch.Tensor) -> None:
+        weight = self.vector_quantizer.embedding.weight
+        if e.data_ptr() != weight.data_ptr() and self._writes_in_place(weight):
+            weight.data.copy_(e)                             # same values into the existing storage (graph replay, FSDP)
+            e = weight.detach()
+        self._publish_weight(weight, e)
+
+    @staticmethod
+    def _communicator(w: torch.Tensor):
+        """The RCCL communicator on which the library issues a one-call step's exchange itself; None while the exchange is
+        logged (the caller's collective, which the log counts, then runs between the call's phases)."""
+        if exchange_log.enabled:
+            return None
+        from .. import rccl
+        return rccl.communicator(w)
 
 
 @VQITQuantizerCallbackRegistry.register_()
@@ -210,7 +225,6 @@ class NormalizeCallback(UpdateMixin, BaseCallback):
 
     def before_encode(self, x: torch.Tensor, memo: Memo) -> torch.Tensor:
         x = super().before_encode(x, memo)
-        from .. import functional as VF
         x = VF.normalize(x)                                   # F.normalize(x): differentiable w.r.t. the encoder
         e = self.vector_quantizer.embedding.weight
         e = ops.normalize_rows(e.detach())
@@ -282,8 +296,7 @@ class VQKDCallback(LazyInitWeightsMixin, NormalizeCallback):
     def fused_forward_ok(self, x: torch.Tensor) -> bool:
         """True when this step can be enqueued by one call: train mode, the lazy init done, device latents with a proposal
         image, cosine distance with the library's fused encode, an EMA, a world the packed exchange covers."""
-        from .distances import CosineDistance
-        q = self.vector_quantizer
+        q = self.quantizer
         if not (q.training and self.with_ema and x.dim() == 2 and x.is_cuda and x.shape[0] > 0 and x.shape[0] < (1 << 31)):
             return False
         if type(q.distance) is not CosineDistance or not ops.coarse_supported(q.embedding_dim) or q._cache_codebook:
@@ -298,9 +311,7 @@ class VQKDCallback(LazyInitWeightsMixin, NormalizeCallback):
         step (normalize.py:22-29, vqkd callbacks.py:114-129, quantizers.py:92-117) from one host call.  Returns
         (xn, quant, z_ste, loss) with the reference's memo side effects; weight.data is rebound (or overwritten in place)
         exactly as the two ``_update_embedding`` calls of the unfused flow leave it."""
-        from .. import functional as VF, train_step
-        from ..utils import all_reduce_sum
-        q = self.vector_quantizer
+        q = self.quantizer
         weight = q.embedding.weight
         K, D = weight.shape
         if getattr(self, '_step_state', None) is None:
@@ -311,27 +322,14 @@ class VQKDCallback(LazyInitWeightsMixin, NormalizeCallback):
         w_out = w_in if inplace else torch.empty_like(w_in)
         xd = x.detach()
         exch = exchanging()
-        comm = None
-        if exch and not exchange_log.enabled:
-            from .. import rccl
-            comm = rccl.communicator(w_in)
-        metric = q.distance.metric_for(D)
-        ordered = ops.use_ordered(K, D, None, xd.shape[0])
-        out = train_step.vqkd_forward(xd, w_in, w_mid, w_out, metric, self._ema.decay, self._step_state, exchange=exch,
-                                      world=get_world_size(), comm=comm, all_reduce=all_reduce_sum if exch else None,
-                                      ordered=ordered, tail=True)
-        if Store.DRY_RUN:
-            assert is_sync(w_out)
-        if not inplace:
-            weight.data = w_out                                  # callbacks/update.py:56 (after the EMA update: callbacks.py:128)
-        q.invalidate_codebook()
+        out = train_step.vqkd_forward(xd, w_in, w_mid, w_out, q.distance.metric_for(D), self._ema.decay, self._step_state,
+                                      exchange=exch, world=get_world_size(), comm=self._communicator(w_in) if exch else None,
+                                      all_reduce=utils.all_reduce_sum if exch else None,
+                                      ordered=ops.use_ordered(K, D, None, xd.shape[0]), tail=True)
+        self._publish_weight(weight, w_out)                      # (after the EMA update: callbacks.py:128)
         done = VF._Computed(xn=out['xn'], z_ste=out['z_ste'], mse=out['mse'], idx=out['idx'])
         xn, z_ste, loss = VF.vqkd_step(x, weight, done)
-        enc = get_memo(memo, 'encode')
-        prepared = out['prepared']
-        enc['distance'] = LazyDistance(q.distance, xn, w_mid, xq=out['xq'], eq=prepared.exact_rows(), metric=ops.metric_name(prepared.metric))
-        enc['hist'] = out['hist']
-        memo['encode'] = enc
+        q._encode_memo(memo, out, xn, w_mid)
         return xn, out['idx'], z_ste, loss
 
     def after_encode(self, x: torch.Tensor, quant: torch.Tensor, memo: Memo) -> torch.Tensor:
@@ -364,9 +362,7 @@ class CVQVAECallback(UpdateMixin, BaseCallback):
         self._anchor = anchor
         self._eps = eps
         self._sparse_anchors = sparse_anchors
-        self._listed = None               # (p tensor, its _version, rows, slot, count, pinned host count, copy event)
-        self._pinned_count = None
-        self._step_state = None           # train_step.CvqStepState of the one-call forward (lazily, on the codebook's device)
+        self._step_state = None           # train_step.CvqStepState: the listed codes of all three flows (`_state`)
         # How a HIP-graph capture of the one-call forward sizes and chains itself (graphs.GraphedQuantizer sets it around its
         # captures; None = launches sized for K, the list rebuilt inside the graph): dict(cap=<capacity of the listed-code
         # launches>, chained=True: the graph trusts rows / slot / count to describe the probabilities it starts from — every
@@ -393,9 +389,7 @@ class CVQVAECallback(UpdateMixin, BaseCallback):
         return self.quantizer.get_buffer('_probability')
 
     def _update_probability(self, value: torch.Tensor) -> None:
-        self._listed = None               # a list prefetched for the old probabilities is void (`_prefetch_listed` re-arms it)
-        if self._step_state is not None:
-            self._step_state.invalidate()
+        # (a list made for the old probabilities is void either way: the state remembers the tensor, its version and its storage)
         if self.quantizer.inplace_updates and '_probability' in self.quantizer._buffers \
                 and self.quantizer._buffers['_probability'].shape == value.shape \
                 and self.quantizer._buffers['_probability'].device == value.device:
@@ -404,16 +398,21 @@ class CVQVAECallback(UpdateMixin, BaseCallback):
             self.quantizer.register_buffer('_probability', value)
 
     # ---- anchors for the codes that can need one ------------------------------------------------------------------
-    def _sparse_ok(self, d, hist32) -> bool:
+    def _sparse_flow_ok(self, tokens: int) -> bool:
+        """The preconditions of the sparse-anchor flow, hook by hook (`_sparse_step`) or as one call (`fused_forward`)."""
         if self._sparse_anchors is False or type(self._anchor) is not NearestAnchor:
             return False
-        if get_world_size() > exchange.MAX_WORLD:                # count pieces no longer exact in fp32: the dense flow below
+        if get_world_size() > exchange.MAX_WORLD:                # count pieces no longer exact in fp32: the dense flow
             return False
-        if self._sync_exchange() and d.shape[0] > ops.SYNC_MAX_ROWS:      # a key holds the row in 24 bits (include/vqhip.h)
+        if self._sync_exchange() and tokens > ops.SYNC_MAX_ROWS:          # a key holds the row in 24 bits (include/vqhip.h)
+            return False
+        if '_probability' not in self.quantizer._buffers:
             return False
         p = self.probability
-        return (isinstance(d, LazyDistance) and hist32 is not None and p.is_cuda and p.dtype == torch.float32
-                and ops.coarse_supported(self.quantizer.embedding_dim))
+        return p.is_cuda and p.dtype == torch.float32 and ops.coarse_supported(self.quantizer.embedding_dim)
+
+    def _sparse_ok(self, d, hist32) -> bool:
+        return isinstance(d, LazyDistance) and hist32 is not None and self._sparse_flow_ok(d.shape[0])
 
     def _sync_exchange(self) -> bool:
         """NearestAnchor(sync=True) over more than one rank: the GLOBAL nearest latent per code (anchors.py:50-57).  The reference
@@ -421,29 +420,19 @@ class CVQVAECallback(UpdateMixin, BaseCallback):
         winner alone contributes its row to the packed SUM (include/vqhip.h: vqhip_cvq_col_keys)."""
         return bool(self._anchor._sync) and exchanging()
 
-    def _listed_codes(self, p: torch.Tensor, K: int, capturing: bool):
-        """(rows, slot, count, cap): the device-side list for the step that starts from ``p`` and a host-known bound on its
-        length.  Eager: the list and its length were produced at the end of the previous step (`_prefetch_listed`); a
-        first step, or a ``p`` changed from outside, computes them now (one synchronisation).  Capture: sized for K."""
-        if capturing:
-            rows, slot, count = ops.cvq_rows(p, K, self._ema.decay, self._eps)
-            return rows, slot, count, K
-        st = self._listed
-        if st is not None and st[0] is self.probability and st[1] == st[0]._version and p.data_ptr() == st[0].data_ptr():
-            st[6].synchronize()                                   # the copy was queued a whole step ago
-            return st[2], st[3], st[4], int(st[5][0])
-        rows, slot, count = ops.cvq_rows(p, K, self._ema.decay, self._eps)
-        return rows, slot, count, int(count.item())
+    def _state(self, p: torch.Tensor | None = None) -> 'train_step.CvqStepState':
+        """The listed-code state of this callback (made at first use, on the device of the probabilities ``p``)."""
+        if p is None:
+            p = self.probability
+        st = self._step_state
+        if st is None or st.device != p.device or st.K != p.numel():
+            st = self._step_state = train_step.CvqStepState(p.numel(), p.device, self._ema.decay, self._eps)
+        return st
 
-    def _prefetch_listed(self, p_new: torch.Tensor, K: int) -> None:
-        rows, slot, count = ops.cvq_rows(p_new, K, self._ema.decay, self._eps)
-        if self._pinned_count is None:                   # one pinned word for the life of the callback
-            self._pinned_count = torch.empty(1, dtype=torch.int32).pin_memory()
-        host = self._pinned_count
-        host.copy_(count, non_blocking=True)
-        ev = torch.cuda.Event()
-        ev.record()
-        self._listed = (p_new, p_new._version, rows, slot, count, host, ev)
+    def refresh_list(self) -> int:
+        """(Re)build the device-side list of codes for the CURRENT probabilities and note its length on the host — what a
+        first step, a loaded checkpoint or a probability buffer replaced from outside needs (one synchronisation)."""
+        return self._state().rebuild(self.probability)
 
     def _sparse_step(self, x: torch.Tensor, quant: torch.Tensor, d: LazyDistance, hist32: torch.Tensor) -> None:
         K = self.quantizer.codebook_size
@@ -451,7 +440,12 @@ class CVQVAECallback(UpdateMixin, BaseCallback):
         weight = self.vector_quantizer.embedding.weight
         w_in, p_in = weight.detach().contiguous(), self.probability.contiguous()
         capturing = torch.cuda.is_current_stream_capturing()
-        rows, slot, count, cap = self._listed_codes(p_in, K, capturing)
+        if capturing:                     # sized for K, the device-side count decides; the list lives in the graph's pool
+            (rows, slot, count), cap = ops.cvq_rows(p_in, K, self._ema.decay, self._eps), K
+        else:                             # the length was copied out at the end of the previous step; a first step, or
+            st = self._state(p_in)        # probabilities changed from outside, count now (one synchronisation)
+            cap = st.wait_count() if st.valid_for(p_in) else st.rebuild(p_in)
+            rows, slot, count = st.rows, st.slot, st.count
         self.last_exchange_rows = cap
         xr = x.detach()
         col = None
@@ -471,123 +465,65 @@ class CVQVAECallback(UpdateMixin, BaseCallback):
         else:                                                    # histogram ‖ token count ‖ [cap, D] anchors: one all-reduce
             packed = exchange.cvq_exchange(hist32, quant.numel(), xr, col, count, cap, K)
             ops.cvq_apply(w_in, w_out, p_in, p_out, slot, self._ema.decay, self._eps, packed=packed, world=world, cap=cap)
-        if inplace:
-            if p_out is not self.probability:                    # (a non-contiguous buffer was copied above)
-                self.probability.copy_(p_out)
-            if w_out.data_ptr() != weight.data_ptr():
-                weight.data.copy_(w_out)
-            if Store.DRY_RUN:
-                assert is_sync(w_out)
-            self.vector_quantizer.invalidate_codebook()
-        else:
+        if not inplace:
             self._update_probability(p_out)
-            self._update_embedding(w_out)
-        if self._step_state is not None:                         # the one-call forward's list described the old probabilities
-            self._step_state.invalidate()
+        elif p_out is not self.probability:                      # (a non-contiguous buffer was copied above)
+            self.probability.copy_(p_out)
+        self._update_embedding(w_out)
         if not capturing:
-            self._prefetch_listed(self.probability, K)
+            st.prefetch(self.probability)
+        elif self._step_state is not None:                       # (replays will move the probabilities on without a host-side record)
+            self._step_state.invalidate()
 
     # ---- the whole training forward as ONE library call (train_step.py, include/vqhip.h: vqhip_cvq_forward) --------------
     def fused_forward_ok(self, x: torch.Tensor) -> bool:
-        """True when this step can be enqueued by one call: the conditions of the sparse-anchor flow (`_sparse_ok`) that can
-        be known before the encode, a distance whose encode is the library's fused one, device latents."""
-        from .distances import CosineDistance, L2Distance
-        q = self.vector_quantizer
+        """True when this step can be enqueued by one call: the conditions of the sparse-anchor flow, a distance whose encode
+        is the library's fused one, device latents."""
+        q = self.quantizer
         if not (q.training and self.with_ema and x.dim() == 2 and x.is_cuda and x.shape[0] > 0 and x.shape[0] < (1 << 31)):
             return False
-        if self._sparse_anchors is False or type(self._anchor) is not NearestAnchor:
-            return False
-        if get_world_size() > exchange.MAX_WORLD or (self._sync_exchange() and x.shape[0] > ops.SYNC_MAX_ROWS):
-            return False
-        if type(q.distance) not in (L2Distance, CosineDistance) or not ops.coarse_supported(q.embedding_dim) or q._cache_codebook:
-            return False
-        if '_probability' not in q._buffers:
+        if type(q.distance) not in (L2Distance, CosineDistance) or q._cache_codebook or not self._sparse_flow_ok(x.shape[0]):
             return False
         p, w = self.probability, q.embedding.weight
-        return (p.is_cuda and p.dtype == torch.float32 and p.is_contiguous() and p.device == x.device
-                and w.is_cuda and w.dtype == torch.float32 and w.is_contiguous())
-
-    def refresh_list(self) -> None:
-        """(Re)build the device-side list of codes for the CURRENT probabilities and note its length on the host — what a
-        first step, a loaded checkpoint or a probability buffer replaced from outside needs (one synchronisation)."""
-        from .. import train_step
-        p = self.probability
-        K = self.quantizer.codebook_size
-        if self._step_state is None or self._step_state.device != p.device or self._step_state.K != K:
-            self._step_state = train_step.CvqStepState(K, p.device)
-        st = self._step_state
-        ops.cvq_rows(p, K, self._ema.decay, self._eps, out=(st.rows, st.slot, st.count))
-        st.count_host[0] = int(st.count.item())
-        st.mark_list(p)
+        return p.is_contiguous() and p.device == x.device and w.is_cuda and w.dtype == torch.float32 and w.is_contiguous()
 
     def fused_forward(self, x: torch.Tensor, memo: Memo, beta: float):
         """_encode + after_encode (sparse-anchor flow of `_sparse_step`) + decode + MSE losses + STE of one training step from
         one host call.  Returns (quant, z_ste, m_cb, m_cm, m_vqgan) with the reference's memo side effects."""
-        from .. import functional as VF, train_step
-        from ..utils import all_reduce_min, all_reduce_sum, get_rank
-        q = self.vector_quantizer
+        q = self.quantizer
         weight = q.embedding.weight
         K, D = weight.shape
-        capturing = torch.cuda.is_current_stream_capturing()
         p_in = self.probability
-        if self._step_state is None or self._step_state.device != p_in.device or self._step_state.K != K:
-            self._step_state = train_step.CvqStepState(K, p_in.device)
-        st = self._step_state
-        if capturing:                     # the launches are sized for a fixed capacity, the device-side count decides
+        st = self._state(p_in)
+        if torch.cuda.is_current_stream_capturing():   # the launches are sized for a fixed capacity, the device-side count decides
             plan = self.capture_plan or {}
             list_ready = prefetch = early = bool(plan.get('chained', False))
             cap = int(plan.get('cap', K))
-        else:
-            if not st.list_valid_for(p_in):
-                self.refresh_list()       # first step / probabilities replaced from outside: counted on the spot
-                st = self._step_state
-                list_ready, cap = True, int(st.count_host[0])
-            else:
-                list_ready, cap = True, -1          # the library reads the count the previous step's prefetch copied out
-            prefetch, early = True, False
+        else:                             # the library reads the count the previous step's prefetch left behind the event; a first
+            list_ready, prefetch, early = True, True, False      # step, or probabilities replaced from outside, count on the spot
+            cap = -1 if st.valid_for(p_in) else self.refresh_list()
         inplace = q.inplace_updates
-        w_inplace = self._writes_in_place(weight)
         w_in = weight.detach()
-        w_out = w_in if w_inplace else torch.empty_like(w_in)
+        w_out = w_in if self._writes_in_place(weight) else torch.empty_like(w_in)
         p_out = p_in if inplace else torch.empty_like(p_in)
         exch = exchanging()
         sync = self._sync_exchange()
-        comm = None
-        if exch and not exchange_log.enabled:
-            from .. import rccl
-            comm = rccl.communicator(w_in)
-        metric = q.distance.metric_for(D)
-        xd = x.detach()
         # the codebook operand of memo['distance'] aliases the storage the encode ran against (quantizers.py:97 clones it)
         e_alias = weight.view_as(weight) if (torch.is_grad_enabled() and weight.requires_grad) else w_in
-        out = train_step.cvq_forward(xd, w_in, p_in, w_out, p_out, metric, self._ema.decay, self._eps, beta, st, cap=cap,
-                                     list_ready=list_ready, prefetch=prefetch, exchange=exch, world=get_world_size(), comm=comm,
-                                     all_reduce=all_reduce_sum if exch else None, tail=True, early_count=early,
-                                     anchor_sync=sync, rank=get_rank() if sync else 0, all_reduce_min=all_reduce_min if sync else None)
+        out = train_step.cvq_forward(x.detach(), w_in, p_in, w_out, p_out, q.distance.metric_for(D), self._ema.decay, self._eps, beta,
+                                     st, cap=cap, list_ready=list_ready, prefetch=prefetch, exchange=exch, world=get_world_size(),
+                                     comm=self._communicator(w_in) if exch else None, all_reduce=utils.all_reduce_sum if exch else None, tail=True,
+                                     early_count=early, anchor_sync=sync, rank=get_rank() if sync else 0,
+                                     all_reduce_min=utils.all_reduce_min if sync else None)
         self.last_exchange_rows = out['cap_used']
-        self._listed = None                                      # (the hook-by-hook flow's prefetched list is void now)
-        if Store.DRY_RUN:
-            assert is_sync(w_out)
-        p_new = p_in
         if not inplace:
             self._update_probability(p_out)
-            p_new = p_out
-        if not w_inplace:
-            weight.data = w_out                                  # callbacks/update.py:56
-        q.invalidate_codebook()
+        self._publish_weight(weight, w_out)
         if prefetch:
-            st.mark_list(p_new)                                  # rows / slot / count now describe p_new (the call's last but one launch)
-        enc = get_memo(memo, 'encode')
-        prepared = out['prepared']
-        cos = out['xq'] is not None
-        x_op = x if (torch.is_grad_enabled() and x.requires_grad) else out['x']
-        enc['distance'] = LazyDistance(q.distance, x_op, e_alias, xq=out['xq'] if cos else out['x'],
-                                       eq=prepared.exact_rows() if cos else w_in, metric=ops.metric_name(prepared.metric))
-        enc['hist'] = out['hist']
-        memo['encode'] = enc
-        done = VF._Computed(z_ste=out['z_ste'], mse=out['mse'], idx=out['idx'])
-        z_ste, m_cb, m_cm, m_vqgan = VF.precomputed_decode_loss(x, weight, done, beta)
-        return out['idx'], z_ste, m_cb, m_cm, m_vqgan
+            st.note_prefetched(p_in if inplace else p_out)       # rows / slot / count now describe the new probabilities
+        q._encode_memo(memo, out, x if (torch.is_grad_enabled() and x.requires_grad) else out['x'], e_alias)
+        done = VF._Computed(xn=None, z_ste=out['z_ste'], mse=out['mse'], idx=out['idx'])
+        return (out['idx'],) + VF.vq_step(x, weight, done, beta)[1:]
 
     def after_encode(self, x: torch.Tensor, quant: torch.Tensor, memo: Memo) -> torch.Tensor:
         quant = super().after_encode(x, quant, memo)
@@ -614,11 +550,7 @@ class CVQVAECallback(UpdateMixin, BaseCallback):
                          self._ema.decay, self._eps)
             if not inplace:
                 self._update_probability(p_out)
-                self._update_embedding(w_out)
-            else:
-                if Store.DRY_RUN:
-                    assert is_sync(w_out)
-                self.vector_quantizer.invalidate_codebook()
+            self._update_embedding(w_out)
             return quant
         # the reference's data flow: statistics exchange, probability update, anchor sampler with its own exchange, blend
         e = self.quantizer.embeddings

@@ -9,12 +9,13 @@ import torch
 from torch import nn
 
 from .. import functional as VF
-from .. import ops
+from .. import ops, train_step
 from ..config import Config, Item, RegistryMeta
 from ..registries import InitRegistry, ModelRegistry, VQITQuantizerDistanceRegistry, VQITQuantizerRegistry
 from .memo import Memo, get_memo
 from .quantizer_api import BaseQuantizer
-from .distances import BaseDistance, LazyDistance
+from .callbacks import CVQVAECallback, NormalizeCallback, VQKDCallback
+from .distances import BaseDistance, CosineDistance, L2Distance, LazyDistance
 from .losses import CodebookLoss, CommitmentLoss, VQGANLoss
 
 
@@ -147,15 +148,19 @@ class VectorQuantizer(BaseQuantizer):
                 return False
         return True
 
-    def _loss_values(self, memo: Memo, m_cb, m_cm, m_vqgan, betas, like: torch.Tensor) -> torch.Tensor:
-        """memo['loss'][name] of every configured (plain MSE) loss from the three values the fused kernel finished, and
-        their fp32 sum (base.py:151-171)."""
+    def _vqgan_beta(self) -> float:
+        """beta of the (first) VQGANLoss: the combination m_cb + beta * m_cm that the fused kernels finish themselves."""
+        return next((loss.beta for loss in self._losses.values() if isinstance(loss, VQGANLoss)), 0.0)
+
+    def _loss_values(self, memo: Memo, m_cb, m_cm, m_vqgan, beta: float, like: torch.Tensor) -> torch.Tensor:
+        """memo['loss'][name] of every configured (plain MSE) loss from the three values the fused kernel finished (``m_vqgan``
+        with ``beta``), and their fp32 sum (base.py:151-171)."""
         losses = {}
         for name, loss in self._losses.items():
             if isinstance(loss, VQGANLoss):
                 # codebook + beta * commitment: finished inside the gather kernel for the (one) VQGANLoss of the shipped
                 # configs; a second VQGANLoss with another beta takes the two-term form
-                losses[name] = m_vqgan if loss.beta == betas[0] else torch.add(m_cb, m_cm, alpha=loss.beta)
+                losses[name] = m_vqgan if loss.beta == beta else torch.add(m_cb, m_cm, alpha=loss.beta)
             elif isinstance(loss, CodebookLoss):
                 losses[name] = m_cb
             else:
@@ -178,8 +183,6 @@ class VectorQuantizer(BaseQuantizer):
         if len(cbs) > 1 or type(self)._encode is not VectorQuantizer._encode or type(self)._decode is not VectorQuantizer._decode \
                 or type(self)._loss is not BaseQuantizer._loss or type(self).encode is not BaseQuantizer.encode:
             return None
-        from .callbacks import CVQVAECallback, NormalizeCallback, VQKDCallback
-        from .distances import CosineDistance, L2Distance
         if len(cbs) == 0 or type(cbs[0]) is NormalizeCallback:
             # no update callback (VQGAN: configs/vqgan/model.py:19-23), or NormalizeCallback alone (LlamaGen: configs/llamagen/
             # vqgan.py:18-20) — train and eval alike: vqhip_vq_forward
@@ -199,53 +202,51 @@ class VectorQuantizer(BaseQuantizer):
             return self._forward_vqkd if (ok and cb.fused_forward_ok(x)) else None
         return None
 
+    def _encode_memo(self, memo: Memo, out: dict, x_op: torch.Tensor, e_op: torch.Tensor) -> None:
+        """memo['encode'] of a one-call step (``out``: what train_step returned): the symbolic distance between ``x_op`` and
+        ``e_op`` (the operands with their graph, where there is one), evaluated on the exact operands the library's encode
+        used, and the code-hit histogram."""
+        enc = get_memo(memo, 'encode')
+        prepared = out['prepared']
+        if out['xq'] is not None:                                # cosine: the normalised rows / the image's exact rows
+            xq, eq = out['xq'], prepared.exact_rows()
+        else:
+            xq, eq = (out['xn'] if out.get('xn') is not None else out['x']), prepared.weight
+        enc['distance'] = LazyDistance(self._distance, x_op, e_op, xq=xq, eq=eq, metric=ops.metric_name(prepared.metric))
+        if out['hist'] is not None:
+            enc['hist'] = out['hist']
+        memo['encode'] = enc
+
     def _forward_cvq(self, x: torch.Tensor, memo: Memo):
-        cb = self._callbacks.callbacks[0]
-        betas = [loss.beta for loss in self._losses.values() if isinstance(loss, VQGANLoss)]
-        quant, z_ste, m_cb, m_cm, m_vqgan = cb.fused_forward(x, memo, betas[0] if betas else 0.0)
+        beta = self._vqgan_beta()
+        quant, z_ste, m_cb, m_cm, m_vqgan = self._callbacks.callbacks[0].fused_forward(x, memo, beta)
         memo.update(x=x, quant=quant)
         memo['decode'] = get_memo(memo, 'decode')
-        return z_ste, self._loss_values(memo, m_cb, m_cm, m_vqgan, betas, x), memo
+        return z_ste, self._loss_values(memo, m_cb, m_cm, m_vqgan, beta, x), memo
 
     def _forward_plain(self, x: torch.Tensor, memo: Memo):
         """encode (+ NormalizeCallback.before_encode) + decode + MSE losses + STE from one library call (train_step.vq_forward)."""
-        from .. import train_step
         cbs = self._callbacks.callbacks
         weight = self._embedding.weight
-        D = weight.shape[1]
         normalize = len(cbs) == 1
         w_in = weight.detach()
         w_out = None
         if normalize:
             w_out = w_in if cbs[0]._writes_in_place(weight) else torch.empty_like(w_in)
-        betas = [loss.beta for loss in self._losses.values() if isinstance(loss, VQGANLoss)]
-        beta = betas[0] if betas else 0.0
-        want_hist = self.training and len(cbs) > 0
-        out = train_step.vq_forward(x.detach(), w_in, w_out, self._distance.metric_for(D), beta, normalize=normalize, want_hist=want_hist)
+        beta = self._vqgan_beta()
+        out = train_step.vq_forward(x.detach(), w_in, w_out, self._distance.metric_for(weight.shape[1]), beta, normalize=normalize,
+                                    want_hist=self.training and len(cbs) > 0)
         if normalize:
-            from ..utils import Store, is_sync
-            if Store.DRY_RUN:
-                assert is_sync(w_out)
-            if w_out.data_ptr() != weight.data_ptr():
-                weight.data = w_out                              # callbacks/update.py:56
-            self.invalidate_codebook()
+            cbs[0]._publish_weight(weight, w_out)
         done = VF._Computed(xn=out['xn'], z_ste=out['z_ste'], mse=out['mse'], idx=out['idx'])
         xn, z_ste, m_cb, m_cm, m_vqgan = VF.vq_step(x, weight, done, beta)
         rows = xn if normalize else x
-        enc = get_memo(memo, 'encode')
-        prepared = out['prepared']
-        cos = out['xq'] is not None
         grad = torch.is_grad_enabled() and (x.requires_grad or weight.requires_grad)
-        e_op = weight.view_as(weight) if (grad and weight.requires_grad) else prepared.weight
-        enc['distance'] = LazyDistance(self._distance, rows if grad else (out['xn'] if normalize else out['x']), e_op,
-                                       xq=out['xq'] if cos else (out['xn'] if normalize else out['x']),
-                                       eq=prepared.exact_rows() if cos else prepared.weight, metric=ops.metric_name(prepared.metric))
-        if out['hist'] is not None:
-            enc['hist'] = out['hist']
-        memo['encode'] = enc
+        self._encode_memo(memo, out, rows if grad else (out['xn'] if normalize else out['x']),
+                          weight.view_as(weight) if (grad and weight.requires_grad) else out['prepared'].weight)
         memo.update(x=rows, quant=out['idx'])
         memo['decode'] = get_memo(memo, 'decode')
-        return z_ste, self._loss_values(memo, m_cb, m_cm, m_vqgan, betas, x), memo
+        return z_ste, self._loss_values(memo, m_cb, m_cm, m_vqgan, beta, x), memo
 
     def _forward_vqkd(self, x: torch.Tensor, memo: Memo):
         cb = self._callbacks.callbacks[0]
@@ -270,10 +271,10 @@ class VectorQuantizer(BaseQuantizer):
             return z, loss, memo
         x, quant, memo = self.encode(x, memo)
         memo.update(x=x, quant=quant)
-        betas = [loss.beta for loss in self._losses.values() if isinstance(loss, VQGANLoss)]
-        z_ste, m_cb, m_cm, m_vqgan = VF.fused_decode_loss(x, self._embedding.weight, quant, betas[0] if betas else 0.0)
+        beta = self._vqgan_beta()
+        z_ste, m_cb, m_cm, m_vqgan = VF.fused_decode_loss(x, self._embedding.weight, quant, beta)
         memo['decode'] = get_memo(memo, 'decode')
-        return z_ste, self._loss_values(memo, m_cb, m_cm, m_vqgan, betas, x), memo
+        return z_ste, self._loss_values(memo, m_cb, m_cm, m_vqgan, beta, x), memo
 
 
     # ---- the same three entry points on the NCHW feature map (models/base.py:116-146) --------------------
@@ -317,10 +318,10 @@ class VectorQuantizer(BaseQuantizer):
         assert self.map_fusable(x_map) and self._fusable()
         x_rows, quant, memo = self.encode_map(x_map, memo)
         memo.update(x=x_rows, quant=quant)
-        betas = [loss.beta for loss in self._losses.values() if isinstance(loss, VQGANLoss)]
-        z_map, m_cb, m_cm, m_vqgan = VF.fused_map_decode_loss(x_map, x_rows, self._embedding.weight, quant, betas[0] if betas else 0.0)
+        beta = self._vqgan_beta()
+        z_map, m_cb, m_cm, m_vqgan = VF.fused_map_decode_loss(x_map, x_rows, self._embedding.weight, quant, beta)
         memo['decode'] = get_memo(memo, 'decode')
-        loss = self._loss_values(memo, m_cb, m_cm, m_vqgan, betas, x_map)
+        loss = self._loss_values(memo, m_cb, m_cm, m_vqgan, beta, x_map)
         return z_map, loss, memo
 
     def decode_map(self, quant: torch.Tensor, memo: Memo) -> tuple[torch.Tensor, Memo]:
