@@ -3,10 +3,14 @@
 MFMA, itself bit-equal to the CPU oracle in tests/) at sizes the CPU oracle cannot reach.  Any mismatch is a bug.
 usage: fuzz_vs_exact.py [seconds] [seed]   (VQ_FUZZ_DIMS=8,16: only those D; VQ_FUZZ_SMALL_N=1: 64 .. 16 384 rows against >= 4096 codes;
 VQ_FUZZ_FORCE_EXACT=1: see below; VQ_FUZZ_BF16=1: bf16 latents in every trial — with VQ_FUZZ_DIMS=256 the batches of more than
-16 384 rows take the proposal kernel that makes its own token fragments)"""
+16 384 rows take the proposal kernel that makes its own token fragments; VQ_FUZZ_HOSTILE=1: only the hostile families of
+oracle/hostile.py — kinds 7 and up: single channels, single codes and single rows at the edges of the fp16 images — which
+otherwise are one kind in four)"""
 import os, sys, time
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
+import numpy as np
 import torch
+from oracle import hostile
 from vector_quantization_amd import ops
 
 budget = float(sys.argv[1]) if len(sys.argv) > 1 else 120.0
@@ -25,7 +29,8 @@ while time.time() < t_end:
         K = [8192, 16384, ri(4096, 20000)][ri(0, 3)]
     if N * K * D > 3e12: N = max(1, int(3e12 / (K * D)))
     metric = 'L2' if ri(0, 3) else ('Cosine' if ri(0, 3) else 'CosineBF16')     # CosineBF16: the bf16-autocast semantics (opt-in)
-    kind = ri(0, 7)
+    HOSTILE = list(hostile.CASES)
+    kind = 7 + ri(0, len(HOSTILE)) if (os.environ.get('VQ_FUZZ_HOSTILE') == '1' or ri(0, 4) == 0) else ri(0, 7)
     scale = 10.0 ** ri(-4, 5)
     w = torch.randn(K, D, device='cuda', generator=g)
     x = torch.randn(N, D, device='cuda', generator=g)
@@ -42,6 +47,10 @@ while time.time() < t_end:
     elif kind == 6:  # unit-norm codebook (NormalizeCallback): L2 takes the constant-norm form (no bias term in the proposal scores)
         w = torch.nn.functional.normalize(w)
         if ri(0, 2): x = torch.nn.functional.normalize(x)
+    elif kind >= 7:  # a hostile family (oracle/hostile.py), made on the host at this trial's shape; the families carry their own scales
+        N = min(N, 100000)
+        xh, wh = hostile.make(HOSTILE[kind - 7], ri(0, 1 << 30), N, max(K, 2), D)
+        x, w, K, scale = torch.from_numpy(xh).cuda(), torch.from_numpy(wh).cuda(), max(K, 2), 1.0
     x, w = x * scale, w * scale
     if 'VQ_FUZZ_FORCE_EXACT' in os.environ:        # send the first V rows of every batch through the last-resort fp32 pass as well
         from vector_quantization_amd import _lib       # (tuning key 12: both forms of that pass, list lengths around the switch at 16)
@@ -70,6 +79,7 @@ while time.time() < t_end:
     # ordered (deterministic) centroid sums against a float64 index_add, and bit-reproducibility
     if K <= 32768 and D % 4 == 0 and ri(0, 8) == 0:
         a = ops.scatter_add_rows(x, ref, K, ordered=True); b = ops.scatter_add_rows(x, ref, K, ordered=True)
+        if kind >= 7: x = x.clamp(-1e30, 1e30)     # (hostile rows may overflow a float32 sum of N of them)
         r64 = torch.zeros(K, D, dtype=torch.float64, device='cuda').index_add_(0, ref, x.double())
         tol = 1e-5 * float(x.abs().max()) * max(1.0, N / K) + 1e-30
         if not torch.equal(a, b) or float((a.double() - r64).abs().max()) > tol * 50:

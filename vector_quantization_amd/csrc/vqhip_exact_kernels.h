@@ -8,7 +8,9 @@
 // STRICTLY smaller distance; sqrt is correctly rounded, hence monotone: radicand t >= tb (the smallest radicand the lane has
 // keyed) implies sqrt(t) >= sqrt(tb) and the code cannot win — its sqrt and key (the larger half of the epilogue's
 // instructions) are skipped.  NaN radicands never compare >= and always go through (NaN sorts first in dist_key).
-__device__ __forceinline__ bool l2_skip(float t, float tb) { return t >= tb; }
+// tb starts at +inf ("nothing keyed yet"): a radicand of +inf (|x|^2 overflows fp32: every distance of the row is inf and
+// index 0 wins) must not be skipped against that start value, or the row never produces a key and keeps its 0xFFFFFFFF.
+__device__ __forceinline__ bool l2_skip(float t, float tb) { return t >= tb && tb < INFINITY; }
 
 // Last-resort path of vqhip_argmin (MFMA form, long lists): LISTED rows against the whole codebook, row argmin via 64-bit atomicMin keys[row].
 // Work item = (tile of 32 listed rows, chunk of 128 codes: one 32-code tile per wave); persistent grid-stride loop over items.
