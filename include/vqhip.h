@@ -219,6 +219,32 @@ int vqhip_fsq_backward(const vqhip_fsq_t *q, const void *x, int x_dtype, int lay
 int vqhip_fsq_decode(const vqhip_fsq_t *q, const void *quant, int quant_dtype, int layout, int64_t N, int64_t HW, float *z,
                      void *stream);
 
+/* ---- EntropyLoss (vq/algorithms/vq/losses.py:130-153) on row blocks of the distance matrix ------------------------------
+ * With a = d / T, p = softmax(a, -1), q_k = (1/N) sum_n p_nk:
+ *   L = (1/N) sum_n (lse_n - sum_k p_nk a_nk) + sum_k q_k log(q_k + 1e-5)
+ *   dL/da_nj = (p_nj / N) (c_j - a_nj - S_n),  c_k = log(q_k + 1e-5) + q_k / (q_k + 1e-5),  S_n = sum_k p_nk (c_k - a_nk).
+ * The caller walks the rows in blocks: `tile` is the dense fp32 [R, K] block of distances (vqhip_distance of a row slice),
+ * 16-byte aligned.  No [N, K] object is needed: forward = vqhip_entropy_rows per block, then vqhip_entropy_finish once;
+ * backward = vqhip_entropy_grad per block on the recomputed tile.  All sums run in a fixed order (no atomics).
+ * `ws`: vqhip_entropy_workspace_bytes(R, K) bytes of scratch (column partials), reusable from block to block.
+ * LIMITS (VQHIP_EINVAL before any launch): 1 <= R < 2^31, 1 <= K <= 2^31 - 2048 (a row is indexed with int), T finite and
+ * non-zero (negative allowed), metric L2 or COS.  The tile's R * K elements are addressed in int64; bounding its bytes is the
+ * caller's business (ops.py: 64 MiB). */
+int64_t vqhip_entropy_workspace_bytes(int64_t R, int64_t K);
+/* lse[R], spa[R] = sum_k p a of the block's rows; qacc double[K] (+)= sum over the block's rows of p_nk (init != 0: the
+ * first block, qacc is overwritten). */
+int vqhip_entropy_rows(const float *tile, int64_t R, int64_t K, float temperature, float *lse, float *spa, double *qacc,
+                       int init, void *ws, int64_t ws_bytes, void *stream);
+/* after the last block: q[K] = qacc / N, c[K], loss[1] from lse[N], spa[N] of all rows */
+int vqhip_entropy_finish(const float *lse, const float *spa, const double *qacc, int64_t N, int64_t K, float *q, float *c,
+                         float *loss, void *stream);
+/* tile <- upstream * dL/dd = upstream * dL/da / T (COS), divided once more by d with 0 where d == 0 (L2: the G of
+ * torch.cdist's backward); rowsum[R] = its row sums; L2 only: colacc double[K] (+)= its column sums (init as above; COS
+ * ignores colacc and ws).  lse, spa: this block's rows; inv_nt = 1 / (N T); upstream: DEVICE scalar (null = 1). */
+int vqhip_entropy_grad(float *tile, int64_t R, int64_t K, float temperature, const float *lse, const float *spa,
+                       const float *c, float inv_nt, const float *upstream, int metric, float *rowsum, double *colacc,
+                       int init, void *ws, int64_t ws_bytes, void *stream);
+
 /* dst[idx[n], :] += src[n, :]  (centroids.scatter_add_, vqkd/quantizers/callbacks.py:60-62; also the
  * dense embedding backward).  fp32 atomics. */
 int vqhip_scatter_add_rows(const float *src, const int64_t *idx, int64_t N, int64_t K, int D, float *dst,

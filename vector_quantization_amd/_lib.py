@@ -98,6 +98,10 @@ SIGNATURES = {
     'vqhip_fsq_encode': (_i32, [ctypes.POINTER(FsqConstants), _vp, _i32, _i32, _i64, _i64, _vp, _vp, _i32, _vp, _vp, _vp]),
     'vqhip_fsq_backward': (_i32, [ctypes.POINTER(FsqConstants), _vp, _i32, _i32, _i64, _i64, _vp, _vp, _vp]),
     'vqhip_fsq_decode': (_i32, [ctypes.POINTER(FsqConstants), _vp, _i32, _i32, _i64, _i64, _vp, _vp]),
+    'vqhip_entropy_workspace_bytes': (_i64, [_i64, _i64]),
+    'vqhip_entropy_rows': (_i32, [_vp, _i64, _i64, _f32, _vp, _vp, _vp, _i32, _vp, _i64, _vp]),
+    'vqhip_entropy_finish': (_i32, [_vp, _vp, _vp, _i64, _i64, _vp, _vp, _vp, _vp]),
+    'vqhip_entropy_grad': (_i32, [_vp, _i64, _i64, _f32, _vp, _vp, _vp, _f32, _vp, _i32, _vp, _vp, _i32, _vp, _i64, _vp]),
     'vqhip_scatter_add_rows': (_i32, [_vp, _vp, _i64, _i64, _i32, _vp, _vp]),
     'vqhip_vqkd_update': (_i32, [_vp, _vp, _vp, _i64, _i32, _f32, _i32, _vp]),
     'vqhip_cvq_update': (_i32, [_vp, _vp, _vp, _i64, _vp, _vp, _i64, _i32, _f32, _f32, _i32, _vp]),

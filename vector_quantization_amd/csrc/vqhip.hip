@@ -7,6 +7,7 @@
 
 #include "vqhip_kernels.h"
 #include "vqhip_fsq_kernels.h"
+#include "vqhip_entropy_kernels.h"
 
 static thread_local char g_err[256] = "";
 
@@ -1199,6 +1200,86 @@ int vqhip_fsq_decode(const vqhip_fsq_t *q, const void *quant, int quant_dtype, i
 #undef VQ_FSQ_DEC
     VQ_CHECK_LAUNCH("fsq_decode_kernel");
     return VQHIP_OK;
+}
+
+// ---- EntropyLoss on row blocks of the distance matrix (vqhip_entropy_kernels.h) ----------------------------------------
+static int entropy_check(const char *what, int64_t R, int64_t K, float T) {
+    // the kernels index a row with int and step by up to VQ_ENT_COLS past K before they stop; R * K elements are addressed in int64
+    if (R <= 0 || K <= 0 || R >= (1ll << 31) || K > (1ll << 31) - 2 * VQ_ENT_COLS) return fail(VQHIP_EINVAL, what, "R must be in 1 .. 2^31 - 1, K in 1 .. 2^31 - 2048");
+    if (!(T == T) || T == 0.0f || T - T != 0.0f) return fail(VQHIP_EINVAL, what, "the temperature must be finite and non-zero");
+    return VQHIP_OK;
+}
+
+int64_t vqhip_entropy_workspace_bytes(int64_t R, int64_t K) {
+    if (R <= 0 || K <= 0) return 0;
+    return ((R + VQ_ENT_CHUNK - 1) / VQ_ENT_CHUNK) * K * (int64_t)sizeof(double);
+}
+
+// column sums of the tile (MODE 0: of p, MODE 1: of its values) added into acc[K], chunk by chunk
+static int entropy_colsums(int mode, const float *tile, int64_t R, int64_t K, float T, const float *lse, double *acc, int init,
+                           void *ws, hipStream_t s) {
+    const int nchunks = (int)((R + VQ_ENT_CHUNK - 1) / VQ_ENT_CHUNK);
+    const dim3 grid((unsigned)((K + VQ_ENT_COLS - 1) / VQ_ENT_COLS), (unsigned)(nchunks < 65535 ? nchunks : 65535));
+#define VQ_ENT_COL(MODE, VEC) entropy_colsum_kernel<MODE, VEC><<<grid, 256, 0, s>>>(tile, (int)R, (int)K, T, lse, (double *)ws)
+    if (K % 4 == 0) { if (mode == 0) VQ_ENT_COL(0, true); else VQ_ENT_COL(1, true); }
+    else { if (mode == 0) VQ_ENT_COL(0, false); else VQ_ENT_COL(1, false); }
+#undef VQ_ENT_COL
+    VQ_CHECK_LAUNCH("entropy_colsum_kernel");
+    int rgrid = (int)((K + 255) / 256); rgrid = rgrid > 4096 ? 4096 : rgrid;
+    entropy_colreduce_kernel<<<rgrid, 256, 0, s>>>((const double *)ws, nchunks, (int)K, acc, init);
+    VQ_CHECK_LAUNCH("entropy_colreduce_kernel");
+    return VQHIP_OK;
+}
+
+int vqhip_entropy_rows(const float *tile, int64_t R, int64_t K, float temperature, float *lse, float *spa, double *qacc,
+                       int init, void *ws, int64_t ws_bytes, void *stream) {
+    const char *what = "vqhip_entropy_rows";
+    if (int rc = entropy_check(what, R, K, temperature)) return rc;
+    if (!tile || !lse || !spa || !qacc || !ws) return fail(VQHIP_EINVAL, what, "null pointer");
+    if ((uintptr_t)tile % 16) return fail(VQHIP_EINVAL, what, "the tile must be 16-byte aligned");
+    VQ_NEED("vqhip_entropy_rows: ws too small", ws_bytes, vqhip_entropy_workspace_bytes(R, K));
+    hipStream_t s = (hipStream_t)stream;
+    int grid = waves_grid(R, 4); grid = grid > 8192 ? 8192 : grid;
+    if (K % 4 == 0) entropy_rows_kernel<true><<<grid, 256, 0, s>>>(tile, (int)R, (int)K, temperature, lse, spa);
+    else entropy_rows_kernel<false><<<grid, 256, 0, s>>>(tile, (int)R, (int)K, temperature, lse, spa);
+    VQ_CHECK_LAUNCH("entropy_rows_kernel");
+    return entropy_colsums(0, tile, R, K, temperature, lse, qacc, init, ws, s);
+}
+
+int vqhip_entropy_finish(const float *lse, const float *spa, const double *qacc, int64_t N, int64_t K, float *q, float *c,
+                         float *loss, void *stream) {
+    const char *what = "vqhip_entropy_finish";
+    if (int rc = entropy_check(what, N, K, 1.0f)) return rc;
+    if (!lse || !spa || !qacc || !q || !c || !loss) return fail(VQHIP_EINVAL, what, "null pointer");
+    entropy_finish_kernel<<<1, 256, 0, (hipStream_t)stream>>>(lse, spa, qacc, (int)N, (int)K, q, c, loss);
+    VQ_CHECK_LAUNCH("entropy_finish_kernel");
+    return VQHIP_OK;
+}
+
+int vqhip_entropy_grad(float *tile, int64_t R, int64_t K, float temperature, const float *lse, const float *spa,
+                       const float *c, float inv_nt, const float *upstream, int metric, float *rowsum, double *colacc,
+                       int init, void *ws, int64_t ws_bytes, void *stream) {
+    const char *what = "vqhip_entropy_grad";
+    if (int rc = entropy_check(what, R, K, temperature)) return rc;
+    if (metric != VQHIP_METRIC_L2 && metric != VQHIP_METRIC_COS) return fail(VQHIP_EINVAL, what, "metric (L2 or COS)");
+    if (!tile || !lse || !spa || !c || !rowsum) return fail(VQHIP_EINVAL, what, "null pointer");
+    if ((uintptr_t)tile % 16) return fail(VQHIP_EINVAL, what, "the tile must be 16-byte aligned");
+    if (!(inv_nt == inv_nt) || inv_nt - inv_nt != 0.0f) return fail(VQHIP_EINVAL, what, "inv_nt must be finite");
+    const bool l2 = metric == VQHIP_METRIC_L2;
+    if (l2) {
+        if (!colacc || !ws) return fail(VQHIP_EINVAL, what, "L2 needs colacc and ws");
+        VQ_NEED("vqhip_entropy_grad: ws too small", ws_bytes, vqhip_entropy_workspace_bytes(R, K));
+    }
+    hipStream_t s = (hipStream_t)stream;
+    int grid = waves_grid(R, 4); grid = grid > 8192 ? 8192 : grid;
+    const int r = (int)R, k = (int)K;
+#define VQ_ENT_GRAD(VEC, L2) entropy_grad_kernel<VEC, L2><<<grid, 256, 0, s>>>(tile, r, k, temperature, lse, spa, c, inv_nt, upstream, rowsum)
+    if (K % 4 == 0) { if (l2) VQ_ENT_GRAD(true, true); else VQ_ENT_GRAD(true, false); }
+    else { if (l2) VQ_ENT_GRAD(false, true); else VQ_ENT_GRAD(false, false); }
+#undef VQ_ENT_GRAD
+    VQ_CHECK_LAUNCH("entropy_grad_kernel");
+    if (!l2) return VQHIP_OK;
+    return entropy_colsums(1, tile, R, K, temperature, lse, colacc, init, ws, s);
 }
 
 int vqhip_scatter_add_rows(const float *src, const int64_t *idx, int64_t N, int64_t K, int D, float *dst, void *stream) {

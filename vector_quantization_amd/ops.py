@@ -256,19 +256,123 @@ def argmin_exact(x: torch.Tensor, e: torch.Tensor, metric='L2', hist: Optional[t
 
 
 @_on_tensor_device
-def distance(x: torch.Tensor, e: torch.Tensor, metric='L2') -> torch.Tensor:
-    """Materialised d[N, K] (memo['distance']); x, e normalised by the caller for cosine."""
+def distance(x: torch.Tensor, e: torch.Tensor, metric='L2', out: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """Materialised d[N, K] (memo['distance']); x, e normalised by the caller for cosine.  ``out``: a dense fp32 [N, K]
+    buffer to fill instead of a new one (the row blocks of ``entropy_loss``)."""
     _require_cuda(x, e)
     x, dt = _latents(x)
     e = _codebook(e)
     N, D = x.shape
     K = e.shape[0]
     L = _lib.lib()
-    d = torch.empty(N, K, dtype=torch.float32, device=x.device)
+    if out is not None:
+        assert out.dtype == torch.float32 and tuple(out.shape) == (N, K) and out.is_contiguous() and out.device == x.device
+    d = out if out is not None else torch.empty(N, K, dtype=torch.float32, device=x.device)
     ws = _bytes(L.vqhip_workspace_bytes(N, K, D), x.device)
     check(L.vqhip_distance(_ptr(x), dt, _ptr(e), N, K, D, METRICS[metric], _ptr(d), _ptr(ws), ws.numel(), _stream()),
           'vqhip_distance')
     return d
+
+
+ENTROPY_TILE_BYTES = 64 << 20      # workspace cap of entropy_loss: one [R, K] fp32 tile (stays in the 256 MiB Infinity Cache)
+
+
+def entropy_block_rows(N: int, K: int, tile_bytes: int = ENTROPY_TILE_BYTES) -> int:
+    """Rows per block of ``entropy_loss``: as many as keep the [R, K] fp32 tile within ``tile_bytes`` (at least one)."""
+    return max(1, min(int(N), int(tile_bytes) // (4 * int(K))))
+
+
+def _entropy_args(x, e, metric, temperature, block_rows):
+    import math
+    _require_cuda(x, e)
+    m = METRICS[metric]
+    if m not in (METRIC_L2, METRIC_COS):
+        raise ValueError(f"entropy_loss: metric must be 'L2' or 'Cosine', got {metric!r}")
+    T = float(temperature)
+    if T == 0.0 or not math.isfinite(T):
+        raise ValueError(f'entropy_loss: the temperature must be finite and non-zero, got {temperature!r}')
+    x, _ = _latents(x)
+    e = _codebook(e)
+    N, D = x.shape
+    K = e.shape[0]
+    if D != e.shape[1]:
+        raise ValueError(f'latent dim {D} != codebook dim {e.shape[1]}')
+    if N < 1 or K < 1:
+        raise ValueError('entropy_loss needs N >= 1 and K >= 1')
+    R = entropy_block_rows(N, K) if block_rows is None else int(block_rows)
+    if R < 1:
+        raise ValueError(f'entropy_loss: block_rows must be >= 1, got {block_rows!r}')
+    return x, e, m, T, N, K, D, min(R, N)
+
+
+@_on_tensor_device
+def entropy_loss(x: torch.Tensor, e: torch.Tensor, metric='L2', temperature: float = 1.0, block_rows: Optional[int] = None):
+    """EntropyLoss (vq/algorithms/vq/losses.py:139-153) of the distances of x [N, D] to e [K, D] without the [N, K] matrix:
+    rows go through one [block_rows, K] fp32 tile (default: what fits ``ENTROPY_TILE_BYTES``) — ``distance`` fills it,
+    vqhip_entropy_rows reduces it.  x, e normalised by the caller for cosine.  Returns (loss fp32 0-dim, saved) with
+    saved = dict(lse[N], spa[N], q[K], c[K], block_rows) for ``entropy_loss_backward``; nothing in it grows with N * K."""
+    x, e, m, T, N, K, D, R = _entropy_args(x, e, metric, temperature, block_rows)
+    L = _lib.lib()
+    dev = x.device
+    tile = _bytes(R * K * 4, dev)[:R * K * 4].view(torch.float32)
+    ws = _bytes(L.vqhip_entropy_workspace_bytes(R, K), dev)
+    lse = torch.empty(N, dtype=torch.float32, device=dev)
+    spa = torch.empty(N, dtype=torch.float32, device=dev)
+    qacc = torch.empty(K, dtype=torch.float64, device=dev)
+    for r0 in range(0, N, R):
+        r = min(R, N - r0)
+        t = tile[:r * K].view(r, K)
+        distance(x[r0:r0 + r], e, m, out=t)
+        check(L.vqhip_entropy_rows(_ptr(t), r, K, T, _ptr(lse[r0:]), _ptr(spa[r0:]), _ptr(qacc), 1 if r0 == 0 else 0,
+                                   _ptr(ws), ws.numel(), _stream()), 'vqhip_entropy_rows')
+    q = torch.empty(K, dtype=torch.float32, device=dev)
+    c = torch.empty(K, dtype=torch.float32, device=dev)
+    loss = torch.empty(1, dtype=torch.float32, device=dev)
+    check(L.vqhip_entropy_finish(_ptr(lse), _ptr(spa), _ptr(qacc), N, K, _ptr(q), _ptr(c), _ptr(loss), _stream()),
+          'vqhip_entropy_finish')
+    return loss.reshape(()), dict(lse=lse, spa=spa, q=q, c=c, block_rows=R)
+
+
+@_on_tensor_device
+def entropy_loss_backward(x: torch.Tensor, e: torch.Tensor, metric, temperature: float, saved: dict,
+                          upstream: Optional[torch.Tensor] = None, need_x: bool = True, need_e: bool = True):
+    """(grad_x fp32 [N, D], grad_e fp32 [K, D]) of ``entropy_loss`` times the device scalar ``upstream`` (None = 1); an output
+    that is not needed is None.  One more sweep of the row blocks: the tile is recomputed, vqhip_entropy_grad overwrites it with
+    dL/dd (cosine) or G = dL/dd / d, 0 where d == 0 (L2), and two library GEMMs per block contract it with the operands exactly
+    as ``distances._L2Matrix`` / ``_DotMatrix`` do: L2  dx = x rowsum(G) - G e,  de = e colsum(G) - G^T x;
+    cosine  dx = -g e,  de = -g^T x.  grad_e is accumulated block by block in block order."""
+    x, e, m, T, N, K, D, R = _entropy_args(x, e, metric, temperature, saved['block_rows'])
+    L = _lib.lib()
+    dev = x.device
+    l2 = m == METRIC_L2
+    if upstream is not None:
+        upstream = upstream.detach().reshape(1).to(device=dev, dtype=torch.float32).contiguous()
+    tile = _bytes(R * K * 4, dev)[:R * K * 4].view(torch.float32)
+    ws = _bytes(L.vqhip_entropy_workspace_bytes(R, K), dev) if l2 else None
+    rowsum = torch.empty(R, dtype=torch.float32, device=dev)
+    colacc = torch.empty(K, dtype=torch.float64, device=dev) if l2 else None
+    gx = torch.empty(N, D, dtype=torch.float32, device=dev) if need_x else None
+    ge = torch.zeros(K, D, dtype=torch.float32, device=dev) if need_e else None
+    lse, spa = saved['lse'], saved['spa']
+    for r0 in range(0, N, R):
+        r = min(R, N - r0)
+        t = tile[:r * K].view(r, K)
+        xb = x[r0:r0 + r]
+        distance(xb, e, m, out=t)
+        check(L.vqhip_entropy_grad(_ptr(t), r, K, T, _ptr(lse[r0:]), _ptr(spa[r0:]), _ptr(saved['c']), 1.0 / (N * T),
+                                   _ptr(upstream), m, _ptr(rowsum), _ptr(colacc), 1 if r0 == 0 else 0, _ptr(ws),
+                                   ws.numel() if ws is not None else 0, _stream()), 'vqhip_entropy_grad')
+        xb32 = xb.float()
+        if need_x:
+            if l2:
+                torch.sub(xb32 * rowsum[:r].unsqueeze(1), t @ e, out=gx[r0:r0 + r])
+            else:
+                torch.neg(t @ e, out=gx[r0:r0 + r])
+        if need_e:
+            ge.addmm_(t.t(), xb32, alpha=-1.0)
+    if need_e and l2:
+        ge.add_(e * colacc.float().unsqueeze(1))
+    return gx, ge
 
 
 @_on_tensor_device

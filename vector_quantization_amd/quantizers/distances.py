@@ -57,6 +57,29 @@ class _DotMatrix(Function):
         return gx, ge, None
 
 
+class _EntropyMatrix(Function):
+    """EntropyLoss (vq/algorithms/vq/losses.py:139-153) of the distance matrix of (x, e) WITHOUT the matrix: the forward walks
+    the rows in blocks of one bounded [R, K] tile (ops.entropy_loss) and saves lse[N], sum p a [N], q[K], c[K] and the operands;
+    the backward recomputes each tile, turns it into dL/dd in place and continues through the distance exactly as
+    ``_L2Matrix`` / ``_DotMatrix`` do (ops.entropy_loss_backward).  For 'Cosine' the operands are already normalised."""
+
+    @staticmethod
+    def forward(ctx, x: torch.Tensor, e: torch.Tensor, metric: str, temperature: float, block_rows: Optional[int] = None):
+        loss, saved = ops.entropy_loss(x.detach(), e.detach(), metric, temperature, block_rows)
+        ctx.save_for_backward(x, e, saved['lse'], saved['spa'], saved['q'], saved['c'])
+        ctx.metric, ctx.temperature, ctx.block_rows = metric, temperature, saved['block_rows']
+        return loss
+
+    @staticmethod
+    def backward(ctx, g):
+        x, e, lse, spa, q, c = ctx.saved_tensors
+        saved = dict(lse=lse, spa=spa, q=q, c=c, block_rows=ctx.block_rows)
+        with torch.autocast('cuda', enabled=False):
+            gx, ge = ops.entropy_loss_backward(x, e, ctx.metric, ctx.temperature, saved, upstream=g,
+                                               need_x=ctx.needs_input_grad[0], need_e=ctx.needs_input_grad[1])
+        return (None if gx is None else gx.to(x.dtype)), (None if ge is None else ge.to(e.dtype)), None, None, None
+
+
 class LazyDistance(torch.Tensor):
     """memo['distance'] (vq/algorithms/vq/quantizers.py:98) without the cost: a tensor-typed handle of shape [N, K]
     whose values are produced (by the HIP distance kernel, with autograd to x and the codebook) only when a consumer
@@ -100,6 +123,11 @@ class LazyDistance(torch.Tensor):
         if self._value is None:
             self._value = self._distance.matrix(self._x, self._e, self._metric)
         return self._value
+
+    def entropy(self, temperature: float, block_rows: Optional[int] = None) -> torch.Tensor:
+        """EntropyLoss of this matrix (before todd's weight) with autograd to the latents and the codebook, without
+        materialising it: ``_EntropyMatrix`` on the handle's operands and metric ('L2' and 'Cosine')."""
+        return self._distance.entropy(self._x, self._e, temperature, self._metric, block_rows)
 
     def fused_argmin(self, dim: int) -> torch.Tensor:
         if dim == 0:        # NearestAnchor: d.argmin(0) — nearest latent per code
@@ -172,6 +200,19 @@ class BaseDistance(nn.Module, ABC):
         """The codebook operand of the fp32 definition alone."""
         return e.detach()
 
+    FUSED_ENTROPY_METRICS: tuple = ()        # metrics whose matrix ``entropy`` reproduces (the shipped distances name theirs)
+
+    def entropy(self, x: torch.Tensor, e: torch.Tensor, temperature: float, metric: Optional[str] = None,
+                block_rows: Optional[int] = None) -> torch.Tensor:
+        """EntropyLoss of ``matrix(x, e, metric)`` from one bounded row-block tile (``_EntropyMatrix``)."""
+        metric = metric or self.metric
+        if metric not in self.FUSED_ENTROPY_METRICS:
+            raise ValueError(f'the fused EntropyLoss exists for {self.FUSED_ENTROPY_METRICS}, not for {metric!r}')
+        x = x.reshape(-1, x.shape[-1])
+        if metric == 'Cosine':
+            x, e = VF.normalize(x), VF.normalize(e)
+        return _EntropyMatrix.apply(x, e, metric, temperature, block_rows)
+
     def metric_for(self, D: int) -> str:
         """The metric of a fused encode over D-dimensional rows (``metric``, unless a distance narrows it by D)."""
         return self.metric
@@ -226,6 +267,7 @@ class BaseDistance(nn.Module, ABC):
 @VQITQuantizerDistanceRegistry.register_()
 class L2Distance(BaseDistance):
     metric = 'L2'
+    FUSED_ENTROPY_METRICS = ('L2',)
 
     def forward(self, x: torch.Tensor, e: torch.Tensor) -> torch.Tensor:
         """torch.cdist(x, e) (mm path), fp32, differentiable."""
@@ -262,6 +304,8 @@ class CosineDistance(BaseDistance):
     The products are summed in the fp32 definition's order, so a row can differ from one particular GEMM's summation
     order only where the fp32 sum straddles a bf16 rounding boundary.  Gradients of a materialised matrix are those of
     the fp32 definition (straight through the rounding)."""
+
+    FUSED_ENTROPY_METRICS = ('Cosine',)
 
     def __init__(self, *args, autocast: Optional[str] = 'auto', **kwargs) -> None:
         super().__init__(*args, **kwargs)

@@ -12,7 +12,7 @@ from .. import functional as VF
 from ..config import BuildPreHookMixin, Config, Item, RegistryMeta
 from ..registries import VQITQuantizerLossRegistry
 from .memo import Memo
-from .distances import as_distance_tensor
+from .distances import LazyDistance, as_distance_tensor
 
 
 class _Weight(nn.Module):
@@ -129,17 +129,34 @@ class VQGANLoss(BuildPreHookMixin, BaseLoss):
 @VQITQuantizerLossRegistry.register_()
 class EntropyLoss(BaseLoss):
     """vq/algorithms/vq/losses.py:130-153 ("TODO: refactor" in the reference; used by no shipped config).
-    Needs the whole [N, K] matrix with autograd, which the fused path never forms: ``memo['distance']`` (a
-    ``LazyDistance``) is materialised on demand by the HIP distance kernel with gradients to the latents and the
-    codebook (``distances._L2Matrix`` / ``_DotMatrix``); the softmax/entropy arithmetic on it is stock device ops.
-    As in the reference the loss reads ``memo['distance']`` of the memo it is handed (the encode-stage memo)."""
+    As in the reference the loss reads ``memo['distance']`` of the memo it is handed (the encode-stage memo).
 
-    def __init__(self, *args, temperature: float, **kwargs) -> None:
+    Fused route: while ``memo['distance']`` is an unmaterialised ``LazyDistance`` of metric 'L2' or 'Cosine', value and
+    gradients come from ``LazyDistance.entropy`` — HIP kernels on one bounded [R, K] row-block tile (64 MiB by default), the
+    matrix is never formed and the handle stays unmaterialised; memory does not grow with N * K.
+    Matrix route (the reference's composition, literally): a plain tensor, an already materialised handle or the
+    bf16-autocast cosine are materialised by the HIP distance kernel with autograd (``distances._L2Matrix`` /
+    ``_DotMatrix``) and the softmax / entropy arithmetic on the matrix is stock device ops.
+
+    ``fused`` (extension; configs need not name it): None (default) — the fused route wherever it applies; False — always
+    the matrix route."""
+
+    def __init__(self, *args, temperature: float, fused: bool | None = None, **kwargs) -> None:
         super().__init__(*args, **kwargs)
+        if fused not in (None, False):
+            raise ValueError(f'EntropyLoss: fused must be None (auto) or False, got {fused!r}')
         self._temperature = temperature
+        self._fused = fused
+
+    def _fusable(self, d) -> bool:
+        return (isinstance(d, LazyDistance) and d._value is None and d.dim() == 2
+                and d.metric in d._distance.FUSED_ENTROPY_METRICS)
 
     def forward(self, z: torch.Tensor, x: torch.Tensor, memo: Memo) -> torch.Tensor:
-        affinity = as_distance_tensor(memo['distance'])
+        d = memo['distance']
+        if self._fused is None and self._fusable(d):
+            return self._reduce_weight(d.entropy(self._temperature))
+        affinity = as_distance_tensor(d)
         flat_affinity = affinity.reshape(-1, affinity.shape[-1]) / self._temperature
         probs = flat_affinity.softmax(-1)
         log_probs = torch.log_softmax(flat_affinity + 1e-5, -1)
