@@ -43,6 +43,47 @@ def test_version_and_sizes(lib):
     assert lib.vqhip_codebook_bytes(0, 256) == 0
 
 
+# Python callers allocate by these numbers: (N, K, D) -> (codebook_bytes(K, D), workspace_bytes, col_workspace_bytes,
+# vqkd_forward_ws_bytes, order_workspace_bytes(N, K), segsum_workspace_bytes(N, D),
+# then for cap in (1, 100, K): col_rows_workspace_bytes(N, cap, D), cvq_forward_ws_bytes(N, K, D, cap)).
+# D with every image form and one without (12), N above and below K and 0: a layout change that moves one moves the contract.
+SIZES = {
+    (1000, 512, 8): (56320, 568320, 568320, 614400, 2048, 1088,
+        188672, 761088, 228608, 801024, 449792, 1022208),
+    (16384, 16384, 8): (1731584, 21955584, 24211456, 23743488, 1048576, 16448,
+        2487296, 24573952, 2527232, 24613888, 24735744, 46822400),
+    (524288, 16384, 8): (1731584, 391726080, 391726080, 444812288, 33554432, 524352,
+        78418944, 470276096, 78458880, 470316032, 87822336, 479679488),
+    (100352, 8192, 32): (1653760, 104288256, 104288256, 121214976, 3211264, 401664,
+        34308096, 138661888, 34357248, 138711040, 56318976, 160672768),
+    (4096, 16384, 64): (6515712, 2688000, 12789760, 4180992, 262144, 33280,
+        2765824, 5584896, 2833408, 5652480, 16984064, 19803136),
+    (100, 4096, 64): (1631232, 128000, 2595840, 206848, 16384, 1536,
+        109568, 270336, 177152, 337920, 3644416, 3805184),
+    (0, 1024, 64): (409600, 48128, 0, 0, 4096, 512,
+        0, 0, 0, 0, 0, 0),
+    (65536, 16384, 256): (25521152, 65604608, 186224640, 139401216, 4194304, 2099200,
+        170019840, 235755520, 170201088, 235936768, 203001856, 268737536),
+    (3072, 1024, 256): (1597440, 3077120, 8986624, 6356992, 12288, 100352,
+        8018944, 11104256, 8200192, 11285504, 10035200, 13120512),
+    (6272, 8192, 768): (38059008, 12743680, 65013760, 32941056, 229376, 608256,
+        48565248, 61374464, 49047552, 61856768, 90179584, 102988800),
+    (16384, 8192, 1024): (50641920, 41583616, 189296640, 111454208, 524288, 2105344,
+        168687616, 210336768, 169320448, 210969600, 222851072, 264500224),
+    (1000, 512, 12): (64512, 502784, 502784, 564224, 2048, 1632,
+        0, 506880, 0, 506880, 0, 506880),
+}
+
+
+def test_buffer_sizes_are_part_of_the_contract(lib):
+    for (N, K, D), want in SIZES.items():
+        got = [lib.vqhip_codebook_bytes(K, D), lib.vqhip_workspace_bytes(N, K, D), lib.vqhip_col_workspace_bytes(N, K, D),
+               lib.vqhip_vqkd_forward_ws_bytes(N, K, D), lib.vqhip_order_workspace_bytes(N, K), lib.vqhip_segsum_workspace_bytes(N, D)]
+        for cap in (1, 100, K):
+            got += [lib.vqhip_col_rows_workspace_bytes(N, cap, D), lib.vqhip_cvq_forward_ws_bytes(N, K, D, cap)]
+        assert tuple(got) == want, (N, K, D)
+
+
 def test_bad_arguments_are_rejected_without_a_gpu(lib):
     # argument validation happens before any HIP call
     rc = lib.vqhip_argmin(None, 0, None, None, 0, 10, 10, 8, 0, None, None, None, 0, None)
@@ -50,6 +91,10 @@ def test_bad_arguments_are_rejected_without_a_gpu(lib):
     assert b'vqhip_argmin' in lib.vqhip_last_error()
     rc = lib.vqhip_codebook_prepare(None, 10, 8, 0, None, 0, None)
     assert rc == -22
+    import ctypes
+    fake = ctypes.c_void_p(0x1000)
+    rc = lib.vqhip_distance(fake, 9, fake, 1000, 512, 64, 0, fake, fake, lib.vqhip_workspace_bytes(1000, 512, 64), None)
+    assert rc == -22 and b'vqhip_distance: x_dtype' in lib.vqhip_last_error()
 
 
 def test_tuning_aids_are_host_state_and_retired_keys_are_refused(lib):

@@ -91,6 +91,12 @@ static int ensure_dyn_lds(const void *kern, size_t bytes, LdsCache &set) {
         }                                                                                                 \
     } while (0)
 
+// a refusal with a fixed text ("entry point: what"), and what most entry points refuse
+#define VQ_REQUIRE(cond, text) do { if (!(cond)) return fail(VQHIP_EINVAL, text); } while (0)
+static inline bool vq_public_metric(int m) { return m == VQHIP_METRIC_L2 || m == VQHIP_METRIC_COS || m == VQHIP_METRIC_COS_BF16; }
+static inline bool vq_row_dtype(int t) { return t == VQHIP_DTYPE_F32 || t == VQHIP_DTYPE_BF16; }
+static inline bool vq_fits_i31(int64_t N, int64_t K) { return N < (1ll << 31) && K < (1ll << 31); }
+
 static inline int waves_grid(int64_t rows, int waves_per_block) {
     return (int)((rows + waves_per_block - 1) / waves_per_block);
 }
@@ -188,8 +194,9 @@ static int balanced_tiles_per_block(int64_t N, int full) {
 }
 
 // The token side made inside the proposal kernel's prologue instead of a token image (coarse_kernel<..., XD>):
-// the D = 256 form with 64 tokens per wave, rows as the caller holds them, the decision stage in its own launch.  One predicate
-// for the front (which then skips its token side), the proposal launch and the second pass (which reads the rows instead).
+// the D = 256 form with 64 tokens per wave, rows as the caller holds them, the decision stage in its own launch.  Evaluated
+// once per pipeline run, by whoever prepares the token side (encode_fused_front, else argmin_pipeline): VqTokenSide carries the
+// answer to the proposal launch and the second pass (which reads the rows instead).
 // The form never decides in-kernel: it needs at least two slices (one slice, forced by key 2 included, decides in-kernel).
 static bool vq_xdirect(int64_t N, int64_t K, int D, int x_dtype, int metric, const int *n_dev) {
     if (D != 256 || n_dev != nullptr || vq_cb_layout(K, D).nstages < 2 || g_tune_slices.load() == 1) return false;
@@ -197,10 +204,12 @@ static bool vq_xdirect(int64_t N, int64_t K, int D, int x_dtype, int metric, con
     // bytes per piece, a round trip per token tile, 58 spilled registers) cost a workgroup +44 us of prologue at 20 000 x 16384 x 256
     // against +3 us for bf16 (profiles/r06_xdirect.txt): they keep the token image
     if (x_dtype != VQHIP_DTYPE_BF16) return false;
-    if (metric != VQHIP_METRIC_L2 && metric != VQHIP_METRIC_COS && metric != VQHIP_METRIC_COS_BF16) return false;   // (not the role-swapped column pass)
+    if (!vq_public_metric(metric)) return false;                                      // (not the role-swapped column pass)
     if (N <= VQ_FUSED_DECIDE_MAX_N) return false;                                     // small batches decide inside the proposal kernel
     return !(N <= 4096 || (N <= 256 * 64 && K <= 4096));                               // the 64-tokens-per-wave form (launch_coarse: !small16)
 }
+// the token side argmin_pipeline finds in its workspace: none (it runs x_prep_kernel itself), the token image, or (vq_xdirect) the housekeeping only
+enum VqTokenSide { VQ_TOKENS_UNPREPARED, VQ_TOKENS_IMAGE, VQ_TOKENS_ROWS };
 
 static int pick_slices(int64_t ntb, int64_t nstages, int min_slices = 2) {
     if (const int forced = g_tune_slices.load(); forced > 0) { int ns = forced; while (ns > 1 && ns > nstages) ns >>= 1; return ns; }
@@ -366,6 +375,21 @@ static int run_exact_tiled(const void *x, int x_dtype, const float *e, const flo
     return VQHIP_OK;
 }
 
+// The fp32-only route over a whole batch, in an encode workspace: the oracle-order norms of both sides under L2, then
+// run_exact_tiled<MODE>.  MODE 0: the keys are armed in front and turned into idx / dmin / hist behind; MODE 2 (`dout`) has none.
+template <int MODE>
+static int exact_whole(const void *x, int x_dtype, const float *e, int64_t N, int64_t K, int D, int metric, const VqWsView &V,
+                       int64_t *idx, float *dmin, int32_t *hist, float *dout, hipStream_t s) {
+    constexpr bool keyed = MODE != 2;
+    const bool l2 = metric == VQHIP_METRIC_L2;
+    if (l2) if (int rc = vqhip_row_sqnorm(e, VQHIP_DTYPE_F32, K, D, V.en, s)) return rc;
+    if constexpr (keyed) { fill_u64_kernel<<<256, 256, 0, s>>>(V.keys, N, ~0ull); VQ_CHECK_LAUNCH("fill_u64_kernel"); }
+    if (l2) if (int rc = vqhip_row_sqnorm(x, x_dtype, N, D, V.xn_whole, s)) return rc;
+    if (int rc = run_exact_tiled<MODE>(x, x_dtype, e, V.en, V.xn_whole, N, K, D, metric, keyed ? V.keys : nullptr, dout, s)) return rc;
+    if constexpr (keyed) { finalize_kernel<<<256, 256, 0, s>>>(V.keys, nullptr, nullptr, N, idx, dmin, hist); VQ_CHECK_LAUNCH("finalize_kernel"); }
+    return VQHIP_OK;
+}
+
 // The few-rows (VALU) form of exact_kernel stages its operands in dynamic LDS: a 64 KiB ring + 64 D bytes.  The request applies to
 // the LAUNCH, i.e. also when the device-side count picks the MFMA form: at D > 512 (96 KiB) that would leave the MFMA form one
 // workgroup per CU, and a part with less LDS per workgroup than asked for would refuse the launch — so the form is offered only
@@ -420,16 +444,41 @@ static int run_segsum(const void *src, int x_dtype, const float *e, const int64_
     return VQHIP_OK;
 }
 
-// |v|^2 / F.normalize for rows of at most 32 elements: 64 / L rows per wave (row_small_kernel)
+// rows of at most 32 elements take L = 8, 16 or 32 lanes each: 64 / L rows per wave
+static inline int vq_small_lanes(int D) { return D <= 8 ? 8 : (D <= 16 ? 16 : 32); }
+
+// |v|^2 / F.normalize for rows of at most 32 elements (row_small_kernel)
 template <bool NORMALIZE>
 static int launch_row_small(const void *v, int dtype, int64_t R, int D, float eps, float *out, hipStream_t s) {
-    const int L = D <= 8 ? 8 : (D <= 16 ? 16 : 32);
+    const int L = vq_small_lanes(D);
     const int grid = waves_grid((R + 64 / L - 1) / (64 / L), 4);
 #define VQ_ROW_SMALL(DT, LL) row_small_kernel<DT, LL, NORMALIZE><<<grid, 256, 0, s>>>(v, R, D, eps, out)
     if (dtype == VQHIP_DTYPE_F32) { if (L == 8) VQ_ROW_SMALL(0, 8); else if (L == 16) VQ_ROW_SMALL(0, 16); else VQ_ROW_SMALL(0, 32); }
     else { if (L == 8) VQ_ROW_SMALL(1, 8); else if (L == 16) VQ_ROW_SMALL(1, 16); else VQ_ROW_SMALL(1, 32); }
 #undef VQ_ROW_SMALL
     VQ_CHECK_LAUNCH("row_small_kernel");
+    return VQHIP_OK;
+}
+
+// hist[K] += bincount(idx) for int64 (hist_kernel, hist_lds_kernel) or int32 tokens (their _i32 twins)
+template <typename IdxT>
+static int launch_hist(const IdxT *idx, int64_t N, int64_t K, int32_t *hist, void *stream) {
+    constexpr bool i64 = sizeof(IdxT) == 8;
+    VQ_REQUIRE(idx && hist && N >= 0 && K > 0, i64 ? "vqhip_hist: bad argument" : "vqhip_hist_i32: bad argument");
+    if (N == 0) return VQHIP_OK;
+    hipStream_t s = (hipStream_t)stream;
+    if (K <= 32768 && N >= 16384) {            // enough tokens per block that the K-bin flush pays: at most 256 blocks, >= 2048 tokens each
+        static LdsCache lds_set;
+        if (int rc = ensure_dyn_lds(i64 ? (const void *)hist_lds_kernel : (const void *)hist_i32_lds_kernel, (size_t)K * 4, lds_set)) return rc;
+        int grid = (int)((N + 2047) / 2048); grid = grid > 256 ? 256 : grid;
+        if constexpr (i64) hist_lds_kernel<<<grid, 1024, (size_t)K * 4, s>>>(idx, N, (int)K, hist);
+        else hist_i32_lds_kernel<<<grid, 1024, (size_t)K * 4, s>>>(idx, N, (int)K, hist);
+    } else {
+        int grid = (int)((N + 255) / 256); grid = grid > 2048 ? 2048 : grid;
+        if constexpr (i64) hist_kernel<<<grid, 256, 0, s>>>(idx, N, K, hist);
+        else hist_i32_kernel<<<grid, 256, 0, s>>>(idx, N, K, hist);
+    }
+    VQ_CHECK_LAUNCH(i64 ? "hist_kernel" : "hist_i32_kernel");
     return VQHIP_OK;
 }
 
@@ -447,7 +496,7 @@ int64_t vqhip_codebook_exact_offset(int64_t K, int D) {
 static int launch_vqkd_front(const float *w_in, float *w_mid, int64_t K, const void *x, int x_dtype, float *xn, int64_t N, int D, float eps,
                              float *zero, int64_t nzero, int w_passes, hipStream_t s) {
     if (D <= 32) {
-        const int L = D <= 8 ? 8 : (D <= 16 ? 16 : 32), rpb = 4 * (64 / L);
+        const int L = vq_small_lanes(D), rpb = 4 * (64 / L);
         const int kblocks = (int)((K + rpb - 1) / rpb), xblocks = (int)((N + rpb - 1) / rpb);
 #define VQ_FRONT_SMALL(DT, LL) vqkd_front_small_kernel<DT, LL><<<kblocks + xblocks, 256, 0, s>>>(w_in, w_mid, K, x, xn, N, D, eps, kblocks, zero, nzero, w_passes)
         if (x_dtype == VQHIP_DTYPE_F32) { if (L == 8) VQ_FRONT_SMALL(0, 8); else if (L == 16) VQ_FRONT_SMALL(0, 16); else VQ_FRONT_SMALL(0, 32); }
@@ -517,54 +566,41 @@ static int codebook_prepare_impl(const float *e, int64_t K, int D, int metric, v
 }
 
 int vqhip_codebook_prepare(const float *e, int64_t K, int D, int metric, void *cb, int64_t cb_bytes, void *stream) {
-    if (!e || !cb || K <= 0 || D <= 0 || (metric != VQHIP_METRIC_L2 && metric != VQHIP_METRIC_COS && metric != VQHIP_METRIC_COS_BF16))
-        return fail(VQHIP_EINVAL, "vqhip_codebook_prepare: bad argument");
+    VQ_REQUIRE(e && cb && K > 0 && D > 0 && vq_public_metric(metric), "vqhip_codebook_prepare: bad argument");
     VQ_NEED("vqhip_codebook_prepare: cb too small", cb_bytes, vqhip_codebook_bytes(K, D));
     return codebook_prepare_impl(e, K, D, metric, cb, stream);
 }
 
-int vqhip_argmin_exact(const void *x, int x_dtype, const float *e, int64_t N, int64_t K, int D, int metric, int64_t *idx,
-                       float *dmin, int32_t *hist, void *ws, int64_t ws_bytes, void *stream);
-
 // The proposal + decision pipeline: N rows `x` against the K codes whose prepared image is `cb` and whose fp32 rows
 // (as used by the exact definition) are `e_exact`.  `metric` may carry the internal words (DOT, SWAP).
-// x_prepared: the token side (x_prep) was already produced into `ws` by pre_kernel (encode_fused_front)
+// tokens: what the front of the call (encode_fused_front) left in `ws`; VQ_TOKENS_UNPREPARED: the token side is made here
 // n_dev (nullable DEVICE int): only rows [0, min(N, *n_dev)) are live; the launches are sized for N
 static int argmin_pipeline(const void *x, int x_dtype, const float *e_exact, const void *cb, int64_t N, int64_t K, int D,
-                           int metric, int64_t *idx, int32_t *hist, void *ws, void *stream, bool x_prepared = false,
+                           int metric, int64_t *idx, int32_t *hist, void *ws, void *stream, VqTokenSide tokens = VQ_TOKENS_UNPREPARED,
                            const int *n_dev = nullptr) {
     hipStream_t s = (hipStream_t)stream;
     VqCbLayout L = vq_cb_layout(K, D);
     VqWsLayout W = vq_ws_layout(N, K, D);
+    const VqWsView V = vq_ws_view(ws, W);
     const char *c = (const char *)cb;
-    char *w = (char *)ws;
     const int64_t Np = (N + 63) / 64 * 64;
-    int *counters = (int *)(w + W.off_counters);
-    float *xh2 = (float *)(w + W.off_xh2), *rho2 = (float *)(w + W.off_rho2), *rec = (float *)(w + W.off_rec);
-    int *flag_list = (int *)(w + W.off_flag);
-    u64 *keys = (u64 *)(w + W.off_keys);
     const float *en = (const float *)(c + L.off_en);
 
     int nslices = 1, rc;
-    char *ximg = w + W.off_ximg;
-    int *rescan_list = flag_list;
-    int *multi_list = (int *)(w + W.off_multi), *exact_list = (int *)(w + W.off_exact);
-    float *thr = (float *)(w + W.off_thr);
-    int *rescan_cnt = (int *)(w + W.off_rcnt), *cand_list = (int *)(w + W.off_rlist);
-    int *arrive = (int *)(w + W.off_arrive);
-    const int narrive = (int)W.narrive;          // arrival counters + the group path's bucket counters (one zeroed range)
-    int xgrid = (int)((N + 31) / 32);
     // no token image: the proposal kernel converts the rows it loads (coarse_kernel<..., XD>); the front only does the housekeeping
-    const bool xd = vq_xdirect(N, K, D, x_dtype, metric, n_dev);
-    if (!x_prepared) {
+    bool xd = tokens == VQ_TOKENS_ROWS;
+    if (tokens == VQ_TOKENS_UNPREPARED) {
+        xd = vq_xdirect(N, K, D, x_dtype, metric, n_dev);
+        int xgrid = (int)((N + 31) / 32);
         if (xd) xgrid = xgrid < 64 ? xgrid : 64;
-        if (x_dtype == VQHIP_DTYPE_F32) x_prep_kernel<0><<<xgrid, 256, 0, s>>>(x, N, D, L.nstep, ximg, xh2, rho2, (float *)(w + W.off_xn), counters, (char *)cb, L, arrive, narrive, xd);
-        else x_prep_kernel<1><<<xgrid, 256, 0, s>>>(x, N, D, L.nstep, ximg, xh2, rho2, (float *)(w + W.off_xn), counters, (char *)cb, L, arrive, narrive, xd);
+        const int narrive = (int)W.narrive;      // arrival counters + the group path's bucket counters (one zeroed range)
+        if (x_dtype == VQHIP_DTYPE_F32) x_prep_kernel<0><<<xgrid, 256, 0, s>>>(x, N, D, L.nstep, V.ximg, V.xh2, V.rho2, V.xn, V.counters, (char *)cb, L, V.arrive, narrive, xd);
+        else x_prep_kernel<1><<<xgrid, 256, 0, s>>>(x, N, D, L.nstep, V.ximg, V.xh2, V.rho2, V.xn, V.counters, (char *)cb, L, V.arrive, narrive, xd);
         VQ_CHECK_LAUNCH("x_prep_kernel");
     }
     // the proposal kernel also runs the decision stage (the workgroup that completes a token block merges its slices)
-    VqDecideOut dec{idx, hist, rescan_list, multi_list, exact_list, counters, keys, thr, rescan_cnt, arrive, n_dev,
-                    x, xh2, rho2, (float *)(w + W.off_xn)};
+    VqDecideOut dec{idx, hist, V.rescan_list, V.multi_list, V.exact_list, V.counters, V.keys, V.thr, V.rescan_cnt, V.arrive, n_dev,
+                    x, V.xh2, V.rho2, V.xn};
     VqDecideOut dec_arg = dec;                   // launch_coarse decides (slice count, batch size) whether the proposal kernel runs the
     int fused_done = 0;                          // decision stage itself and reports it here
     // D <= 32 group path: request lists of the proposal kernel (cap = an equal share of the pool per code tile, whole batches of 32)
@@ -575,39 +611,35 @@ static int argmin_pipeline(const void *x, int x_dtype, const float *e_exact, con
     if (W.nbkt > 0 && ntiles_cb <= VQ_GROUP_MAX_TILES && N < (1ll << 30)) {
         grp.R = vq_group_replicas(ntiles_cb / VQ_GROUP_TILES);
         nbuckets = ntiles_cb / VQ_GROUP_TILES * grp.R;
-        grp.bcnt = (int *)(w + W.off_bcnt);
-        grp.blist = (uint32_t *)(w + W.off_blist);
-        grp.bfrag = w + W.off_bfrag;
-        grp.rece2 = (float *)(w + W.off_rece2);
+        grp.bcnt = V.bcnt; grp.blist = V.blist; grp.bfrag = V.bfrag; grp.rece2 = V.rece2;
         grp.cap = (int)(W.blist_entries / nbuckets / 32 * 32);
         uint32_t bits = 1;                                   // group ids ride in the low mantissa bits of the running group maxima
         while ((1u << bits) < (uint32_t)(ntiles_cb / VQ_GROUP_TILES)) ++bits;
         grp.idmask = (1u << bits) - 1u;
     }
-    rc = launch_coarse(ximg, N, L, c + L.off_frag, rec, Np, (const VqCbStats *)(c + L.off_stats), xh2, rho2, metric, dec_arg, &nslices, &fused_done, s, grp, &grun, xd);
+    rc = launch_coarse(V.ximg, N, L, c + L.off_frag, V.rec, Np, (const VqCbStats *)(c + L.off_stats), V.xh2, V.rho2, metric, dec_arg, &nslices, &fused_done, s, grp, &grun, xd);
     if (rc) return rc;
     const float *rece2 = nullptr;
     if (grun.used) {             // identify the group records: one candidate per request, written into the records
         const int igrid = (nbuckets + 3) / 4;                   // one wave per bucket
-        if (grun.ks == 1) identify32_kernel<1, VQ_GROUP_TILES><<<igrid, 256, 0, s>>>(c + L.off_frag, L.nstages, nslices, nbuckets, rec, Np, (const VqCbStats *)(c + L.off_stats), grp, grun.pad_stage, grun.noaux);
-        else identify32_kernel<2, VQ_GROUP_TILES><<<igrid, 256, 0, s>>>(c + L.off_frag, L.nstages, nslices, nbuckets, rec, Np, (const VqCbStats *)(c + L.off_stats), grp, grun.pad_stage, grun.noaux);
+        if (grun.ks == 1) identify32_kernel<1, VQ_GROUP_TILES><<<igrid, 256, 0, s>>>(c + L.off_frag, L.nstages, nslices, nbuckets, V.rec, Np, (const VqCbStats *)(c + L.off_stats), grp, grun.pad_stage, grun.noaux);
+        else identify32_kernel<2, VQ_GROUP_TILES><<<igrid, 256, 0, s>>>(c + L.off_frag, L.nstages, nslices, nbuckets, V.rec, Np, (const VqCbStats *)(c + L.off_stats), grp, grun.pad_stage, grun.noaux);
         VQ_CHECK_LAUNCH("identify32_kernel");
         rece2 = grp.rece2;
     }
     if (!fused_done) {
         // (1024-thread workgroups: 256 and 512 measured 1-2 % slower per encode at configs[2] and the tokenizer shape, level at D = 256)
-        refine_decide_kernel<<<(int)((N + 1023) / 1024), 1024, 0, s>>>(c, L, N, metric, nslices, rec, xh2, rho2, Np, dec, rece2);
+        refine_decide_kernel<<<(int)((N + 1023) / 1024), 1024, 0, s>>>(c, L, N, metric, nslices, V.rec, V.xh2, V.rho2, Np, dec, rece2);
         VQ_CHECK_LAUNCH("refine_decide_kernel");
     }
     // second-chance proposals for rows with a possibly unidentified candidate (the kernel gathers their fragments from
     // the token image itself) ...
-    float *xnorm = (float *)(w + W.off_xn);
     {
         const char *frag = c + L.off_frag;
         int rrc = VQHIP_OK;
-        if (xd) rrc = launch_rescan_cfg<16, 2, 8, VQ_TPS16, 4, 1>(ximg, frag, L.nstages, rescan_list, counters, thr, rescan_cnt, cand_list, s, x);
+        if (xd) rrc = launch_rescan_cfg<16, 2, 8, VQ_TPS16, 4, 1>(V.ximg, frag, L.nstages, V.rescan_list, V.counters, V.thr, V.rescan_cnt, V.cand_list, s, x);
         else switch (L.nstep) {
-#define VQ_RESCAN(NS, TT, ...) case NS: rrc = launch_rescan_cfg<NS, TT, 8, __VA_ARGS__>(ximg, frag, L.nstages, rescan_list, counters, thr, rescan_cnt, cand_list, s); break;
+#define VQ_RESCAN(NS, TT, ...) case NS: rrc = launch_rescan_cfg<NS, TT, 8, __VA_ARGS__>(V.ximg, frag, L.nstages, V.rescan_list, V.counters, V.thr, V.rescan_cnt, V.cand_list, s); break;
             VQ_RESCAN(2, 2, VQ_TPS_D32, 4) VQ_RESCAN(4, 2, 4, 4) VQ_RESCAN(8, 2, 4, 4) VQ_RESCAN(16, 2, VQ_TPS16, 4) VQ_RESCAN(32, 2, 2) VQ_RESCAN(48, 2, 1) VQ_RESCAN(64, 1, 1)
 #undef VQ_RESCAN
             default: return fail(VQHIP_EINVAL, "vqhip_argmin: unsupported padded D");
@@ -623,22 +655,18 @@ static int argmin_pipeline(const void *x, int x_dtype, const float *e_exact, con
         // the re-rank is a latency chain per (row, candidate) pair: it wants one row per wave however short the queues
         // are (64 + 64 workgroups made it 80 us instead of 14 at N = 3072, cosine, 16 slices); idle workgroups exit at once
         const int64_t g0 = 2048, g1 = 1024;
-        if (x_dtype == VQHIP_DTYPE_F32)
-            refine_rerank_kernel<0><<<(int)(g0 + g1), 256, 0, s>>>(x, e_exact, c, L, D, metric, nslices, S0, (int)g0, rec, xh2, rho2,
-                                                                  xnorm, Np, idx, hist, multi_list, rescan_list, counters,
-                                                                  rescan_cnt, cand_list, exact_list, keys, grun.used);
-        else
-            refine_rerank_kernel<1><<<(int)(g0 + g1), 256, 0, s>>>(x, e_exact, c, L, D, metric, nslices, S0, (int)g0, rec, xh2, rho2,
-                                                                  xnorm, Np, idx, hist, multi_list, rescan_list, counters,
-                                                                  rescan_cnt, cand_list, exact_list, keys, grun.used);
+#define VQ_RERANK(DT) refine_rerank_kernel<DT><<<(int)(g0 + g1), 256, 0, s>>>(x, e_exact, c, L, D, metric, nslices, S0, (int)g0, V.rec, V.xh2, V.rho2, \
+        V.xn, Np, idx, hist, V.multi_list, V.rescan_list, V.counters, V.rescan_cnt, V.cand_list, V.exact_list, V.keys, grun.used)
+        if (x_dtype == VQHIP_DTYPE_F32) VQ_RERANK(0); else VQ_RERANK(1);
+#undef VQ_RERANK
         VQ_CHECK_LAUNCH("refine_rerank_kernel");
     }
     // last resort: whole-codebook fp32 pass (non-finite data, overflowing candidate lists)
     if (const int force = g_tune_force_exact.load()) {
-        force_exact_rows_kernel<<<1, 1024, 0, s>>>((int)(force < N ? force : N), exact_list, counters, keys);
+        force_exact_rows_kernel<<<1, 1024, 0, s>>>((int)(force < N ? force : N), V.exact_list, V.counters, V.keys);
         VQ_CHECK_LAUNCH("force_exact_rows_kernel");
     }
-    return run_exact_rows(x, x_dtype, e_exact, en, xnorm, N, K, D, metric, exact_list, counters + 2, keys, counters + 3, idx, hist, s);
+    return run_exact_rows(x, x_dtype, e_exact, en, V.xn, N, K, D, metric, V.exact_list, V.counters + 2, V.keys, V.counters + 3, idx, hist, s);
 }
 
 // Front of an encode whose codebook image is made in the same call: ONE launch for the codebook statistics and the whole
@@ -647,12 +675,14 @@ static int argmin_pipeline(const void *x, int x_dtype, const float *e_exact, con
 // hw > 0: `rows` is the feature map [N / hw, D, hw] (NCHW); the token-major rows go to `xrows` (input dtype; cosine: xq)
 // grows != nullptr (vqhip_col_argmin_rows, fp32 `rows` = the codebook, no normalisation): row t of the call is rows[grows[t]] for
 // t < *gcount and zeros up to N; the gathered rows are written to `xrows`
+// *tokens: the form of the token side argmin_pipeline is to go on from
 static int encode_fused_front(const void *rows, int rows_dtype, int64_t N, const float *codes, int64_t Kc, int D, int cb_metric,
-                              void *cb, void *ws, bool xnorm, float *xq, hipStream_t s, int32_t *hist_zero = nullptr,
+                              void *cb, void *ws, bool xnorm, float *xq, VqTokenSide *tokens, hipStream_t s, int32_t *hist_zero = nullptr,
                               int64_t hw = 0, void *xrows = nullptr, const int32_t *grows = nullptr, const int32_t *gcount = nullptr) {
     VqCbLayout L = vq_cb_layout(Kc, D);
     VqWsLayout W = vq_ws_layout(N, Kc, D);
-    char *w = (char *)ws, *c = (char *)cb;
+    const VqWsView V = vq_ws_view(ws, W);
+    char *c = (char *)cb;
     // cosine: the whole codebook preparation rides in the same launch (normalised rows need no statistics pass for their
     // scale).  DOT — the role-swapped NearestAnchor pass under the cosine metric, whose operands the caller has normalised
     // (include/vqhip.h: "COS: x and e already normalised") — takes the same form on the rows as given: constant scale 2^13,
@@ -660,21 +690,20 @@ static int encode_fused_front(const void *rows, int rows_dtype, int64_t N, const
     // scale raise the non-finite flag and the rows take the fp32 pass)
     const bool cosimg = VQ_IS_COS(cb_metric) || (cb_metric & 3) == VQ_METRIC_DOT;
     const int nblk_stats = cosimg ? (int)(L.nstages * L.tps) : (int)((Kc + 15) / 16);
-    // the rows the pipeline will be handed are the rows given here (no normalisation, token-major, no gather): where the proposal
-    // kernel makes its own fragments (vq_xdirect: the same predicate argmin_pipeline evaluates) the token side is housekeeping only
-    const int toff = (!xnorm && hw == 0 && grows == nullptr && vq_xdirect(N, Kc, D, rows_dtype, cb_metric, nullptr)) ? 1 : 0;
+    // the pipeline is handed the rows given here (hw > 0: their token-major copy), no normalisation, no gather: where the proposal kernel
+    // makes its own fragments of them (vq_xdirect) the token side is housekeeping only (hw > 0: the blocks that write the copy still run in full)
+    const bool xd = !xnorm && grows == nullptr && vq_xdirect(N, Kc, D, rows_dtype, cb_metric, nullptr);
+    *tokens = xd ? VQ_TOKENS_ROWS : VQ_TOKENS_IMAGE;
+    const int toff = (xd && hw == 0) ? 1 : 0;
     int xgrid = (int)((N + 31) / 32);
     if (toff) xgrid = xgrid < 64 ? xgrid : 64;
-    const int narrive = (int)W.narrive;
-    int *counters = (int *)(w + W.off_counters), *arrive = (int *)(w + W.off_arrive);
-    float *xh2 = (float *)(w + W.off_xh2), *rho2 = (float *)(w + W.off_rho2), *xn = (float *)(w + W.off_xn);
-    char *ximg = w + W.off_ximg;
-#define VQ_PRE(DT, XN, MAP, COSI) pre_kernel<DT, XN, MAP, COSI><<<nblk_stats + xgrid, 256, 0, s>>>(codes, Kc, cb_metric, c, L, nblk_stats, rows, N, D, L.nstep, ximg, xh2, rho2, xn, counters, arrive, narrive, xq, 1e-12f, hist_zero, hw, xrows, nullptr, nullptr, toff)
+#define VQ_PRE_ARGS codes, Kc, cb_metric, c, L, nblk_stats, rows, N, D, L.nstep, V.ximg, V.xh2, V.rho2, V.xn, V.counters, V.arrive, (int)W.narrive, xq, 1e-12f, hist_zero, hw, xrows
+#define VQ_PRE(DT, XN, MAP, COSI) pre_kernel<DT, XN, MAP, COSI><<<nblk_stats + xgrid, 256, 0, s>>>(VQ_PRE_ARGS, nullptr, nullptr, toff)
 #define VQ_PRE2(DT, XN, MAP) do { if (cosimg) VQ_PRE(DT, XN, MAP, true); else VQ_PRE(DT, XN, MAP, false); } while (0)
     if (grows != nullptr) {
         if (rows_dtype != VQHIP_DTYPE_F32 || xnorm || hw > 0 || L.nstep == 2) return fail(VQHIP_EINVAL, "encode_fused_front: gather form");
-        if (cosimg) pre_kernel<0, false, false, true, true><<<nblk_stats + xgrid, 256, 0, s>>>(codes, Kc, cb_metric, c, L, nblk_stats, rows, N, D, L.nstep, ximg, xh2, rho2, xn, counters, arrive, narrive, xq, 1e-12f, hist_zero, hw, xrows, grows, gcount);
-        else pre_kernel<0, false, false, false, true><<<nblk_stats + xgrid, 256, 0, s>>>(codes, Kc, cb_metric, c, L, nblk_stats, rows, N, D, L.nstep, ximg, xh2, rho2, xn, counters, arrive, narrive, xq, 1e-12f, hist_zero, hw, xrows, grows, gcount);
+        if (cosimg) pre_kernel<0, false, false, true, true><<<nblk_stats + xgrid, 256, 0, s>>>(VQ_PRE_ARGS, grows, gcount);
+        else pre_kernel<0, false, false, false, true><<<nblk_stats + xgrid, 256, 0, s>>>(VQ_PRE_ARGS, grows, gcount);
     } else
     if (hw > 0) {
         if (rows_dtype == VQHIP_DTYPE_F32) { if (xnorm) VQ_PRE2(0, true, true); else VQ_PRE2(0, false, true); }
@@ -685,6 +714,7 @@ static int encode_fused_front(const void *rows, int rows_dtype, int64_t N, const
     }
 #undef VQ_PRE2
 #undef VQ_PRE
+#undef VQ_PRE_ARGS
     VQ_CHECK_LAUNCH("pre_kernel");
     if (cosimg) return VQHIP_OK;
     cb_image_kernel<<<(int)(L.nstages * L.tps), 256, 0, s>>>(codes, Kc, D, cb_metric, c, L);
@@ -705,10 +735,10 @@ int vqhip_encode_ex(const void *x, int x_dtype, const float *e, int64_t N, int64
     }
     if (N == 0) return e && cb && K > 0 && D > 0 ? vqhip_codebook_prepare(e, K, D, metric, cb, cb_bytes, stream) : fail(VQHIP_EINVAL, "vqhip_encode: bad argument");
     if (!x || !e || !cb || !idx || !ws || N < 0 || K <= 0 || D <= 0) return fail(VQHIP_EINVAL, "vqhip_encode: bad argument");
-    if (metric != VQHIP_METRIC_L2 && metric != VQHIP_METRIC_COS && metric != VQHIP_METRIC_COS_BF16) return fail(VQHIP_EINVAL, "vqhip_encode: metric");
-    if (x_dtype != VQHIP_DTYPE_F32 && x_dtype != VQHIP_DTYPE_BF16) return fail(VQHIP_EINVAL, "vqhip_encode: x_dtype");
+    VQ_REQUIRE(vq_public_metric(metric), "vqhip_encode: metric");
+    VQ_REQUIRE(vq_row_dtype(x_dtype), "vqhip_encode: x_dtype");
     if (VQ_IS_COS(metric) && !xq) return fail(VQHIP_EINVAL, "vqhip_encode: the cosine metric needs the xq buffer");
-    if (N >= (1ll << 31) || K >= (1ll << 31)) return fail(VQHIP_EINVAL, "vqhip_encode: N or K too large");
+    VQ_REQUIRE(vq_fits_i31(N, K), "vqhip_encode: N or K too large");
     VQ_NEED("vqhip_encode: cb too small", cb_bytes, vqhip_codebook_bytes(K, D));
     VQ_NEED("vqhip_encode: ws too small", ws_bytes, vqhip_workspace_bytes(N, K, D));
     if (!vq_coarse_supported(D)) {          // no fp16 proposal image for this D: the separate entry points do the work
@@ -723,12 +753,13 @@ int vqhip_encode_ex(const void *x, int x_dtype, const float *e, int64_t N, int64
     }
     hipStream_t s = (hipStream_t)stream;
     const bool cos = VQ_IS_COS(metric);
-    if (int rc = encode_fused_front(x, x_dtype, N, e, K, D, metric, cb, ws, cos, xq, s, zero_hist ? hist : nullptr)) return rc;
+    VqTokenSide tokens;
+    if (int rc = encode_fused_front(x, x_dtype, N, e, K, D, metric, cb, ws, cos, xq, &tokens, s, zero_hist ? hist : nullptr)) return rc;
     VqCbLayout L = vq_cb_layout(K, D);
     const float *e_exact = cos ? (const float *)((const char *)cb + L.off_eexact) : e;
     // from here on the rows are what vqhip_argmin would have been given: the normalised fp32 rows for cosine
     return argmin_pipeline(cos ? (const void *)xq : x, cos ? VQHIP_DTYPE_F32 : x_dtype, e_exact, cb, N, K, D, metric, idx, hist, ws,
-                           stream, /*x_prepared=*/true);
+                           stream, tokens);
 }
 
 int vqhip_encode_map(const void *x_map, int x_dtype, const float *e, int64_t B, int64_t HW, int64_t K, int D, int metric, void *cb,
@@ -737,32 +768,33 @@ int vqhip_encode_map(const void *x_map, int x_dtype, const float *e, int64_t B, 
     const int64_t N = B * HW;
     if (!x_map || !e || !cb || !idx || !xrows || !ws || B <= 0 || HW <= 0 || K <= 0 || D <= 0) return fail(VQHIP_EINVAL, "vqhip_encode_map: bad argument");
     if (VQ_IS_COS(metric) && !xq) return fail(VQHIP_EINVAL, "vqhip_encode_map: the cosine metric needs the xq buffer");
-    if (metric != VQHIP_METRIC_L2 && metric != VQHIP_METRIC_COS && metric != VQHIP_METRIC_COS_BF16) return fail(VQHIP_EINVAL, "vqhip_encode_map: metric");
-    if (x_dtype != VQHIP_DTYPE_F32 && x_dtype != VQHIP_DTYPE_BF16) return fail(VQHIP_EINVAL, "vqhip_encode_map: x_dtype");
-    if (N >= (1ll << 31) || K >= (1ll << 31)) return fail(VQHIP_EINVAL, "vqhip_encode_map: N or K too large");
+    VQ_REQUIRE(vq_public_metric(metric), "vqhip_encode_map: metric");
+    VQ_REQUIRE(vq_row_dtype(x_dtype), "vqhip_encode_map: x_dtype");
+    VQ_REQUIRE(vq_fits_i31(N, K), "vqhip_encode_map: N or K too large");
     if (!vq_coarse_supported(D)) return fail(VQHIP_EINVAL, "vqhip_encode_map: needs D <= 1024, D % 8 == 0 (transpose and use vqhip_encode)");
     VQ_NEED("vqhip_encode_map: cb too small", cb_bytes, vqhip_codebook_bytes(K, D));
     VQ_NEED("vqhip_encode_map: ws too small", ws_bytes, vqhip_workspace_bytes(N, K, D));
     hipStream_t s = (hipStream_t)stream;
     const bool cos = VQ_IS_COS(metric);
     const bool zero_hist = hist != nullptr && (flags & VQHIP_ENCODE_ZERO_HIST) != 0;
-    if (int rc = encode_fused_front(x_map, x_dtype, N, e, K, D, metric, cb, ws, cos, cos ? xq : nullptr, s,
+    VqTokenSide tokens;
+    if (int rc = encode_fused_front(x_map, x_dtype, N, e, K, D, metric, cb, ws, cos, cos ? xq : nullptr, &tokens, s,
                                     zero_hist ? hist : nullptr, HW, xrows)) return rc;
     VqCbLayout L = vq_cb_layout(K, D);
     const float *e_exact = cos ? (const float *)((const char *)cb + L.off_eexact) : e;
     // from here on the rows are token-major: what the front wrote (L2: the copy in the input dtype; cosine: the normalised fp32 rows)
     return argmin_pipeline(cos ? (const void *)xq : (const void *)xrows, cos ? VQHIP_DTYPE_F32 : x_dtype, e_exact, cb, N, K, D, metric,
-                           idx, hist, ws, stream, /*x_prepared=*/true);
+                           idx, hist, ws, stream, tokens);
 }
 
 int vqhip_argmin(const void *x, int x_dtype, const float *e, const void *cb, int64_t cb_bytes, int64_t N, int64_t K, int D, int metric,
                  int64_t *idx, int32_t *hist, void *ws, int64_t ws_bytes, void *stream) {
     if (N == 0) return VQHIP_OK;
     if (!x || !cb || !idx || !ws || N < 0 || K <= 0 || D <= 0) return fail(VQHIP_EINVAL, "vqhip_argmin: bad argument");
-    if (metric != VQHIP_METRIC_L2 && metric != VQHIP_METRIC_COS && metric != VQHIP_METRIC_COS_BF16) return fail(VQHIP_EINVAL, "vqhip_argmin: metric");
-    if (x_dtype != VQHIP_DTYPE_F32 && x_dtype != VQHIP_DTYPE_BF16) return fail(VQHIP_EINVAL, "vqhip_argmin: x_dtype");
+    VQ_REQUIRE(vq_public_metric(metric), "vqhip_argmin: metric");
+    VQ_REQUIRE(vq_row_dtype(x_dtype), "vqhip_argmin: x_dtype");
     if (metric == VQHIP_METRIC_L2 && !e) return fail(VQHIP_EINVAL, "vqhip_argmin: e is required for L2");
-    if (N >= (1ll << 31) || K >= (1ll << 31)) return fail(VQHIP_EINVAL, "vqhip_argmin: N or K too large");
+    VQ_REQUIRE(vq_fits_i31(N, K), "vqhip_argmin: N or K too large");
     VQ_NEED("vqhip_argmin: cb too small", cb_bytes, vqhip_codebook_bytes(K, D));
     VQ_NEED("vqhip_argmin: ws too small", ws_bytes, vqhip_workspace_bytes(N, K, D));
     VqCbLayout L = vq_cb_layout(K, D);
@@ -779,93 +811,68 @@ int vqhip_argmin_exact(const void *x, int x_dtype, const float *e, int64_t N, in
                        float *dmin, int32_t *hist, void *ws, int64_t ws_bytes, void *stream) {
     if (N == 0) return VQHIP_OK;
     if (!x || !e || !idx || !ws || N < 0 || K <= 0 || D <= 0) return fail(VQHIP_EINVAL, "vqhip_argmin_exact: bad argument");
-    if (x_dtype != VQHIP_DTYPE_F32 && x_dtype != VQHIP_DTYPE_BF16) return fail(VQHIP_EINVAL, "vqhip_argmin_exact: x_dtype");
-    if (N >= (1ll << 31) || K >= (1ll << 31)) return fail(VQHIP_EINVAL, "vqhip_argmin_exact: N or K too large");
+    VQ_REQUIRE(vq_row_dtype(x_dtype), "vqhip_argmin_exact: x_dtype");
+    VQ_REQUIRE(vq_fits_i31(N, K), "vqhip_argmin_exact: N or K too large");
     VQ_NEED("vqhip_argmin_exact: ws too small", ws_bytes, vqhip_workspace_bytes(N, K, D));
-    hipStream_t s = (hipStream_t)stream;
-    VqWsLayout W = vq_ws_layout(N, K, D);
-    char *w = (char *)ws;
-    u64 *keys = (u64 *)(w + W.off_keys);
-    float *en = (float *)(w + W.off_en);
-    if (metric == VQHIP_METRIC_L2) {
-        int rc = vqhip_row_sqnorm(e, VQHIP_DTYPE_F32, K, D, en, stream);
-        if (rc) return rc;
-    }
-    fill_u64_kernel<<<256, 256, 0, s>>>(keys, N, ~0ull);
-    VQ_CHECK_LAUNCH("fill_u64_kernel");
-    float *xn = (float *)(w + W.off_xh2);
-    if (metric == VQHIP_METRIC_L2) {
-        int rc0 = vqhip_row_sqnorm(x, x_dtype, N, D, xn, stream);
-        if (rc0) return rc0;
-    }
-    int rc = run_exact_tiled<0>(x, x_dtype, e, en, xn, N, K, D, metric, keys, nullptr, s);
-    if (rc) return rc;
-    finalize_kernel<<<256, 256, 0, s>>>(keys, nullptr, nullptr, N, idx, dmin, hist);
-    VQ_CHECK_LAUNCH("finalize_kernel");
+    return exact_whole<0>(x, x_dtype, e, N, K, D, metric, vq_ws_view(ws, vq_ws_layout(N, K, D)), idx, dmin, hist, nullptr, (hipStream_t)stream);
+}
+
+// The column pass, roles swapped: the codebook rows are the "rows", the N latents are the "codes"; the same proposal + exact
+// re-rank pipeline then returns for every code its nearest latent.  Its metric word: the exact finishing keeps the reference's
+// operand order, (chain + |x_n|^2) + |e_k|^2 = (chain + code norm) + row norm (VQ_METRIC_SWAP); cosine uses the operands as
+// given (both normalised by the caller): VQ_METRIC_DOT.
+static inline int vq_swapped_metric(int metric) {
+    return (metric == VQHIP_METRIC_L2) ? (VQHIP_METRIC_L2 | VQ_METRIC_SWAP) : (VQ_METRIC_DOT | (metric & VQ_METRIC_BF16));
+}
+// the latents as the fp32 rows an image is made from: themselves, or (bf16) their copy in `copy`
+static int latents_as_f32(const void *x, int x_dtype, int64_t N, int D, float *copy, hipStream_t s, const float **rows) {
+    *rows = (const float *)x;
+    if (x_dtype != VQHIP_DTYPE_BF16) return VQHIP_OK;
+    int64_t n = N * (int64_t)D;
+    int grid = (int)((n + 255) / 256); grid = grid > 4096 ? 4096 : grid;
+    bf16_to_f32_kernel<<<grid, 256, 0, s>>>((const uint16_t *)x, n, copy);
+    VQ_CHECK_LAUNCH("bf16_to_f32_kernel");
+    *rows = copy;
     return VQHIP_OK;
 }
 
 int64_t vqhip_col_workspace_bytes(int64_t N, int64_t K, int D) {
     if (N <= 0 || K <= 0 || D <= 0) return 0;
-    // [pipeline workspace for K rows against N codes][image of the latents as codes][fp32 copy of bf16 latents]
-    int64_t a = (vq_ws_layout(K, N, D).total + 1023) / 1024 * 1024;
-    int64_t b = (vq_cb_layout(N, D).total + 1023) / 1024 * 1024;
-    int64_t legacy = vq_ws_layout(N, K, D).total;        // fp32-only route (D without a proposal image)
-    int64_t t = a + b + N * (int64_t)D * 4;
+    const int64_t legacy = vq_ws_layout(N, K, D).total;        // fp32-only route (D without a proposal image)
+    const int64_t t = vq_col_layout(K, N, D, false).total;
     return t > legacy ? t : legacy;
 }
 
 int vqhip_col_argmin(const void *x, int x_dtype, const float *e, int64_t N, int64_t K, int D, int metric,
                      int64_t *col_idx, void *ws, int64_t ws_bytes, void *stream) {
     if (!x || !e || !col_idx || !ws || N <= 0 || K <= 0 || D <= 0) return fail(VQHIP_EINVAL, "vqhip_col_argmin: bad argument");
-    if (N >= (1ll << 31) || K >= (1ll << 31)) return fail(VQHIP_EINVAL, "vqhip_col_argmin: N or K too large");
-    if (x_dtype != VQHIP_DTYPE_F32 && x_dtype != VQHIP_DTYPE_BF16) return fail(VQHIP_EINVAL, "vqhip_col_argmin: x_dtype");
-    if (metric != VQHIP_METRIC_L2 && metric != VQHIP_METRIC_COS && metric != VQHIP_METRIC_COS_BF16) return fail(VQHIP_EINVAL, "vqhip_col_argmin: metric");
+    VQ_REQUIRE(vq_fits_i31(N, K), "vqhip_col_argmin: N or K too large");
+    VQ_REQUIRE(vq_row_dtype(x_dtype), "vqhip_col_argmin: x_dtype");
+    VQ_REQUIRE(vq_public_metric(metric), "vqhip_col_argmin: metric");
     VQ_NEED("vqhip_col_argmin: ws too small", ws_bytes, vqhip_col_workspace_bytes(N, K, D));
     hipStream_t s = (hipStream_t)stream;
     char *w = (char *)ws;
     if (vq_coarse_supported(D)) {
-        // Roles swapped: the K codebook rows are the "rows", the N latents are the "codes"; the same proposal + exact
-        // re-rank pipeline then returns for every code its nearest latent.  The exact finishing keeps the reference's
-        // operand order: (chain + |x_n|^2) + |e_k|^2 = (chain + code norm) + row norm  (VQ_METRIC_SWAP); cosine uses
-        // the operands as given (both normalised by the caller): VQ_METRIC_DOT.
-        const int64_t a = (vq_ws_layout(K, N, D).total + 1023) / 1024 * 1024;
-        const int64_t b = (vq_cb_layout(N, D).total + 1023) / 1024 * 1024;
-        char *pipe_ws = w, *img = w + a;
-        const float *codes = (const float *)x;
-        if (x_dtype == VQHIP_DTYPE_BF16) {
-            float *copy = (float *)(w + a + b);
-            int64_t n = N * (int64_t)D;
-            int grid = (int)((n + 255) / 256); grid = grid > 4096 ? 4096 : grid;
-            bf16_to_f32_kernel<<<grid, 256, 0, s>>>((const uint16_t *)x, n, copy);
-            VQ_CHECK_LAUNCH("bf16_to_f32_kernel");
-            codes = copy;
-        }
-        const int m = (metric == VQHIP_METRIC_L2) ? (VQHIP_METRIC_L2 | VQ_METRIC_SWAP) : (VQ_METRIC_DOT | (metric & VQ_METRIC_BF16));
+        const VqColLayout C = vq_col_layout(K, N, D, false);
+        char *pipe_ws = w, *img = w + C.off_img;
+        const float *codes;
+        if (int rc = latents_as_f32(x, x_dtype, N, D, (float *)(w + C.off_copy), s, &codes)) return rc;
+        const int m = vq_swapped_metric(metric);
         // statistics of the latents-as-codebook and the token side of the codes-as-rows in one launch, then the image
-        int rc = encode_fused_front(e, VQHIP_DTYPE_F32, K, codes, N, D, m, img, pipe_ws, false, nullptr, s);
-        if (rc) return rc;
-        return argmin_pipeline(e, VQHIP_DTYPE_F32, codes, img, K, N, D, m, col_idx, nullptr, pipe_ws, stream, /*x_prepared=*/true);
+        VqTokenSide tokens;
+        if (int rc = encode_fused_front(e, VQHIP_DTYPE_F32, K, codes, N, D, m, img, pipe_ws, false, nullptr, &tokens, s)) return rc;
+        return argmin_pipeline(e, VQHIP_DTYPE_F32, codes, img, K, N, D, m, col_idx, nullptr, pipe_ws, stream, tokens);
     }
-    VqWsLayout W = vq_ws_layout(N, K, D);
-    u64 *keys = (u64 *)(w + W.off_keys);
-    float *en = (float *)(w + W.off_en);
+    // D without a proposal image: the fp32-only route with one key per code
+    const VqWsView V = vq_ws_view(ws, vq_ws_layout(N, K, D));
     if (metric == VQHIP_METRIC_L2) {
-        int rc = vqhip_row_sqnorm(e, VQHIP_DTYPE_F32, K, D, en, stream);
-        if (rc) return rc;
+        if (int rc = vqhip_row_sqnorm(e, VQHIP_DTYPE_F32, K, D, V.en, stream)) return rc;
+        if (int rc = vqhip_row_sqnorm(x, x_dtype, N, D, V.xn_whole, stream)) return rc;
     }
-    float *xn = (float *)(w + W.off_xh2);
-    if (metric == VQHIP_METRIC_L2) {
-        int rc0 = vqhip_row_sqnorm(x, x_dtype, N, D, xn, stream);
-        if (rc0) return rc0;
-    }
-    fill_u64_kernel<<<256, 256, 0, s>>>(keys, K, ~0ull);
+    fill_u64_kernel<<<256, 256, 0, s>>>(V.keys, K, ~0ull);
     VQ_CHECK_LAUNCH("fill_u64_kernel");
-    {
-        int rc1 = run_exact_tiled<1>(x, x_dtype, e, en, xn, N, K, D, metric, keys, nullptr, s);
-        if (rc1) return rc1;
-    }
-    finalize_kernel<<<256, 256, 0, s>>>(keys, nullptr, nullptr, K, col_idx, nullptr, nullptr);
+    if (int rc = run_exact_tiled<1>(x, x_dtype, e, V.en, V.xn_whole, N, K, D, metric, V.keys, nullptr, s)) return rc;
+    finalize_kernel<<<256, 256, 0, s>>>(V.keys, nullptr, nullptr, K, col_idx, nullptr, nullptr);
     VQ_CHECK_LAUNCH("finalize_kernel");
     return VQHIP_OK;
 }
@@ -880,31 +887,27 @@ int vqhip_col_argmin(const void *x, int x_dtype, const float *e, int64_t N, int6
 #ifndef VQ_COL_DIRECT_MAX_WORK
 #define VQ_COL_DIRECT_MAX_WORK (1ll << 18)
 #endif
-static inline int64_t col_direct_bytes(int64_t N, int64_t cap, int D, int64_t K) {
-    (void)cap; (void)D;
-    return (K * 8 + 1023) / 1024 * 1024 + 1024 + (N * 4 + 1023) / 1024 * 1024 + (K * 4 + 1023) / 1024 * 1024;
-}
 static bool col_direct_ok(int x_dtype, int metric, int64_t cap, int64_t N, int64_t K, int D, int64_t ws_bytes) {
     if (cap <= 0 || (D % 4) != 0) return false;
     if (x_dtype != VQHIP_DTYPE_F32) return false;        // the pass reads the tokens as fp32 rows, whatever the metric
     if (((cap + 31) / 32) * ((N + 127) / 128) * (int64_t)D > VQ_COL_DIRECT_MAX_WORK) return false;
-    return ws_bytes >= col_direct_bytes(N, cap, D, K);
+    return ws_bytes >= vq_col_direct_layout(N, K).total;
 }
 // x: the tokens [N, D] as the exact definition consumes them (fp32), e: the codebook rows [K, D] likewise; tok_norm / row_norm:
 // oracle-order |x_n|^2 [N] / |e_k|^2 [K] where a caller has them already (L2 only; nullable: computed here)
 static int col_rows_direct(const void *x, const float *e, const int32_t *rows, const int32_t *count, int64_t cap, int64_t N,
                            int64_t K, int D, int metric, int64_t *col_idx, char *ws, const float *tok_norm, const float *row_norm,
                            hipStream_t s) {
+    const VqColDirectLayout C = vq_col_direct_layout(N, K);
     u64 *keys = (u64 *)ws;
-    int *ticket = (int *)(ws + (K * 8 + 1023) / 1024 * 1024);
-    float *en = (float *)((char *)ticket + 1024);
-    float *xn = (float *)((char *)en + (N * 4 + 1023) / 1024 * 1024);
+    int *ticket = (int *)(ws + C.off_ticket);
+    float *tok_ws = (float *)(ws + C.off_tok_norm), *row_ws = (float *)(ws + C.off_row_norm);
     col_direct_init_kernel<<<(int)((cap + 255) / 256), 256, 0, s>>>(rows, count, cap, keys, ticket);
     VQ_CHECK_LAUNCH("col_direct_init_kernel");
-    const int m = (metric == VQHIP_METRIC_L2) ? (VQHIP_METRIC_L2 | VQ_METRIC_SWAP) : (VQ_METRIC_DOT | (metric & VQ_METRIC_BF16));
+    const int m = vq_swapped_metric(metric);
     if (metric == VQHIP_METRIC_L2) {
-        if (!tok_norm) { if (int rc = vqhip_row_sqnorm(x, VQHIP_DTYPE_F32, N, D, en, s)) return rc; tok_norm = en; }
-        if (!row_norm) { if (int rc = vqhip_row_sqnorm(e, VQHIP_DTYPE_F32, K, D, xn, s)) return rc; row_norm = xn; }
+        if (!tok_norm) { if (int rc = vqhip_row_sqnorm(x, VQHIP_DTYPE_F32, N, D, tok_ws, s)) return rc; tok_norm = tok_ws; }
+        if (!row_norm) { if (int rc = vqhip_row_sqnorm(e, VQHIP_DTYPE_F32, K, D, row_ws, s)) return rc; row_norm = row_ws; }
     }
     const int64_t ncb = (N + 63) / 64;
     const int grid = (int)(ncb < 256 ? 256 : (ncb > 1024 ? 1024 : ncb));
@@ -921,13 +924,9 @@ static int col_rows_direct(const void *x, const float *e, const int32_t *rows, c
 
 int64_t vqhip_col_rows_workspace_bytes(int64_t N, int64_t cap, int D) {
     if (N <= 0 || cap <= 0 || D <= 0 || !vq_coarse_supported(D)) return 0;
-    // [pipeline workspace for cap rows against N codes][image of the latents as codes][the listed codebook rows][fp32 copy of bf16 latents]
-    const int64_t a = (vq_ws_layout(cap, N, D).total + 1023) / 1024 * 1024;
-    const int64_t b = (vq_cb_layout(N, D).total + 1023) / 1024 * 1024;
-    const int64_t c = (cap * (int64_t)D * 4 + 1023) / 1024 * 1024;
     // (the direct form of a short list, col_rows_direct, lives in the same buffer: 12 K + 4 N bytes — it is taken only where the
     //  buffer it is handed is large enough for it, which the size below is unless K exceeds ~N D / 2)
-    return a + b + c + N * (int64_t)D * 4;
+    return vq_col_layout(cap, N, D, true).total;
 }
 
 int vqhip_col_argmin_rows(const void *x, int x_dtype, const float *e, const int32_t *rows, const int32_t *count, int64_t cap,
@@ -936,19 +935,17 @@ int vqhip_col_argmin_rows(const void *x, int x_dtype, const float *e, const int3
         return fail(VQHIP_EINVAL, "vqhip_col_argmin_rows: bad argument");
     if (cap == 0) return VQHIP_OK;
     if (!vq_coarse_supported(D)) return fail(VQHIP_EINVAL, "vqhip_col_argmin_rows: needs D <= 1024, D % 8 == 0 (use vqhip_col_argmin)");
-    if (N >= (1ll << 31) || K >= (1ll << 31)) return fail(VQHIP_EINVAL, "vqhip_col_argmin_rows: N or K too large");
-    if (x_dtype != VQHIP_DTYPE_F32 && x_dtype != VQHIP_DTYPE_BF16) return fail(VQHIP_EINVAL, "vqhip_col_argmin_rows: x_dtype");
-    if (metric != VQHIP_METRIC_L2 && metric != VQHIP_METRIC_COS && metric != VQHIP_METRIC_COS_BF16) return fail(VQHIP_EINVAL, "vqhip_col_argmin_rows: metric");
+    VQ_REQUIRE(vq_fits_i31(N, K), "vqhip_col_argmin_rows: N or K too large");
+    VQ_REQUIRE(vq_row_dtype(x_dtype), "vqhip_col_argmin_rows: x_dtype");
+    VQ_REQUIRE(vq_public_metric(metric), "vqhip_col_argmin_rows: metric");
     VQ_NEED("vqhip_col_argmin_rows: ws too small", ws_bytes, vqhip_col_rows_workspace_bytes(N, cap, D));
     hipStream_t s = (hipStream_t)stream;
     char *w = (char *)ws;
     if (col_direct_ok(x_dtype, metric, cap, N, K, D, ws_bytes))      // a short list: the fp32 pass itself, two launches (four for L2)
         return col_rows_direct(x, e, rows, count, cap, N, K, D, metric, col_idx, w, nullptr, nullptr, s);
-    const int64_t a = (vq_ws_layout(cap, N, D).total + 1023) / 1024 * 1024;
-    const int64_t b = (vq_cb_layout(N, D).total + 1023) / 1024 * 1024;
-    const int64_t c = (cap * (int64_t)D * 4 + 1023) / 1024 * 1024;
-    char *pipe_ws = w, *img = w + a;
-    float *esub = (float *)(w + a + b);
+    const VqColLayout C = vq_col_layout(cap, N, D, true);
+    char *pipe_ws = w, *img = w + C.off_img;
+    float *esub = (float *)(w + C.off_rows);
     // the gather of the listed rows rides in the front launch of the pipeline (token side of pre_kernel) except at a padded
     // dimension of 32, whose token side is the wave-level form
     const bool fused_gather = vq_cb_layout(N, D).nstep != 2;
@@ -956,47 +953,24 @@ int vqhip_col_argmin_rows(const void *x, int x_dtype, const float *e, const int3
         gather_listed_rows_kernel<<<waves_grid(cap, 4), 256, 0, s>>>(e, rows, count, cap, D, esub);
         VQ_CHECK_LAUNCH("gather_listed_rows_kernel");
     }
-    const float *codes = (const float *)x;
-    if (x_dtype == VQHIP_DTYPE_BF16) {
-        float *copy = (float *)(w + a + b + c);
-        int64_t n = N * (int64_t)D;
-        int grid = (int)((n + 255) / 256); grid = grid > 4096 ? 4096 : grid;
-        bf16_to_f32_kernel<<<grid, 256, 0, s>>>((const uint16_t *)x, n, copy);
-        VQ_CHECK_LAUNCH("bf16_to_f32_kernel");
-        codes = copy;
-    }
+    const float *codes;
+    if (int rc = latents_as_f32(x, x_dtype, N, D, (float *)(w + C.off_copy), s, &codes)) return rc;
     // the role-swapped pipeline of vqhip_col_argmin on the listed codes: sized for `cap` rows, live for *count of them
-    const int m = (metric == VQHIP_METRIC_L2) ? (VQHIP_METRIC_L2 | VQ_METRIC_SWAP) : (VQ_METRIC_DOT | (metric & VQ_METRIC_BF16));
-    int rc = fused_gather ? encode_fused_front(e, VQHIP_DTYPE_F32, cap, codes, N, D, m, img, pipe_ws, false, nullptr, s, nullptr, 0, esub, rows, count)
-                          : encode_fused_front(esub, VQHIP_DTYPE_F32, cap, codes, N, D, m, img, pipe_ws, false, nullptr, s);
+    const int m = vq_swapped_metric(metric);
+    VqTokenSide tokens;
+    int rc = fused_gather ? encode_fused_front(e, VQHIP_DTYPE_F32, cap, codes, N, D, m, img, pipe_ws, false, nullptr, &tokens, s, nullptr, 0, esub, rows, count)
+                          : encode_fused_front(esub, VQHIP_DTYPE_F32, cap, codes, N, D, m, img, pipe_ws, false, nullptr, &tokens, s);
     if (rc) return rc;
-    return argmin_pipeline(esub, VQHIP_DTYPE_F32, codes, img, cap, N, D, m, col_idx, nullptr, pipe_ws, stream, /*x_prepared=*/true, count);
+    return argmin_pipeline(esub, VQHIP_DTYPE_F32, codes, img, cap, N, D, m, col_idx, nullptr, pipe_ws, stream, tokens, count);
 }
 
 int vqhip_distance(const void *x, int x_dtype, const float *e, int64_t N, int64_t K, int D, int metric, float *d, void *ws,
                    int64_t ws_bytes, void *stream) {
     if (!x || !e || !d || !ws || N <= 0 || K <= 0 || D <= 0) return fail(VQHIP_EINVAL, "vqhip_distance: bad argument");
     VQ_NEED("vqhip_distance: ws too small", ws_bytes, vqhip_workspace_bytes(N, K, D));
-    hipStream_t s = (hipStream_t)stream;
-    VqWsLayout W = vq_ws_layout(N, K, D);
-    char *w = (char *)ws;
-    float *en = (float *)(w + W.off_en);
-    if (metric == VQHIP_METRIC_L2) {
-        int rc = vqhip_row_sqnorm(e, VQHIP_DTYPE_F32, K, D, en, stream);
-        if (rc) return rc;
-    }
-    float *xn = (float *)(w + W.off_xh2);
-    if (metric == VQHIP_METRIC_L2) {
-        int rc0 = vqhip_row_sqnorm(x, x_dtype, N, D, xn, stream);
-        if (rc0) return rc0;
-    }
-    if (x_dtype != VQHIP_DTYPE_F32 && x_dtype != VQHIP_DTYPE_BF16) return fail(VQHIP_EINVAL, "vqhip_distance: x_dtype");
-    {
-        int rc1 = run_exact_tiled<2>(x, x_dtype, e, en, xn, N, K, D, metric, nullptr, d, s);
-        if (rc1) return rc1;
-    }
-    VQ_CHECK_LAUNCH("exact_kernel<dist>");
-    return VQHIP_OK;
+    VQ_REQUIRE(vq_row_dtype(x_dtype), "vqhip_distance: x_dtype");
+    VQ_REQUIRE(vq_public_metric(metric), "vqhip_distance: metric");
+    return exact_whole<2>(x, x_dtype, e, N, K, D, metric, vq_ws_view(ws, vq_ws_layout(N, K, D)), nullptr, nullptr, nullptr, d, (hipStream_t)stream);
 }
 
 static int gather_ste_impl(const void *x, int x_dtype, const float *e, const int64_t *idx, int64_t N, int D, float *z,
@@ -1021,7 +995,7 @@ int vqhip_gather_ste_map(const void *x_rows, int x_dtype, const float *e, const 
         return fail(VQHIP_EINVAL, "vqhip_gather_ste_map: bad argument");
     hipStream_t s = (hipStream_t)stream;
     double *sse = x_rows ? (double *)scratch16 : nullptr;
-    if (x_rows && x_dtype != VQHIP_DTYPE_F32 && x_dtype != VQHIP_DTYPE_BF16) return fail(VQHIP_EINVAL, "vqhip_gather_ste_map: x_dtype");
+    VQ_REQUIRE(!x_rows || vq_row_dtype(x_dtype), "vqhip_gather_ste_map: x_dtype");
     if (HW % 256 == 0 && D % 32 == 0) {
         // images of a multiple of 256 positions: whole 1 KiB channel rows per wave-store (gather_ste_map256_kernel)
         const int64_t nt = N / 256;
@@ -1066,38 +1040,8 @@ static int gather_ste_impl(const void *x, int x_dtype, const float *e, const int
     return VQHIP_OK;
 }
 
-int vqhip_hist(const int64_t *idx, int64_t N, int64_t K, int32_t *hist, void *stream) {
-    if (!idx || !hist || N < 0 || K <= 0) return fail(VQHIP_EINVAL, "vqhip_hist: bad argument");
-    if (N == 0) return VQHIP_OK;
-    if (K <= 32768 && N >= 16384) {
-        // enough tokens per block that the K-bin flush pays: at most 256 blocks, >= 2048 tokens each
-        static LdsCache lds_set;
-        if (int rc = ensure_dyn_lds((const void *)hist_lds_kernel, (size_t)K * 4, lds_set)) return rc;
-        int grid = (int)((N + 2047) / 2048); grid = grid > 256 ? 256 : grid;
-        hist_lds_kernel<<<grid, 1024, (size_t)K * 4, (hipStream_t)stream>>>(idx, N, (int)K, hist);
-    } else {
-        int grid = (int)((N + 255) / 256); grid = grid > 2048 ? 2048 : grid;
-        hist_kernel<<<grid, 256, 0, (hipStream_t)stream>>>(idx, N, K, hist);
-    }
-    VQ_CHECK_LAUNCH("hist_kernel");
-    return VQHIP_OK;
-}
-
-int vqhip_hist_i32(const int32_t *idx, int64_t N, int64_t K, int32_t *hist, void *stream) {
-    if (!idx || !hist || N < 0 || K <= 0) return fail(VQHIP_EINVAL, "vqhip_hist_i32: bad argument");
-    if (N == 0) return VQHIP_OK;
-    if (K <= 32768 && N >= 16384) {
-        static LdsCache lds_set;
-        if (int rc = ensure_dyn_lds((const void *)hist_i32_lds_kernel, (size_t)K * 4, lds_set)) return rc;
-        int grid = (int)((N + 2047) / 2048); grid = grid > 256 ? 256 : grid;
-        hist_i32_lds_kernel<<<grid, 1024, (size_t)K * 4, (hipStream_t)stream>>>(idx, N, (int)K, hist);
-    } else {
-        int grid = (int)((N + 255) / 256); grid = grid > 2048 ? 2048 : grid;
-        hist_i32_kernel<<<grid, 256, 0, (hipStream_t)stream>>>(idx, N, K, hist);
-    }
-    VQ_CHECK_LAUNCH("hist_i32_kernel");
-    return VQHIP_OK;
-}
+int vqhip_hist(const int64_t *idx, int64_t N, int64_t K, int32_t *hist, void *stream) { return launch_hist(idx, N, K, hist, stream); }
+int vqhip_hist_i32(const int32_t *idx, int64_t N, int64_t K, int32_t *hist, void *stream) { return launch_hist(idx, N, K, hist, stream); }
 
 // ---- FiniteScalarQuantizer ----------------------------------------------------------------------------------------------
 // Validates the caller's constants and the shape, and turns them into the kernels' by-value argument.  Every refusal names
@@ -1148,7 +1092,7 @@ int vqhip_fsq_encode(const vqhip_fsq_t *q, const void *x, int x_dtype, int layou
     int grid = 0;
     if (int rc = fsq_setup(what, q, layout, N, HW, &k, &grid)) return rc;
     if (!x || !quant) return fail(VQHIP_EINVAL, what, "x and quant are required");
-    if (x_dtype != VQHIP_DTYPE_F32 && x_dtype != VQHIP_DTYPE_BF16) return fail(VQHIP_EINVAL, what, "x_dtype");
+    if (!vq_row_dtype(x_dtype)) return fail(VQHIP_EINVAL, what, "x_dtype");
     if (x_rows && layout != VQHIP_LAYOUT_MAP) return fail(VQHIP_EINVAL, what, "x_rows is a by-product of the map layout");
     if (N == 0) return VQHIP_OK;
     const int vec = fsq_aligned(x, VQ_FSQ_VEC_X) | fsq_aligned(z, VQ_FSQ_VEC_Z) | fsq_aligned(x_rows, VQ_FSQ_VEC_ROWS);
@@ -1169,7 +1113,7 @@ int vqhip_fsq_backward(const vqhip_fsq_t *q, const void *x, int x_dtype, int lay
     int grid = 0;
     if (int rc = fsq_setup(what, q, layout, N, HW, &k, &grid)) return rc;
     if (!x || !g || !grad_x) return fail(VQHIP_EINVAL, what, "x, g and grad_x are required");
-    if (x_dtype != VQHIP_DTYPE_F32 && x_dtype != VQHIP_DTYPE_BF16) return fail(VQHIP_EINVAL, what, "x_dtype");
+    if (!vq_row_dtype(x_dtype)) return fail(VQHIP_EINVAL, what, "x_dtype");
     if (N == 0) return VQHIP_OK;
     const int vec = fsq_aligned(x, VQ_FSQ_VEC_X) | fsq_aligned(grad_x, VQ_FSQ_VEC_Z) | fsq_aligned(g, VQ_FSQ_VEC_G);
     hipStream_t s = (hipStream_t)stream;
@@ -1416,7 +1360,7 @@ int vqhip_cvq_col_keys(const void *x, int x_dtype, const float *e, const int32_t
         return fail(VQHIP_EINVAL, "vqhip_cvq_col_keys: bad argument");
     if (N > VQHIP_SYNC_MAX_ROWS || rank < 0 || rank >= VQ_PACK_MAX_WORLD)
         return fail(VQHIP_EINVAL, "vqhip_cvq_col_keys: a key holds 24 bits of row and 8 bits of rank (N <= 2^24, rank < 256)");
-    if (metric != VQHIP_METRIC_L2 && metric != VQHIP_METRIC_COS && metric != VQHIP_METRIC_COS_BF16) return fail(VQHIP_EINVAL, "vqhip_cvq_col_keys: metric");
+    VQ_REQUIRE(vq_public_metric(metric), "vqhip_cvq_col_keys: metric");
     if (cap == 0) return VQHIP_OK;
     hipStream_t s = (hipStream_t)stream;
     const int grid = (int)((cap + 63) / 64);
@@ -1443,22 +1387,18 @@ int vqhip_cvq_pack_sync(const int32_t *hist, int64_t numel, const void *x, int x
 }
 
 // ---- one host call per training forward (include/vqhip.h) ------------------------------------------------------------
-static inline int64_t vq_align1k(int64_t v) { return (v + 1023) / 1024 * 1024; }
-
-// workspace of vqhip_cvq_forward: [row pass: vqhip_workspace_bytes(N, K, D)][col_idx: K int64][column pass over <= cap_max codes]
 int64_t vqhip_cvq_forward_ws_bytes(int64_t N, int64_t K, int D, int64_t cap_max) {
     if (N <= 0 || K <= 0 || D <= 0 || cap_max < 0 || cap_max > K) return 0;
-    return vq_align1k(vqhip_workspace_bytes(N, K, D)) + vq_align1k(K * 8) + (cap_max > 0 ? vqhip_col_rows_workspace_bytes(N, cap_max, D) : 0);
+    return vq_cvq_ws_layout(N, K, D, cap_max).total;
 }
 
 int vqhip_cvq_forward(vqhip_cvq_forward_t *a, void *stream) {
     if (!a || a->struct_bytes != (int64_t)sizeof(vqhip_cvq_forward_t)) return fail(VQHIP_EINVAL, "vqhip_cvq_forward: struct_bytes != sizeof(vqhip_cvq_forward_t)");
     const int64_t N = a->N, K = a->K;
     const int D = a->D, metric = a->metric;
-    if (N <= 0 || K <= 0 || D <= 0 || N >= (1ll << 31) || K >= (1ll << 31) || !vq_coarse_supported(D))
-        return fail(VQHIP_EINVAL, "vqhip_cvq_forward: needs N, K > 0 and D <= 1024, D % 8 == 0");
-    if (metric != VQHIP_METRIC_L2 && metric != VQHIP_METRIC_COS && metric != VQHIP_METRIC_COS_BF16) return fail(VQHIP_EINVAL, "vqhip_cvq_forward: metric");
-    if (a->x_dtype != VQHIP_DTYPE_F32 && a->x_dtype != VQHIP_DTYPE_BF16) return fail(VQHIP_EINVAL, "vqhip_cvq_forward: x_dtype");
+    VQ_REQUIRE(N > 0 && K > 0 && D > 0 && vq_fits_i31(N, K) && vq_coarse_supported(D), "vqhip_cvq_forward: needs N, K > 0 and D <= 1024, D % 8 == 0");
+    VQ_REQUIRE(vq_public_metric(metric), "vqhip_cvq_forward: metric");
+    VQ_REQUIRE(vq_row_dtype(a->x_dtype), "vqhip_cvq_forward: x_dtype");
     const bool sync = a->exchange && a->anchor_sync;
     if (a->phases < 1 || (a->phases > VQHIP_STEP_ALL && !(sync && a->phases == VQHIP_STEP_PACK_SYNC))) return fail(VQHIP_EINVAL, "vqhip_cvq_forward: phases");
     if (!a->x || !a->w_in || !a->p_in || !a->w_out || !a->p_out || !a->rows || !a->slot || !a->count || !a->cb || !a->idx || !a->hist || !a->ws)
@@ -1478,15 +1418,15 @@ int vqhip_cvq_forward(vqhip_cvq_forward_t *a, void *stream) {
         if (N > VQHIP_SYNC_MAX_ROWS) return fail(VQHIP_EINVAL, "vqhip_cvq_forward: anchor_sync holds a row in 24 bits (N <= 2^24 per rank)");
     }
     hipStream_t s = (hipStream_t)stream;
-    const int64_t enc_bytes = vq_align1k(vqhip_workspace_bytes(N, K, D));
-    VQ_NEED("vqhip_cvq_forward: ws too small", a->ws_bytes, enc_bytes + vq_align1k(K * 8));
+    const VqCvqWsLayout C = vq_cvq_ws_layout(N, K, D, 0);       // the column pass is sized once this step's capacity is known
+    VQ_NEED("vqhip_cvq_forward: ws too small", a->ws_bytes, C.total);
     char *w = (char *)a->ws;
-    int64_t *col_idx = (int64_t *)(w + enc_bytes);
-    char *col_ws = w + enc_bytes + vq_align1k(K * 8);
-    const int64_t col_ws_have = a->ws_bytes - enc_bytes - vq_align1k(K * 8);
+    int64_t *col_idx = (int64_t *)(w + C.off_col_idx);
+    char *col_ws = w + C.off_col_ws;
+    const int64_t col_ws_have = a->ws_bytes - C.off_col_ws;
     if (a->phases != VQHIP_STEP_PACK_SYNC && (a->phases & VQHIP_STEP_BEFORE_EXCHANGE)) {
         if (int rc = vqhip_encode_ex(a->x, a->x_dtype, a->w_in, N, K, D, metric, a->cb, a->cb_bytes, a->idx, a->hist, a->xq, a->ws,
-                                     enc_bytes, VQHIP_ENCODE_ZERO_HIST, stream)) return rc;
+                                     C.enc_bytes, VQHIP_ENCODE_ZERO_HIST, stream)) return rc;
         if (!a->list_ready)
             if (int rc = vqhip_cvq_rows(a->p_in, K, a->ema_decay, a->eps, a->rows, a->slot, a->count, stream)) return rc;
         if (!a->exchange && a->early_word_host && a->early_seq_dev) {     // one rank: the histogram is final behind the encode
@@ -1547,35 +1487,22 @@ int vqhip_cvq_forward(vqhip_cvq_forward_t *a, void *stream) {
     return VQHIP_OK;
 }
 
-// workspace of vqhip_vqkd_forward: [encode: vqhip_workspace_bytes(N, K, D)][ordered sums: counts K, offsets K + 1, order N int32,
-// vqhip_order_workspace_bytes, vqhip_segsum_workspace_bytes]
-static inline void vqkd_ws_offsets(int64_t N, int64_t K, int D, int64_t *o_counts, int64_t *o_offsets, int64_t *o_order, int64_t *o_ows,
-                                   int64_t *o_sws, int64_t *o_x2, int64_t *total) {
-    int64_t p = vq_align1k(vq_ws_layout(N, K, D).total);
-    *o_x2 = p; p += vq_align1k(N * (int64_t)D * 4);        // F.normalize(xn) for the ordered sums under the bf16-autocast metric (xq is rounded there)
-    *o_counts = p; p += vq_align1k(K * 4);
-    *o_offsets = p; p += vq_align1k((K + 1) * 4);
-    *o_order = p; p += vq_align1k(N * 4);
-    *o_ows = p; p += vq_align1k(vqhip_order_workspace_bytes(N, K));
-    *o_sws = p; p += vq_align1k(vqhip_segsum_workspace_bytes(N, D));
-    *total = p;
+static inline VqKdWsLayout vqkd_ws_layout(int64_t N, int64_t K, int D) {
+    return vq_kd_ws_layout(N, K, D, vqhip_order_workspace_bytes(N, K), vqhip_segsum_workspace_bytes(N, D));
 }
 
 int64_t vqhip_vqkd_forward_ws_bytes(int64_t N, int64_t K, int D) {
     if (N <= 0 || K <= 0 || D <= 0) return 0;
-    int64_t a, b, c, d, e, f, total;
-    vqkd_ws_offsets(N, K, D, &a, &b, &c, &d, &e, &f, &total);
-    return total;
+    return vqkd_ws_layout(N, K, D).total;
 }
 
 int vqhip_vqkd_forward(vqhip_vqkd_forward_t *a, void *stream) {
     if (!a || a->struct_bytes != (int64_t)sizeof(vqhip_vqkd_forward_t)) return fail(VQHIP_EINVAL, "vqhip_vqkd_forward: struct_bytes != sizeof(vqhip_vqkd_forward_t)");
     const int64_t N = a->N, K = a->K;
     const int D = a->D;
-    if (N <= 0 || K <= 0 || D <= 0 || N >= (1ll << 31) || K >= (1ll << 31) || !vq_coarse_supported(D))
-        return fail(VQHIP_EINVAL, "vqhip_vqkd_forward: needs N, K > 0 and D <= 1024, D % 8 == 0");
+    VQ_REQUIRE(N > 0 && K > 0 && D > 0 && vq_fits_i31(N, K) && vq_coarse_supported(D), "vqhip_vqkd_forward: needs N, K > 0 and D <= 1024, D % 8 == 0");
     if (a->metric != VQHIP_METRIC_COS && a->metric != VQHIP_METRIC_COS_BF16) return fail(VQHIP_EINVAL, "vqhip_vqkd_forward: metric (cosine only)");
-    if (a->x_dtype != VQHIP_DTYPE_F32 && a->x_dtype != VQHIP_DTYPE_BF16) return fail(VQHIP_EINVAL, "vqhip_vqkd_forward: x_dtype");
+    VQ_REQUIRE(vq_row_dtype(a->x_dtype), "vqhip_vqkd_forward: x_dtype");
     if (a->phases < 1 || a->phases > VQHIP_STEP_ALL) return fail(VQHIP_EINVAL, "vqhip_vqkd_forward: phases");
     if (!a->x || !a->w_in || !a->w_mid || !a->w_out || !a->xn || !a->xq || !a->cb || !a->idx || !a->hist || !a->packed || !a->ws)
         return fail(VQHIP_EINVAL, "vqhip_vqkd_forward: null pointer");
@@ -1586,9 +1513,8 @@ int vqhip_vqkd_forward(vqhip_vqkd_forward_t *a, void *stream) {
     if (a->ordered && (K > 32768 || (D % 4) != 0)) return fail(VQHIP_EINVAL, "vqhip_vqkd_forward: ordered sums need K <= 32768 and D % 4 == 0");
     const int64_t floats = vqhip_pack_floats(K, K, D);
     VQ_NEED("vqhip_vqkd_forward: packed buffer too small (floats)", a->packed_floats, floats);
-    int64_t o_counts, o_offsets, o_order, o_ows, o_sws, o_x2, total;
-    vqkd_ws_offsets(N, K, D, &o_counts, &o_offsets, &o_order, &o_ows, &o_sws, &o_x2, &total);
-    VQ_NEED("vqhip_vqkd_forward: ws too small", a->ws_bytes, total);
+    const VqKdWsLayout C = vqkd_ws_layout(N, K, D);
+    VQ_NEED("vqhip_vqkd_forward: ws too small", a->ws_bytes, C.total);
     hipStream_t s = (hipStream_t)stream;
     char *w = (char *)a->ws;
     float *payload = a->packed + VQ_PACK_HEADER(K);
@@ -1603,17 +1529,17 @@ int vqhip_vqkd_forward(vqhip_vqkd_forward_t *a, void *stream) {
         if (int rc = launch_vqkd_front(a->w_in, a->w_mid, K, a->x, a->x_dtype, a->xn, N, D, 1e-12f, payload, nzero, 2, s)) return rc;
         const int xblocks = (int)((N + 3) / 4);             // wave per token: the scatter below
         if (int rc = vqhip_encode_ex(a->xn, VQHIP_DTYPE_F32, a->w_mid, N, K, D, a->metric, a->cb, a->cb_bytes, a->idx, a->hist, a->xq, a->ws,
-                                     vq_align1k(vq_ws_layout(N, K, D).total), VQHIP_ENCODE_ZERO_HIST, stream)) return rc;
+                                     C.enc_bytes, VQHIP_ENCODE_ZERO_HIST, stream)) return rc;
         const int hb = (int)((K + 255) / 256);
         if (a->ordered) {
-            int32_t *counts = (int32_t *)(w + o_counts), *offsets = (int32_t *)(w + o_offsets), *order = (int32_t *)(w + o_order);
-            if (int rc = vqhip_token_order(a->idx, N, K, counts, offsets, order, w + o_ows, vqhip_order_workspace_bytes(N, K), stream)) return rc;
+            int32_t *counts = (int32_t *)(w + C.off_counts), *offsets = (int32_t *)(w + C.off_offsets), *order = (int32_t *)(w + C.off_order);
+            if (int rc = vqhip_token_order(a->idx, N, K, counts, offsets, order, w + C.off_order_ws, vqhip_order_workspace_bytes(N, K), stream)) return rc;
             const float *x2 = a->xq;                      // F.normalize(xn): the encode's by-product — except under the bf16-autocast
             if (VQ_IS_BF16(a->metric)) {                  // metric, where xq holds the ROUNDED rows (the operand of that metric)
-                if (int rc = vqhip_normalize_rows(a->xn, VQHIP_DTYPE_F32, N, D, 1e-12f, (float *)(w + o_x2), stream)) return rc;
-                x2 = (const float *)(w + o_x2);
+                if (int rc = vqhip_normalize_rows(a->xn, VQHIP_DTYPE_F32, N, D, 1e-12f, (float *)(w + C.off_x2), stream)) return rc;
+                x2 = (const float *)(w + C.off_x2);
             }
-            if (int rc = vqhip_segsum_rows(x2, a->idx, order, offsets, N, K, D, payload, w + o_sws, vqhip_segsum_workspace_bytes(N, D), stream)) return rc;
+            if (int rc = vqhip_segsum_rows(x2, a->idx, order, offsets, N, K, D, payload, w + C.off_segsum_ws, vqhip_segsum_workspace_bytes(N, D), stream)) return rc;
             vqkd_scatter_pack_kernel<<<hb, 256, 0, s>>>(a->hist, N, a->xn, a->idx, N, K, D, 1e-12f, a->packed, hb, 0);
         } else {
             vqkd_scatter_pack_kernel<<<hb + xblocks, 256, 0, s>>>(a->hist, N, a->xn, a->idx, N, K, D, 1e-12f, a->packed, hb, 1);
@@ -1627,9 +1553,9 @@ int vqhip_vqkd_forward(vqhip_vqkd_forward_t *a, void *stream) {
         VQ_CHECK_LAUNCH("vqkd_update_packed_kernel");
         if (a->tail) {
             // per-workgroup partial sums of the loss (<= 256 doubles): the record area of the encode's workspace, free by now
-            double *tail_partials = (double *)((char *)a->ws + vq_ws_layout(N, K, D).off_rec);
+            double *tail_partials = (double *)vq_ws_view(a->ws, vq_ws_layout(N, K, D)).rec;
             if (D <= 32) {                                  // L lanes per token (vqhip_step_kernels.h)
-                const int L = D <= 8 ? 8 : (D <= 16 ? 16 : 32), rpb = 16 * (64 / L);
+                const int L = vq_small_lanes(D), rpb = 16 * (64 / L);
                 int grid = (int)((N + rpb - 1) / rpb); grid = grid > 256 ? 256 : grid;
                 if (L == 8) vqkd_tail_small_kernel<8><<<grid, 1024, 0, s>>>(a->xn, a->w_out, a->idx, N, D, 1e-12f, a->z_ste, (double *)a->scratch16, a->mse, tail_partials);
                 else if (L == 16) vqkd_tail_small_kernel<16><<<grid, 1024, 0, s>>>(a->xn, a->w_out, a->idx, N, D, 1e-12f, a->z_ste, (double *)a->scratch16, a->mse, tail_partials);
@@ -1648,9 +1574,9 @@ int vqhip_vq_forward(vqhip_vq_forward_t *a, void *stream) {
     if (!a || a->struct_bytes != (int64_t)sizeof(vqhip_vq_forward_t)) return fail(VQHIP_EINVAL, "vqhip_vq_forward: struct_bytes != sizeof(vqhip_vq_forward_t)");
     const int64_t N = a->N, K = a->K;
     const int D = a->D;
-    if (N <= 0 || K <= 0 || D <= 0 || N >= (1ll << 31) || K >= (1ll << 31)) return fail(VQHIP_EINVAL, "vqhip_vq_forward: N, K, D");
-    if (a->metric != VQHIP_METRIC_L2 && a->metric != VQHIP_METRIC_COS && a->metric != VQHIP_METRIC_COS_BF16) return fail(VQHIP_EINVAL, "vqhip_vq_forward: metric");
-    if (a->x_dtype != VQHIP_DTYPE_F32 && a->x_dtype != VQHIP_DTYPE_BF16) return fail(VQHIP_EINVAL, "vqhip_vq_forward: x_dtype");
+    VQ_REQUIRE(N > 0 && K > 0 && D > 0 && vq_fits_i31(N, K), "vqhip_vq_forward: N, K, D");
+    VQ_REQUIRE(vq_public_metric(a->metric), "vqhip_vq_forward: metric");
+    VQ_REQUIRE(vq_row_dtype(a->x_dtype), "vqhip_vq_forward: x_dtype");
     if (!a->x || !a->w_in || !a->cb || !a->idx || !a->ws || (a->normalize && (!a->w_out || !a->xn))) return fail(VQHIP_EINVAL, "vqhip_vq_forward: null pointer");
     if (VQ_IS_COS(a->metric) && !a->xq) return fail(VQHIP_EINVAL, "vqhip_vq_forward: the cosine metric needs the xq buffer");
     if ((a->z_ste || a->mse) && (!a->mse || !a->scratch16)) return fail(VQHIP_EINVAL, "vqhip_vq_forward: the decode tail needs mse and scratch16");
@@ -1675,9 +1601,9 @@ int vqhip_vqkd_backward(const void *x, int x_dtype, const float *xn, const float
     if (!x || !xn || !w || !idx || !grad_x || N < 0 || D <= 0) return fail(VQHIP_EINVAL, "vqhip_vqkd_backward: bad argument");
     if (N == 0) return VQHIP_OK;
     hipStream_t s = (hipStream_t)stream;
-    if (x_dtype != VQHIP_DTYPE_F32 && x_dtype != VQHIP_DTYPE_BF16) return fail(VQHIP_EINVAL, "vqhip_vqkd_backward: x_dtype");
+    VQ_REQUIRE(vq_row_dtype(x_dtype), "vqhip_vqkd_backward: x_dtype");
     if (D <= 32) {                                          // L lanes per token (vqhip_step_kernels.h)
-        const int L = D <= 8 ? 8 : (D <= 16 ? 16 : 32), rpb = 4 * (64 / L);
+        const int L = vq_small_lanes(D), rpb = 4 * (64 / L);
         int grid = (int)((N + rpb - 1) / rpb); grid = grid > 2048 ? 2048 : grid;
 #define VQ_BWD_SMALL(DT, LL) vqkd_backward_small_kernel<DT, LL><<<grid, 256, 0, s>>>(x, xn, w, idx, N, D, 1e-12f, g_zste, g_loss, grad_x)
         if (x_dtype == VQHIP_DTYPE_F32) { if (L == 8) VQ_BWD_SMALL(0, 8); else if (L == 16) VQ_BWD_SMALL(0, 16); else VQ_BWD_SMALL(0, 32); }
@@ -1740,8 +1666,7 @@ int vqhip_vq_backward_map(const void *x_rows, int x_dtype, const float *e, const
                           void *stream) {
     if (!x_rows || !e || !idx || !grad_map || B <= 0 || HW <= 0 || D <= 0) return fail(VQHIP_EINVAL, "vqhip_vq_backward_map: bad argument");
     if ((HW % 256) != 0 || (D % 32) != 0) return fail(VQHIP_EINVAL, "vqhip_vq_backward_map: needs HW % 256 == 0 and D % 32 == 0 (transpose and use vqhip_vq_backward_ex)");
-    if ((x_dtype != VQHIP_DTYPE_F32 && x_dtype != VQHIP_DTYPE_BF16) || (grad_dtype != VQHIP_DTYPE_F32 && grad_dtype != VQHIP_DTYPE_BF16))
-        return fail(VQHIP_EINVAL, "vqhip_vq_backward_map: dtype");
+    VQ_REQUIRE(vq_row_dtype(x_dtype) && vq_row_dtype(grad_dtype), "vqhip_vq_backward_map: dtype");
     const int64_t N = B * HW, nt = N / 256;
     int csplit = 1;
     while (nt * csplit < 512 && (D / 32) % (csplit * 2) == 0) csplit *= 2;
@@ -1815,7 +1740,7 @@ int vqhip_vq_backward_w_ordered(const void *x, int x_dtype, const float *e, cons
     if (!x || !e || !idx || !order || !offsets || !grad_w || !ws || N < 0 || K <= 0 || D <= 0 || (D % 4) != 0)
         return fail(VQHIP_EINVAL, "vqhip_vq_backward_w_ordered: bad argument (D must be a multiple of 4)");
     VQ_NEED("vqhip_vq_backward_w_ordered: ws too small", ws_bytes, vqhip_segsum_workspace_bytes(N, D));
-    if (x_dtype != VQHIP_DTYPE_F32 && x_dtype != VQHIP_DTYPE_BF16) return fail(VQHIP_EINVAL, "vqhip_vq_backward_w_ordered: x_dtype");
+    VQ_REQUIRE(vq_row_dtype(x_dtype), "vqhip_vq_backward_w_ordered: x_dtype");
     return run_segsum<1>(x, x_dtype, e, idx, order, offsets, N, K, D, g_cb, grad_w, ws, (hipStream_t)stream);
 }
 
@@ -1869,26 +1794,22 @@ int vqhip_debug_proposal_scores(const void *x, int x_dtype, const void *cb, int6
     VQ_NEED("vqhip_debug_proposal_scores: ws too small", ws_bytes, vqhip_workspace_bytes(N, K, D));
     hipStream_t s = (hipStream_t)stream;
     VqCbLayout L = vq_cb_layout(K, D);
-    VqWsLayout W = vq_ws_layout(N, K, D);
+    const VqWsView V = vq_ws_view(ws, vq_ws_layout(N, K, D));
     const char *c = (const char *)cb;
-    char *w = (char *)ws;
-    int *counters = (int *)(w + W.off_counters);
-    float *xh2 = (float *)(w + W.off_xh2), *rho2 = (float *)(w + W.off_rho2);
-    char *ximg = w + W.off_ximg;
     const int xgrid = (int)((N + 31) / 32);
-    if (x_dtype == VQHIP_DTYPE_F32) x_prep_kernel<0><<<xgrid, 256, 0, s>>>(x, N, D, L.nstep, ximg, xh2, rho2, (float *)(w + W.off_xn), counters, (char *)cb, L);
-    else if (x_dtype == VQHIP_DTYPE_BF16) x_prep_kernel<1><<<xgrid, 256, 0, s>>>(x, N, D, L.nstep, ximg, xh2, rho2, (float *)(w + W.off_xn), counters, (char *)cb, L);
+    if (x_dtype == VQHIP_DTYPE_F32) x_prep_kernel<0><<<xgrid, 256, 0, s>>>(x, N, D, L.nstep, V.ximg, V.xh2, V.rho2, V.xn, V.counters, (char *)cb, L);
+    else if (x_dtype == VQHIP_DTYPE_BF16) x_prep_kernel<1><<<xgrid, 256, 0, s>>>(x, N, D, L.nstep, V.ximg, V.xh2, V.rho2, V.xn, V.counters, (char *)cb, L);
     else return fail(VQHIP_EINVAL, "vqhip_debug_proposal_scores: x_dtype");
     VQ_CHECK_LAUNCH("x_prep_kernel");
     const char *frag = c + L.off_frag;
     switch (L.nstep) {
-#define VQ_DBG(NS, TPS) case NS: debug_scores_kernel<NS, TPS><<<512, 256, 0, s>>>(ximg, frag, L.nstages, N, K, scores); break;
+#define VQ_DBG(NS, TPS) case NS: debug_scores_kernel<NS, TPS><<<512, 256, 0, s>>>(V.ximg, frag, L.nstages, N, K, scores); break;
         VQ_DBG(2, VQ_TPS_D32) VQ_DBG(4, 4) VQ_DBG(8, 4) VQ_DBG(16, VQ_TPS16) VQ_DBG(32, 2) VQ_DBG(48, 1) VQ_DBG(64, 1)
 #undef VQ_DBG
         default: return fail(VQHIP_EINVAL, "vqhip_debug_proposal_scores: unsupported padded D");
     }
     VQ_CHECK_LAUNCH("debug_scores_kernel");
-    debug_margin_kernel<<<(int)((N + 255) / 256), 256, 0, s>>>(c, L, N, metric, xh2, rho2, margin, scale);
+    debug_margin_kernel<<<(int)((N + 255) / 256), 256, 0, s>>>(c, L, N, metric, V.xh2, V.rho2, margin, scale);
     VQ_CHECK_LAUNCH("debug_margin_kernel");
     return VQHIP_OK;
 }

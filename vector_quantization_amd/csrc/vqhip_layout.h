@@ -172,3 +172,80 @@ VQ_HD VqWsLayout vq_ws_layout(int64_t N, int64_t K, int D) {
     W.total = W.off_ximg + img;
     return W;
 }
+
+// ---- host-only views and layouts (never passed to a kernel) ----------------------------------------------------------
+inline int64_t vq_align1k(int64_t v) { return (v + 1023) / 1024 * 1024; }
+
+// Typed pointers into an encode workspace: every array of vq_ws_layout is named here, once.
+struct VqWsView {
+    int *counters;                  // [0..2] as above, [3] the ticket of the last-resort pass
+    float *xh2, *rho2, *rec, *thr, *en, *xn;
+    int *rescan_list, *multi_list, *exact_list, *rescan_cnt, *cand_list, *arrive;
+    unsigned long long *keys;
+    int *bcnt; float *rece2; uint32_t *blist; char *bfrag;      // the D <= 32 group path (meaningful where W.nbkt > 0)
+    char *ximg;
+    // The fp32-only entry points (vqhip_argmin_exact, vqhip_distance, vqhip_col_argmin without an image) run no proposal pass:
+    // they keep the oracle-order |x_n|^2 of their rows in the storage of xh2 (same address, Np floats).
+    float *xn_whole;
+};
+inline VqWsView vq_ws_view(void *ws, const VqWsLayout &W) {
+    char *w = (char *)ws;
+    VqWsView v;
+    v.counters = (int *)(w + W.off_counters);
+    v.xh2 = (float *)(w + W.off_xh2); v.rho2 = (float *)(w + W.off_rho2); v.rec = (float *)(w + W.off_rec);
+    v.thr = (float *)(w + W.off_thr); v.en = (float *)(w + W.off_en); v.xn = (float *)(w + W.off_xn);
+    v.rescan_list = (int *)(w + W.off_flag); v.multi_list = (int *)(w + W.off_multi); v.exact_list = (int *)(w + W.off_exact);
+    v.rescan_cnt = (int *)(w + W.off_rcnt); v.cand_list = (int *)(w + W.off_rlist); v.arrive = (int *)(w + W.off_arrive);
+    v.keys = (unsigned long long *)(w + W.off_keys);
+    v.bcnt = (int *)(w + W.off_bcnt); v.rece2 = (float *)(w + W.off_rece2); v.blist = (uint32_t *)(w + W.off_blist); v.bfrag = w + W.off_bfrag;
+    v.ximg = w + W.off_ximg;
+    v.xn_whole = v.xh2;
+    return v;
+}
+
+// Buffer of the role-swapped column pass (vqhip_col_argmin, vqhip_col_argmin_rows): [pipeline workspace for `rows` rows against
+// N codes][image of the N latents as codes][the listed codebook rows (`listed`)][fp32 copy of bf16 latents]
+struct VqColLayout { int64_t off_img, off_rows, off_copy, total; };
+inline VqColLayout vq_col_layout(int64_t rows, int64_t N, int D, bool listed) {
+    VqColLayout C;
+    C.off_img = vq_align1k(vq_ws_layout(rows, N, D).total);
+    C.off_rows = C.off_img + vq_align1k(vq_cb_layout(N, D).total);
+    C.off_copy = C.off_rows + (listed ? vq_align1k(rows * (int64_t)D * 4) : 0);
+    C.total = C.off_copy + N * (int64_t)D * 4;
+    return C;
+}
+// ... and of its direct fp32 form for a short list (col_rows_direct), in the same buffer: [keys: K u64][ticket: 1 KiB][|x_n|^2: N][|e_k|^2: K]
+struct VqColDirectLayout { int64_t off_ticket, off_tok_norm, off_row_norm, total; };
+inline VqColDirectLayout vq_col_direct_layout(int64_t N, int64_t K) {
+    VqColDirectLayout C;
+    C.off_ticket = vq_align1k(K * 8);
+    C.off_tok_norm = C.off_ticket + 1024;
+    C.off_row_norm = C.off_tok_norm + vq_align1k(N * 4);
+    C.total = C.off_row_norm + vq_align1k(K * 4);
+    return C;
+}
+
+// Workspace of vqhip_cvq_forward: [row pass: vq_ws_layout(N, K, D)][col_idx: K int64][column pass over <= cap_max listed codes]
+struct VqCvqWsLayout { int64_t enc_bytes, off_col_idx, off_col_ws, total; };
+inline VqCvqWsLayout vq_cvq_ws_layout(int64_t N, int64_t K, int D, int64_t cap_max) {
+    VqCvqWsLayout C;
+    C.enc_bytes = C.off_col_idx = vq_align1k(vq_ws_layout(N, K, D).total);
+    C.off_col_ws = C.off_col_idx + vq_align1k(K * 8);
+    C.total = C.off_col_ws + (cap_max > 0 && vq_coarse_supported(D) ? vq_col_layout(cap_max, N, D, true).total : 0);
+    return C;
+}
+
+// Workspace of vqhip_vqkd_forward: [encode: vq_ws_layout(N, K, D)][F.normalize(xn): N x D][ordered sums: counts K, offsets K + 1,
+// order N int32, then order_bytes = vqhip_order_workspace_bytes(N, K) and segsum_bytes = vqhip_segsum_workspace_bytes(N, D)]
+struct VqKdWsLayout { int64_t enc_bytes, off_x2, off_counts, off_offsets, off_order, off_order_ws, off_segsum_ws, total; };
+inline VqKdWsLayout vq_kd_ws_layout(int64_t N, int64_t K, int D, int64_t order_bytes, int64_t segsum_bytes) {
+    VqKdWsLayout C;
+    C.enc_bytes = C.off_x2 = vq_align1k(vq_ws_layout(N, K, D).total);
+    C.off_counts = C.off_x2 + vq_align1k(N * (int64_t)D * 4);   // x2: for the ordered sums under the bf16-autocast metric (xq is rounded there)
+    C.off_offsets = C.off_counts + vq_align1k(K * 4);
+    C.off_order = C.off_offsets + vq_align1k((K + 1) * 4);
+    C.off_order_ws = C.off_order + vq_align1k(N * 4);
+    C.off_segsum_ws = C.off_order_ws + vq_align1k(order_bytes);
+    C.total = C.off_segsum_ws + vq_align1k(segsum_bytes);
+    return C;
+}
