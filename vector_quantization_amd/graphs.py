@@ -102,7 +102,8 @@ class GraphedQuantizer(nn.Module):
         super().__init__()
         if not sample_x.is_cuda:
             raise ValueError('GraphedQuantizer needs a device tensor (no CPU path)')
-        if len(getattr(quantizer, '_forward_pre_hooks', {})) > 0:
+        from .quantizers import routes
+        if routes.no_module_hooks(quantizer, forward_hooks=False):
             raise RuntimeError('the quantizer still has a pending forward pre-hook (lazy init): run one eager step first')
         self.quantizer = quantizer
         quantizer.inplace_updates = True
@@ -177,11 +178,8 @@ class GraphedQuantizer(nn.Module):
     @staticmethod
     def _chained_cvq_callback(quantizer: nn.Module, sample_x: torch.Tensor):
         """The CVQVAECallback of a quantizer whose train step is the one-call CVQ-VAE forward (capacity buckets), else None."""
-        step = getattr(quantizer, '_one_call_step', None)
-        if step is None or sample_x.dim() != 2:
-            return None
-        from .quantizers.vector_quantizer import VectorQuantizer
-        if getattr(step(sample_x), '__func__', None) is not VectorQuantizer._forward_cvq:
+        from .quantizers import routes
+        if routes.step(quantizer, sample_x).name != 'one_call_cvq':
             return None
         return quantizer._callbacks.callbacks[0]
 

@@ -18,8 +18,8 @@ from ..config import BuildPreHookMixin, Config, Item, RegistryMeta
 from ..registries import AnchorRegistry, VQITQuantizerCallbackRegistry
 from ..utils import (EMA, PriorityQueue, Store, all_reduce_statistics, broadcast_, exchange_log, exchanging, gather_to_rank0,
                      get_rank, get_world_size, is_sync)
-from .anchors import NearestAnchor
-from .distances import CosineDistance, L2Distance, LazyDistance
+from . import routes
+from .distances import LazyDistance
 from .memo import Memo, get_memo
 from .quantizer_api import BaseQuantizer
 from .statistics import QuantStatistics
@@ -76,8 +76,6 @@ class BaseCallback(QuantizerHolderMixin):
         return loss
 
 
-_DECODE_LOSS_HOOKS = ('before_decode', 'after_decode', 'before_loss', 'after_loss')
-
 # The nine hooks of the protocol (callbacks/composed.py:16-19) -> positions of the arguments a callback may replace by its
 # return value: none for the two notification hooks, one for the value-threading hooks, two for before_loss.
 _HOOK_THREADS = {
@@ -116,11 +114,7 @@ class ComposedCallback(BuildPreHookMixin, BaseCallback):
 
     def overrides_decode_or_loss(self) -> bool:
         """True when some callback customises a decode/loss hook (the fused decode+loss path must then be skipped)."""
-        for cb in self.callbacks:
-            for name in _DECODE_LOSS_HOOKS:
-                if getattr(type(cb), name) is not getattr(BaseCallback, name):
-                    return True
-        return False
+        return bool(routes.leaves(self, *routes.DECODE_LOSS_HOOKS))
 
 
 def _make_dispatcher(hook: str, threaded: tuple):
@@ -294,17 +288,8 @@ class VQKDCallback(LazyInitWeightsMixin, NormalizeCallback):
 
     # ---- the whole training forward as ONE library call (train_step.py, include/vqhip.h: vqhip_vqkd_forward) ------------
     def fused_forward_ok(self, x: torch.Tensor) -> bool:
-        """True when this step can be enqueued by one call: train mode, the lazy init done, device latents with a proposal
-        image, cosine distance with the library's fused encode, an EMA, a world the packed exchange covers."""
-        q = self.quantizer
-        if not (q.training and self.with_ema and x.dim() == 2 and x.is_cuda and x.shape[0] > 0 and x.shape[0] < (1 << 31)):
-            return False
-        if type(q.distance) is not CosineDistance or not ops.coarse_supported(q.embedding_dim) or q._cache_codebook:
-            return False
-        if len(q._forward_pre_hooks) > 0 or get_world_size() > exchange.MAX_WORLD:
-            return False
-        w = q.embedding.weight
-        return w.is_cuda and w.dtype == torch.float32 and w.is_contiguous()
+        """True when this callback can enqueue the step by one call (routes.callback_forward_why)."""
+        return not routes.callback_forward_why(self, x)
 
     def fused_forward(self, x: torch.Tensor, memo: Memo):
         """NormalizeCallback.before_encode + _encode + after_encode + decode + CommitmentLoss(norm=True) + STE of one training
@@ -398,22 +383,6 @@ class CVQVAECallback(UpdateMixin, BaseCallback):
             self.quantizer.register_buffer('_probability', value)
 
     # ---- anchors for the codes that can need one ------------------------------------------------------------------
-    def _sparse_flow_ok(self, tokens: int) -> bool:
-        """The preconditions of the sparse-anchor flow, hook by hook (`_sparse_step`) or as one call (`fused_forward`)."""
-        if self._sparse_anchors is False or type(self._anchor) is not NearestAnchor:
-            return False
-        if get_world_size() > exchange.MAX_WORLD:                # count pieces no longer exact in fp32: the dense flow
-            return False
-        if self._sync_exchange() and tokens > ops.SYNC_MAX_ROWS:          # a key holds the row in 24 bits (include/vqhip.h)
-            return False
-        if '_probability' not in self.quantizer._buffers:
-            return False
-        p = self.probability
-        return p.is_cuda and p.dtype == torch.float32 and ops.coarse_supported(self.quantizer.embedding_dim)
-
-    def _sparse_ok(self, d, hist32) -> bool:
-        return isinstance(d, LazyDistance) and hist32 is not None and self._sparse_flow_ok(d.shape[0])
-
     def _sync_exchange(self) -> bool:
         """NearestAnchor(sync=True) over more than one rank: the GLOBAL nearest latent per code (anchors.py:50-57).  The reference
         all-gathers latents and the [N, K] matrix; here the ranks agree on the winner by a MIN all-reduce of 8-byte keys and the
@@ -477,15 +446,8 @@ class CVQVAECallback(UpdateMixin, BaseCallback):
 
     # ---- the whole training forward as ONE library call (train_step.py, include/vqhip.h: vqhip_cvq_forward) --------------
     def fused_forward_ok(self, x: torch.Tensor) -> bool:
-        """True when this step can be enqueued by one call: the conditions of the sparse-anchor flow, a distance whose encode
-        is the library's fused one, device latents."""
-        q = self.quantizer
-        if not (q.training and self.with_ema and x.dim() == 2 and x.is_cuda and x.shape[0] > 0 and x.shape[0] < (1 << 31)):
-            return False
-        if type(q.distance) not in (L2Distance, CosineDistance) or q._cache_codebook or not self._sparse_flow_ok(x.shape[0]):
-            return False
-        p, w = self.probability, q.embedding.weight
-        return p.is_contiguous() and p.device == x.device and w.is_cuda and w.dtype == torch.float32 and w.is_contiguous()
+        """True when this callback can enqueue the step by one call (routes.callback_forward_why)."""
+        return not routes.callback_forward_why(self, x)
 
     def fused_forward(self, x: torch.Tensor, memo: Memo, beta: float):
         """_encode + after_encode (sparse-anchor flow of `_sparse_step`) + decode + MSE losses + STE of one training step from
@@ -532,12 +494,11 @@ class CVQVAECallback(UpdateMixin, BaseCallback):
         K = self.quantizer.codebook_size
         d = memo['encode']['distance']
         hist32 = memo['encode'].get('hist')
-        if self._sparse_ok(d, hist32):
+        route = routes.cvq_update(self, d, hist32).name
+        if route == 'sparse':
             self._sparse_step(x, quant, d, hist32)
             return quant
-        if (not exchanging() and type(self._anchor) is NearestAnchor and not self._anchor._sync
-                and isinstance(d, LazyDistance) and hist32 is not None
-                and self.probability.is_cuda and self.probability.dtype == torch.float32):
+        if route == 'dense_one_launch':
             # one rank, dense form: the whole update in one launch on the epilogue histogram, the column argmin and the
             # latents (vqhip_cvq_step; bit-identical to the staged form below)
             weight = self.vector_quantizer.embedding.weight

@@ -1,0 +1,337 @@
+"""Which route a quantizer step takes: the one place that decides, and says why.
+
+A decision returns ``Route(name, why)``.  ``why`` is empty when the fastest route of that decision is taken; otherwise it names
+the first clause that refused it.  Every clause is written once, as a function that returns '' or the reason.  A decision has
+a configuration part, which reads only the module (usable on a module built on the CPU), and an input part (tensor device,
+shape, dtype, alignment, the probability buffer, the world size, train / eval).  Both are evaluated on every call.
+
+    step          one_call_plain | one_call_cvq | one_call_vqkd | fused_tail | hooks
+    cvq_update    sparse | dense_one_launch | reference
+    map_entry     map | tokens
+    decode_entry  map | tokens
+"""
+from __future__ import annotations
+
+from typing import NamedTuple
+
+import torch
+
+from .. import exchange, ops
+from ..utils import exchanging, get_world_size
+# (the three modules, not names out of them: each of them imports this module the same way, so neither side of the cycle reads an
+#  attribute of the other before a call, and any of the four may be imported first)
+from . import callbacks as _cb, scalar_quantizer as _sq, vector_quantizer as _vq
+from .anchors import NearestAnchor
+from .distances import CosineDistance, L2Distance, LazyDistance
+from .losses import CodebookLoss, CommitmentLoss, VQGANLoss
+from .memo import get_memo
+from .quantizer_api import BaseQuantizer
+
+
+class Route(NamedTuple):
+    name: str
+    why: str = ''
+
+
+DECODE_LOSS_HOOKS = ('before_decode', 'after_decode', 'before_loss', 'after_loss')
+
+
+# ---- the clauses: '' or the reason ---------------------------------------------------------------------------------------
+
+def token_rows(x: torch.Tensor) -> str:
+    """[N, D] rows on a device, with a row count the kernels index in 32 bits."""
+    if x.dim() != 2:
+        return f'the latents are {x.dim()}-D, not [N, D] token rows'
+    if not x.is_cuda:
+        return f'the latents are on device {x.device}, not on a GPU'
+    if not 0 < x.shape[0] < (1 << 31):
+        return f'N={x.shape[0]} is outside 1 .. 2^31-1'
+    return ''
+
+
+def dense_codebook(w: torch.Tensor) -> str:
+    if not w.is_cuda:
+        return f'the codebook is on device {w.device}, not on a GPU'
+    if w.dtype != torch.float32:
+        return f'the codebook is {w.dtype}, not float32'
+    return '' if w.is_contiguous() else 'the codebook is not contiguous'
+
+
+def nchw_map(x: torch.Tensor, D: int, aligned: bool) -> str:
+    """A map [B, D, H, W] the kernels read as it is (``aligned``: the encode reads it in 16-byte pieces; FSQ's does not)."""
+    if x.dim() != 4:
+        return f'the map is {x.dim()}-D, not [B, C, H, W]'
+    if not x.is_cuda:
+        return f'the map is on device {x.device}, not on a GPU'
+    if not x.is_contiguous():
+        return 'the map is not NCHW-contiguous'
+    if x.dtype not in (torch.float32, torch.bfloat16):
+        return f'the map is {x.dtype}, not float32 or bfloat16'
+    if x.shape[1] != D:
+        return f'C={x.shape[1]} is not embedding_dim={D}'
+    return 'the map is not 16-byte aligned' if aligned and x.data_ptr() % 16 else ''
+
+
+def no_module_hooks(q, forward_hooks: bool = True) -> str:
+    """A route that is called directly, not through nn.Module.__call__, or that folds the first hook-by-hook step away, would
+    bypass a registered hook (the one-shot lazy-init pre-hook of LazyInitWeightsMixin, or anything a user attached)."""
+    if len(q._forward_pre_hooks) > 0:
+        return 'forward pre-hook registered (lazy init pending)'
+    return 'forward hook registered' if forward_hooks and len(q._forward_hooks) > 0 else ''
+
+
+def own(obj, base: type, *names: str) -> str:
+    """``type(obj)`` has not overridden ``base``'s methods ``names``."""
+    for name in names:
+        if getattr(type(obj), name) is not getattr(base, name):
+            return f'{type(obj).__name__} overrides {name}'
+    return ''
+
+
+def leaves(callbacks, *hooks: str) -> str:
+    """No callback of the ComposedCallback ``callbacks`` customises one of ``hooks``."""
+    for cb in callbacks.callbacks:
+        why = own(cb, _cb.BaseCallback, *hooks)
+        if why:
+            return why
+    return ''
+
+
+def proposal_image(D: int) -> str:
+    return '' if ops.coarse_supported(D) else f'D={D} has no proposal image'
+
+
+def fused_distance(q, *kinds: type) -> str:
+    return '' if type(q.distance) in kinds else f'{type(q.distance).__name__} has no fused encode for this step'
+
+
+def is_token_major(x: torch.Tensor) -> bool:
+    """True when a [B,C,H,W] tensor is stored channels-last, i.e. its memory already is the [(B H W), C] token matrix."""
+    return x.dim() == 4 and x.permute(0, 2, 3, 1).is_contiguous()
+
+
+def fused(q) -> str:
+    return '' if q._fused else 'fused=False'
+
+
+def with_ema(cb) -> str:
+    return '' if cb.with_ema else 'ema=None'
+
+
+def nearest_anchor(cb) -> str:
+    return '' if type(cb._anchor) is NearestAnchor else f'the anchor is {type(cb._anchor).__name__}, not NearestAnchor'
+
+
+def fp32_device_probabilities(p: torch.Tensor) -> str:
+    return '' if p.is_cuda and p.dtype == torch.float32 else f'the probabilities are {p.dtype} on device {p.device}, not float32 on a GPU'
+
+
+def no_cache(q) -> str:
+    return 'cache_codebook=True' if q._cache_codebook else ''
+
+
+def training(q) -> str:
+    return '' if q.training else 'eval mode: there is no codebook update to fold in'
+
+
+def packed_world() -> str:
+    world = get_world_size()
+    return f'world size {world} is beyond the packed exchange ({exchange.MAX_WORLD})' if world > exchange.MAX_WORLD else ''
+
+
+def probability(cb) -> str:
+    """The fp32 device probabilities of a CVQVAECallback (registered by init_weights in train mode, or loaded)."""
+    if '_probability' not in cb.quantizer._buffers:
+        return 'no probability buffer yet (init_weights in train mode registers it)'
+    return fp32_device_probabilities(cb.probability)
+
+
+# ---- decode + loss as one kernel ------------------------------------------------------------------------------------------
+
+def tail(q) -> str:
+    """'' when nothing customises decode or loss: VectorQuantizer — gather, STE and the plain MSE losses are one kernel with one
+    backward; FiniteScalarQuantizer — no loss at all, so forward_map returns the encode's z map."""
+    if isinstance(q, _sq.FiniteScalarQuantizer):
+        return (leaves(q._callbacks, *DECODE_LOSS_HOOKS) or ('a loss is configured' if len(q._losses) > 0 else '')
+                or own(q, _sq.FiniteScalarQuantizer, '_decode', 'decode') or own(q, BaseQuantizer, '_loss', 'loss', 'forward'))
+    why = fused(q) or leaves(q._callbacks, *DECODE_LOSS_HOOKS) \
+        or own(q, _vq.VectorQuantizer, '_decode') or own(q, BaseQuantizer, '_loss')
+    if why:
+        return why
+    for name, loss in q._losses.items():
+        if not (isinstance(loss, (VQGANLoss, CodebookLoss, CommitmentLoss)) and loss.plain):
+            return f'loss {name!r} is not a plain MSE loss'
+    return ''
+
+
+# ---- step ------------------------------------------------------------------------------------------------------------------
+
+def _sparse_flow_config(cb) -> str:
+    if cb._sparse_anchors is False:
+        return 'sparse_anchors=False'
+    return nearest_anchor(cb) or proposal_image(cb.quantizer.embedding_dim)
+
+
+def _sparse_flow_input(cb, tokens: int) -> str:
+    if cb._sync_exchange() and tokens > ops.SYNC_MAX_ROWS:               # a key holds the row in 24 bits (include/vqhip.h)
+        return f'N={tokens} is beyond the synchronised anchor exchange ({ops.SYNC_MAX_ROWS})'
+    return packed_world() or probability(cb)
+
+
+def _cvq_forward_config(cb) -> str:
+    q = cb.quantizer
+    return with_ema(cb) or fused_distance(q, L2Distance, CosineDistance) or no_cache(q) or _sparse_flow_config(cb)
+
+
+def _cvq_forward_input(cb, x: torch.Tensor) -> str:
+    why = training(cb.quantizer) or _sparse_flow_input(cb, x.shape[0])
+    if why:
+        return why
+    p = cb.probability
+    if not p.is_contiguous():
+        return 'the probabilities are not contiguous'
+    if p.device != x.device:
+        return f'the probabilities are on device {p.device}, the latents on {x.device}'
+    return dense_codebook(cb.quantizer.embedding.weight)
+
+
+def _vqkd_forward_config(cb) -> str:
+    q = cb.quantizer
+    return with_ema(cb) or fused_distance(q, CosineDistance) or proposal_image(q.embedding_dim) or no_cache(q) \
+        or no_module_hooks(q, forward_hooks=False)
+
+
+def _vqkd_forward_input(cb, x: torch.Tensor) -> str:
+    return training(cb.quantizer) or packed_world() or dense_codebook(cb.quantizer.embedding.weight)
+
+
+def callback_forward_why(cb, x: torch.Tensor) -> str:
+    """The callback's own part of one_call_cvq / one_call_vqkd (``cb.fused_forward_ok``): '' when it can enqueue this step by one call."""
+    if isinstance(cb, _cb.CVQVAECallback):
+        return token_rows(x) or _cvq_forward_config(cb) or _cvq_forward_input(cb, x)
+    return token_rows(x) or _vqkd_forward_config(cb) or _vqkd_forward_input(cb, x)
+
+
+def _one_call_config(q) -> tuple[str, str, str]:
+    """(the one-call route this configuration is made for, why it does not take it, the route of a step that does not)."""
+    tail_why = tail(q)
+    fallback = 'hooks' if tail_why else 'fused_tail'
+    cbs = q._callbacks.callbacks
+    why = ('' if q.one_call_steps else 'one_call_steps=False') or fused(q) \
+        or (f'{len(cbs)} callbacks' if len(cbs) > 1 else '') \
+        or own(q, _vq.VectorQuantizer, '_encode', '_decode') or own(q, BaseQuantizer, '_loss', 'encode')
+    if why:
+        return '', why, fallback
+    kind = type(cbs[0]) if cbs else None
+    if kind is None or kind is _cb.NormalizeCallback:
+        # no update callback (VQGAN: configs/vqgan/model.py:19-23), or NormalizeCallback alone (LlamaGen: configs/llamagen/
+        # vqgan.py:18-20), train and eval alike: vqhip_vq_forward
+        return 'one_call_plain', tail_why or no_cache(q) or fused_distance(q, L2Distance, CosineDistance), fallback
+    if kind is _cb.CVQVAECallback:               # the sparse-anchor flow as one call: vqhip_cvq_forward
+        return 'one_call_cvq', tail_why or _cvq_forward_config(cbs[0]), fallback
+    if kind is _cb.VQKDCallback:                 # VQKDCallback + CommitmentLoss(norm=True) (configs/vqkd/model.py:20-26): vqhip_vqkd_forward
+        losses = list(q._losses.values())
+        ok = (len(losses) == 1 and type(losses[0]) is CommitmentLoss and losses[0]._mse.norm
+              and losses[0]._mse._weight._value == 1.0 and losses[0]._weight._value == 1.0)
+        return 'one_call_vqkd', ('' if ok else 'the loss is not one CommitmentLoss(norm=True) of weight 1') or _vqkd_forward_config(cbs[0]), fallback
+    return '', f'{kind.__name__} has no one-call forward', fallback
+
+
+def step_config(q) -> Route:
+    """The configuration part of ``step``: the route of a training step on device rows."""
+    if not isinstance(q, _vq.VectorQuantizer):        # (hook by hook is all there is: its fastest route)
+        return Route('hooks')
+    name, why, fallback = _one_call_config(q)
+    return Route(fallback, why) if why else Route(name)
+
+
+def step(q, x: torch.Tensor) -> Route:
+    """How ``forward`` runs: one library call (train_step.py), encode hook by hook + the fused decode/loss tail, or hook by hook."""
+    if not isinstance(q, _vq.VectorQuantizer):
+        return step_config(q)
+    name, why, fallback = _one_call_config(q)
+    why = token_rows(x) or why
+    if not why:
+        if name == 'one_call_plain':
+            why = dense_codebook(q.embedding.weight)
+        else:
+            why = (_cvq_forward_input if name == 'one_call_cvq' else _vqkd_forward_input)(q._callbacks.callbacks[0], x)
+        if not why:
+            return Route(name)
+    return Route(fallback if x.dim() == 2 else 'hooks', why)
+
+
+# ---- the CVQ-VAE update of a hook-by-hook step -------------------------------------------------------------------------------
+
+def _dense_update_config(cb) -> str:
+    return nearest_anchor(cb) or ('the anchor is synchronised' if cb._anchor._sync else '')
+
+
+def cvq_update_config(cb) -> Route:
+    why = _sparse_flow_config(cb)
+    if not why:
+        return Route('sparse')
+    dense = _dense_update_config(cb)
+    return Route('reference', why if dense == why else f'{why}; {dense}') if dense else Route('dense_one_launch', why)
+
+
+def cvq_update(cb, d, hist32) -> Route:
+    """CVQVAECallback.after_encode: anchors for the listed codes only (`_sparse_step`), the dense update in one launch
+    (vqhip_cvq_step, one rank), or the reference's staged data flow."""
+    epilogue = ('' if isinstance(d, LazyDistance) else 'memo distance is a matrix, not the lazy handle of the fused encode') \
+        or ('' if hist32 is not None else 'the encode left no histogram')
+    why = epilogue or _sparse_flow_config(cb) or _sparse_flow_input(cb, d.shape[0])
+    if not why:
+        return Route('sparse')
+    dense = ('an exchange between ranks is active' if exchanging() else '') or _dense_update_config(cb) or epilogue
+    dense = dense or fp32_device_probabilities(cb.probability)
+    return Route('reference', why if dense == why else f'{why}; {dense}') if dense else Route('dense_one_launch', why)
+
+
+# ---- the NCHW map entry points (tokenization.quantize / encode_to_quant / decode_from_quant) -----------------------------------
+
+def map_config(q, decode: bool) -> str:
+    """'' when nothing in the module needs the token matrix before the encode, no hook would be bypassed (the map entry points
+    are not called through nn.Module.__call__) and, for ``decode``, the tail is the fused one."""
+    if isinstance(q, _vq.VectorQuantizer):
+        # (NormalizeCallback rewrites the latents before the encode: the normalised rows are a new token-major tensor anyway)
+        why = no_cache(q) or own(q, _vq.VectorQuantizer, '_encode') \
+            or ('' if hasattr(q._distance, 'encode_map') else f'{type(q._distance).__name__} has no encode_map') \
+            or no_module_hooks(q) or leaves(q._callbacks, 'before_encode') or proposal_image(q.embedding_dim)
+    elif isinstance(q, _sq.FiniteScalarQuantizer):
+        why = own(q, _sq.FiniteScalarQuantizer, '_encode') or no_module_hooks(q) or leaves(q._callbacks, 'before_encode', 'after_encode')
+    else:
+        return f'{type(q).__name__} has no map entry points'
+    return why or (tail(q) if decode else '')
+
+
+def map_why(q, x: torch.Tensor, decode: bool = False) -> str:
+    """'' when ``encode_map`` (``decode``: ``forward_map``) can take the NCHW map ``x`` as it is."""
+    if not isinstance(q, (_vq.VectorQuantizer, _sq.FiniteScalarQuantizer)):
+        return map_config(q, decode)
+    return nchw_map(x, q.embedding_dim, aligned=isinstance(q, _vq.VectorQuantizer)) or map_config(q, decode)
+
+
+def map_entry(q, x: torch.Tensor, decode: bool) -> Route:
+    """tokenization.quantize (``decode``) / encode_to_quant: the map goes to the quantizer as it is, or through the token matrix."""
+    why = ('the map is channels-last: its memory already is the token matrix' if is_token_major(x) else '') or map_why(q, x, decode)
+    return Route('tokens', why) if why else Route('map')
+
+
+def decode_config(q) -> str:
+    if isinstance(q, _vq.VectorQuantizer):
+        return fused(q) or own(q, _vq.VectorQuantizer, '_decode') or leaves(q._callbacks, *DECODE_LOSS_HOOKS)
+    if isinstance(q, _sq.FiniteScalarQuantizer):
+        return tail(q)
+    return f'{type(q).__name__} has no decode_map'
+
+
+def decode_entry(q, quant: torch.Tensor, memo: dict, token_major: bool) -> Route:
+    """tokenization.decode_from_quant: tokens [B, H, W] decoded straight into the NCHW map, or rows first."""
+    why = ('' if quant.is_cuda else f'the tokens are on device {quant.device}, not on a GPU') or decode_config(q) \
+        or ('token_major=True asks for the channels-last view of the rows' if token_major else '')
+    if not why and isinstance(q, _vq.VectorQuantizer):
+        why = 'autograd is on: decode_map gives no gradient' if torch.is_grad_enabled() else ''
+    elif not why:
+        why = "memo['encode']['z'] is there to be handed on" if 'z' in get_memo(get_memo(memo, 'quantizer'), 'encode') else ''
+    return Route('tokens', why) if why else Route('map')

@@ -16,6 +16,7 @@ from torch import nn
 from .. import functional as VF
 from .. import ops
 from ..registries import VQITQuantizerRegistry
+from . import routes
 from .memo import Memo, get_memo
 from .quantizer_api import BaseQuantizer
 
@@ -73,6 +74,7 @@ class FiniteScalarQuantizer(ScalarQuantizer):
         quant = torch.arange(self.codebook_size)
         digits = (quant[:, None] // self._base_converter.cumprod) % self._base_converter.max_per_digit
         self.register_buffer('_embeddings', digits / (self._base_converter.max_per_digit // 2) - 1)
+        self.last_route = None                # what the last map entry decided (diagnostics: routes.py)
 
     @property
     def embedding_dim(self) -> int:
@@ -114,31 +116,18 @@ class FiniteScalarQuantizer(ScalarQuantizer):
 
     # ---- the NCHW feature map without transposes (tokenization.quantize / encode_to_quant / decode_from_quant) ------------
     def map_fusable(self, x: torch.Tensor) -> bool:
-        """True when an NCHW-contiguous fp32 / bf16 device map can go to the kernels as it is: the encode is this class's own,
-        no forward hook would be bypassed (the map entry points are not called through nn.Module.__call__), and no callback
-        rewrites the latents before the encode or reads them after it."""
-        from .callbacks import BaseCallback
-        if not (x.dim() == 4 and x.is_cuda and x.is_contiguous() and x.dtype in (torch.float32, torch.bfloat16)):
-            return False
-        if x.shape[1] != self.embedding_dim or type(self)._encode is not FiniteScalarQuantizer._encode:
-            return False
-        if len(self._forward_pre_hooks) > 0 or len(self._forward_hooks) > 0:
-            return False
-        return all(type(cb).before_encode is BaseCallback.before_encode and type(cb).after_encode is BaseCallback.after_encode
-                   for cb in self._callbacks.callbacks)
+        """True when ``encode_map`` takes the NCHW map ``x`` as it is (routes.map_why)."""
+        return not routes.map_why(self, x)
 
     def _fusable(self) -> bool:
         """True when decode and loss are the plain ones (no loss configured, nothing overridden): forward_map may then return
         the z map straight from the encode."""
-        if self._callbacks.overrides_decode_or_loss() or len(self._losses) > 0:
-            return False
-        cls = type(self)
-        return (cls._decode is FiniteScalarQuantizer._decode and cls.decode is FiniteScalarQuantizer.decode
-                and cls._loss is BaseQuantizer._loss and cls.loss is BaseQuantizer.loss and cls.forward is BaseQuantizer.forward)
+        return not routes.tail(self)
 
     def encode_map(self, x_map: torch.Tensor, memo: Memo) -> tuple[torch.Tensor, torch.Tensor, Memo]:
         """``encode`` of the map [B, C, H, W]: (x_rows [B*H*W, C] in x's dtype, quant int32 [B*H*W], memo), one launch.
         memo['encode']['z'] is the token-major z [B*H*W, C] of the token route (no gradient: the tokens are the product here)."""
+        self.last_route = routes.Route('map')
         enc = get_memo(memo, 'encode')
         quant, z, x_rows = ops.fsq_encode(x_map.detach(), self._consts, z_rows=True, want_rows=True)
         enc['z'] = z
@@ -148,7 +137,9 @@ class FiniteScalarQuantizer(ScalarQuantizer):
     def forward_map(self, x_map: torch.Tensor, memo: Memo) -> tuple[torch.Tensor, torch.Tensor, Memo]:
         """``forward`` on the map: (z_map [B, C, H, W] fp32 NCHW-contiguous with the gradient to x_map, loss, memo) — one
         launch forward, one backward.  memo['encode']['z'] and memo['decode']['z'] are that z map, memo['x'] is the map."""
-        assert self.map_fusable(x_map) and self._fusable()
+        why = routes.map_why(self, x_map, decode=True)
+        assert not why, why
+        self.last_route = routes.Route('map')
         enc = get_memo(memo, 'encode')
         z_map, quant = VF.fsq(x_map, self._consts)
         enc['z'] = z_map

@@ -13,10 +13,10 @@ from .. import ops, train_step
 from ..config import Config, Item, RegistryMeta
 from ..registries import InitRegistry, ModelRegistry, VQITQuantizerDistanceRegistry, VQITQuantizerRegistry
 from .memo import Memo, get_memo
+from . import routes
 from .quantizer_api import BaseQuantizer
-from .callbacks import CVQVAECallback, NormalizeCallback, VQKDCallback
-from .distances import BaseDistance, CosineDistance, L2Distance, LazyDistance
-from .losses import CodebookLoss, CommitmentLoss, VQGANLoss
+from .distances import BaseDistance, LazyDistance
+from .losses import CodebookLoss, VQGANLoss
 
 
 @VQITQuantizerRegistry.register_()
@@ -39,6 +39,7 @@ class VectorQuantizer(BaseQuantizer):
         self._cache_codebook = cache_codebook
         self._prepared: Optional[ops.PreparedCodebook] = None
         self._prepared_key = None
+        self.last_route: Optional[routes.Route] = None      # what the last forward / map entry decided (diagnostics: routes.py)
 
     @classmethod
     def embedding_build_pre_hook(cls, config: Config, registry: RegistryMeta, item: Item) -> Config:
@@ -139,14 +140,7 @@ class VectorQuantizer(BaseQuantizer):
 
     # ---- forward ---------------------------------------------------------------------------------------------------
     def _fusable(self) -> bool:
-        if not self._fused or self._callbacks.overrides_decode_or_loss():
-            return False
-        if type(self)._decode is not VectorQuantizer._decode or type(self)._loss is not BaseQuantizer._loss:
-            return False
-        for loss in self._losses.values():
-            if not (isinstance(loss, (VQGANLoss, CodebookLoss, CommitmentLoss)) and loss.plain):
-                return False
-        return True
+        return not routes.tail(self)
 
     def _vqgan_beta(self) -> float:
         """beta of the (first) VQGANLoss: the combination m_cb + beta * m_cm that the fused kernels finish themselves."""
@@ -173,34 +167,13 @@ class VectorQuantizer(BaseQuantizer):
             return values[0]
         return sum(values, like.new_zeros([], dtype=torch.float32))
 
+    # routes.step's one-call names -> the method that enqueues that forward by ONE library call (train_step.py)
+    _ONE_CALL = {'one_call_plain': '_forward_plain', 'one_call_cvq': '_forward_cvq', 'one_call_vqkd': '_forward_vqkd'}
+
     def _one_call_step(self, x: torch.Tensor):
-        """The training forwards that ONE library call enqueues (train_step.py): a VQGAN-style quantizer whose only callback
-        is a CVQVAECallback in its sparse-anchor flow, or a VQ-KD quantizer (VQKDCallback + CommitmentLoss with norm=True:
-        configs/vqkd/model.py:20-26).  None: the step runs hook by hook as below."""
-        if not (self.one_call_steps and self._fused and x.dim() == 2):
-            return None
-        cbs = self._callbacks.callbacks
-        if len(cbs) > 1 or type(self)._encode is not VectorQuantizer._encode or type(self)._decode is not VectorQuantizer._decode \
-                or type(self)._loss is not BaseQuantizer._loss or type(self).encode is not BaseQuantizer.encode:
-            return None
-        if len(cbs) == 0 or type(cbs[0]) is NormalizeCallback:
-            # no update callback (VQGAN: configs/vqgan/model.py:19-23), or NormalizeCallback alone (LlamaGen: configs/llamagen/
-            # vqgan.py:18-20) — train and eval alike: vqhip_vq_forward
-            w = self._embedding.weight
-            ok = (self._fusable() and not self._cache_codebook and type(self._distance) in (L2Distance, CosineDistance)
-                  and x.is_cuda and 0 < x.shape[0] < (1 << 31) and w.is_cuda and w.dtype == torch.float32 and w.is_contiguous())
-            return self._forward_plain if ok else None
-        if not self.training:
-            return None
-        cb = cbs[0]
-        if type(cb) is CVQVAECallback:
-            return self._forward_cvq if (self._fusable() and cb.fused_forward_ok(x)) else None
-        if type(cb) is VQKDCallback:
-            losses = list(self._losses.values())
-            ok = (len(losses) == 1 and type(losses[0]) is CommitmentLoss and losses[0]._mse.norm
-                  and losses[0]._mse._weight._value == 1.0 and losses[0]._weight._value == 1.0)
-            return self._forward_vqkd if (ok and cb.fused_forward_ok(x)) else None
-        return None
+        """The one-call training forward this step takes (bound), or None: it runs hook by hook (routes.step)."""
+        name = self._ONE_CALL.get(routes.step(self, x).name)
+        return getattr(self, name) if name else None
 
     def _encode_memo(self, memo: Memo, out: dict, x_op: torch.Tensor, e_op: torch.Tensor) -> None:
         """memo['encode'] of a one-call step (``out``: what train_step returned): the symbolic distance between ``x_op`` and
@@ -262,10 +235,10 @@ class VectorQuantizer(BaseQuantizer):
         """quantizers.py:110-117 (BaseQuantizer.forward, then ste(z, memo['x'])).  When nothing customises
         decode/loss the gather, the STE expression and the MSE sums are one kernel with one fused backward; the two
         callback-driven training configs (CVQ-VAE, VQ-KD) are one library call for the whole forward."""
-        step = self._one_call_step(x)
-        if step is not None:
-            return step(x, memo)
-        if not self._fusable() or x.dim() != 2:
+        self.last_route = route = routes.step(self, x)
+        if route.name in self._ONE_CALL:
+            return getattr(self, self._ONE_CALL[route.name])(x, memo)
+        if route.name == 'hooks':
             z, loss, memo = super().forward(x, memo)
             z = VF.ste(z, memo['x'])
             return z, loss, memo
@@ -276,29 +249,16 @@ class VectorQuantizer(BaseQuantizer):
         memo['decode'] = get_memo(memo, 'decode')
         return z_ste, self._loss_values(memo, m_cb, m_cm, m_vqgan, beta, x), memo
 
-
     # ---- the same three entry points on the NCHW feature map (models/base.py:116-146) --------------------
     def map_fusable(self, x: torch.Tensor) -> bool:
-        """True when ``forward_map`` / ``encode_map`` take the route without transposes: an NCHW-contiguous fp32 / bf16
-        device map, a D with a proposal image, no callback that rewrites the latents before the encode (NormalizeCallback:
-        the normalised rows are a new token-major tensor anyway), and a decode/loss tail that can be fused."""
-        from .callbacks import BaseCallback
-        if not (x.dim() == 4 and x.is_cuda and x.is_contiguous() and x.dtype in (torch.float32, torch.bfloat16)):
-            return False
-        if x.shape[1] != self.embedding_dim or not ops.coarse_supported(x.shape[1]) or x.data_ptr() % 16 or self._cache_codebook:
-            return False
-        if type(self)._encode is not VectorQuantizer._encode or not hasattr(self._distance, 'encode_map'):
-            return False
-        # the map entry points are called directly, not through nn.Module.__call__: a registered hook (the one-shot lazy-init
-        # pre-hook of LazyInitWeightsMixin, or anything a user attached) would never run — such a module takes the token route
-        if len(self._forward_pre_hooks) > 0 or len(self._forward_hooks) > 0:
-            return False
-        return all(type(cb).before_encode is BaseCallback.before_encode for cb in self._callbacks.callbacks)
+        """True when ``encode_map`` takes the NCHW map ``x`` as it is (routes.map_why; ``forward_map`` also needs ``_fusable``)."""
+        return not routes.map_why(self, x)
 
     def encode_map(self, x_map: torch.Tensor, memo: Memo) -> tuple[torch.Tensor, torch.Tensor, Memo]:
         """``encode`` for latents given as the feature map [B, D, H, W]: (x_rows [B*H*W, D], quant [B*H*W], memo).  The
         'b c h w -> (b h w) c' of models/base.py:124,140 happens inside the encode's first kernel; ``x_rows`` — the token
         matrix the callbacks and the rest of the step see — is its by-product (detached)."""
+        self.last_route = routes.Route('map')
         enc = get_memo(memo, 'encode')
         w = self._embedding.weight.detach()
         hist = None
@@ -315,7 +275,8 @@ class VectorQuantizer(BaseQuantizer):
     def forward_map(self, x_map: torch.Tensor, memo: Memo) -> tuple[torch.Tensor, torch.Tensor, Memo]:
         """``forward`` on the feature map: (z_map [B, D, H, W] NCHW-contiguous, loss, memo) — BaseModel.quantize
         (models/base.py:116-128) without either rearrangement kernel.  Gradients flow to ``x_map`` and the codebook."""
-        assert self.map_fusable(x_map) and self._fusable()
+        why = routes.map_why(self, x_map, decode=True)
+        assert not why, why
         x_rows, quant, memo = self.encode_map(x_map, memo)
         memo.update(x=x_rows, quant=quant)
         beta = self._vqgan_beta()

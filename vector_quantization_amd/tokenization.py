@@ -21,6 +21,9 @@ import torch.distributed as dist
 from torch.autograd import Function
 
 from . import ops
+from .quantizers import routes
+from .quantizers.memo import get_memo
+from .quantizers.routes import is_token_major
 from .utils import get_rank, get_world_size
 
 
@@ -52,11 +55,6 @@ class _ToMap(Function):
         return ops.transpose_last2(g.reshape(b, c, h * w)).reshape(b * h * w, c), None, None, None
 
 
-def is_token_major(x: torch.Tensor) -> bool:
-    """True when a [B,C,H,W] tensor is stored channels-last, i.e. its memory already is the [(B H W), C] token matrix."""
-    return x.dim() == 4 and x.permute(0, 2, 3, 1).is_contiguous()
-
-
 def to_tokens(x: torch.Tensor) -> torch.Tensor:
     """einops 'b c h w -> (b h w) c' (models/base.py:124,140).  A channels-last map (what a 1x1 connector conv
     produces when it runs in ``torch.channels_last``) already IS the token matrix: returned as a zero-copy view;
@@ -76,39 +74,33 @@ def to_map(z: torch.Tensor, b: int, h: int, w: int, token_major: bool = False) -
     return _ToMap.apply(z, b, h, w)
 
 
-def _map_route(quantizer, x: torch.Tensor, decode: bool) -> bool:
-    """An NCHW-contiguous map can be handed to the quantizer as it is (no transpose kernels either side) when the quantizer
-    has the map entry points and nothing in its configuration needs the token matrix earlier (``map_fusable``)."""
-    if not hasattr(quantizer, 'map_fusable') or not quantizer.map_fusable(x):
-        return False
-    return quantizer._fusable() if decode else True
-
-
 def quantize(quantizer, x: torch.Tensor, memo: dict):
     """BaseModel.quantize (models/base.py:116-128): returns (z [B,C,H,W], q_loss, memo)."""
-    from .quantizers.memo import get_memo
     b, _, h, w = x.shape
     quantizer_memo = get_memo(memo, 'quantizer')
     quantizer_memo['x_shape'] = x.shape
-    token_major = is_token_major(x)
-    if not token_major and _map_route(quantizer, x, decode=True):
+    route = routes.map_entry(quantizer, x, decode=True)
+    if route.name == 'map':
         # NCHW map: both rearrangements of models/base.py:124-127 are folded into the quantizer's own kernels
         z, q_loss, memo['quantizer'] = quantizer.forward_map(x, quantizer_memo)
-        return z, q_loss, memo
-    z, q_loss, memo['quantizer'] = quantizer(to_tokens(x), quantizer_memo)
-    return to_map(z, b, h, w, token_major), q_loss, memo
+    else:
+        z, q_loss, memo['quantizer'] = quantizer(to_tokens(x), quantizer_memo)
+        z = to_map(z, b, h, w, is_token_major(x))
+    quantizer.last_route = route              # (after the call: forward has left its own decision there, this one is the caller's)
+    return z, q_loss, memo
 
 
 def encode_to_quant(quantizer, x: torch.Tensor, memo: dict):
     """BaseModel.encode_to_quant after the encoder (models/base.py:135-146): returns (quant [B,H,W], memo)."""
-    from .quantizers.memo import get_memo
     b, _, h, w = x.shape
     quantizer_memo = get_memo(memo, 'quantizer')
     quantizer_memo['x_shape'] = x.shape
-    if not is_token_major(x) and _map_route(quantizer, x, decode=False):
+    route = routes.map_entry(quantizer, x, decode=False)
+    if route.name == 'map':
         xt, quant, quantizer_memo = quantizer.encode_map(x, quantizer_memo)
     else:
         xt, quant, quantizer_memo = quantizer.encode(to_tokens(x), quantizer_memo)
+    quantizer.last_route = route
     quantizer_memo.update(x=xt, quant=quant)
     memo['quantizer'] = quantizer_memo
     return quant.reshape(b, h, w), memo
@@ -117,17 +109,10 @@ def encode_to_quant(quantizer, x: torch.Tensor, memo: dict):
 def decode_from_quant(quantizer, quant: torch.Tensor, memo: dict, token_major: bool = False):
     """BaseModel.decode_from_quant before the decoder (image_reconstruction/models.py:97-106): quant [B,H,W] →
     z [B,C,H,W] (``token_major=True``: as a zero-copy channels-last view of the gathered rows)."""
-    from .quantizers.memo import get_memo
     b, h, w = quant.shape
-    from .quantizers.vector_quantizer import VectorQuantizer
-    if (not token_major and isinstance(quantizer, VectorQuantizer) and quant.is_cuda and not torch.is_grad_enabled()
-            and getattr(quantizer, '_fused', True) and type(quantizer)._decode is VectorQuantizer._decode
-            and not quantizer._callbacks.overrides_decode_or_loss()):
-        return quantizer.decode_map(quant, get_memo(memo, 'quantizer'))[0], memo     # rows gathered straight into the NCHW map
-    from .quantizers.scalar_quantizer import FiniteScalarQuantizer
-    if (not token_major and isinstance(quantizer, FiniteScalarQuantizer) and quant.is_cuda and quantizer._fusable()
-            and 'z' not in get_memo(get_memo(memo, 'quantizer'), 'encode')):
-        return quantizer.decode_map(quant, get_memo(memo, 'quantizer'))[0], memo     # tokens decoded straight into the NCHW map
+    quantizer.last_route = route = routes.decode_entry(quantizer, quant, memo, token_major)
+    if route.name == 'map':                   # rows gathered (FSQ: tokens decoded) straight into the NCHW map
+        return quantizer.decode_map(quant, get_memo(memo, 'quantizer'))[0], memo
     z, memo['quantizer'] = quantizer.decode(quant.reshape(-1), get_memo(memo, 'quantizer'))
     return to_map(z, b, h, w, token_major), memo
 
