@@ -219,6 +219,29 @@ int vqhip_fsq_backward(const vqhip_fsq_t *q, const void *x, int x_dtype, int lay
 int vqhip_fsq_decode(const vqhip_fsq_t *q, const void *quant, int quant_dtype, int layout, int64_t N, int64_t HW, float *z,
                      void *stream);
 
+/* ---- pooled code features (the linear probe, vq/tasks/image_classification/models.py:101-109) ---------------------------
+ * tokens quant [B, HW] (quant_dtype VQHIP_DTYPE_I32 or VQHIP_DTYPE_I64) -> the mean over the positions of the decoded rows,
+ * out fp32 [B, D]: `quantizer.decode` followed by einops.reduce(z, 'b h w c -> b c', 'mean'), one launch, and the decoded
+ * [B * HW, D] rows never exist in memory.  Everything is fp32 IEEE arithmetic without contraction, in ONE order.  With
+ * v_p = e[quant[b, p], c] (vqhip_fsq_decode_pool: the fp32 value vqhip_fsq_decode gives for that token and channel, bit for bit):
+ *   s_j = +0.0f;  for p = j, j + 8, j + 16, .. < HW (increasing):  s_j = s_j + v_p              (j = 0 .. 7)
+ *   out[b, c] = (((s_0 + s_1) + (s_2 + s_3)) + ((s_4 + s_5) + (s_6 + s_7))) / (float)HW         (a true division)
+ * The order depends on HW alone — not on B, D, the launch geometry or the token dtype — and the forward uses no float atomics:
+ * the result is bit-reproducible from run to run and from shape to shape.
+ * Tokens outside [0, K) (vqhip_decode_pool): never dereferenced; every channel of that image's row of `out` is NaN; the
+ * backward skips them.  vqhip_fsq_decode_pool decodes any token, as vqhip_fsq_decode does.
+ * vqhip_decode_pool_bwd: grad_e[quant[b, p], c] += g[b, c] / (float)HW with float atomics (not ordered); grad_e is accumulated
+ * into, the caller zeroes it.
+ * LIMITS (VQHIP_EINVAL, checked before any HIP call): no null pointer, B >= 1, HW >= 1, B * HW < 2^31, K >= 1, D >= 1 (any D:
+ * 16-byte loads where D % 4 == 0 and e, out are 16-byte aligned, channel by channel otherwise), the token dtype one of the
+ * two; vqhip_fsq_decode_pool also the limits of the FSQ constants above.  No allocation, no synchronisation, no workspace. */
+int vqhip_decode_pool(const float *e, int64_t K, int D, const void *quant, int quant_dtype, int64_t B, int64_t HW,
+                      float *out /* [B, D] */, void *stream);
+int vqhip_decode_pool_bwd(const float *g /* [B, D] */, const void *quant, int quant_dtype, int64_t B, int64_t HW, int64_t K, int D,
+                          float *grad_e /* [K, D], += */, void *stream);
+int vqhip_fsq_decode_pool(const vqhip_fsq_t *q, const void *quant, int quant_dtype, int64_t B, int64_t HW,
+                          float *out /* [B, C] */, void *stream);
+
 /* ---- EntropyLoss (vq/algorithms/vq/losses.py:130-153) on row blocks of the distance matrix ------------------------------
  * With a = d / T, p = softmax(a, -1), q_k = (1/N) sum_n p_nk:
  *   L = (1/N) sum_n (lse_n - sum_k p_nk a_nk) + sum_k q_k log(q_k + 1e-5)

@@ -98,6 +98,9 @@ SIGNATURES = {
     'vqhip_fsq_encode': (_i32, [ctypes.POINTER(FsqConstants), _vp, _i32, _i32, _i64, _i64, _vp, _vp, _i32, _vp, _vp, _vp]),
     'vqhip_fsq_backward': (_i32, [ctypes.POINTER(FsqConstants), _vp, _i32, _i32, _i64, _i64, _vp, _vp, _vp]),
     'vqhip_fsq_decode': (_i32, [ctypes.POINTER(FsqConstants), _vp, _i32, _i32, _i64, _i64, _vp, _vp]),
+    'vqhip_decode_pool': (_i32, [_vp, _i64, _i32, _vp, _i32, _i64, _i64, _vp, _vp]),
+    'vqhip_decode_pool_bwd': (_i32, [_vp, _vp, _i32, _i64, _i64, _i64, _i32, _vp, _vp]),
+    'vqhip_fsq_decode_pool': (_i32, [ctypes.POINTER(FsqConstants), _vp, _i32, _i64, _i64, _vp, _vp]),
     'vqhip_entropy_workspace_bytes': (_i64, [_i64, _i64]),
     'vqhip_entropy_rows': (_i32, [_vp, _i64, _i64, _f32, _vp, _vp, _vp, _i32, _vp, _i64, _vp]),
     'vqhip_entropy_finish': (_i32, [_vp, _vp, _vp, _i64, _i64, _vp, _vp, _vp, _vp]),

@@ -1146,6 +1146,79 @@ int vqhip_fsq_decode(const vqhip_fsq_t *q, const void *quant, int quant_dtype, i
     return VQHIP_OK;
 }
 
+// ---- pooled code features (vqhip_pool_kernels.h) -----------------------------------------------------------------------
+// what the three entry points refuse alike: B, HW >= 1 and B * HW < 2^31 (tokens are counted in 32 bits), a token dtype
+static int pool_check(const char *what, int quant_dtype, int64_t B, int64_t HW) {
+    if (B < 1 || HW < 1) return fail(VQHIP_EINVAL, what, "B and HW must be >= 1");
+    if (B >= (1ll << 31) || HW >= (1ll << 31) || !vq_fits_i31(B * HW, 0)) return fail(VQHIP_EINVAL, what, "B * HW must be below 2^31");
+    if (quant_dtype != VQHIP_DTYPE_I32 && quant_dtype != VQHIP_DTYPE_I64) return fail(VQHIP_EINVAL, what, "quant_dtype");
+    return VQHIP_OK;
+}
+
+static inline int pool_log2_ceil(int64_t v, int cap_log2) {
+    int l = 0;
+    while (l < cap_log2 && (1ll << l) < v) ++l;
+    return l;
+}
+
+int vqhip_decode_pool(const float *e, int64_t K, int D, const void *quant, int quant_dtype, int64_t B, int64_t HW, float *out,
+                      void *stream) {
+    const char *what = "vqhip_decode_pool";
+    VQ_REQUIRE(e && quant && out, "vqhip_decode_pool: e, quant and out are required");
+    VQ_REQUIRE(K >= 1 && D >= 1, "vqhip_decode_pool: K and D must be >= 1");
+    if (int rc = pool_check(what, quant_dtype, B, HW)) return rc;
+    // 16-byte columns where every row and the output row start aligned; else channel by channel
+    const bool vec = D % 4 == 0 && (uintptr_t)e % 16 == 0 && (uintptr_t)out % 16 == 0;
+    const int64_t cols = vec ? D / 4 : D;
+    const int cw_log2 = pool_log2_ceil(cols, 6);
+    const int64_t nchunks = (cols + (1ll << cw_log2) - 1) >> cw_log2;
+    const int group_threads = VQ_POOL_PARTIALS << cw_log2;
+    const int block = group_threads > 256 ? group_threads : 256;
+    const int64_t per_block = block / group_threads;
+    const int64_t grid = (B * nchunks + per_block - 1) / per_block;          // (B < 2^31, nchunks < 2^31: no overflow)
+    VQ_REQUIRE(grid < (1ll << 31), "vqhip_decode_pool: B * ceil(D / 256) is beyond one launch");
+    hipStream_t s = (hipStream_t)stream;
+#define VQ_POOL(I64, VEC) decode_pool_kernel<I64, VEC><<<(unsigned)grid, block, 0, s>>>(e, K, D, quant, B, (int)HW, cw_log2, (int)nchunks, out)
+    if (quant_dtype == VQHIP_DTYPE_I64) { if (vec) VQ_POOL(true, true); else VQ_POOL(true, false); }
+    else { if (vec) VQ_POOL(false, true); else VQ_POOL(false, false); }
+#undef VQ_POOL
+    VQ_CHECK_LAUNCH("decode_pool_kernel");
+    return VQHIP_OK;
+}
+
+int vqhip_decode_pool_bwd(const float *g, const void *quant, int quant_dtype, int64_t B, int64_t HW, int64_t K, int D,
+                          float *grad_e, void *stream) {
+    const char *what = "vqhip_decode_pool_bwd";
+    VQ_REQUIRE(g && quant && grad_e, "vqhip_decode_pool_bwd: g, quant and grad_e are required");
+    VQ_REQUIRE(K >= 1 && D >= 1, "vqhip_decode_pool_bwd: K and D must be >= 1");
+    if (int rc = pool_check(what, quant_dtype, B, HW)) return rc;
+    const int64_t N = B * HW;
+    const int lp_log2 = pool_log2_ceil(D, 6);
+    const int64_t grid = ((N << lp_log2) + 255) / 256;                       // N < 2^31, at most 64 lanes each
+    VQ_REQUIRE(grid < (1ll << 31), "vqhip_decode_pool_bwd: B * HW is beyond one launch");
+    hipStream_t s = (hipStream_t)stream;
+    if (quant_dtype == VQHIP_DTYPE_I64) decode_pool_bwd_kernel<true><<<(unsigned)grid, 256, 0, s>>>(g, quant, N, (int)HW, K, D, lp_log2, grad_e);
+    else decode_pool_bwd_kernel<false><<<(unsigned)grid, 256, 0, s>>>(g, quant, N, (int)HW, K, D, lp_log2, grad_e);
+    VQ_CHECK_LAUNCH("decode_pool_bwd_kernel");
+    return VQHIP_OK;
+}
+
+int vqhip_fsq_decode_pool(const vqhip_fsq_t *q, const void *quant, int quant_dtype, int64_t B, int64_t HW, float *out, void *stream) {
+    const char *what = "vqhip_fsq_decode_pool";
+    VQ_REQUIRE(q && quant && out, "vqhip_fsq_decode_pool: q, quant and out are required");
+    if (int rc = pool_check(what, quant_dtype, B, HW)) return rc;
+    VqFsqConsts k;
+    int unused = 0;
+    if (int rc = fsq_setup(what, q, VQHIP_LAYOUT_MAP, B * HW, HW, &k, &unused)) return rc;
+    const int64_t grid = (B * k.C * VQ_POOL_PARTIALS + 255) / 256;           // B < 2^31, C <= 16
+    VQ_REQUIRE(grid < (1ll << 31), "vqhip_fsq_decode_pool: B is beyond one launch");
+    hipStream_t s = (hipStream_t)stream;
+    if (quant_dtype == VQHIP_DTYPE_I64) fsq_decode_pool_kernel<true><<<(unsigned)grid, 256, 0, s>>>(k, quant, B, (int)HW, out);
+    else fsq_decode_pool_kernel<false><<<(unsigned)grid, 256, 0, s>>>(k, quant, B, (int)HW, out);
+    VQ_CHECK_LAUNCH("fsq_decode_pool_kernel");
+    return VQHIP_OK;
+}
+
 // ---- EntropyLoss on row blocks of the distance matrix (vqhip_entropy_kernels.h) ----------------------------------------
 static int entropy_check(const char *what, int64_t R, int64_t K, float T) {
     // the kernels index a row with int and step by up to VQ_ENT_COLS past K before they stop; R * K elements are addressed in int64

@@ -15,6 +15,7 @@
 // i.e. neighbouring lanes touch neighbouring words of one channel row.  Token-major by-products of the map form (x_rows,
 // z rows) go out through the same LDS tile.
 // ------------------------------------------------------------------------------------------------
+#pragma once
 #define VQ_FSQ_MAX_C 16
 #define VQ_FSQ_TILE 256
 

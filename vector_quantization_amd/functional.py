@@ -37,6 +37,29 @@ def embedding(weight: torch.Tensor, idx: torch.Tensor) -> torch.Tensor:
     return _Embedding.apply(weight, idx)
 
 
+class _DecodePool(Function):
+    """features[b] = mean_p W[quant[b, p]] (``decode`` + einops.reduce 'b h w c -> b c' mean of the linear probe,
+    vq/tasks/image_classification/models.py:105-109) in one launch; backward = atomics into W (tokens get no gradient)."""
+
+    @staticmethod
+    def forward(ctx, weight: torch.Tensor, quant: torch.Tensor) -> torch.Tensor:
+        ctx.save_for_backward(quant)
+        ctx.K = weight.shape[0]
+        ctx.wdtype = weight.dtype
+        return ops.decode_pool(weight, quant)
+
+    @staticmethod
+    def backward(ctx, g):
+        (quant,) = ctx.saved_tensors
+        gw = ops.decode_pool_bwd(g, quant, ctx.K).to(ctx.wdtype) if ctx.needs_input_grad[0] else None
+        return gw, None
+
+
+def decode_pool(weight: torch.Tensor, quant: torch.Tensor) -> torch.Tensor:
+    """fp32 [B, D] mean-pooled code embeddings of tokens ``quant`` [B, *]; the gradient goes to ``weight`` only."""
+    return _DecodePool.apply(weight, quant)
+
+
 class _MSE(Function):
     """mean((a-b)^2) (todd MSELoss, mean reduction; vq/algorithms/vq/losses.py:50,62)."""
 

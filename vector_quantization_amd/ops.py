@@ -616,6 +616,59 @@ def fsq_decode(quant: torch.Tensor, q: _lib.FsqConstants, map_shape: Optional[tu
     return z
 
 
+# ---- pooled code features (the linear probe, vq/tasks/image_classification/models.py:101-109) ----------------------------
+
+def _pool_tokens(quant: torch.Tensor, what: str):
+    """(dense tokens, token dtype code, B, HW) of ``quant`` [B, *]: positions are everything after the first dimension."""
+    if quant.dim() < 2:
+        raise ValueError(f'{what}: expected tokens [B, *] with at least two dimensions, got {tuple(quant.shape)}')
+    if quant.dtype not in (torch.int32, torch.int64):
+        raise ValueError(f'{what}: tokens must be int32 or int64, got {quant.dtype}')
+    B = quant.shape[0]
+    quant = quant.reshape(B, -1).contiguous()
+    return quant, (_lib.DTYPE_I32 if quant.dtype == torch.int32 else _lib.DTYPE_I64), B, quant.shape[1]
+
+
+@_on_tensor_device
+def decode_pool(e: torch.Tensor, quant: torch.Tensor) -> torch.Tensor:
+    """features fp32 [B, D] = mean over the positions of e[quant] for tokens ``quant`` [B, *] (int32 / int64), one launch, in the
+    fixed summation order of include/vqhip.h; the decoded rows are never written.  A token outside [0, K) makes its image's
+    row NaN."""
+    _require_cuda(e, quant)
+    e = _codebook(e)
+    quant, qdt, B, HW = _pool_tokens(quant, 'decode_pool')
+    K, D = e.shape
+    out = torch.empty(B, D, dtype=torch.float32, device=quant.device)
+    check(_lib.lib().vqhip_decode_pool(_ptr(e), K, D, _ptr(quant), qdt, B, HW, _ptr(out), _stream()), 'vqhip_decode_pool')
+    return out
+
+
+@_on_tensor_device
+def decode_pool_bwd(g: torch.Tensor, quant: torch.Tensor, K: int) -> torch.Tensor:
+    """grad_e fp32 [K, D] of ``decode_pool`` from g = dL/dfeatures [B, D]: grad_e[quant[b, p]] += g[b] / HW (float atomics);
+    tokens outside [0, K) contribute nothing."""
+    _require_cuda(g, quant)
+    quant, qdt, B, HW = _pool_tokens(quant, 'decode_pool_bwd')
+    g = g.float().contiguous()
+    if g.dim() != 2 or g.shape[0] != B:
+        raise ValueError(f'decode_pool_bwd: expected g [{B}, D], got {tuple(g.shape)}')
+    D = g.shape[1]
+    grad_e = torch.zeros(K, D, dtype=torch.float32, device=g.device)
+    check(_lib.lib().vqhip_decode_pool_bwd(_ptr(g), _ptr(quant), qdt, B, HW, K, D, _ptr(grad_e), _stream()), 'vqhip_decode_pool_bwd')
+    return grad_e
+
+
+@_on_tensor_device
+def fsq_decode_pool(quant: torch.Tensor, q: _lib.FsqConstants) -> torch.Tensor:
+    """features fp32 [B, C] = mean over the positions of ``fsq_decode``'s values for tokens ``quant`` [B, *] (int32 / int64), one
+    launch, same summation order as ``decode_pool``; any token decodes (negative and >= K ones as ``fsq_decode`` gives them)."""
+    _require_cuda(quant)
+    quant, qdt, B, HW = _pool_tokens(quant, 'fsq_decode_pool')
+    out = torch.empty(B, q.C, dtype=torch.float32, device=quant.device)
+    check(_lib.lib().vqhip_fsq_decode_pool(ctypes.byref(q), _ptr(quant), qdt, B, HW, _ptr(out), _stream()), 'vqhip_fsq_decode_pool')
+    return out
+
+
 ORDERED_MAX_K = 32768     # the ordered (deterministic) route keeps one code histogram per 1024-token chunk in LDS
 
 

@@ -9,6 +9,7 @@ shape, dtype, alignment, the probability buffer, the world size, train / eval). 
     cvq_update    sparse | dense_one_launch | reference
     map_entry     map | tokens
     decode_entry  map | tokens
+    pooled_entry  pooled | rows
 """
 from __future__ import annotations
 
@@ -335,3 +336,25 @@ def decode_entry(q, quant: torch.Tensor, memo: dict, token_major: bool) -> Route
     elif not why:
         why = "memo['encode']['z'] is there to be handed on" if 'z' in get_memo(get_memo(memo, 'quantizer'), 'encode') else ''
     return Route('tokens', why) if why else Route('map')
+
+
+# ---- pooled code features (tokenization.pool_from_quant / pooled_features) ------------------------------------------------------
+
+def pooled_config(q) -> str:
+    """'' when ``decode`` is the plain one — the codebook gather (FiniteScalarQuantizer: the digits of the token) with no callback
+    before or after it — so that its mean over the positions can be taken inside the decode kernel."""
+    if isinstance(q, _vq.VectorQuantizer):
+        return own(q, _vq.VectorQuantizer, '_decode') or own(q, BaseQuantizer, 'decode') or leaves(q._callbacks, 'before_decode', 'after_decode')
+    if isinstance(q, _sq.FiniteScalarQuantizer):
+        return own(q, _sq.FiniteScalarQuantizer, '_decode', 'decode') or leaves(q._callbacks, 'before_decode', 'after_decode')
+    return f'{type(q).__name__} has no decode_pooled'
+
+
+def pooled_entry(q, quant: torch.Tensor) -> Route:
+    """tokenization.pool_from_quant: tokens [B, *] -> features [B, D] in one launch (``decode_pooled``), or ``decode`` to rows and
+    their mean over the positions."""
+    why = pooled_config(q) or ('' if quant.is_cuda else f'the tokens are on device {quant.device}, not on a GPU') \
+        or ('' if quant.dim() >= 2 else f'the tokens are {quant.dim()}-D, not [B, *]') \
+        or ('' if quant.dtype in (torch.int32, torch.int64) else f'the tokens are {quant.dtype}, not int32 or int64') \
+        or ('' if 0 < quant.numel() < (1 << 31) else f'{quant.numel()} tokens are outside 1 .. 2^31-1')
+    return Route('rows', why) if why else Route('pooled')

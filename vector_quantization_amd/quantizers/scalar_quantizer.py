@@ -157,3 +157,13 @@ class FiniteScalarQuantizer(ScalarQuantizer):
         """``decode`` of an image-shaped token tensor [B, H, W] (int32 or int64) straight into the map [B, C, H, W]."""
         b, h, w = quant.shape
         return ops.fsq_decode(quant, self._consts, map_shape=(b, h, w)), memo
+
+    def decode_pooled(self, quant: torch.Tensor, memo: Memo) -> tuple[torch.Tensor, Memo]:
+        """``decode`` of tokens [B, *] (int32 or int64) followed by the mean over the positions, one launch: (features [B, C]
+        fp32, memo).  Every value is the one ``ops.fsq_decode`` gives for the token, summed in the fixed order of include/vqhip.h.
+        Needs the plain decode on device tokens (routes.pooled_entry)."""
+        route = routes.pooled_entry(self, quant)
+        assert route.name == 'pooled', route.why
+        self.last_route = route
+        memo['decode'] = get_memo(memo, 'decode')
+        return ops.fsq_decode_pool(quant, self._consts), memo

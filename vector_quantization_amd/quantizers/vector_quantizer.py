@@ -292,6 +292,18 @@ class VectorQuantizer(BaseQuantizer):
         z_map, _ = ops.gather_ste_map(None, self._embedding.weight.detach(), quant.reshape(-1), b, h, w)
         return z_map, memo
 
+    def decode_pooled(self, quant: torch.Tensor, memo: Memo) -> tuple[torch.Tensor, Memo]:
+        """``decode`` of tokens [B, *] followed by the mean over the positions (the linear probe's features,
+        image_classification/models.py:105-109) as ONE launch: (features [B, D] fp32, memo); the [B, *, D] rows are never written.
+        The summation order is fixed (include/vqhip.h), a token outside the codebook makes its image's row NaN instead of the
+        reference's device assert, and the gradient goes to the codebook.  Needs the plain decode on device tokens
+        (routes.pooled_entry; tokenization.pool_from_quant takes ``decode`` + mean otherwise)."""
+        route = routes.pooled_entry(self, quant)
+        assert route.name == 'pooled', route.why
+        self.last_route = route
+        memo['decode'] = get_memo(memo, 'decode')
+        return VF.decode_pool(self._embedding.weight, quant), memo
+
 
 @VQITQuantizerRegistry.register_()
 class VQGANQuantizer(VectorQuantizer):

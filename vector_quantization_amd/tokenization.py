@@ -2,7 +2,8 @@
 
 * the BCHW <-> (BHW)C rearrangement around the quantizer call and the model-level entry points
   ``quantize`` / ``encode_to_quant`` / ``decode_from_quant``
-  (vq/tasks/image_tokenization/models/base.py:116-146, vq/tasks/image_reconstruction/models.py:97-108);
+  (vq/tasks/image_tokenization/models/base.py:116-146, vq/tasks/image_reconstruction/models.py:97-108), and the linear probe's
+  ``pool_from_quant`` / ``pooled_features`` (vq/tasks/image_classification/models.py:98-109);
 * the on-disk token formats of the tokenize runners
   (vq/tasks/image_tokenization/runners/callbacks.py:23-53, tools/tokenize_llamagen.py:65-103);
 * the codebook metrics (vq/tasks/image_tokenization/runners/metrics.py:25-73).
@@ -115,6 +116,30 @@ def decode_from_quant(quantizer, quant: torch.Tensor, memo: dict, token_major: b
         return quantizer.decode_map(quant, get_memo(memo, 'quantizer'))[0], memo
     z, memo['quantizer'] = quantizer.decode(quant.reshape(-1), get_memo(memo, 'quantizer'))
     return to_map(z, b, h, w, token_major), memo
+
+
+def pool_from_quant(quantizer, quant: torch.Tensor, memo: dict):
+    """The linear probe's features (image_classification/models.py:105-109): ``quantizer.decode(tokens)`` followed by
+    einops.reduce(z, 'b h w c -> b c', 'mean').  quant [B,H,W] → (features [B,C], memo).  Where the decode is the plain one and
+    the tokens are on a GPU this is one launch that never writes the decoded rows (``decode_pooled``); otherwise the rows are
+    decoded and averaged (routes.pooled_entry says which, and why, in ``quantizer.last_route``)."""
+    route = routes.pooled_entry(quantizer, quant)
+    if route.name == 'pooled':
+        features, memo['quantizer'] = quantizer.decode_pooled(quant, get_memo(memo, 'quantizer'))
+    else:
+        z, memo['quantizer'] = quantizer.decode(quant, get_memo(memo, 'quantizer'))
+        features = z.reshape(quant.shape[0], -1, z.shape[-1]).mean(dim=1)
+    quantizer.last_route = route
+    return features, memo
+
+
+def pooled_features(quantizer, x: torch.Tensor, memo: dict):
+    """The frozen-tokenizer half of the linear probe after the encoder (image_classification/models.py:98-109):
+    ``encode_to_quant`` followed by ``pool_from_quant``.  x [B,C,H,W] → (features [B,C], quant [B,H,W], memo); memo['quantizer']
+    holds the encode's entries, then the decode's."""
+    quant, memo = encode_to_quant(quantizer, x, memo)
+    features, memo = pool_from_quant(quantizer, quant, memo)
+    return features, quant, memo
 
 
 # ---- on-disk token formats ---------------------------------------------------------------------------------------------
