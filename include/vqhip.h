@@ -56,6 +56,8 @@ extern "C" {
 
 #define VQHIP_DTYPE_F32 0
 #define VQHIP_DTYPE_BF16 1
+/* (2 and 3 are the token dtypes VQHIP_DTYPE_I32 / VQHIP_DTYPE_I64, defined with the FSQ entry points below) */
+#define VQHIP_DTYPE_F16 4   /* logits of vqhip_sample_tokens only: every other entry point takes F32 or BF16 rows */
 
 #define VQHIP_OK 0
 #define VQHIP_EINVAL (-22)      /* bad argument (null pointer, unsupported D, ...) */
@@ -241,6 +243,57 @@ int vqhip_decode_pool_bwd(const float *g /* [B, D] */, const void *quant, int qu
                           float *grad_e /* [K, D], += */, void *stream);
 int vqhip_fsq_decode_pool(const vqhip_fsq_t *q, const void *quant, int quant_dtype, int64_t B, int64_t HW,
                           float *out /* [B, C] */, void *stream);
+
+/* ---- fused token sampler of stage-2 generation (vq/tasks/sequence_modeling/models/samplers.py:20-120) --------------------
+ * BaseSampler / TopKTopPSampler / CFGSampler as BaseTransformer.sample calls them once per generated position
+ * (vq/tasks/sequence_modeling/models/transformers.py:58-70): slice, CFG mix, temperature, top-k, top-p, one draw per row, + start and
+ * the CFG duplication, ONE launch, one workgroup per output row.  No sort, no [R, V] temporary, no workspace.
+ * INPUT   logits [R, >= end] in `dtype` (VQHIP_DTYPE_F32, _BF16 or _F16), element stride 1, row stride `row_stride` >= end elements;
+ *   only columns [start, end) are read, V = end - start.  The pointer and the slice start need only element alignment (16-byte
+ *   loads are used where a row's slice allows them, element loads otherwise: bf16 with start = 1001 is a shipped case).  Every
+ *   element is converted to fp32 exactly; all arithmetic below is fp32 IEEE without contraction.  (The reference computes in the
+ *   input dtype: for 16-bit logits this is a stated difference, not a parity claim.)
+ * CFG     cfg != 0: R even, Ro = R / 2 output rows; row r < Ro is unconditional, row r + Ro conditional (logits.chunk(2));
+ *   a = fl(fl((float)(1.0 - (double)cfg_alpha) * uncond) + fl(cfg_alpha * cond)).  cfg == 0: Ro = R, a = the logit.
+ * TEMPERATURE  a = a / temperature, a true fp32 division, skipped when temperature == 1.  (-0 counts as +0 from here on.)
+ * ORDER   tokens of a row are ordered by (a, -index): among equal values the lower index ranks higher.
+ * TOP-K   top_k <= 0: off.  Else k = min(top_k, V); a token survives iff a >= the k-th largest value of the row; all ties at that
+ *   value survive (transformers' TopKLogitsWarper).  Pure comparison: exact.
+ * TOP-P   applied iff 0 <= top_p <= 1.  m_i = exp(a_i - max) over the top-k survivors; c_i = the share of the survivors' mass held
+ *   by the tokens ranked at or below i (ascending cumulative); token i is removed iff c_i <= 1 - top_p (1.0 - (double)top_p); the
+ *   top-ranked token is never removed.  The kept set is an upper set of the order.  This restates transformers 4.35.2's
+ *   ascending-sort TopPLogitsWarper with min_tokens_to_keep = 1 from memory; that library version was not at hand when this was
+ *   written, and THE DEFINITION WRITTEN HERE GOVERNS.
+ * DRAW    u [Ro] fp32 in [0, 1).  Walk the kept tokens in index order with running mass C; the token is the first j with
+ *   C_j > u * Z (Z = the kept mass); if rounding leaves none, the last kept one (the inverse-CDF draw multinomial makes on a row).
+ * OUTPUT  tokens int64: tokens[r] = j + start for r < Ro; under CFG also tokens[r + Ro] (einops.repeat 'b ... -> (two b) ...').
+ * BAD ROWS  a row whose inputs or mixed values contain a NaN or a +inf, or no finite value, gets -1 (both halves) and a zeroed cut
+ *   with cut_index = -1; nothing is dereferenced out of range and no other row is affected.  -inf is an ordinary token of mass 0.
+ * CUT (nullable, [Ro]): kept / topk_kept = tokens that survive both filters / top-k alone; cut_value, cut_index = the lowest-ranked
+ *   kept token (the kept set is {a > cut_value} + {a == cut_value, index <= cut_index}); max = the row maximum of a; z = Z.
+ * MASSES AND THE ERROR BOUND  a mass is computed as expf(fl(a_i - max)) (expf: at most 1 ulp), multiplied by 2^40 exactly and
+ *   truncated to a 64-bit integer; every sum of masses is an integer sum - exact, below 2^61 for V <= 2^20, and independent of the
+ *   order of the additions, so the result is bit-reproducible from run to run; no float atomic exists in the kernel.  The
+ *   comparisons c_i <= 1 - p and C_j > u Z are made on those integers against floor((1 - p) Z) and floor(u Z) formed in fp64.
+ *   Distance between the kernel's share and the exact share (float64 exp of the exact difference):
+ *       delta(V) = 2^-18 + V * 2^-39          (VQHIP_SAMPLE_DELTA; 5.7e-6 at V = 2^20, 3.8e-6 at V = 16 384)
+ *   Derivation: a mass that is not truncated to 0 has |a_i - max| < 28, so its relative error is at most 28 * 2^-24 (the rounded
+ *   difference in the exponent) + 2^-23 (expf) < 1.8e-6 = e; truncation loses less than 2^-40 per token.  A share S / Z of two
+ *   such sums with Z >= 1 is then off by at most 2 (e Z + V 2^-40) / (Z (1 - e) - V 2^-40) <= 2^-18 + V 2^-39; the fp64 products
+ *   add less than 2^-50.  A token whose exact share lies further than delta from the threshold is decided as the definition says.
+ * LIMITS (VQHIP_EINVAL before any HIP call): logits, u, tokens not null; 1 <= R < 2^31, R even under CFG; 0 <= start < end <=
+ *   row_stride; V <= 2^20; temperature finite and > 0; cfg_alpha finite (under CFG).  Rows up to V = 32 768 keep their keys in LDS
+ *   after one read; longer rows re-read the logits in every pass; both forms give the same bits. */
+#define VQHIP_SAMPLE_DELTA(V) (3.814697265625e-06 + (double)(V) * 1.8189894035458565e-12)
+typedef struct vqhip_sample_cut_t {
+    int32_t kept, topk_kept;
+    float cut_value;
+    int32_t cut_index;
+    float max, z;
+} vqhip_sample_cut_t;
+int vqhip_sample_tokens(const void *logits, int dtype, int64_t R, int64_t row_stride, int64_t start, int64_t end,
+                        float cfg_alpha, int cfg, float temperature, int top_k, float top_p,
+                        const float *u, int64_t *tokens, vqhip_sample_cut_t *cut /* or NULL */, void *stream);
 
 /* ---- EntropyLoss (vq/algorithms/vq/losses.py:130-153) on row blocks of the distance matrix ------------------------------
  * With a = d / T, p = softmax(a, -1), q_k = (1/N) sum_n p_nk:

@@ -15,6 +15,7 @@ LIB_PATH = os.environ.get('VQHIP_LIB') or os.path.join(_HERE, 'libvqhip.so')   #
 ABI_VERSION = 600          # VQHIP_VERSION of include/vqhip.h this binding was written against
 METRIC_L2, METRIC_COS, METRIC_COS_BF16 = 0, 1, 5
 DTYPE_F32, DTYPE_BF16 = 0, 1
+DTYPE_F16 = 4                              # logits of vqhip_sample_tokens only (2 and 3 are the token dtypes below)
 DTYPE_I32, DTYPE_I64 = 2, 3                # token dtypes of vqhip_fsq_decode
 LAYOUT_ROWS, LAYOUT_MAP = 0, 1             # [N, C] token-major / NCHW-contiguous map [B, C, H*W]
 FSQ_MAX_C = 16
@@ -70,6 +71,17 @@ class FsqConstants(ctypes.Structure):
                 ('shift', _f32 * FSQ_MAX_C), ('scale', _f32 * FSQ_MAX_C)]
 
 
+class SampleCut(ctypes.Structure):
+    """vqhip_sample_cut_t of include/vqhip.h, field for field (24 bytes per output row)."""
+    _fields_ = [('kept', ctypes.c_int32), ('topk_kept', ctypes.c_int32), ('cut_value', _f32), ('cut_index', ctypes.c_int32),
+                ('max', _f32), ('z', _f32)]
+
+
+def sample_delta(V: int) -> float:
+    """VQHIP_SAMPLE_DELTA(V) of include/vqhip.h: the bound on |kernel share - exact share| of vqhip_sample_tokens."""
+    return 2.0 ** -18 + V * 2.0 ** -39
+
+
 STEP_BEFORE_EXCHANGE, STEP_AFTER_EXCHANGE, STEP_ALL, STEP_PACK_SYNC = 1, 2, 3, 4
 
 # name -> (restype, argtypes); mirrors include/vqhip.h one to one
@@ -101,6 +113,7 @@ SIGNATURES = {
     'vqhip_decode_pool': (_i32, [_vp, _i64, _i32, _vp, _i32, _i64, _i64, _vp, _vp]),
     'vqhip_decode_pool_bwd': (_i32, [_vp, _vp, _i32, _i64, _i64, _i64, _i32, _vp, _vp]),
     'vqhip_fsq_decode_pool': (_i32, [ctypes.POINTER(FsqConstants), _vp, _i32, _i64, _i64, _vp, _vp]),
+    'vqhip_sample_tokens': (_i32, [_vp, _i32, _i64, _i64, _i64, _i64, _f32, _i32, _f32, _i32, _f32, _vp, _vp, _vp, _vp]),
     'vqhip_entropy_workspace_bytes': (_i64, [_i64, _i64]),
     'vqhip_entropy_rows': (_i32, [_vp, _i64, _i64, _f32, _vp, _vp, _vp, _i32, _vp, _i64, _vp]),
     'vqhip_entropy_finish': (_i32, [_vp, _vp, _vp, _i64, _i64, _vp, _vp, _vp, _vp]),

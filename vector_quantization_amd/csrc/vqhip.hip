@@ -8,6 +8,7 @@
 #include "vqhip_kernels.h"
 #include "vqhip_fsq_kernels.h"
 #include "vqhip_entropy_kernels.h"
+#include "vqhip_sample_kernels.h"
 
 static thread_local char g_err[256] = "";
 
@@ -479,6 +480,23 @@ static int launch_hist(const IdxT *idx, int64_t N, int64_t K, int32_t *hist, voi
         else hist_i32_kernel<<<grid, 256, 0, s>>>(idx, N, K, hist);
     }
     VQ_CHECK_LAUNCH(i64 ? "hist_kernel" : "hist_i32_kernel");
+    return VQHIP_OK;
+}
+
+// ---- fused token sampler: the launch (vqhip_sample_kernels.h) -----------------------------------------------------------
+static LdsCache g_sample_lds[3];
+
+template <int DT>
+static int launch_sample(const VqSampleArgs &a, hipStream_t s) {
+    if (a.V <= VQ_SAMPLE_RESIDENT_MAX) {
+        const size_t lds = (size_t)a.V * sizeof(unsigned int);
+        if (lds > 32768)                                                         // beyond the default budget next to the static part
+            if (int rc = ensure_dyn_lds((const void *)sample_tokens_kernel<DT, true>, lds, g_sample_lds[DT == VQHIP_DTYPE_F32 ? 0 : (DT == VQHIP_DTYPE_BF16 ? 1 : 2)])) return rc;
+        sample_tokens_kernel<DT, true><<<(unsigned)a.Ro, VQ_SAMPLE_THREADS, lds, s>>>(a);
+    } else {
+        sample_tokens_kernel<DT, false><<<(unsigned)a.Ro, VQ_SAMPLE_THREADS, 0, s>>>(a);
+    }
+    VQ_CHECK_LAUNCH("sample_tokens_kernel");
     return VQHIP_OK;
 }
 
@@ -1217,6 +1235,37 @@ int vqhip_fsq_decode_pool(const vqhip_fsq_t *q, const void *quant, int quant_dty
     else fsq_decode_pool_kernel<false><<<(unsigned)grid, 256, 0, s>>>(k, quant, B, (int)HW, out);
     VQ_CHECK_LAUNCH("fsq_decode_pool_kernel");
     return VQHIP_OK;
+}
+
+// ---- fused token sampler (vqhip_sample_kernels.h) ---------------------------------------------------------------------------
+int vqhip_sample_tokens(const void *logits, int dtype, int64_t R, int64_t row_stride, int64_t start, int64_t end, float cfg_alpha,
+                        int cfg, float temperature, int top_k, float top_p, const float *u, int64_t *tokens,
+                        vqhip_sample_cut_t *cut, void *stream) {
+    VQ_REQUIRE(logits && u && tokens, "vqhip_sample_tokens: logits, u and tokens are required");
+    VQ_REQUIRE(dtype == VQHIP_DTYPE_F32 || dtype == VQHIP_DTYPE_BF16 || dtype == VQHIP_DTYPE_F16, "vqhip_sample_tokens: dtype");
+    VQ_REQUIRE(R >= 1 && R < (1ll << 31), "vqhip_sample_tokens: R must be in 1 .. 2^31 - 1");
+    VQ_REQUIRE(!cfg || R % 2 == 0, "vqhip_sample_tokens: R must be even under CFG");
+    VQ_REQUIRE(start >= 0 && start < end && end <= row_stride, "vqhip_sample_tokens: need 0 <= start < end <= row_stride");
+    VQ_REQUIRE(end - start <= VQ_SAMPLE_MAX_V, "vqhip_sample_tokens: end - start is beyond 2^20");
+    VQ_REQUIRE(temperature - temperature == 0.0f && temperature > 0.0f, "vqhip_sample_tokens: the temperature must be finite and > 0");
+    VQ_REQUIRE(!cfg || cfg_alpha - cfg_alpha == 0.0f, "vqhip_sample_tokens: alpha must be finite");
+    VqSampleArgs a;
+    a.logits = logits; a.row_stride = row_stride; a.start = start;
+    a.V = (int)(end - start);
+    a.Ro = (int)(cfg ? R / 2 : R);
+    a.cfg = cfg ? 1 : 0;
+    a.w_uncond = (float)(1.0 - (double)cfg_alpha); a.w_cond = cfg_alpha;
+    a.temperature = temperature;
+    a.k = top_k <= 0 ? 0 : (top_k < a.V ? top_k : a.V);
+    a.use_top_p = (top_p >= 0.0f && top_p <= 1.0f) ? 1 : 0;
+    a.one_minus_p = 1.0 - (double)top_p;
+    a.u = u; a.tokens = tokens; a.cut = cut;
+    hipStream_t s = (hipStream_t)stream;
+    switch (dtype) {
+    case VQHIP_DTYPE_F32: return launch_sample<VQHIP_DTYPE_F32>(a, s);
+    case VQHIP_DTYPE_BF16: return launch_sample<VQHIP_DTYPE_BF16>(a, s);
+    default: return launch_sample<VQHIP_DTYPE_F16>(a, s);
+    }
 }
 
 // ---- EntropyLoss on row blocks of the distance matrix (vqhip_entropy_kernels.h) ----------------------------------------

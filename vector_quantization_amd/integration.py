@@ -17,6 +17,15 @@ REPLACED = {
     'VQITConnectorRegistry': ('BaseConnector', 'ConvConnector'),
 }
 
+# The samplers of stage-2 generation (vq/tasks/sequence_modeling/models/registries.py: VQSMSamplerRegistry) that
+# vector_quantization_amd/samplers.py provides under the reference's names.  A listing only: the reference's sequence_modeling package
+# cannot be imported without `transformers.top_k_top_p_filtering` (its models/__init__.py pulls samplers.py in), and its registry
+# wraps a `cfg=` config in its OWN CFGSampler, so these classes are used through this package's VQSMSamplerRegistry
+# (registries.py), which builds the same config dicts.
+REPLACED_SAMPLERS = {
+    'VQSMSamplerRegistry': ('BaseSampler', 'TopKTopPSampler', 'CFGSampler'),
+}
+
 
 def register_into_reference() -> dict:
     """Force-register the MI355X implementations under the reference's names; returns {registry: [names]}."""

@@ -616,6 +616,64 @@ def fsq_decode(quant: torch.Tensor, q: _lib.FsqConstants, map_shape: Optional[tu
     return z
 
 
+# ---- fused token sampler (stage-2 generation, vq/tasks/sequence_modeling/models/samplers.py) -----------------------------
+
+SAMPLE_DTYPES = {torch.float32: _lib.DTYPE_F32, torch.bfloat16: _lib.DTYPE_BF16, torch.float16: _lib.DTYPE_F16}
+SAMPLE_MAX_V = 1 << 20
+
+
+@_on_tensor_device
+def sample_tokens(logits: torch.Tensor, start: int, end: int, *, u: torch.Tensor, temperature: float = 1.0, top_k: int = 0,
+                  top_p: float = 2.0, cfg_alpha: Optional[float] = None, want_cut: bool = False):
+    """One token per row of ``logits[..., start:end]`` in ONE launch (vqhip_sample_tokens of include/vqhip.h): CFG mix
+    (``cfg_alpha`` not None: the first half of the rows is unconditional, the second conditional), temperature, top-k
+    (``top_k <= 0``: off), top-p (applied iff ``0 <= top_p <= 1``) and the inverse-CDF draw with the uniforms ``u`` (fp32, one per
+    OUTPUT row, in [0, 1)).  The logits are read in place, in their own dtype (fp32 / bf16 / fp16), through their row stride: any
+    leading shape whose last dimension has stride 1 and which flattens to rows as a view (ValueError otherwise: never a copy);
+    ``end`` may not pass the last dimension.  Returns int64 tokens shaped
+    ``logits.shape[:-1]`` with ``+ start`` added and the CFG duplication done; a bad row (NaN, +inf, nothing finite) gets -1.
+    ``want_cut``: also the per-output-row cut records as an int32 tensor [Ro, 6] (the 24-byte vqhip_sample_cut_t: kept,
+    topk_kept, cut_value bits, cut_index, max bits, z bits)."""
+    _require_cuda(logits, u)
+    if logits.dim() < 1 or logits.dtype not in SAMPLE_DTYPES:
+        raise ValueError(f'sample_tokens: logits must be fp32, bf16 or fp16 with at least one dimension, got {logits.dtype} {tuple(logits.shape)}')
+    shape = logits.shape
+    try:
+        rows = logits if logits.dim() == 2 else logits.view(-1, shape[-1])       # never a copy: the logits are read in place
+    except RuntimeError:
+        raise ValueError(f'sample_tokens: logits of shape {tuple(shape)} and strides {logits.stride()} do not flatten to rows '
+                         'without a copy') from None
+    if not 0 <= start < end <= shape[-1]:
+        raise ValueError(f'sample_tokens: need 0 <= start < end <= {shape[-1]} (the last dimension), got [{start}, {end})')
+    if rows.stride(1) != 1 and rows.shape[1] > 1:
+        raise ValueError('sample_tokens: the last dimension of the logits must have stride 1')
+    R = rows.shape[0]
+    stride = rows.stride(0) if R > 1 else max(rows.stride(0), rows.shape[1])
+    if stride < rows.shape[1]:
+        raise ValueError('sample_tokens: rows of the logits overlap')
+    cfg = cfg_alpha is not None
+    Ro = R // 2 if cfg else R
+    if u.dtype != torch.float32 or u.numel() != Ro or not u.is_contiguous():
+        raise ValueError(f'sample_tokens: u must be {Ro} contiguous fp32 uniforms, got {u.dtype} {tuple(u.shape)}')
+    tokens = torch.empty(R, dtype=torch.int64, device=logits.device)
+    cut = torch.empty(Ro, 6, dtype=torch.int32, device=logits.device) if want_cut else None
+    # the library checks the limits (R, the slice, V <= 2^20, temperature, alpha) before any HIP call
+    check(_lib.lib().vqhip_sample_tokens(_ptr(rows), SAMPLE_DTYPES[logits.dtype], R, stride, int(start), int(end),
+                                         float(cfg_alpha) if cfg else 0.0, 1 if cfg else 0, float(temperature), int(top_k),
+                                         float(top_p), _ptr(u), _ptr(tokens), _ptr(cut), _stream()), 'vqhip_sample_tokens')
+    tokens = tokens.reshape(shape[:-1])
+    return (tokens, cut) if want_cut else tokens
+
+
+def sample_cut_fields(cut: torch.Tensor) -> dict:
+    """The [Ro, 6] int32 records of ``sample_tokens(want_cut=True)`` as named host arrays (numpy)."""
+    import numpy as np
+    c = cut.cpu().numpy()
+    f = np.ascontiguousarray(c).view(np.float32)
+    return dict(kept=c[:, 0].copy(), topk_kept=c[:, 1].copy(), cut_value=f[:, 2].copy(), cut_index=c[:, 3].copy(),
+                max=f[:, 4].copy(), z=f[:, 5].copy())
+
+
 # ---- pooled code features (the linear probe, vq/tasks/image_classification/models.py:101-109) ----------------------------
 
 def _pool_tokens(quant: torch.Tensor, what: str):

@@ -10,6 +10,7 @@ shape, dtype, alignment, the probability buffer, the world size, train / eval). 
     map_entry     map | tokens
     decode_entry  map | tokens
     pooled_entry  pooled | rows
+    sampler_why   fused | torch
 """
 from __future__ import annotations
 
@@ -358,3 +359,72 @@ def pooled_entry(q, quant: torch.Tensor) -> Route:
         or ('' if quant.dtype in (torch.int32, torch.int64) else f'the tokens are {quant.dtype}, not int32 or int64') \
         or ('' if 0 < quant.numel() < (1 << 31) else f'{quant.numel()} tokens are outside 1 .. 2^31-1')
     return Route('rows', why) if why else Route('pooled')
+
+
+# ---- the sampler of stage-2 generation (vector_quantization_amd/samplers.py) ---------------------------------------------
+
+def plain_sampler(s) -> str:
+    """``s`` draws as BaseSampler or TopKTopPSampler do: one of the two classes, or a subclass that keeps their ``sample``."""
+    from .. import samplers as S
+    if isinstance(s, S.CFGSampler):
+        return f'{type(s).__name__} is not one of the two plain samplers'
+    for base in (S.TopKTopPSampler, S.BaseSampler):
+        if isinstance(s, base):
+            return own(s, base, 'sample', 'fused_arguments')
+    return f'{type(s).__name__} is not one of the two plain samplers'
+
+
+def sampler_config(s) -> str:
+    """The configuration part: what the fused launch computes is what ``s.sample`` would."""
+    from .. import samplers as S
+    if isinstance(s, S.CFGSampler):
+        why = own(s, S.CFGSampler, 'sample', 'fused_arguments')
+        inner = plain_sampler(s._sampler)
+        return why or (f'the CFG inner sampler: {inner}' if inner else '')
+    return plain_sampler(s)
+
+
+def sampler_arguments(s) -> str:
+    """The temperature the launch divides by is finite and > 0 (anything else: the reference's own arithmetic decides)."""
+    t = s.fused_arguments()['temperature']
+    try:
+        ok = 0.0 < float(t) < float('inf')
+    except (TypeError, ValueError):
+        ok = False
+    return '' if ok else f'temperature={t!r} is not a finite number > 0'
+
+
+def sampler_rows(logits: torch.Tensor, start: int, end: int) -> str:
+    """[..., V_total] is rows of ONE stride that do not overlap, read as a view, and [start, end) lies inside the last dimension."""
+    if not 0 <= start < end <= logits.shape[-1]:
+        return f'[{start}, {end}) is not a non-empty slice of the last dimension ({logits.shape[-1]})'
+    if end - start > ops.SAMPLE_MAX_V:
+        return f'V={end - start} is beyond 2^20'
+    if not _flattens(logits):
+        return 'the leading dimensions of the logits do not flatten without a copy'
+    rows = logits if logits.dim() == 2 else logits.view(-1, logits.shape[-1])
+    if rows.shape[0] > 1 and rows.stride(0) < rows.shape[1]:
+        return f'the rows of the logits overlap (row stride {rows.stride(0)} < {rows.shape[1]})'
+    return ''
+
+
+def sampler_why(sampler, logits: torch.Tensor, start: int = 0, end=None) -> Route:
+    """A sampler step: ONE launch of ``ops.sample_tokens`` on the logits as they are (``fused``), or the reference's composition
+    with torch ops (``torch``), with the first clause that refused the launch."""
+    end = logits.shape[-1] if end is None else end
+    why = ('' if logits.is_cuda else f'the logits are on device {logits.device}, not on a GPU') \
+        or ('' if logits.dim() >= 1 and (logits.stride(-1) == 1 or logits.shape[-1] == 1) else 'the last dimension of the logits does not have stride 1') \
+        or ('' if logits.dtype in ops.SAMPLE_DTYPES else f'the logits are {logits.dtype}, not float32, bfloat16 or float16') \
+        or sampler_config(sampler) or sampler_arguments(sampler) or sampler_rows(logits, start, end)
+    return Route('torch', why) if why else Route('fused')
+
+
+def _flattens(x: torch.Tensor) -> bool:
+    """[..., V] is [-1, V] rows with ONE row stride, as a view."""
+    if x.dim() <= 2:
+        return True
+    try:
+        x.view(-1, x.shape[-1])
+        return True
+    except RuntimeError:
+        return False

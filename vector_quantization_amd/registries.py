@@ -55,6 +55,23 @@ class VQITQuantizerLossRegistry(VQITQuantizerRegistry):
     pass
 
 
+class VQSMSamplerRegistry(VQModelRegistry):
+    """The samplers of stage-2 generation (vq/tasks/sequence_modeling/models/registries.py:21-34).  As there, a ``cfg`` key in a
+    sampler's config wraps the built sampler: ``dict(type='TopKTopPSampler', cfg=1.75)`` is ``CFGSampler(sampler=..., alpha=1.75)``
+    (configs/ar/cfg.py)."""
+
+    @classmethod
+    def build(cls, config, **kwargs):
+        config = dict(config)
+        config.update(kwargs)
+        cfg = config.pop('cfg', None)
+        sampler = type(cls).build(cls, config)                                   # RegistryMeta.build: the plain lookup and pre-hook
+        if cfg is not None:
+            from .samplers import CFGSampler
+            sampler = CFGSampler(sampler=sampler, alpha=cfg)
+        return sampler
+
+
 class AnchorRegistry(Registry):
     pass
 
