@@ -12,6 +12,7 @@ import numpy as np
 import pytest
 import torch
 
+import forward_ref as fr
 from oracle import synth, torch_ref as tr
 
 pytestmark = pytest.mark.gpu
@@ -75,7 +76,11 @@ def run_steps(q, xs, gz, one_call, autocast=False):
     return rec
 
 
-def assert_same(a, b, exact_w=True, tol=1e-6):
+def assert_same(a, b, exact_w=True, tol=1e-6, derived=False):
+    """``derived``: the loss is a plain term (the MSE or VQGANLoss's combination) of the same rows, tokens and codebook on both sides,
+    outside autocast: each side is within the derived bound of the float64 value (tests/forward_ref.py, held against it in
+    tests/test_gpu_forward.py), so the two differ by at most twice that bound, relative.  The VQ-KD routes (their codebooks
+    differ in the last bits below 32 768 tokens) and the autocast runs keep ``tol``."""
     for sa, sb in zip(a, b):
         assert torch.equal(sa['quant'], sb['quant'])
         assert torch.equal(sa['hist'], sb['hist'])
@@ -85,7 +90,12 @@ def assert_same(a, b, exact_w=True, tol=1e-6):
         else:
             torch.testing.assert_close(sa['w'], sb['w'], rtol=0, atol=3e-6)
             torch.testing.assert_close(sa['z'], sb['z'], rtol=0, atol=3e-6)
-        assert abs(float(sa['loss']) - float(sb['loss'])) <= tol * max(1.0, abs(float(sb['loss'])))
+        loss_tol = tol * max(1.0, abs(float(sb['loss'])))
+        if derived:
+            assert exact_w
+            N, D = sb['z'].shape
+            loss_tol = min(loss_tol, fr.route_pair_bound(float(sb['loss']), D, N * D))
+        assert abs(float(sa['loss']) - float(sb['loss'])) <= loss_tol, (float(sa['loss']), float(sb['loss']), loss_tol)
         assert sa['loss_memo'].keys() == sb['loss_memo'].keys()
         torch.testing.assert_close(sa['gx'], sb['gx'], rtol=1e-5, atol=1e-9)
         assert (sa['gw'] is None) == (sb['gw'] is None)
@@ -106,7 +116,7 @@ def test_cvq_one_call_equals_hook_by_hook(dist, D, bf16):
         rows.append(q._callbacks.callbacks[0].last_exchange_rows)
         recs[-1].append(dict(p=q.get_buffer('_probability').clone()))
     assert torch.equal(recs[0][-1]['p'], recs[1][-1]['p'])
-    assert_same(recs[0][:-1], recs[1][:-1])
+    assert_same(recs[0][:-1], recs[1][:-1], derived=True)
     assert rows[0] == rows[1] and 0 < rows[1] < K, rows           # the one-call route sized its launches from the prefetched count
 
 
@@ -145,7 +155,7 @@ def test_cvq_one_call_in_place_updates_and_external_probability_change():
         rec += run_steps(q, xs[3:], gz, one_call)
         outs.append((rec, q.get_buffer('_probability').clone()))
     for other in outs[1:]:
-        assert_same(outs[0][0], other[0])
+        assert_same(outs[0][0], other[0], derived=True)
         assert torch.equal(outs[0][1], other[1])
 
 
@@ -228,7 +238,7 @@ def test_forced_exchange_takes_the_two_phase_route(monkeypatch):
     import vector_quantization_amd.utils as U
     monkeypatch.setattr(U, 'all_reduce_sum', lambda t: calls.append(t.numel()) or t)
     forced = run_steps(build(cvq_cfg(K, D, 'Cosine'), w0), xs, gz, True)
-    assert_same(base, forced)
+    assert_same(base, forced, derived=True)
     assert len(calls) == len(xs) and calls[0] == 2 * K + 4 + K * D and calls[-1] < calls[0]     # the payload shrinks with the list
     calls.clear()
     forced_k = run_steps(build(vqkd_cfg(K, 32), wk, True), xk, gk, True)
@@ -366,7 +376,7 @@ def test_cvq_routes_alternating_on_one_module(dist, inplace):
     for routes in ([i % 2 == 1 for i in range(n)], [i % 2 == 0 for i in range(n)], [(i // 2) % 2 == 1 for i in range(n)]):
         rec, rows, probs = run(routes)
         for ref_rec, ref_rows, ref_probs in fixed:
-            assert_same(ref_rec, rec)
+            assert_same(ref_rec, rec, derived=True)
             assert rows == ref_rows, (routes, rows, ref_rows)
             for i, (pa, pb) in enumerate(zip(ref_probs, probs)):
                 assert torch.equal(pa, pb), (routes, i)
@@ -406,7 +416,7 @@ def test_plain_and_normalize_forward_one_call_equals_hook_by_hook(kind, dist, D,
                             memo_x=memo['x'].detach().clone(), loss_memo={k: v.detach().clone() for k, v in memo['loss'].items()}))
             assert memo['encode']['distance'].shape == (N, K)
         recs.append(rec)
-    assert_same(recs[0], recs[1])
+    assert_same(recs[0], recs[1], derived=True)
 
 
 @pytest.mark.parametrize('metric,D,dtype', [('Cosine', 256, torch.float32), ('L2', 256, torch.float32), ('CosineBF16', 64, torch.float32),

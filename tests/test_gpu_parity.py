@@ -12,6 +12,7 @@ import numpy as np
 import pytest
 import torch
 
+import forward_ref as fr
 from oracle import c_oracle as co, synth
 
 pytestmark = pytest.mark.gpu
@@ -90,14 +91,15 @@ def test_encode_matches_oracle_and_golden(ops, path):
     hist = torch.zeros(spec['K'], dtype=torch.int32, device='cuda')
     ops.argmin(xq, cb, hist=hist)
     np.testing.assert_array_equal(hist.cpu().numpy().astype(np.int64), co.bincount(oracle_idx, spec['K']))
-    # decode + STE bit-exact, loss within 1e-5
+    # decode + STE bit-exact, loss within twice the derived bound of tests/forward_ref.py
     zt, zs, sse = ops.gather_ste_loss(xd, wd, idx)
     zo, zso = co.gather_ste(xo, wo, oracle_idx)
     np.testing.assert_array_equal(zt.cpu().numpy(), zo)
     np.testing.assert_array_equal(zs.cpu().numpy(), zso)
     mse = float(sse.item()) / (spec['N'] * spec['D'])
     ref = float(co.mse(zo, xo))
-    assert abs(mse - ref) <= 1e-5 * max(1.0, abs(ref))
+    # kernel and C oracle are each within the derived bound of the float64 mean (tests/forward_ref.py): twice the bound, relative
+    assert abs(mse - ref) <= fr.pair_bound(ref, fr.c_plain(spec['D']), spec['N'] * spec['D']), (mse, ref)
     # the same pass with the mean finished on the device: identical value, twice (the scratch comes back zeroed)
     want = (sse / (spec['N'] * spec['D'])).float()
     for _ in range(2):
