@@ -295,6 +295,90 @@ int vqhip_sample_tokens(const void *logits, int dtype, int64_t R, int64_t row_st
                         float cfg_alpha, int cfg, float temperature, int top_k, float top_p,
                         const float *u, int64_t *tokens, vqhip_sample_cut_t *cut /* or NULL */, void *stream);
 
+/* ---- fused token cross-entropy of stage-2 training --------------------------------------------------------------------------
+ * The loss a stage-2 transformer trains on: AR, the shifted mean cross-entropy HF computes for `labels=tokens`
+ * (vq/algorithms/ar/transformers/hf.py:61-69); NAR, MAGE's LabelSmoothingCrossEntropy(0.1) averaged with the mask as weights
+ * (vq/algorithms/nar/transformers/mage.py:107-123, 479-489).  Forward: the logits are read ONCE (one workgroup per row) and a
+ * second, single-workgroup launch forms the scalars.  Backward: one read of the logits, one write of the gradient.  No
+ * [R, V] temporary, no workspace, no atomics, no allocation and no synchronisation.
+ * INPUT   logits [R, >= end] in `dtype` (VQHIP_DTYPE_F32, _BF16 or _F16), element stride 1, row stride `row_stride` >= end
+ *   elements, element alignment only; columns [start, end) are read, V = end - start.  Every element a_j (j the index inside the
+ *   slice) is converted to fp32 exactly; all arithmetic below is fp32 IEEE without contraction, expf / logf at <= 1 ulp.
+ * TARGETS [R] int32 or int64 (`target_dtype` VQHIP_DTYPE_I32 / _I64), values in the vocabulary: class t means a_{t - start}.
+ *   shift_len = 0: the target of row r is targets[r].  shift_len = L > 0 (R % L == 0): the rows are R / L sequences of L
+ *   positions, the target of row r is targets[r + 1], and the last row of every sequence is IGNORED (HF's logits[..., :-1, :]
+ *   against labels[..., 1:] with neither tensor sliced).  A target equal to `ignore_index` makes its row IGNORED: loss 0, hit 0, a
+ *   zero gradient row, not counted in W.  Any other target outside [start, end) is never dereferenced: that row's loss and its
+ *   gradient slice are NaN (and so are the scalars).
+ * DEFINITION  with e = label_smoothing, t the row's target, w_r = weight[r] (1 without weights):
+ *       lse_r  = max + log(sum_j exp(a_j - max))
+ *       loss_r = lse_r - a_t                                               (e == 0: the smoothing term is not formed)
+ *       loss_r = (1 - e)(lse_r - a_t) + e (lse_r - (sum_j a_j) / V)        (e > 0;  1 - e is (float)(1.0 - (double)e))
+ *       hit_r  = 1 iff lse_r is not NaN and the arg-max of the slice, the LOWEST index among equal values, is t; else 0
+ *       out[0] = sum_r w_r loss_r, out[1] = W = sum_r w_r, both over the rows that are not ignored; out[2] = (float)(sum_r hit_r)
+ *       (an exact integer sum, converted once); out[3] = out[0] / out[1], a true division on the device: W = 0 gives NaN.
+ *       grad[r, j] = c_r ((p_j - (1 - e)[j = t]) - e / V),  p_j = exp(a_j - lse_r) from the SAVED lse (no second reduction),
+ *       c_r = g w_r / W with `wsum` (the mean: pass out + 1), c_r = g w_r without; g = g[r] if g_per_row else g[0].
+ *   The gradient is rounded to nearest even into the logits' dtype and written to grad [R, row_stride_out]: columns [0, cols)
+ *   of every row are written, zeros outside [start, end) and in every column of an ignored row (the caller does not memset);
+ *   columns [cols, row_stride_out) are not touched.
+ * ORDER OF EVERY SUM  T = 256 threads, W = 4 (fp32) or 8 (16-bit) elements per 16 bytes.  The slice is cut by the index j, not by
+ *   the address: piece q is elements [W q, W q + W) for q < V / W, then V % W pieces of one element; piece q belongs to thread
+ *   q % T, which takes its pieces in increasing q.  A thread keeps (m, s, sa) = (-inf, 0, 0) and for a piece with maximum pm:
+ *   if pm > m: s = s * expf(m - pm), m = pm;  then for its elements in order  s = s + expf(a - m),  sa = sa + a.  Two partials
+ *   merge as M = max(m_A, m_B), s = s_A f_A + s_B f_B with f_X = 1 if m_X == M else expf(m_X - M), sa = sa_A + sa_B; the 256
+ *   threads merge as a balanced binary tree in thread order.  lse = M + logf(s).  The scalars: partial j = r mod 256 adds its
+ *   rows in increasing r (s_j = s_j + w_r * loss_r; W alike), the 256 partials add as the same balanced tree.  The order is a
+ *   function of V and the dtype's W for a row and of R alone for the scalars: not of the address or alignment of a row (a
+ *   strided view and its copy give the same bits), not of the target dtype, not of the other rows, and run to run the same bits.
+ * NON-FINITE INPUTS  (the pattern float64 log_softmax arithmetic gives; a row never affects another row's per-row outputs)
+ *       the slice holds                          lse     loss, e == 0        loss, e > 0     gradient slice
+ *       a NaN                                    NaN     NaN                 NaN             NaN
+ *       a +inf                                   NaN     NaN                 NaN             NaN
+ *       -inf entries, finite maximum             finite  finite              +inf            finite (p = 0 at the -inf entries)
+ *       the same with a_t = -inf                 finite  +inf                +inf            finite
+ *       nothing but -inf                         NaN     NaN                 NaN             NaN
+ *   hit is 0 wherever lse is NaN.  A non-finite loss_r reaches out[0] and out[3] as IEEE addition carries it.
+ * ERROR BOUND  against the exact value of the definition on the converted inputs, amax = the row's largest |a_j|, all a_j
+ *   finite; N = VQHIP_TOKEN_CE_CHAIN(V) = V / 256 + 20 (integer division) bounds the longest chain of fp32 additions of a row (a thread
+ *   adds at most ceil(V / (256 W)) W + 1 <= V / 256 + 10 elements, the tree adds 8 levels).  In units of u = 2^-24, first order:
+ *     s: a term expf(fl(a - m)) carries 2 amax (the rounded difference, |a - m| <= 2 amax) + 2 (expf); the rescalings of a
+ *        partial telescope, since m only grows: sum |m_old - m_new| <= 2 amax, so all of them together carry 2 amax, plus 2
+ *        (expf) + 1 (the product) for each of at most N rescalings; the additions of positive terms carry N.  Relative error of
+ *        s: (4 amax + 2 + 4 N) u.   (Terms flushed below 2^-126 change s >= 1 by less than V 2^-126.)
+ *     lse = fl(M + logf(s)): the above, + 2 ln(V) <= 28 (logf at 1 ulp of ln s <= ln V < 14), + amax + 14 (the last addition):
+ *        VQHIP_TOKEN_CE_LSE_BOUND = (5 amax + 44 + 4 N) u (1 + 2^-9); the last factor covers every second-order product
+ *        (the sum is below 2^-9 for V <= 2^20, amax <= 2^10).
+ *     loss: d1 = fl(lse - a_t) and d2 = fl(lse - fl(sa / V)) are each <= 2 amax + 14 in size; sa / V carries N amax (the chain,
+ *        |a| <= amax) + amax (the division); the two products, the rounded 1 - e and the final addition carry 5 (2 amax + 14):
+ *        VQHIP_TOKEN_CE_BOUND = VQHIP_TOKEN_CE_LSE_BOUND + ((N + 11) amax + 70) u   (holds for lse and for loss_r, any e).
+ *     gradient element in fp32, before the rounding to the output dtype, per unit of |c_r|: the exponent fl(a - lse) carries
+ *        the lse error + (2 amax + 14), expf 2, on p <= 1 (1 + small); the two subtractions, the rounded 1 - e and e / V and the
+ *        product carry 6 on values <= 1:  VQHIP_TOKEN_CE_GRAD_BOUND = VQHIP_TOKEN_CE_LSE_BOUND + (2 amax + 22) u.
+ *        c_r itself is fl(fl(g w_r) / W): 2 u relative, plus W's own sum, (R / 256 + 20) u relative (exact for unit weights
+ *        below 2^24 rows).  The scalars add (R / 256 + 20) u sum_r |w_r loss_r| to sum_r w_r (error of loss_r).
+ *   A measurement beyond these bounds means the kernel or this derivation is wrong.
+ * LIMITS (VQHIP_EINVAL before any HIP call): logits, targets, loss, lse, out (fwd) / logits, targets, lse, g, grad (bwd) not
+ *   null (hit, weight, wsum may be); 1 <= R < 2^31; 0 <= start < end <= row_stride; V <= 2^20; 0 <= label_smoothing < 1;
+ *   shift_len >= 0 and R % shift_len == 0; dtype one of F32 / BF16 / F16; target_dtype one of I32 / I64; bwd: end <= cols <=
+ *   row_stride_out, cols < 2^31. */
+#define VQHIP_TOKEN_CE_CHAIN(V) ((double)((V) / 256 + 20))
+#define VQHIP_TOKEN_CE_LSE_BOUND(V, amax) \
+    ((5.0 * (double)(amax) + 44.0 + 4.0 * VQHIP_TOKEN_CE_CHAIN(V)) * 5.9604644775390625e-08 * 1.001953125)
+#define VQHIP_TOKEN_CE_BOUND(V, amax) \
+    (VQHIP_TOKEN_CE_LSE_BOUND(V, amax) + ((VQHIP_TOKEN_CE_CHAIN(V) + 11.0) * (double)(amax) + 70.0) * 5.9604644775390625e-08)
+#define VQHIP_TOKEN_CE_GRAD_BOUND(V, amax) \
+    (VQHIP_TOKEN_CE_LSE_BOUND(V, amax) + (2.0 * (double)(amax) + 22.0) * 5.9604644775390625e-08)
+int vqhip_token_ce_fwd(const void *logits, int dtype, int64_t R, int64_t row_stride, int64_t start, int64_t end,
+                       const void *targets, int target_dtype, int64_t shift_len, int64_t ignore_index, float label_smoothing,
+                       const float *weight /* [R] or NULL */, float *loss /* [R] */, float *lse /* [R] */,
+                       int32_t *hit /* [R] or NULL */, float *out /* [4] */, void *stream);
+int vqhip_token_ce_bwd(const void *logits, int dtype, int64_t R, int64_t row_stride, int64_t start, int64_t end,
+                       const void *targets, int target_dtype, int64_t shift_len, int64_t ignore_index, float label_smoothing,
+                       const float *weight /* [R] or NULL */, const float *lse /* [R] */, const float *g /* [R] or [1] */,
+                       int g_per_row, const float *wsum /* [1] (the mean) or NULL */, void *grad /* [R, row_stride_out] */,
+                       int64_t cols, int64_t row_stride_out, void *stream);
+
 /* ---- EntropyLoss (vq/algorithms/vq/losses.py:130-153) on row blocks of the distance matrix ------------------------------
  * With a = d / T, p = softmax(a, -1), q_k = (1/N) sum_n p_nk:
  *   L = (1/N) sum_n (lse_n - sum_k p_nk a_nk) + sum_k q_k log(q_k + 1e-5)

@@ -9,12 +9,14 @@ from . import _lib  # noqa: F401
 from .config import BuildPreHookMixin, Config, Registry, RegistryMeta
 from .registries import (AnchorRegistry, InitRegistry, ModelRegistry, VQITQuantizerCallbackRegistry,
                          VQITQuantizerDistanceRegistry, VQITQuantizerLossRegistry, VQITQuantizerRegistry)
+from .sequence_losses import CausalTokenLoss, LabelSmoothingCrossEntropy, MaskedTokenLoss
 from .utils import EMA, ema
 
 __all__ = [
     'BuildPreHookMixin', 'Config', 'Registry', 'RegistryMeta', 'AnchorRegistry', 'InitRegistry', 'ModelRegistry',
     'VQITQuantizerCallbackRegistry', 'VQITQuantizerDistanceRegistry', 'VQITQuantizerLossRegistry',
-    'VQITQuantizerRegistry', 'EMA', 'ema', 'build_quantizer',
+    'VQITQuantizerRegistry', 'EMA', 'ema', 'build_quantizer', 'CausalTokenLoss', 'LabelSmoothingCrossEntropy',
+    'MaskedTokenLoss',
 ]
 __version__ = '0.1.0'
 

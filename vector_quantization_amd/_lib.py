@@ -82,6 +82,26 @@ def sample_delta(V: int) -> float:
     return 2.0 ** -18 + V * 2.0 ** -39
 
 
+def token_ce_chain(n: int) -> float:
+    """VQHIP_TOKEN_CE_CHAIN of include/vqhip.h: the longest chain of fp32 additions over n elements (a row) or n rows."""
+    return float(n // 256 + 20)
+
+
+def token_ce_lse_bound(V: int, amax: float) -> float:
+    """VQHIP_TOKEN_CE_LSE_BOUND(V, amax) of include/vqhip.h: |kernel lse - exact lse| of vqhip_token_ce_fwd."""
+    return (5.0 * amax + 44.0 + 4.0 * token_ce_chain(V)) * 2.0 ** -24 * (1.0 + 2.0 ** -9)
+
+
+def token_ce_bound(V: int, amax: float) -> float:
+    """VQHIP_TOKEN_CE_BOUND(V, amax): the bound that holds for lse and for the per-row loss, any label smoothing."""
+    return token_ce_lse_bound(V, amax) + ((token_ce_chain(V) + 11.0) * amax + 70.0) * 2.0 ** -24
+
+
+def token_ce_grad_bound(V: int, amax: float) -> float:
+    """VQHIP_TOKEN_CE_GRAD_BOUND(V, amax): a gradient element in fp32, before the rounding to the output dtype, per unit |c_r|."""
+    return token_ce_lse_bound(V, amax) + (2.0 * amax + 22.0) * 2.0 ** -24
+
+
 STEP_BEFORE_EXCHANGE, STEP_AFTER_EXCHANGE, STEP_ALL, STEP_PACK_SYNC = 1, 2, 3, 4
 
 # name -> (restype, argtypes); mirrors include/vqhip.h one to one
@@ -114,6 +134,9 @@ SIGNATURES = {
     'vqhip_decode_pool_bwd': (_i32, [_vp, _vp, _i32, _i64, _i64, _i64, _i32, _vp, _vp]),
     'vqhip_fsq_decode_pool': (_i32, [ctypes.POINTER(FsqConstants), _vp, _i32, _i64, _i64, _vp, _vp]),
     'vqhip_sample_tokens': (_i32, [_vp, _i32, _i64, _i64, _i64, _i64, _f32, _i32, _f32, _i32, _f32, _vp, _vp, _vp, _vp]),
+    'vqhip_token_ce_fwd': (_i32, [_vp, _i32, _i64, _i64, _i64, _i64, _vp, _i32, _i64, _i64, _f32, _vp, _vp, _vp, _vp, _vp, _vp]),
+    'vqhip_token_ce_bwd': (_i32, [_vp, _i32, _i64, _i64, _i64, _i64, _vp, _i32, _i64, _i64, _f32, _vp, _vp, _vp, _i32, _vp, _vp,
+                                  _i64, _i64, _vp]),
     'vqhip_entropy_workspace_bytes': (_i64, [_i64, _i64]),
     'vqhip_entropy_rows': (_i32, [_vp, _i64, _i64, _f32, _vp, _vp, _vp, _i32, _vp, _i64, _vp]),
     'vqhip_entropy_finish': (_i32, [_vp, _vp, _vp, _i64, _i64, _vp, _vp, _vp, _vp]),

@@ -9,6 +9,7 @@
 #include "vqhip_fsq_kernels.h"
 #include "vqhip_entropy_kernels.h"
 #include "vqhip_sample_kernels.h"
+#include "vqhip_token_ce_kernels.h"
 
 static thread_local char g_err[256] = "";
 
@@ -497,6 +498,24 @@ static int launch_sample(const VqSampleArgs &a, hipStream_t s) {
         sample_tokens_kernel<DT, false><<<(unsigned)a.Ro, VQ_SAMPLE_THREADS, 0, s>>>(a);
     }
     VQ_CHECK_LAUNCH("sample_tokens_kernel");
+    return VQHIP_OK;
+}
+
+// ---- fused token cross-entropy: the launches (vqhip_token_ce_kernels.h) ---------------------------------------------------
+template <int DT, bool I64>
+static int launch_token_ce_fwd(const VqCeArgs &a, float *loss, float *lse, int32_t *hit, float *out, hipStream_t s) {
+    token_ce_fwd_kernel<DT, I64><<<(unsigned)a.R, VQ_CE_THREADS, 0, s>>>(a, loss, lse, hit);
+    VQ_CHECK_LAUNCH("token_ce_fwd_kernel");
+    token_ce_reduce_kernel<I64><<<1, VQ_CE_THREADS, 0, s>>>(a, loss, hit, out);
+    VQ_CHECK_LAUNCH("token_ce_reduce_kernel");
+    return VQHIP_OK;
+}
+
+template <int DT, bool I64>
+static int launch_token_ce_bwd(const VqCeArgs &a, const float *lse, const float *g, int g_per_row, const float *wsum, void *grad,
+                               int cols, int64_t row_stride_out, hipStream_t s) {
+    token_ce_bwd_kernel<DT, I64><<<(unsigned)a.R, VQ_CE_THREADS, 0, s>>>(a, lse, g, g_per_row, wsum, grad, cols, row_stride_out);
+    VQ_CHECK_LAUNCH("token_ce_bwd_kernel");
     return VQHIP_OK;
 }
 
@@ -1267,6 +1286,61 @@ int vqhip_sample_tokens(const void *logits, int dtype, int64_t R, int64_t row_st
     default: return launch_sample<VQHIP_DTYPE_F16>(a, s);
     }
 }
+
+// ---- fused token cross-entropy (vqhip_token_ce_kernels.h) -----------------------------------------------------------------
+// what the two entry points refuse alike, and the arguments the kernels share
+static int token_ce_setup(const char *what, const void *logits, int dtype, int64_t R, int64_t row_stride, int64_t start, int64_t end,
+                          const void *targets, int target_dtype, int64_t shift_len, int64_t ignore_index, float eps,
+                          const float *weight, VqCeArgs *a) {
+    if (!logits || !targets) return fail(VQHIP_EINVAL, what, "logits and targets are required");
+    if (dtype != VQHIP_DTYPE_F32 && dtype != VQHIP_DTYPE_BF16 && dtype != VQHIP_DTYPE_F16) return fail(VQHIP_EINVAL, what, "dtype");
+    if (target_dtype != VQHIP_DTYPE_I32 && target_dtype != VQHIP_DTYPE_I64) return fail(VQHIP_EINVAL, what, "target_dtype");
+    if (R < 1 || R >= (1ll << 31)) return fail(VQHIP_EINVAL, what, "R must be in 1 .. 2^31 - 1");
+    if (!(start >= 0 && start < end && end <= row_stride)) return fail(VQHIP_EINVAL, what, "need 0 <= start < end <= row_stride");
+    if (end - start > VQ_CE_MAX_V) return fail(VQHIP_EINVAL, what, "end - start is beyond 2^20");
+    if (!(eps >= 0.0f && eps < 1.0f)) return fail(VQHIP_EINVAL, what, "label_smoothing must be in [0, 1)");
+    if (shift_len < 0 || (shift_len > 0 && R % shift_len != 0)) return fail(VQHIP_EINVAL, what, "shift_len must be 0 or divide R");
+    a->logits = logits; a->row_stride = row_stride; a->start = start;
+    a->V = (int)(end - start);
+    a->R = R;
+    a->targets = targets; a->shift_len = shift_len; a->ignore_index = ignore_index;
+    a->eps = eps; a->one_minus_eps = (float)(1.0 - (double)eps); a->eps_over_v = eps / (float)a->V;
+    a->weight = weight;
+    return VQHIP_OK;
+}
+
+#define VQ_TOKEN_CE_DISPATCH(fn, ...)                                                                                   \
+    do {                                                                                                                \
+        const bool i64__ = target_dtype == VQHIP_DTYPE_I64;                                                             \
+        switch (dtype) {                                                                                                \
+        case VQHIP_DTYPE_F32: return i64__ ? fn<VQHIP_DTYPE_F32, true>(__VA_ARGS__) : fn<VQHIP_DTYPE_F32, false>(__VA_ARGS__);      \
+        case VQHIP_DTYPE_BF16: return i64__ ? fn<VQHIP_DTYPE_BF16, true>(__VA_ARGS__) : fn<VQHIP_DTYPE_BF16, false>(__VA_ARGS__);   \
+        default: return i64__ ? fn<VQHIP_DTYPE_F16, true>(__VA_ARGS__) : fn<VQHIP_DTYPE_F16, false>(__VA_ARGS__);                  \
+        }                                                                                                               \
+    } while (0)
+
+int vqhip_token_ce_fwd(const void *logits, int dtype, int64_t R, int64_t row_stride, int64_t start, int64_t end, const void *targets,
+                       int target_dtype, int64_t shift_len, int64_t ignore_index, float label_smoothing, const float *weight,
+                       float *loss, float *lse, int32_t *hit, float *out, void *stream) {
+    VqCeArgs a;
+    if (int rc = token_ce_setup("vqhip_token_ce_fwd", logits, dtype, R, row_stride, start, end, targets, target_dtype, shift_len,
+                                ignore_index, label_smoothing, weight, &a)) return rc;
+    VQ_REQUIRE(loss && lse && out, "vqhip_token_ce_fwd: loss, lse and out are required");
+    VQ_TOKEN_CE_DISPATCH(launch_token_ce_fwd, a, loss, lse, hit, out, (hipStream_t)stream);
+}
+
+int vqhip_token_ce_bwd(const void *logits, int dtype, int64_t R, int64_t row_stride, int64_t start, int64_t end, const void *targets,
+                       int target_dtype, int64_t shift_len, int64_t ignore_index, float label_smoothing, const float *weight,
+                       const float *lse, const float *g, int g_per_row, const float *wsum, void *grad, int64_t cols,
+                       int64_t row_stride_out, void *stream) {
+    VqCeArgs a;
+    if (int rc = token_ce_setup("vqhip_token_ce_bwd", logits, dtype, R, row_stride, start, end, targets, target_dtype, shift_len,
+                                ignore_index, label_smoothing, weight, &a)) return rc;
+    VQ_REQUIRE(lse && g && grad, "vqhip_token_ce_bwd: lse, g and grad are required");
+    VQ_REQUIRE(end <= cols && cols <= row_stride_out && cols < (1ll << 31), "vqhip_token_ce_bwd: need end <= cols <= row_stride_out, cols < 2^31");
+    VQ_TOKEN_CE_DISPATCH(launch_token_ce_bwd, a, lse, g, g_per_row ? 1 : 0, wsum, grad, (int)cols, row_stride_out, (hipStream_t)stream);
+}
+#undef VQ_TOKEN_CE_DISPATCH
 
 // ---- EntropyLoss on row blocks of the distance matrix (vqhip_entropy_kernels.h) ----------------------------------------
 static int entropy_check(const char *what, int64_t R, int64_t K, float T) {

@@ -291,3 +291,56 @@ def fused_decode_loss(x: torch.Tensor, weight: torch.Tensor, idx: torch.Tensor, 
     else:
         _, z_ste, mse = ops.gather_ste_mse(xd, weight.detach(), idx, beta=beta)   # means and their combination finished inside the kernel
     return vq_step(x, weight, _Computed(xn=None, z_ste=z_ste, mse=mse, idx=idx), beta)[1:]
+
+
+class _TokenCE(Function):
+    """The fused token cross-entropy (vqhip_token_ce_fwd / _bwd of include/vqhip.h).  Saves ``lse`` and the logits AS GIVEN (a
+    view stays a view: no copy); the backward is one launch that writes every element of the gradient."""
+
+    @staticmethod
+    def forward(ctx, logits, targets, weight, start, end, label_smoothing, ignore_index, shift, reduction):
+        kw = dict(label_smoothing=label_smoothing, ignore_index=ignore_index, weight=weight, shift=shift)
+        f = ops.token_ce_forward(logits, targets, start, end, **kw)
+        ctx.save_for_backward(logits, targets, weight, f['lse'], f['out'])
+        ctx.args, ctx.kw, ctx.reduction = (start, end), kw, reduction
+        out = f['out']
+        if reduction == 'mean':
+            value = out[3]
+        elif reduction == 'sum':
+            value = out[0]
+        else:
+            rows = f['loss'] if weight is None else f['loss'] * weight.reshape(-1).to(torch.float32)
+            value = rows.view(logits.shape[:-1])
+        stats = (f['lse'], f['loss'], f['hit'], out)
+        ctx.mark_non_differentiable(*stats)
+        return (value.clone(),) + stats                                        # (its own storage: the statistics are outputs too)
+
+    @staticmethod
+    def backward(ctx, g, *unused):
+        logits, targets, weight, lse, out = ctx.saved_tensors
+        if not ctx.needs_input_grad[0]:
+            return (None,) * 9
+        grad = ops.token_ce_backward(logits, targets, lse, g, *ctx.args, **dict(ctx.kw, weight=weight),
+                                     weight_sum=out[1:2] if ctx.reduction == 'mean' else None)
+        return (grad,) + (None,) * 8
+
+
+def token_cross_entropy(logits: torch.Tensor, targets: torch.Tensor, start: int = 0, end: Optional[int] = None, *,
+                        label_smoothing: float = 0.0, ignore_index: int = -100, weight: Optional[torch.Tensor] = None,
+                        shift: bool = False, reduction: str = 'mean', want_stats: bool = False):
+    """The cross-entropy of stage-2 training in fp32 from logits of any of the three dtypes, read in place:
+    ``logits`` [..., V_total] (the view rules of ``ops.sample_tokens``), ``targets`` int32 / int64 of shape ``logits.shape[:-1]``
+    holding vocabulary indices in [start, end) or ``ignore_index``; ``weight`` one value per row (MAGE's mask); ``shift``: row
+    (b, l) is held to ``targets[b, l + 1]`` and the last position of every sequence is ignored (HF's ``labels=tokens``).
+    ``reduction``: 'mean' (sum w loss / sum w over the rows that are not ignored, divided on the device), 'sum', or 'none' (w_r
+    loss_r, shaped ``logits.shape[:-1]``).  Returns the fp32 loss; with ``want_stats`` also a dict of ``lse``, per-row ``loss``
+    (unweighted), ``hit``, and the device scalars ``weight_sum`` and ``hits``."""
+    if reduction not in ops.TOKEN_CE_REDUCTIONS:
+        raise ValueError(f'token_cross_entropy: reduction must be one of {ops.TOKEN_CE_REDUCTIONS}, got {reduction!r}')
+    end = logits.shape[-1] if end is None else end
+    value, lse, loss, hit, out = _TokenCE.apply(logits, targets, weight, int(start), int(end), float(label_smoothing),
+                                                int(ignore_index), bool(shift), reduction)
+    if not want_stats:
+        return value
+    shape = logits.shape[:-1]
+    return value, dict(lse=lse.view(shape), loss=loss.view(shape), hit=hit.view(shape), weight_sum=out[1], hits=out[2])

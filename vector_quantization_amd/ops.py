@@ -622,6 +622,28 @@ SAMPLE_DTYPES = {torch.float32: _lib.DTYPE_F32, torch.bfloat16: _lib.DTYPE_BF16,
 SAMPLE_MAX_V = 1 << 20
 
 
+def _logit_rows(what: str, logits: torch.Tensor, start: int, end: int):
+    """``logits`` [..., V_total] as the kernels read it in place: (rows [R, V_total] as a VIEW, R, the row stride in elements).
+    ValueError where that takes a copy, the last dimension is strided, the rows overlap or [start, end) is not inside it."""
+    if logits.dim() < 1 or logits.dtype not in SAMPLE_DTYPES:
+        raise ValueError(f'{what}: logits must be fp32, bf16 or fp16 with at least one dimension, got {logits.dtype} {tuple(logits.shape)}')
+    shape = logits.shape
+    try:
+        rows = logits if logits.dim() == 2 else logits.view(-1, shape[-1])       # never a copy: the logits are read in place
+    except RuntimeError:
+        raise ValueError(f'{what}: logits of shape {tuple(shape)} and strides {logits.stride()} do not flatten to rows '
+                         'without a copy') from None
+    if not 0 <= start < end <= shape[-1]:
+        raise ValueError(f'{what}: need 0 <= start < end <= {shape[-1]} (the last dimension), got [{start}, {end})')
+    if rows.stride(1) != 1 and rows.shape[1] > 1:
+        raise ValueError(f'{what}: the last dimension of the logits must have stride 1')
+    R = rows.shape[0]
+    stride = rows.stride(0) if R > 1 else max(rows.stride(0), rows.shape[1])
+    if stride < rows.shape[1]:
+        raise ValueError(f'{what}: rows of the logits overlap')
+    return rows, R, stride
+
+
 @_on_tensor_device
 def sample_tokens(logits: torch.Tensor, start: int, end: int, *, u: torch.Tensor, temperature: float = 1.0, top_k: int = 0,
                   top_p: float = 2.0, cfg_alpha: Optional[float] = None, want_cut: bool = False):
@@ -635,22 +657,8 @@ def sample_tokens(logits: torch.Tensor, start: int, end: int, *, u: torch.Tensor
     ``want_cut``: also the per-output-row cut records as an int32 tensor [Ro, 6] (the 24-byte vqhip_sample_cut_t: kept,
     topk_kept, cut_value bits, cut_index, max bits, z bits)."""
     _require_cuda(logits, u)
-    if logits.dim() < 1 or logits.dtype not in SAMPLE_DTYPES:
-        raise ValueError(f'sample_tokens: logits must be fp32, bf16 or fp16 with at least one dimension, got {logits.dtype} {tuple(logits.shape)}')
     shape = logits.shape
-    try:
-        rows = logits if logits.dim() == 2 else logits.view(-1, shape[-1])       # never a copy: the logits are read in place
-    except RuntimeError:
-        raise ValueError(f'sample_tokens: logits of shape {tuple(shape)} and strides {logits.stride()} do not flatten to rows '
-                         'without a copy') from None
-    if not 0 <= start < end <= shape[-1]:
-        raise ValueError(f'sample_tokens: need 0 <= start < end <= {shape[-1]} (the last dimension), got [{start}, {end})')
-    if rows.stride(1) != 1 and rows.shape[1] > 1:
-        raise ValueError('sample_tokens: the last dimension of the logits must have stride 1')
-    R = rows.shape[0]
-    stride = rows.stride(0) if R > 1 else max(rows.stride(0), rows.shape[1])
-    if stride < rows.shape[1]:
-        raise ValueError('sample_tokens: rows of the logits overlap')
+    rows, R, stride = _logit_rows('sample_tokens', logits, start, end)
     cfg = cfg_alpha is not None
     Ro = R // 2 if cfg else R
     if u.dtype != torch.float32 or u.numel() != Ro or not u.is_contiguous():
@@ -672,6 +680,78 @@ def sample_cut_fields(cut: torch.Tensor) -> dict:
     f = np.ascontiguousarray(c).view(np.float32)
     return dict(kept=c[:, 0].copy(), topk_kept=c[:, 1].copy(), cut_value=f[:, 2].copy(), cut_index=c[:, 3].copy(),
                 max=f[:, 4].copy(), z=f[:, 5].copy())
+
+
+# ---- fused token cross-entropy (stage-2 training: hf.py:61-69, mage.py:107-123 / 479-489) ---------------------------------
+
+TOKEN_DTYPES = {torch.int32: _lib.DTYPE_I32, torch.int64: _lib.DTYPE_I64}
+TOKEN_CE_REDUCTIONS = ('mean', 'sum', 'none')
+
+
+def _token_ce_args(what: str, logits, targets, start, end, label_smoothing, ignore_index, weight, shift):
+    """The arguments vqhip_token_ce_fwd and _bwd share, from tensors that are read in place (the logits) or are [R] vectors."""
+    _require_cuda(logits, targets, weight)
+    end = logits.shape[-1] if end is None else end
+    rows, R, stride = _logit_rows(what, logits, start, end)
+    if targets.dtype not in TOKEN_DTYPES or targets.shape != logits.shape[:-1]:
+        raise ValueError(f'{what}: targets must be int32 or int64 of shape {tuple(logits.shape[:-1])}, got {targets.dtype} {tuple(targets.shape)}')
+    if shift and logits.dim() < 2:
+        raise ValueError(f'{what}: shift needs logits [..., L, V_total]')
+    targets = targets.reshape(-1).contiguous()
+    if weight is not None:
+        if weight.numel() != R:
+            raise ValueError(f'{what}: weight must have one value per row ({R}), got {tuple(weight.shape)}')
+        weight = weight.reshape(-1).to(torch.float32).contiguous()
+    head = (_ptr(rows), SAMPLE_DTYPES[logits.dtype], R, stride, int(start), int(end), _ptr(targets), TOKEN_DTYPES[targets.dtype],
+            int(logits.shape[-2]) if shift else 0, int(ignore_index), float(label_smoothing), _ptr(weight))
+    return head, R, (rows, targets, weight)
+
+
+@_on_tensor_device
+def token_ce_forward(logits: torch.Tensor, targets: torch.Tensor, start: int = 0, end: Optional[int] = None, *,
+                     label_smoothing: float = 0.0, ignore_index: int = -100, weight: Optional[torch.Tensor] = None,
+                     shift: bool = False) -> dict:
+    """vqhip_token_ce_fwd of include/vqhip.h on ``logits[..., start:end]`` read in place (the view rules of ``sample_tokens``):
+    fp32 ``loss`` [R], ``lse`` [R], int32 ``hit`` [R] and the device scalars ``out`` [4] = (sum w loss, W, hits, sum / W).  Two
+    launches, no copy of the logits, no synchronisation."""
+    head, R, keep = _token_ce_args('token_ce_forward', logits, targets, start, end, label_smoothing, ignore_index, weight, shift)
+    dev = logits.device
+    loss, lse = torch.empty(R, dtype=torch.float32, device=dev), torch.empty(R, dtype=torch.float32, device=dev)
+    hit, out = torch.empty(R, dtype=torch.int32, device=dev), torch.empty(4, dtype=torch.float32, device=dev)
+    check(_lib.lib().vqhip_token_ce_fwd(*head, _ptr(loss), _ptr(lse), _ptr(hit), _ptr(out), _stream()), 'vqhip_token_ce_fwd')
+    return dict(loss=loss, lse=lse, hit=hit, out=out)
+
+
+@_on_tensor_device
+def token_ce_backward(logits: torch.Tensor, targets: torch.Tensor, lse: torch.Tensor, g: torch.Tensor, start: int = 0,
+                      end: Optional[int] = None, *, label_smoothing: float = 0.0, ignore_index: int = -100,
+                      weight: Optional[torch.Tensor] = None, shift: bool = False, weight_sum: Optional[torch.Tensor] = None,
+                      out: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """vqhip_token_ce_bwd: the gradient over the logits, in their dtype and shape (contiguous), every element written by the
+    kernel (zeros outside the slice and in ignored rows).  ``g``: fp32, one value (sum, mean) or one per row (none);
+    ``weight_sum``: the device scalar W of the forward for the mean, None otherwise.  ``out``: a buffer to write into."""
+    head, R, keep = _token_ce_args('token_ce_backward', logits, targets, start, end, label_smoothing, ignore_index, weight, shift)
+    _require_cuda(lse, g, weight_sum, out)
+    g = g.reshape(-1).to(torch.float32).contiguous()
+    if g.numel() not in (1, R) or lse.dtype != torch.float32 or lse.numel() != R or not lse.is_contiguous():
+        raise ValueError(f'token_ce_backward: g must hold 1 or {R} values and lse {R} contiguous fp32 values')
+    Vt = logits.shape[-1]
+    grad = torch.empty(logits.shape, dtype=logits.dtype, device=logits.device) if out is None else out
+    if grad.shape != logits.shape or grad.dtype != logits.dtype or not grad.is_contiguous():
+        raise ValueError('token_ce_backward: out must be contiguous, of the shape and dtype of the logits')
+    check(_lib.lib().vqhip_token_ce_bwd(*head, _ptr(lse), _ptr(g), 1 if g.numel() == R and R > 1 else 0, _ptr(weight_sum),
+                                        _ptr(grad), Vt, Vt, _stream()), 'vqhip_token_ce_bwd')
+    return grad
+
+
+def token_cross_entropy(logits: torch.Tensor, targets: torch.Tensor, start: int = 0, end: Optional[int] = None, *,
+                        label_smoothing: float = 0.0, ignore_index: int = -100, weight: Optional[torch.Tensor] = None,
+                        shift: bool = False, reduction: str = 'mean', want_stats: bool = False):
+    """Cross-entropy of ``logits[..., start:end]`` against ``targets`` (vocabulary indices, shape ``logits.shape[:-1]``), with
+    autograd: see ``functional.token_cross_entropy``."""
+    from . import functional
+    return functional.token_cross_entropy(logits, targets, start, end, label_smoothing=label_smoothing, ignore_index=ignore_index,
+                                          weight=weight, shift=shift, reduction=reduction, want_stats=want_stats)
 
 
 # ---- pooled code features (the linear probe, vq/tasks/image_classification/models.py:101-109) ----------------------------

@@ -11,6 +11,7 @@ shape, dtype, alignment, the probability buffer, the world size, train / eval). 
     decode_entry  map | tokens
     pooled_entry  pooled | rows
     sampler_why   fused | torch
+    token_ce_why  fused | torch
 """
 from __future__ import annotations
 
@@ -428,3 +429,32 @@ def _flattens(x: torch.Tensor) -> bool:
         return True
     except RuntimeError:
         return False
+
+
+# ---- the token cross-entropy of stage-2 training (vector_quantization_amd/sequence_losses.py) -----------------------------
+
+def token_ce_targets(logits: torch.Tensor, targets: torch.Tensor, shift: bool) -> str:
+    """One int32 / int64 target per row, next to the logits; fewer than 2^31 rows."""
+    if targets.dtype not in ops.TOKEN_DTYPES:
+        return f'the targets are {targets.dtype}, not int32 or int64'
+    if targets.shape != logits.shape[:-1]:
+        return f'the targets are {tuple(targets.shape)}, not {tuple(logits.shape[:-1])} (one per row of the logits)'
+    if targets.device != logits.device:
+        return f'the targets are on device {targets.device}, the logits on {logits.device}'
+    if shift and logits.dim() < 2:
+        return 'shift needs logits [..., L, V_total]'
+    return '' if 0 < targets.numel() < (1 << 31) else f'{targets.numel()} rows are outside 1 .. 2^31-1'
+
+
+def token_ce_why(logits: torch.Tensor, targets: torch.Tensor, start: int = 0, end=None, *, label_smoothing: float = 0.0,
+                 weight=None, shift: bool = False) -> Route:
+    """A stage-2 loss: the fused launches of ``ops.token_cross_entropy`` on the logits as they are (``fused``), or the reference's
+    composition with log_softmax / gather (``torch``), with the first clause that refused the launches."""
+    end = logits.shape[-1] if end is None else end
+    why = ('' if logits.is_cuda else f'the logits are on device {logits.device}, not on a GPU') \
+        or ('' if logits.dim() >= 1 and (logits.stride(-1) == 1 or logits.shape[-1] == 1) else 'the last dimension of the logits does not have stride 1') \
+        or ('' if logits.dtype in ops.SAMPLE_DTYPES else f'the logits are {logits.dtype}, not float32, bfloat16 or float16') \
+        or sampler_rows(logits, start, end) or token_ce_targets(logits, targets, shift) \
+        or ('' if 0.0 <= label_smoothing < 1.0 else f'label_smoothing={label_smoothing!r} is outside [0, 1)') \
+        or ('' if weight is None or weight.numel() == targets.numel() else f'the weights are {tuple(weight.shape)}, not one per row')
+    return Route('torch', why) if why else Route('fused')
