@@ -379,6 +379,64 @@ int vqhip_token_ce_bwd(const void *logits, int dtype, int64_t R, int64_t row_str
                        int g_per_row, const float *wsum /* [1] (the mean) or NULL */, void *grad /* [R, row_stride_out] */,
                        int64_t cols, int64_t row_stride_out, void *stream);
 
+/* ---- fused reconstruction metrics: L1, MSE, PSNR and SSIM of a validation pass ---------------------------------------------
+ * The four numbers of the reference's table per tokenizer (docs/pretrained_models.md:47-51) that come from ImageLossMetric
+ * (vq/runners/metrics/loss.py) over L1Loss, MSELoss, PSNRLoss and SSIMLoss (vq/tasks/image_reconstruction/losses.py), each of
+ * which decodes both images again, and SSIM on the host through scikit-image.  Here: two launches, both images read once, no
+ * image-sized intermediate, no atomics, no memset, no allocation and no synchronisation.
+ * INPUT   pred and image, both [B, C, H, W], each with its own dtype (VQHIP_DTYPE_F32, _BF16, _F16: values in the model's range
+ *   [-1, 1]; VQHIP_DTYPE_U8: bytes already decoded) and its own layout (VQHIP_IMAGE_NCHW contiguous, VQHIP_IMAGE_NHWC
+ *   channels-last dense); element alignment only.
+ * DECODE  vq/datasets/base.py:70-73, `((v + 1) * 127.5).clamp(0, 255).to(uint8)`, literally in the tensor's dtype:
+ *       fp32           t = (v + 1.0f) * 127.5f                                   (two fp32 operations, no contraction)
+ *       bf16 / fp16    t1 = rnd(float(v) + 1.0f);  t = rnd(float(t1) * 127.5f)   (rnd: nearest even into the dtype, as torch)
+ *       byte = (uint8)min(max(t, 0), 255), truncated.  The bytes equal the reference's decode of the same tensor bit for bit.
+ *   A NaN has no defined byte in torch (the cast is undefined there): here it counts as byte 0 in the integer sums, and makes
+ *   all four values of ITS image NaN; other images are untouched.  +-inf decode to 255 / 0 like any value beyond the range.
+ * SUMS    with the bytes p (pred), q (image) and n = C H W, per image:  abs_sum = sum |p - q|,  sq_sum = sum (p - q)^2, int64, exact.
+ * VALUES  l1 = abs_sum / (255 n);  mse = sq_sum / (255^2 n): one IEEE double division each (255 n and 65025 n are exact);
+ *   psnr = -10 log10(mse) in double, +inf where sq_sum == 0.
+ *   ssim: scikit-image's structural_similarity(pred / 255, image / 255, channel_axis=0, data_range=1) with its defaults -
+ *   uniform 7 x 7 window, sample covariance (N / (N - 1), N = 49), K1 = 0.01, K2 = 0.03, a 3-pixel border cropped (every window
+ *   lies inside the image: the filter's boundary mode never matters), mean over the windows of a channel, then over channels -
+ *   evaluated from EXACT integer moments.  Per window, with the sums sx, sy, sxx, syy, sxy of p, q, p^2, q^2, p q (int32):
+ *       ux = sx / (49 * 255)                       uy = sy / (49 * 255)
+ *       vx  = (49 sxx - sx^2)  / (49 * 48 * 255^2)  vy = (49 syy - sy^2) / (49 * 48 * 255^2)
+ *       vxy = (49 sxy - sx sy) / (49 * 48 * 255^2)                        (the numerators are exact integers below 2^28)
+ *       S   = ((2 ux uy + c1) (2 vxy + c2)) / ((ux^2 + uy^2 + c1) (vx + vy + c2))                  in double, no contraction
+ *   c1, c2 are passed by value: the doubles Python gives for (0.01 * 1) ** 2 and (0.03 * 1) ** 2.  Each window adds
+ *   llrint(S 2^40) to an int64; ssim = (double)sum / 2^40 / (C (H - 6) (W - 6)).  The differences that cancel in scikit-image's
+ *   float32 filter are exact here.  An identical pair gives S == 1 in every window (numerator and denominator are the same
+ *   doubles) and ssim == 1.0 exactly.  want_ssim == 0: the ssim column is NaN, nothing of SSIM is computed, any H, W >= 1.
+ * ORDER   every sum over pixels or windows is an integer sum, so no result depends on the order of the additions: not on the
+ *   tile size, the grid, the layout, the other images of the batch, and run to run the same bits.
+ * ERROR BOUND of ssim against the float64 evaluation of the same definition, VQHIP_IMAGE_SSIM_BOUND = 2^-40.  With u = 2^-53:
+ *   ux, uy, vx, vy, vxy carry one rounding each.  The factors of positive terms (2 ux uy + c1, ux^2 + uy^2 + c1, vx + vy + c2)
+ *   carry at most 4 u relative.  2 vxy + c2 may cancel: its absolute error is at most 3 u (|2 vxy| + c2) <= 3 u (vx + vy + c2),
+ *   because |2 vxy| <= vx + vy, which is 3 u relative to the denominator's factor, so it moves S by at most 3 u.  The two
+ *   products and the division add 3 u on |S| <= 1.  |S_kernel - S_exact| <= 14 u (1 + small) < 2^-49; another float64
+ *   evaluation of the definition is as far from S_exact, so two evaluations differ by less than 2^-48.  The rounding to fixed
+ *   point adds 2^-41 per window, and a mean does not exceed its largest term; the conversion of the int64 sum and the two last
+ *   divisions add 3 u.  In all 2^-41 + 2^-48 + 3 u < 2^-40.  A measurement beyond it means the kernel or this derivation is wrong.
+ * WORKSPACE  vqhip_image_metrics_workspace_bytes(B, C, H, W): 32 bytes per workgroup (one per image, channel and T x T tile of
+ *   pixels, T = VQHIP_IMAGE_METRICS_TILE), every byte written before it is read.
+ * OUTPUT  values64 [B, 4] double = l1, mse, psnr, ssim;  values32 [B, 4] float = the same, rounded once;  sums [B, 2] int64 =
+ *   abs_sum, sq_sum.
+ * LIMITS (VQHIP_EINVAL before any HIP call): no null pointer; dtypes and layouts as above; B, C >= 1; 1 <= H, W <= 2^30;
+ *   B * C * ceil(H / T) * ceil(W / T) < 2^31 and C H W < 2^37; with want_ssim: H >= 7 and W >= 7 (scikit-image raises there
+ *   too) and C (H - 6) (W - 6) <= 2^22 (beyond it the fixed-point sum could leave int64); ws_bytes as asked for. */
+#define VQHIP_DTYPE_U8 5      /* images of vqhip_image_metrics only */
+#define VQHIP_IMAGE_NCHW 0
+#define VQHIP_IMAGE_NHWC 1
+#define VQHIP_IMAGE_METRICS_TILE 32
+#define VQHIP_IMAGE_SSIM_MAX_WINDOWS (1ll << 22)
+#define VQHIP_IMAGE_SSIM_BOUND 9.094947017729282e-13   /* 2^-40 */
+int64_t vqhip_image_metrics_workspace_bytes(int64_t B, int64_t C, int64_t H, int64_t W);
+int vqhip_image_metrics(const void *pred, int pred_dtype, int pred_layout, const void *image, int image_dtype, int image_layout,
+                        int64_t B, int64_t C, int64_t H, int64_t W, int want_ssim, double c1, double c2,
+                        void *ws, int64_t ws_bytes, double *values64 /* [B, 4] */, float *values32 /* [B, 4] */,
+                        int64_t *sums /* [B, 2] */, void *stream);
+
 /* ---- EntropyLoss (vq/algorithms/vq/losses.py:130-153) on row blocks of the distance matrix ------------------------------
  * With a = d / T, p = softmax(a, -1), q_k = (1/N) sum_n p_nk:
  *   L = (1/N) sum_n (lse_n - sum_k p_nk a_nk) + sum_k q_k log(q_k + 1e-5)

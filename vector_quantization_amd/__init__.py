@@ -9,6 +9,7 @@ from . import _lib  # noqa: F401
 from .config import BuildPreHookMixin, Config, Registry, RegistryMeta
 from .registries import (AnchorRegistry, InitRegistry, ModelRegistry, VQITQuantizerCallbackRegistry,
                          VQITQuantizerDistanceRegistry, VQITQuantizerLossRegistry, VQITQuantizerRegistry)
+from .image_losses import L1Loss, MSELoss, PSNRLoss, SSIMLoss
 from .sequence_losses import CausalTokenLoss, LabelSmoothingCrossEntropy, MaskedTokenLoss
 from .utils import EMA, ema
 
@@ -16,7 +17,7 @@ __all__ = [
     'BuildPreHookMixin', 'Config', 'Registry', 'RegistryMeta', 'AnchorRegistry', 'InitRegistry', 'ModelRegistry',
     'VQITQuantizerCallbackRegistry', 'VQITQuantizerDistanceRegistry', 'VQITQuantizerLossRegistry',
     'VQITQuantizerRegistry', 'EMA', 'ema', 'build_quantizer', 'CausalTokenLoss', 'LabelSmoothingCrossEntropy',
-    'MaskedTokenLoss',
+    'MaskedTokenLoss', 'L1Loss', 'MSELoss', 'PSNRLoss', 'SSIMLoss',
 ]
 __version__ = '0.1.0'
 

@@ -17,10 +17,16 @@ METRIC_L2, METRIC_COS, METRIC_COS_BF16 = 0, 1, 5
 DTYPE_F32, DTYPE_BF16 = 0, 1
 DTYPE_F16 = 4                              # logits of vqhip_sample_tokens only (2 and 3 are the token dtypes below)
 DTYPE_I32, DTYPE_I64 = 2, 3                # token dtypes of vqhip_fsq_decode
+DTYPE_U8 = 5                               # images of vqhip_image_metrics only
+IMAGE_NCHW, IMAGE_NHWC = 0, 1              # layouts of vqhip_image_metrics
+IMAGE_METRICS_TILE = 32                    # VQHIP_IMAGE_METRICS_TILE: pixels per side of a workgroup's tile
+IMAGE_SSIM_MAX_WINDOWS = 1 << 22           # VQHIP_IMAGE_SSIM_MAX_WINDOWS
+IMAGE_SSIM_BOUND = 2.0 ** -40              # VQHIP_IMAGE_SSIM_BOUND: |kernel ssim - float64 ssim| (derivation in include/vqhip.h)
 LAYOUT_ROWS, LAYOUT_MAP = 0, 1             # [N, C] token-major / NCHW-contiguous map [B, C, H*W]
 FSQ_MAX_C = 16
 
 _vp, _i64, _i32, _f32 = ctypes.c_void_p, ctypes.c_int64, ctypes.c_int, ctypes.c_float
+_f64 = ctypes.c_double
 
 
 class CvqForwardArgs(ctypes.Structure):
@@ -137,6 +143,9 @@ SIGNATURES = {
     'vqhip_token_ce_fwd': (_i32, [_vp, _i32, _i64, _i64, _i64, _i64, _vp, _i32, _i64, _i64, _f32, _vp, _vp, _vp, _vp, _vp, _vp]),
     'vqhip_token_ce_bwd': (_i32, [_vp, _i32, _i64, _i64, _i64, _i64, _vp, _i32, _i64, _i64, _f32, _vp, _vp, _vp, _i32, _vp, _vp,
                                   _i64, _i64, _vp]),
+    'vqhip_image_metrics_workspace_bytes': (_i64, [_i64, _i64, _i64, _i64]),
+    'vqhip_image_metrics': (_i32, [_vp, _i32, _i32, _vp, _i32, _i32, _i64, _i64, _i64, _i64, _i32, _f64, _f64, _vp, _i64, _vp, _vp,
+                                   _vp, _vp]),
     'vqhip_entropy_workspace_bytes': (_i64, [_i64, _i64]),
     'vqhip_entropy_rows': (_i32, [_vp, _i64, _i64, _f32, _vp, _vp, _vp, _i32, _vp, _i64, _vp]),
     'vqhip_entropy_finish': (_i32, [_vp, _vp, _vp, _i64, _i64, _vp, _vp, _vp, _vp]),

@@ -10,6 +10,7 @@
 #include "vqhip_entropy_kernels.h"
 #include "vqhip_sample_kernels.h"
 #include "vqhip_token_ce_kernels.h"
+#include "vqhip_image_metrics_kernels.h"
 
 static thread_local char g_err[256] = "";
 
@@ -1341,6 +1342,66 @@ int vqhip_token_ce_bwd(const void *logits, int dtype, int64_t R, int64_t row_str
     VQ_TOKEN_CE_DISPATCH(launch_token_ce_bwd, a, lse, g, g_per_row ? 1 : 0, wsum, grad, (int)cols, row_stride_out, (hipStream_t)stream);
 }
 #undef VQ_TOKEN_CE_DISPATCH
+
+// ---- fused reconstruction metrics (vqhip_image_metrics_kernels.h) ---------------------------------------------------------
+// what both entry points refuse; on success the number of workgroups of the first launch and the tiles along each axis
+static int image_metrics_grid(const char *what, int64_t B, int64_t C, int64_t H, int64_t W, int64_t *groups, int64_t *tiles_x, int64_t *tiles_y) {
+    if (B < 1 || C < 1 || H < 1 || W < 1 || H > (1ll << 30) || W > (1ll << 30)) return fail(VQHIP_EINVAL, what, "need B, C >= 1 and 1 <= H, W <= 2^30");
+    *tiles_x = (W + VQ_IM_T - 1) / VQ_IM_T;
+    *tiles_y = (H + VQ_IM_T - 1) / VQ_IM_T;
+    const int64_t tiles = *tiles_x * *tiles_y;                                 // below 2^50
+    const int64_t cap = 1ll << 31;
+    if (tiles >= cap || C >= cap || B >= cap || tiles * C >= cap || tiles * C * B >= cap) return fail(VQHIP_EINVAL, what, "B * C * tiles must be below 2^31");
+    // C * H * W <= 1024 * tiles * C < 2^41: no overflow; below 2^37 the divisors 255 n and 65025 n are exact doubles
+    if (C * H * W >= (1ll << 37)) return fail(VQHIP_EINVAL, what, "C * H * W must be below 2^37");
+    *groups = tiles * C * B;
+    return VQHIP_OK;
+}
+
+int64_t vqhip_image_metrics_workspace_bytes(int64_t B, int64_t C, int64_t H, int64_t W) {
+    int64_t groups, tx, ty;
+    if (image_metrics_grid("vqhip_image_metrics_workspace_bytes", B, C, H, W, &groups, &tx, &ty)) return 0;
+    return groups * VQ_IM_SLOT * (int64_t)sizeof(long long);
+}
+
+static int image_metrics_side(const char *what, const void *p, int dtype, int layout, int64_t C, int64_t H, int64_t W, VqImSide *s) {
+    if (!p) return fail(VQHIP_EINVAL, what, "pred and image are required");
+    if (dtype != VQHIP_DTYPE_F32 && dtype != VQHIP_DTYPE_BF16 && dtype != VQHIP_DTYPE_F16 && dtype != VQHIP_DTYPE_U8) return fail(VQHIP_EINVAL, what, "dtype");
+    if (layout != VQHIP_IMAGE_NCHW && layout != VQHIP_IMAGE_NHWC) return fail(VQHIP_EINVAL, what, "layout");
+    s->p = p; s->dtype = dtype; s->sb = C * H * W;
+    if (layout == VQHIP_IMAGE_NCHW) { s->sc = H * W; s->sy = W; s->sx = 1; }
+    else { s->sc = 1; s->sy = W * C; s->sx = C; }
+    return VQHIP_OK;
+}
+
+int vqhip_image_metrics(const void *pred, int pred_dtype, int pred_layout, const void *image, int image_dtype, int image_layout,
+                        int64_t B, int64_t C, int64_t H, int64_t W, int want_ssim, double c1, double c2, void *ws, int64_t ws_bytes,
+                        double *values64, float *values32, int64_t *sums, void *stream) {
+    const char *what = "vqhip_image_metrics";
+    int64_t groups, tiles_x, tiles_y;
+    if (int rc = image_metrics_grid(what, B, C, H, W, &groups, &tiles_x, &tiles_y)) return rc;
+    VqImArgs a;
+    if (int rc = image_metrics_side(what, pred, pred_dtype, pred_layout, C, H, W, &a.a)) return rc;
+    if (int rc = image_metrics_side(what, image, image_dtype, image_layout, C, H, W, &a.b)) return rc;
+    VQ_REQUIRE(ws && values64 && values32 && sums, "vqhip_image_metrics: ws, values64, values32 and sums are required");
+    int64_t windows = 0;
+    if (want_ssim) {
+        VQ_REQUIRE(H >= 7 && W >= 7, "vqhip_image_metrics: SSIM needs H >= 7 and W >= 7 (a 7 x 7 window)");
+        windows = C * (H - 6) * (W - 6);                                       // C, H, W checked above: no overflow
+        VQ_REQUIRE(windows <= VQHIP_IMAGE_SSIM_MAX_WINDOWS, "vqhip_image_metrics: C * (H - 6) * (W - 6) is beyond 2^22 windows");
+        VQ_REQUIRE(c1 > 0.0 && c2 > 0.0, "vqhip_image_metrics: c1 and c2 must be positive");
+    }
+    VQ_NEED("vqhip_image_metrics: ws too small", ws_bytes, groups * VQ_IM_SLOT * (int64_t)sizeof(long long));
+    a.C = (int)C; a.H = (int)H; a.W = (int)W; a.tiles_x = (int)tiles_x; a.tiles_y = (int)tiles_y;
+    a.want_ssim = want_ssim ? 1 : 0; a.c1 = c1; a.c2 = c2;
+    hipStream_t s = (hipStream_t)stream;
+    image_metrics_tile_kernel<<<(unsigned)groups, VQ_IM_THREADS, 0, s>>>(a, (long long *)ws);
+    VQ_CHECK_LAUNCH("image_metrics_tile_kernel");
+    image_metrics_finish_kernel<<<1, VQ_IM_THREADS, 0, s>>>((const long long *)ws, B, groups / B, (double)(C * H * W), (double)windows,
+                                                            a.want_ssim, values64, values32, (long long *)sums);
+    VQ_CHECK_LAUNCH("image_metrics_finish_kernel");
+    return VQHIP_OK;
+}
 
 // ---- EntropyLoss on row blocks of the distance matrix (vqhip_entropy_kernels.h) ----------------------------------------
 static int entropy_check(const char *what, int64_t R, int64_t K, float T) {

@@ -754,6 +754,72 @@ def token_cross_entropy(logits: torch.Tensor, targets: torch.Tensor, start: int 
                                           weight=weight, shift=shift, reduction=reduction, want_stats=want_stats)
 
 
+# ---- fused reconstruction metrics (validation: vq/runners/metrics/loss.py over vq/tasks/image_reconstruction/losses.py) -----
+
+IMAGE_DTYPES = {torch.float32: _lib.DTYPE_F32, torch.bfloat16: _lib.DTYPE_BF16, torch.float16: _lib.DTYPE_F16,
+                torch.uint8: _lib.DTYPE_U8}
+IMAGE_METRIC_COLUMNS = ('l1', 'mse', 'psnr', 'ssim')
+SSIM_C1, SSIM_C2 = (0.01 * 1) ** 2, (0.03 * 1) ** 2           # scikit-image's (K1 * data_range) ** 2, (K2 * data_range) ** 2
+
+
+def image_layout(t: torch.Tensor):
+    """IMAGE_NCHW / IMAGE_NHWC of include/vqhip.h for a dense [B, C, H, W] tensor, None for any other arrangement."""
+    if t.is_contiguous():
+        return _lib.IMAGE_NCHW
+    if t.dim() == 4 and t.is_contiguous(memory_format=torch.channels_last):
+        return _lib.IMAGE_NHWC
+    return None
+
+
+def image_metrics_refusal(pred: torch.Tensor, image: torch.Tensor, ssim: bool = True) -> str:
+    """Why vqhip_image_metrics would refuse this pair ('' if it would not): the clauses of its LIMITS that depend on the tensors."""
+    if pred.dim() != 4 or pred.shape != image.shape:
+        return f'pred and image must both be [B, C, H, W], got {tuple(pred.shape)} and {tuple(image.shape)}'
+    for name, t in (('pred', pred), ('image', image)):
+        if t.dtype not in IMAGE_DTYPES:
+            return f'{name} is {t.dtype}, not float32, bfloat16, float16 or uint8'
+    if pred.numel() == 0:
+        return f'empty images {tuple(pred.shape)}'
+    for name, t in (('pred', pred), ('image', image)):
+        if image_layout(t) is None:
+            return f'{name} with strides {t.stride()} is neither NCHW-contiguous nor channels-last dense'
+    B, C, H, W = pred.shape
+    if ssim and (H < 7 or W < 7):
+        return f'SSIM needs H >= 7 and W >= 7 (a 7 x 7 window), got {H} x {W}'
+    if ssim and C * (H - 6) * (W - 6) > _lib.IMAGE_SSIM_MAX_WINDOWS:
+        return f'C (H - 6) (W - 6) = {C * (H - 6) * (W - 6)} windows are beyond the size cap of 2^22 of the fixed-point SSIM sum'
+    return ''
+
+
+@_on_tensor_device
+def image_metrics(pred: torch.Tensor, image: torch.Tensor, *, ssim: bool = True) -> dict:
+    """vqhip_image_metrics of include/vqhip.h: ``pred`` and ``image`` [B, C, H, W] - fp32 / bf16 / fp16 in the model's range
+    [-1, 1], or uint8 already decoded; NCHW-contiguous or channels-last, each tensor on its own - to one row per image:
+    fp32 ``l1``, ``mse``, ``psnr``, ``ssim`` [B] (columns of ``values32``), float64 ``values64`` [B, 4], int64 ``abs_sum`` and
+    ``sq_sum`` [B].  Two launches, no copy of an image, no synchronisation.  ``ssim=False``: the ssim column is NaN and any
+    H, W >= 1 is taken.  ValueError for what the library refuses."""
+    why = image_metrics_refusal(pred, image, ssim)
+    if why:
+        raise ValueError(f'image_metrics: {why}')
+    _require_cuda(pred, image)
+    B, C, H, W = pred.shape
+    L, dev = _lib.lib(), pred.device
+    ws_bytes = L.vqhip_image_metrics_workspace_bytes(B, C, H, W)
+    ws = torch.empty(max(ws_bytes // 8, 1), dtype=torch.int64, device=dev)
+    values64 = torch.empty(B, 4, dtype=torch.float64, device=dev)
+    values32 = torch.empty(B, 4, dtype=torch.float32, device=dev)
+    sums = torch.empty(B, 2, dtype=torch.int64, device=dev)
+    rc = L.vqhip_image_metrics(_ptr(pred), IMAGE_DTYPES[pred.dtype], image_layout(pred), _ptr(image), IMAGE_DTYPES[image.dtype],
+                               image_layout(image), B, C, H, W, 1 if ssim else 0, SSIM_C1, SSIM_C2, _ptr(ws), ws_bytes,
+                               _ptr(values64), _ptr(values32), _ptr(sums), _stream())
+    if rc == -22:                                                              # VQHIP_EINVAL
+        raise ValueError(f'image_metrics: {L.vqhip_last_error().decode()}')
+    check(rc, 'vqhip_image_metrics')
+    out = {name: values32[:, k] for k, name in enumerate(IMAGE_METRIC_COLUMNS)}
+    out.update(values64=values64, values32=values32, abs_sum=sums[:, 0], sq_sum=sums[:, 1])
+    return out
+
+
 # ---- pooled code features (the linear probe, vq/tasks/image_classification/models.py:101-109) ----------------------------
 
 def _pool_tokens(quant: torch.Tensor, what: str):

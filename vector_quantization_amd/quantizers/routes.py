@@ -12,6 +12,7 @@ shape, dtype, alignment, the probability buffer, the world size, train / eval). 
     pooled_entry  pooled | rows
     sampler_why   fused | torch
     token_ce_why  fused | torch
+    image_metrics_why  fused | torch
 """
 from __future__ import annotations
 
@@ -457,4 +458,24 @@ def token_ce_why(logits: torch.Tensor, targets: torch.Tensor, start: int = 0, en
         or sampler_rows(logits, start, end) or token_ce_targets(logits, targets, shift) \
         or ('' if 0.0 <= label_smoothing < 1.0 else f'label_smoothing={label_smoothing!r} is outside [0, 1)') \
         or ('' if weight is None or weight.numel() == targets.numel() else f'the weights are {tuple(weight.shape)}, not one per row')
+    return Route('torch', why) if why else Route('fused')
+
+
+# ---- the reconstruction metrics of a validation pass (vector_quantization_amd/image_losses.py, runners.ImageLossMetric) -------
+
+def image_metrics_why(pred: torch.Tensor, image: torch.Tensor, *, ssim: bool = True, loss=None) -> Route:
+    """L1 / MSE / PSNR / SSIM of a pair of image batches: the two launches of ``ops.image_metrics`` on the tensors as they are
+    (``fused``), or the reference's composition with torch ops (``torch``), with the first clause that refused the launches:
+    a CPU tensor, float64 (or any dtype the kernel does not decode), a layout that is neither NCHW-contiguous nor channels-last,
+    the size cap of the fixed-point SSIM sum, a ``loss`` that is none of the four plain classes, or one whose class overrides
+    their ``forward``."""
+    from .. import image_losses
+    why = ''
+    if loss is not None and not image_losses.column_of(loss):
+        why = f'{type(loss).__name__} is none of L1Loss, MSELoss, PSNRLoss and SSIMLoss'
+    elif loss is not None and not image_losses.is_plain(loss):
+        why = f'{type(loss).__name__} overrides forward of the plain loss classes'
+    for name, t in (('pred', pred), ('image', image)):
+        why = why or ('' if t.is_cuda else f'{name} is on device {t.device}, not on a GPU')
+    why = why or ops.image_metrics_refusal(pred, image, ssim)
     return Route('torch', why) if why else Route('fused')

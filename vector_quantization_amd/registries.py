@@ -1,6 +1,7 @@
 """Registry hierarchy of the quantizer path, same names as the reference
 (vq/registries.py:18-35, vq/tasks/image_tokenization/registries.py:11-16, .../runners/registries.py:11-16,
-vq/tasks/image_tokenization/models/registries.py,
+vq/tasks/image_tokenization/models/registries.py, vq/models/registries.py:20, vq/tasks/image_reconstruction/registries.py:16,
+vq/runners/registries.py:15,
 .../quantizers/registries.py:9-14, vq/algorithms/vq/distances.py:19-20, vq/algorithms/cvqvae/registries.py:8)."""
 from .config import Registry
 
@@ -55,6 +56,14 @@ class VQITQuantizerLossRegistry(VQITQuantizerRegistry):
     pass
 
 
+class VQLossRegistry(VQRegistry):
+    pass
+
+
+class VQIRLossRegistry(VQModelRegistry, VQLossRegistry):
+    """The losses of image reconstruction (vq/tasks/image_reconstruction/losses.py): image_losses.py."""
+
+
 class VQSMSamplerRegistry(VQModelRegistry):
     """The samplers of stage-2 generation (vq/tasks/sequence_modeling/models/registries.py:21-34).  As there, a ``cfg`` key in a
     sampler's config wraps the built sampler: ``dict(type='TopKTopPSampler', cfg=1.75)`` is ``CFGSampler(sampler=..., alpha=1.75)``
@@ -92,5 +101,9 @@ class VQITCallbackRegistry(VQITRunnerRegistry):
     pass
 
 
-class VQITMetricRegistry(VQITRunnerRegistry):
+class VQMetricRegistry(VQRegistry):
+    """vq/runners/registries.py:15 (there also under todd's MetricRegistry)."""
+
+
+class VQITMetricRegistry(VQITRunnerRegistry, VQMetricRegistry):
     pass

@@ -6,7 +6,9 @@
 * ``LlamaGenTokenizeCallback``  tools/tokenize_llamagen.py:65-103 (there also called TokenizeCallback, registered with
                            ``force=True``) — ten-crop codes / labels as ``{i}.npy``;
 * ``CodebookUsageMetric`` / ``CodebookPPLMetric``   runners/metrics.py:25-73 — bincount per iteration, one all-reduce at
-                           summary time.
+                           summary time;
+* ``ImageLossMetric``      vq/runners/metrics/loss.py:21-37 — L1 / MSE / PSNR / SSIM of ``pred_image`` against ``image``, all
+                           four from one launch pair per batch (``vqhip_image_metrics``).
 
 The reference builds these through todd's runner machinery (dataset / dataloader / strategy / logging builders, ETA,
 checkpoints).  That machinery is control plane and out of scope; what is here is the protocol those four classes live in —
@@ -26,12 +28,14 @@ import torch.distributed as dist
 from torch import nn
 
 from . import ops, tokenization
-from .registries import VQITCallbackRegistry, VQITMetricRegistry, VQITRunnerRegistry
+from . import image_losses
+from .config import BuildPreHookMixin
+from .registries import VQITCallbackRegistry, VQITMetricRegistry, VQITRunnerRegistry, VQLossRegistry, VQMetricRegistry
 from .tokenization import Tokens
 from .utils import get_rank, get_world_size
 
 __all__ = ['Tokenizer', 'TokenizerModel', 'TokenizeCallback', 'LlamaGenTokenizeCallback', 'Tokens', 'CodebookMixin',
-           'CodebookUsageMetric', 'CodebookPPLMetric', 'BaseCallback', 'BaseMetric', 'get_']
+           'CodebookUsageMetric', 'CodebookPPLMetric', 'BaseCallback', 'BaseMetric', 'get_', 'ImageLossMetric', 'ImageRangeMixin']
 
 _STEP = re.compile(r'''\[\s*(?:"([^"]*)"|'([^']*)'|(-?\d+))\s*\]|\.([A-Za-z_]\w*)''')
 
@@ -190,6 +194,121 @@ class CodebookPPLMetric(CodebookMixin):
 
     def _summary(self, memo: dict, counts: torch.Tensor) -> float:
         return float(ops.codebook_metrics(counts)[1].item())
+
+
+# ---- reconstruction metrics ---------------------------------------------------------------------------------------------------
+
+class ImageRangeMixin:
+    """The image range the model sees, [-1, 1], back to bytes: what ``vqhip_image_metrics`` does inside its launch, bit for bit.
+    ``image_range_decode = True`` on a dataset (class or instance) declares its own ``decode`` to be this expression."""
+
+    image_range_decode = True
+
+    @staticmethod
+    def decode(images: torch.Tensor) -> torch.Tensor:
+        return ((images + 1) * 127.5).clamp(0, 255).to(torch.uint8)
+
+
+def _tensor_key(*tensors: torch.Tensor) -> tuple:
+    return tuple((t.data_ptr(), t._version, tuple(t.shape), t.dtype) for t in tensors)
+
+
+@VQMetricRegistry.register_()
+class ImageLossMetric(BuildPreHookMixin, BaseMetric):
+    """vq/runners/metrics/loss.py:21-37: ``loss(dataset.decode(pred_image) / 255, dataset.decode(image) / 255)`` averaged per
+    image, with ``pred_image`` / ``image`` accessor strings into the memo and ``loss`` a config of ``VQIRLossRegistry``.
+
+    When the loss is one of the four plain classes of ``image_losses``, the RAW model-range images go to ``ops.image_metrics``,
+    which decodes them as ``ImageRangeMixin.decode`` does, bit for bit, and yields all four values.  The result is kept in the
+    iteration's memo under ``'image_metrics'``, keyed by the two tensors' ``data_ptr``, ``_version``, shape and dtype, so the
+    four metric entries of the shipped configs cost ONE launch pair per batch.  Every entry holds the tensors it was made
+    from, so an address in a key cannot be handed to another tensor while the memo lives.
+
+    Which decode: without a runner, or with a dataset that has no ``decode``, the kernel's.  A dataset's ``decode`` stands for
+    the kernel's only where that is DECLARED - ``image_range_decode = True`` on the dataset (``ImageRangeMixin`` has it) or as
+    this metric's argument - because a function cannot be compared by what it computes: the reference's own dataset class
+    (vq/datasets/base.py:70-73) is the same expression, but undeclared it is treated like any other and ASKED to decode.
+    Then the dataset's uint8 result goes to the kernel (still fused, one decode of each image and one launch pair per batch
+    for all four metrics: the decoded pair is kept in the memo, keyed by the raw tensors and the decode function), at the
+    price of those two torch decodes.  A loss whose class overrides ``forward``, or is none of the four, runs as written on
+    ``decode(v) / 255`` (route ``torch``, as for CPU tensors); ``last_route`` tells which.
+
+    Per-image values are accumulated on the device in float64; ``summary()`` is their mean over everything THIS rank saw.
+    todd's LossMetric, which owns the reference's accumulation and its cross-rank behaviour, is not in the reference tree and
+    is not rebuilt: no collective is issued here."""
+
+    last_route = None
+
+    def __init__(self, *args, pred_image: str, image: str, loss, image_range_decode: Optional[bool] = None, **kwargs) -> None:
+        super().__init__(*args, **kwargs)
+        self._inputs = dict(pred_image=pred_image, image=image)
+        self._loss = loss
+        self._image_range_decode = image_range_decode
+        self._sum: Any = 0.0
+        self._count = 0
+        self.last: Optional[torch.Tensor] = None                                  # the per-image values of the last batch
+
+    @classmethod
+    def build_pre_hook(cls, config, registry, item):
+        config = super().build_pre_hook(config, registry, item)
+        config.loss = VQLossRegistry.build_or_return(config.loss, reduction='none')
+        return config
+
+    def _decode(self):
+        """(decode, own): the dataset's decode where the runner has one, and whether the kernel's decode stands for it."""
+        dataset = getattr(self._runner, 'dataset', None) if self._runner is not None else None
+        decode = getattr(dataset, 'decode', None)
+        if decode is None:
+            return ImageRangeMixin.decode, True
+        declared = self._image_range_decode
+        return decode, bool(getattr(dataset, 'image_range_decode', False) if declared is None else declared)
+
+    @staticmethod
+    def _decoded(memo: dict, decode, pred: torch.Tensor, image: torch.Tensor):
+        """``decode`` of both images, once per (raw pair, decode function) and memo."""
+        cache = memo.setdefault('image_metrics', {})
+        fn = getattr(decode, '__func__', decode)                                  # (a bound method is a new object per access)
+        key = ('decoded', fn, getattr(decode, '__self__', None)) + _tensor_key(pred, image)
+        if key not in cache:
+            cache[key] = dict(raw=(pred, image), decoded=(decode(pred), decode(image)))
+        return cache[key]['decoded']
+
+    def _forward(self, batch: Mapping, memo: dict):
+        from .quantizers import routes
+        pred, image = (get_(memo, v) for v in self._inputs.values())
+        decode, own = self._decode()
+        column = image_losses.column_of(self._loss)
+        decoded = image_losses.is_plain(self._loss) and not own
+        if decoded:                                                               # the dataset's own bytes go to the kernel
+            pred, image = self._decoded(memo, decode, pred, image)
+        # all four values from one call where SSIM fits; without it where only its clauses refuse and this metric is another
+        ssim = True
+        route = routes.image_metrics_why(pred, image, ssim=True, loss=self._loss)
+        if route.name != 'fused' and column != 'ssim':
+            without = routes.image_metrics_why(pred, image, ssim=False, loss=self._loss)
+            if without.name == 'fused':
+                ssim, route = False, without
+        self.last_route = route
+        if route.name != 'fused':
+            if not decoded:
+                pred, image = decode(pred), decode(image)
+            loss = self._loss(pred / 255, image / 255)
+            return loss.reshape(loss.shape[0], -1).mean(dim=1), memo
+        cache = memo.setdefault('image_metrics', {})
+        key = ('values', ssim) + _tensor_key(pred, image)
+        if key not in cache:
+            cache[key] = dict(inputs=(pred, image), **ops.image_metrics(pred, image, ssim=ssim))
+        return cache[key][column], memo
+
+    def forward(self, batch: Mapping, memo: dict) -> dict:
+        loss, memo = self._forward(batch, memo)
+        self.last = loss
+        self._sum = self._sum + loss.detach().double().sum()
+        self._count += loss.numel()
+        return memo
+
+    def summary(self, memo: dict) -> float:
+        return float(self._sum / self._count) if self._count else 0.
 
 
 # ---- the model the runner drives, and the runner ----------------------------------------------------------------------------
