@@ -379,6 +379,91 @@ int vqhip_token_ce_bwd(const void *logits, int dtype, int64_t R, int64_t row_str
                        int g_per_row, const float *wsum /* [1] (the mean) or NULL */, void *grad /* [R, row_stride_out] */,
                        int64_t cols, int64_t row_stride_out, void *stream);
 
+/* ---- fused CosineEmbeddingLoss of VQ-KD distillation: loss and gradient ---------------------------------------------------
+ * The reconstruction loss of VQ-KD (vq/algorithms/utils/losses.py:13-65, wired as r_loss in configs/vqkd/model.py:62-74 and added
+ * to the quantizer's loss in vq/algorithms/vqkd/base.py:82-92): ATen's cosine_embedding_loss for target +1 - the only branch
+ * the reference reaches - between the decoder's pred_features and the frozen teacher's target_features.  Forward: pred and
+ * target are read ONCE, each in its own dtype, and a second, single-workgroup launch forms the scalars.  Backward: one launch,
+ * one read of each, one write of the gradient.  No fp32 copy, no [R, C] temporary, no workspace, no atomics, no allocation
+ * and no synchronisation.  No gradient is formed for the target.
+ * INPUT   R = B * P rows of C channels.  target [R, C] in `target_dtype`, element stride 1, row stride `target_row_stride` >= C.
+ *   pred in `pred_dtype`, either VQHIP_LAYOUT_ROWS: [R, C], element stride 1, row stride `pred_row_stride` >= C (B and P only
+ *   enter through their product), or VQHIP_LAYOUT_MAP: the NCHW-contiguous map [B, C, P], row r = b P + p, read through the
+ *   channel stride P with no transpose and no copy (`pred_row_stride` is ignored).  dtypes VQHIP_DTYPE_F32, _BF16 or _F16, the
+ *   two may differ; element alignment only.  Every element is converted to fp32 exactly; all arithmetic below is fp32 IEEE
+ *   without contraction, division and square root correctly rounded.
+ * DEFINITION  per row, with e = (float)1e-12, the float constant ATen adds in every dtype (float64 included):
+ *       dot = sum_j p_j t_j      pp = sum_j p_j^2 + e      tt = sum_j t_j^2 + e
+ *       cos = dot / sqrt(pp tt)                   loss_r = 1 - cos
+ *       stats[r] = (1 / sqrt(pp tt), cos, 1 / pp)             (what the backward needs: it does no second reduction)
+ *       out[0] = sum_r loss_r,   out[1] = out[0] / (float)R, a true division on the device
+ *       grad[r, j] = c_r ((cos (1 / pp)) p_j - t_j (1 / sqrt(pp tt)))  =  c_r dloss_r / dp_j,  from the SAVED stats;
+ *       c_r = g (g / (float)R with `mean`, a true division); g = g[r] if g_per_row else g[0].
+ *   The gradient is rounded to nearest even into pred's dtype and written in pred's layout (rows: row stride
+ *   `grad_row_stride` >= C; map: [B, C, P] contiguous, `grad_row_stride` ignored): every element of every row is written (the
+ *   caller does not memset); the columns [C, grad_row_stride) of a strided row are not touched.
+ * ORDER OF EVERY SUM  W = 4 (fp32) or 8 (16-bit) elements per 16 bytes, PW = the larger W of the two operands.
+ *   Rows: ONE WAVE OWNS A ROW.  The row is cut by the index j, not by the address: piece q is elements [PW q, PW q + PW) for
+ *   q < C / PW (one or two 16-byte loads per operand), then C % PW pieces of one element; piece q belongs to lane q % 64, which
+ *   takes its pieces in increasing q and adds element by element, in increasing j, to its three partial sums (from +0; each
+ *   product rounded once); the 64 lanes add as a balanced binary tree in lane order; then + e.
+ *   Map: a workgroup owns 32 consecutive rows times 8 channel groups.  Channels are cut into quads [4 k, 4 k + 4), k < C / 4; quad
+ *   k belongs to group k % 8, which takes its quads in increasing k; a thread keeps four partial triples, triple i for channel
+ *   4 k + i; the C % 4 last channels 4 (C / 4) + i go to group 0's triple i after its quads.  A thread's triples add as
+ *   (a0 + a1) + (a2 + a3), the groups as ((g0 + g1) + (g2 + g3)) + ((g4 + g5) + (g6 + g7)); then + e.
+ *   The scalars: partial j = r mod 256 adds its rows in increasing r, the 256 partials add as a balanced tree in order.
+ *   In each layout a row's outputs are a function of C and the two dtypes alone, the scalars of R and the rows: not of the
+ *   address or alignment of a row (a strided view and its copy give the same bits), not of R or the other rows, and run to run
+ *   the same bits.  The two layouts add in different orders and need not agree bit for bit.
+ * DEGENERATE AND NON-FINITE ROWS  (the pattern the float64 evaluation of the definition gives; a row never affects another
+ *   row's loss, stats or gradient)
+ *       the row holds                            cos     loss    gradient row
+ *       pred all zero, target not                0       1       finite: -c_r t_j / sqrt(e tt)
+ *       target all zero (pred zero or not)       0       1       finite: 0 (both zero: exactly; pred not zero: t_j = 0 and cos = 0)
+ *       a NaN in pred or in target               NaN     NaN     NaN in every element
+ *       a +inf or -inf in pred or in target      NaN     NaN     NaN in every element   (inf / inf, or inf * 0 inside dot)
+ *   A non-finite loss_r reaches out[0] and out[1] as IEEE addition carries it.
+ * ERROR BOUND  against the exact value of the definition on the converted inputs, in units of u = 2^-24, first order, for
+ *   2^-60 <= pp, tt <= 2^60 (no sum or product overflows, pp tt is normal, and the products p_j^2, t_j^2, p_j t_j that fall below
+ *   2^-126 change a sum of at least 2^-60 by less than C 2^-149 / 2^-60 < 2^-73 of it).
+ *   N = VQHIP_COSINE_EMBED_CHAIN(C) = C / 32 + 16 (integer division) bounds, in either layout, the additions one partial sum
+ *   goes through plus one for the rounding of its product: rows C / 64 + 8 + 1 (a lane) + 6 (the tree) + 1; map C / 32 + 1 + 1 (a
+ *   triple) + 5 (the merges) + 1.
+ *     dot: its error is at most N u sum_j |p_j t_j| <= N u |p| |t| (Cauchy-Schwarz), and sqrt(pp tt) >= |p| |t|: N u in cos,
+ *        absolute and free of the inputs' scale.
+ *     pp, tt: positive terms, (N + 1) u relative each (the chain and the addition of e), so (N + 1) u / 2 each
+ *        under the square root; the product pp tt adds 1 / 2, the square root 1, the division 1: on |cos| <= 1 (1 + small).
+ *     loss = fl(1 - cos): one rounding of a value <= 2, absolute: 2 u.  (The cancellation for cos near 1 is absolute, not
+ *        relative: the bound does not shrink with the loss.)
+ *        VQHIP_COSINE_EMBED_BOUND(C) = (2 N + 6) u (1 + 2^-9)  for cos and for loss_r; the last factor covers every second-order
+ *        product (their sum is below 2^-9 for C <= 2^16).
+ *     gradient element in fp32, before the rounding to the output dtype, per unit of |g| (|g| / R for the mean), in units of
+ *        h = 1 / sqrt(pp) <= 1 / |p| (the gradient scales as 1 / |p|; both terms below are at most h in size):
+ *        t_j / sqrt(pp tt): (N + 1) + 1 / 2 + 1 + 1 for the stored reciprocal, + 1 for the product: (N + 5) u h;
+ *        cos p_j / pp: the error of cos, 2 N + 4, on |p_j| / pp <= h; 1 / pp carries (N + 1) + 1, the two products 2: (3 N + 8) u h;
+ *        the subtraction, of a value <= 2 h: 2; the product with c_r: 2; c_r itself for the mean (the conversion of R, the
+ *        division), on 2 h: 4.
+ *        VQHIP_COSINE_EMBED_GRAD_BOUND(C, h) = (4 N + 21) u (1 + 2^-9) h.
+ *     The scalars add (R / 256 + 10) u sum_r |loss_r| to the sum of the rows' errors; out[1] adds 2 u of itself.
+ *   Outside the range nothing is trapped: the fp32 arithmetic of the definition decides, as it does in ATen's fp32 evaluation
+ *   (pp tt = inf gives cos = 0 and loss = 1; pp tt flushed towards 0 loses the relative accuracy of the denominator).
+ *   A measurement beyond these bounds inside the range means the kernel or this derivation is wrong.
+ * LIMITS (VQHIP_EINVAL before any HIP call): pred, target, loss, stats, out (fwd) / pred, target, stats, g, grad (bwd) not null;
+ *   both dtypes one of F32 / BF16 / F16; pred_layout one of ROWS / MAP; B, P >= 1 and R = B P < 2^31; 1 <= C <= 2^16
+ *   (VQHIP_COSINE_EMBED_MAX_C); target_row_stride >= C; rows layout: pred_row_stride >= C and (bwd) grad_row_stride >= C. */
+#define VQHIP_COSINE_EMBED_MAX_C (1 << 16)
+#define VQHIP_COSINE_EMBED_CHAIN(C) ((double)((C) / 32 + 16))
+#define VQHIP_COSINE_EMBED_BOUND(C) ((2.0 * VQHIP_COSINE_EMBED_CHAIN(C) + 6.0) * 5.9604644775390625e-08 * 1.001953125)
+#define VQHIP_COSINE_EMBED_GRAD_BOUND(C, h) \
+    ((4.0 * VQHIP_COSINE_EMBED_CHAIN(C) + 21.0) * 5.9604644775390625e-08 * 1.001953125 * (double)(h))
+int vqhip_cosine_embed_fwd(const void *pred, int pred_dtype, int pred_layout, int64_t pred_row_stride, const void *target,
+                           int target_dtype, int64_t target_row_stride, int64_t B, int64_t P, int64_t C,
+                           float *loss /* [R] */, float *stats /* [R, 3] */, float *out /* [2] */, void *stream);
+int vqhip_cosine_embed_bwd(const void *pred, int pred_dtype, int pred_layout, int64_t pred_row_stride, const void *target,
+                           int target_dtype, int64_t target_row_stride, int64_t B, int64_t P, int64_t C,
+                           const float *stats /* [R, 3] */, const float *g /* [R] or [1] */, int g_per_row, int mean,
+                           void *grad, int64_t grad_row_stride, void *stream);
+
 /* ---- fused reconstruction metrics: L1, MSE, PSNR and SSIM of a validation pass ---------------------------------------------
  * The four numbers of the reference's table per tokenizer (docs/pretrained_models.md:47-51) that come from ImageLossMetric
  * (vq/runners/metrics/loss.py) over L1Loss, MSELoss, PSNRLoss and SSIMLoss (vq/tasks/image_reconstruction/losses.py), each of

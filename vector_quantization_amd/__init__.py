@@ -10,6 +10,7 @@ from .config import BuildPreHookMixin, Config, Registry, RegistryMeta
 from .registries import (AnchorRegistry, InitRegistry, ModelRegistry, VQITQuantizerCallbackRegistry,
                          VQITQuantizerDistanceRegistry, VQITQuantizerLossRegistry, VQITQuantizerRegistry)
 from .image_losses import L1Loss, MSELoss, PSNRLoss, SSIMLoss
+from .distill_losses import CosineEmbeddingLoss
 from .sequence_losses import CausalTokenLoss, LabelSmoothingCrossEntropy, MaskedTokenLoss
 from .utils import EMA, ema
 
@@ -17,7 +18,7 @@ __all__ = [
     'BuildPreHookMixin', 'Config', 'Registry', 'RegistryMeta', 'AnchorRegistry', 'InitRegistry', 'ModelRegistry',
     'VQITQuantizerCallbackRegistry', 'VQITQuantizerDistanceRegistry', 'VQITQuantizerLossRegistry',
     'VQITQuantizerRegistry', 'EMA', 'ema', 'build_quantizer', 'CausalTokenLoss', 'LabelSmoothingCrossEntropy',
-    'MaskedTokenLoss', 'L1Loss', 'MSELoss', 'PSNRLoss', 'SSIMLoss',
+    'MaskedTokenLoss', 'L1Loss', 'MSELoss', 'PSNRLoss', 'SSIMLoss', 'CosineEmbeddingLoss',
 ]
 __version__ = '0.1.0'
 

@@ -108,6 +108,25 @@ def token_ce_grad_bound(V: int, amax: float) -> float:
     return token_ce_lse_bound(V, amax) + (2.0 * amax + 22.0) * 2.0 ** -24
 
 
+COSINE_EMBED_MAX_C = 1 << 16               # VQHIP_COSINE_EMBED_MAX_C
+
+
+def cosine_embed_chain(C: int) -> float:
+    """VQHIP_COSINE_EMBED_CHAIN(C) of include/vqhip.h: the longest chain of fp32 additions of a row's sums, either layout."""
+    return float(C // 32 + 16)
+
+
+def cosine_embed_bound(C: int) -> float:
+    """VQHIP_COSINE_EMBED_BOUND(C): |kernel - exact| of a row's cos and loss of vqhip_cosine_embed_fwd, absolute."""
+    return (2.0 * cosine_embed_chain(C) + 6.0) * 2.0 ** -24 * (1.0 + 2.0 ** -9)
+
+
+def cosine_embed_grad_bound(C: int, h: float) -> float:
+    """VQHIP_COSINE_EMBED_GRAD_BOUND(C, h): a gradient element in fp32, before the rounding to the output dtype, per unit |c_r|;
+    h = 1 / sqrt(|p|^2 + 1e-12)."""
+    return (4.0 * cosine_embed_chain(C) + 21.0) * 2.0 ** -24 * (1.0 + 2.0 ** -9) * h
+
+
 STEP_BEFORE_EXCHANGE, STEP_AFTER_EXCHANGE, STEP_ALL, STEP_PACK_SYNC = 1, 2, 3, 4
 
 # name -> (restype, argtypes); mirrors include/vqhip.h one to one
@@ -143,6 +162,8 @@ SIGNATURES = {
     'vqhip_token_ce_fwd': (_i32, [_vp, _i32, _i64, _i64, _i64, _i64, _vp, _i32, _i64, _i64, _f32, _vp, _vp, _vp, _vp, _vp, _vp]),
     'vqhip_token_ce_bwd': (_i32, [_vp, _i32, _i64, _i64, _i64, _i64, _vp, _i32, _i64, _i64, _f32, _vp, _vp, _vp, _i32, _vp, _vp,
                                   _i64, _i64, _vp]),
+    'vqhip_cosine_embed_fwd': (_i32, [_vp, _i32, _i32, _i64, _vp, _i32, _i64, _i64, _i64, _i64, _vp, _vp, _vp, _vp]),
+    'vqhip_cosine_embed_bwd': (_i32, [_vp, _i32, _i32, _i64, _vp, _i32, _i64, _i64, _i64, _i64, _vp, _vp, _i32, _i32, _vp, _i64, _vp]),
     'vqhip_image_metrics_workspace_bytes': (_i64, [_i64, _i64, _i64, _i64]),
     'vqhip_image_metrics': (_i32, [_vp, _i32, _i32, _vp, _i32, _i32, _i64, _i64, _i64, _i64, _i32, _f64, _f64, _vp, _i64, _vp, _vp,
                                    _vp, _vp]),

@@ -10,6 +10,7 @@
 #include "vqhip_entropy_kernels.h"
 #include "vqhip_sample_kernels.h"
 #include "vqhip_token_ce_kernels.h"
+#include "vqhip_cosine_embed_kernels.h"
 #include "vqhip_image_metrics_kernels.h"
 
 static thread_local char g_err[256] = "";
@@ -517,6 +518,36 @@ static int launch_token_ce_bwd(const VqCeArgs &a, const float *lse, const float 
                                int cols, int64_t row_stride_out, hipStream_t s) {
     token_ce_bwd_kernel<DT, I64><<<(unsigned)a.R, VQ_CE_THREADS, 0, s>>>(a, lse, g, g_per_row, wsum, grad, cols, row_stride_out);
     VQ_CHECK_LAUNCH("token_ce_bwd_kernel");
+    return VQHIP_OK;
+}
+
+// ---- fused CosineEmbeddingLoss: the launches (vqhip_cosine_embed_kernels.h) -----------------------------------------------
+template <int DP, int DT>
+static int launch_cosine_embed_fwd(const VqCoseArgs &a, int layout, float *loss, float *stats, float *out, hipStream_t s) {
+    if (layout == VQHIP_LAYOUT_ROWS) {
+        cosine_embed_rows_fwd_kernel<DP, DT><<<(unsigned)((a.R + VQ_COSE_WAVES - 1) / VQ_COSE_WAVES), VQ_COSE_THREADS, 0, s>>>(a, loss, stats);
+        VQ_CHECK_LAUNCH("cosine_embed_rows_fwd_kernel");
+    } else {
+        cosine_embed_map_fwd_kernel<DP, DT><<<(unsigned)((a.R + VQ_COSE_MAP_POS - 1) / VQ_COSE_MAP_POS), VQ_COSE_THREADS, 0, s>>>(a, loss, stats);
+        VQ_CHECK_LAUNCH("cosine_embed_map_fwd_kernel");
+    }
+    cosine_embed_reduce_kernel<<<1, VQ_COSE_THREADS, 0, s>>>(loss, a.R, out);
+    VQ_CHECK_LAUNCH("cosine_embed_reduce_kernel");
+    return VQHIP_OK;
+}
+
+template <int DP, int DT>
+static int launch_cosine_embed_bwd(const VqCoseArgs &a, int layout, const float *stats, const float *g, int g_per_row, int mean,
+                                   void *grad, int64_t grad_stride, hipStream_t s) {
+    if (layout == VQHIP_LAYOUT_ROWS) {
+        cosine_embed_rows_bwd_kernel<DP, DT><<<(unsigned)((a.R + VQ_COSE_WAVES - 1) / VQ_COSE_WAVES), VQ_COSE_THREADS, 0, s>>>(
+            a, stats, g, g_per_row, mean, grad, grad_stride);
+        VQ_CHECK_LAUNCH("cosine_embed_rows_bwd_kernel");
+    } else {
+        cosine_embed_map_bwd_kernel<DP, DT><<<(unsigned)((a.R + VQ_COSE_MAP_POS - 1) / VQ_COSE_MAP_POS), VQ_COSE_THREADS, 0, s>>>(
+            a, stats, g, g_per_row, mean, grad);
+        VQ_CHECK_LAUNCH("cosine_embed_map_bwd_kernel");
+    }
     return VQHIP_OK;
 }
 
@@ -1342,6 +1373,65 @@ int vqhip_token_ce_bwd(const void *logits, int dtype, int64_t R, int64_t row_str
     VQ_TOKEN_CE_DISPATCH(launch_token_ce_bwd, a, lse, g, g_per_row ? 1 : 0, wsum, grad, (int)cols, row_stride_out, (hipStream_t)stream);
 }
 #undef VQ_TOKEN_CE_DISPATCH
+
+// ---- fused CosineEmbeddingLoss (vqhip_cosine_embed_kernels.h) --------------------------------------------------------------
+// what the two entry points refuse alike, and the arguments the kernels share
+static int cosine_embed_setup(const char *what, const void *pred, int pred_dtype, int pred_layout, int64_t pred_row_stride,
+                              const void *target, int target_dtype, int64_t target_row_stride, int64_t B, int64_t P, int64_t C,
+                              VqCoseArgs *a) {
+    if (!pred || !target) return fail(VQHIP_EINVAL, what, "pred and target are required");
+    for (int dtype : {pred_dtype, target_dtype})
+        if (dtype != VQHIP_DTYPE_F32 && dtype != VQHIP_DTYPE_BF16 && dtype != VQHIP_DTYPE_F16) return fail(VQHIP_EINVAL, what, "dtype");
+    if (pred_layout != VQHIP_LAYOUT_ROWS && pred_layout != VQHIP_LAYOUT_MAP) return fail(VQHIP_EINVAL, what, "pred_layout");
+    const int64_t cap = 1ll << 31;
+    if (B < 1 || P < 1 || B >= cap || P >= cap || B * P >= cap) return fail(VQHIP_EINVAL, what, "R = B * P must be in 1 .. 2^31 - 1");
+    if (C < 1 || C > VQHIP_COSINE_EMBED_MAX_C) return fail(VQHIP_EINVAL, what, "C must be in 1 .. 2^16");
+    if (target_row_stride < C || (pred_layout == VQHIP_LAYOUT_ROWS && pred_row_stride < C))
+        return fail(VQHIP_EINVAL, what, "a row stride is below C");
+    a->pred = pred; a->target = target;
+    a->pred_stride = pred_row_stride; a->target_stride = target_row_stride;
+    a->R = B * P; a->P = P; a->C = (int)C;
+    return VQHIP_OK;
+}
+
+#define VQ_COSE_DISPATCH_T(fn, DP, ...)                                                                                 \
+    switch (target_dtype) {                                                                                             \
+    case VQHIP_DTYPE_F32: return fn<DP, VQHIP_DTYPE_F32>(__VA_ARGS__);                                                  \
+    case VQHIP_DTYPE_BF16: return fn<DP, VQHIP_DTYPE_BF16>(__VA_ARGS__);                                                \
+    default: return fn<DP, VQHIP_DTYPE_F16>(__VA_ARGS__);                                                               \
+    }
+#define VQ_COSE_DISPATCH(fn, ...)                                                                                       \
+    do {                                                                                                                \
+        switch (pred_dtype) {                                                                                           \
+        case VQHIP_DTYPE_F32: VQ_COSE_DISPATCH_T(fn, VQHIP_DTYPE_F32, __VA_ARGS__)                                      \
+        case VQHIP_DTYPE_BF16: VQ_COSE_DISPATCH_T(fn, VQHIP_DTYPE_BF16, __VA_ARGS__)                                    \
+        default: VQ_COSE_DISPATCH_T(fn, VQHIP_DTYPE_F16, __VA_ARGS__)                                                   \
+        }                                                                                                               \
+    } while (0)
+
+int vqhip_cosine_embed_fwd(const void *pred, int pred_dtype, int pred_layout, int64_t pred_row_stride, const void *target,
+                           int target_dtype, int64_t target_row_stride, int64_t B, int64_t P, int64_t C, float *loss, float *stats,
+                           float *out, void *stream) {
+    VqCoseArgs a;
+    if (int rc = cosine_embed_setup("vqhip_cosine_embed_fwd", pred, pred_dtype, pred_layout, pred_row_stride, target, target_dtype,
+                                    target_row_stride, B, P, C, &a)) return rc;
+    VQ_REQUIRE(loss && stats && out, "vqhip_cosine_embed_fwd: loss, stats and out are required");
+    VQ_COSE_DISPATCH(launch_cosine_embed_fwd, a, pred_layout, loss, stats, out, (hipStream_t)stream);
+}
+
+int vqhip_cosine_embed_bwd(const void *pred, int pred_dtype, int pred_layout, int64_t pred_row_stride, const void *target,
+                           int target_dtype, int64_t target_row_stride, int64_t B, int64_t P, int64_t C, const float *stats,
+                           const float *g, int g_per_row, int mean, void *grad, int64_t grad_row_stride, void *stream) {
+    VqCoseArgs a;
+    if (int rc = cosine_embed_setup("vqhip_cosine_embed_bwd", pred, pred_dtype, pred_layout, pred_row_stride, target, target_dtype,
+                                    target_row_stride, B, P, C, &a)) return rc;
+    VQ_REQUIRE(stats && g && grad, "vqhip_cosine_embed_bwd: stats, g and grad are required");
+    VQ_REQUIRE(pred_layout != VQHIP_LAYOUT_ROWS || grad_row_stride >= C, "vqhip_cosine_embed_bwd: the row stride of grad is below C");
+    VQ_COSE_DISPATCH(launch_cosine_embed_bwd, a, pred_layout, stats, g, g_per_row ? 1 : 0, mean ? 1 : 0, grad, grad_row_stride,
+                     (hipStream_t)stream);
+}
+#undef VQ_COSE_DISPATCH
+#undef VQ_COSE_DISPATCH_T
 
 // ---- fused reconstruction metrics (vqhip_image_metrics_kernels.h) ---------------------------------------------------------
 // what both entry points refuse; on success the number of workgroups of the first launch and the tiles along each axis

@@ -344,3 +344,38 @@ def token_cross_entropy(logits: torch.Tensor, targets: torch.Tensor, start: int 
         return value
     shape = logits.shape[:-1]
     return value, dict(lse=lse.view(shape), loss=loss.view(shape), hit=hit.view(shape), weight_sum=out[1], hits=out[2])
+
+
+class _CosineEmbed(Function):
+    """The fused CosineEmbeddingLoss (vqhip_cosine_embed_fwd / _bwd of include/vqhip.h).  Saves ``stats`` and both tensors AS
+    GIVEN (a view stays a view, a bf16 activation stays bf16: no copy); the backward is one launch that writes every element of
+    the gradient.  The target gets no gradient (the teacher is frozen)."""
+
+    @staticmethod
+    def forward(ctx, pred, target, layout, reduction):
+        f = ops.cosine_embedding_forward(pred, target, layout=layout)
+        ctx.save_for_backward(pred, target, f['stats'])
+        ctx.layout, ctx.reduction = layout, reduction
+        if reduction == 'mean':
+            return f['out'][1].clone()
+        if reduction == 'sum':
+            return f['out'][0].clone()
+        return f['loss'].view(pred.shape[:-1] if layout != 'map' else pred.shape[:1] + pred.shape[2:])
+
+    @staticmethod
+    def backward(ctx, g):
+        pred, target, stats = ctx.saved_tensors
+        if not ctx.needs_input_grad[0]:
+            return None, None, None, None
+        grad = ops.cosine_embedding_backward(pred, target, stats, g, layout=ctx.layout, mean=ctx.reduction == 'mean')
+        return grad, None, None, None
+
+
+def cosine_embedding_loss(pred: torch.Tensor, target: torch.Tensor, reduction: str = 'mean', *, layout: Optional[str] = None):
+    """``F.cosine_embedding_loss(pred, target, ones)`` in fp32 from operands of any of the three dtypes, read in place:
+    ``pred`` and ``target`` [..., C] ('rows', the default), or ``pred`` the NCHW-contiguous map [B, C, *positions] against
+    ``target`` [B, *positions, C] ('map').  ``reduction``: 'mean' (divided on the device), 'sum', or 'none' (shaped
+    ``pred.shape[:-1]``; map: [B, *positions]).  The gradient goes to ``pred`` only, in its dtype and layout."""
+    if reduction not in ops.COSINE_REDUCTIONS:
+        raise ValueError(f'cosine_embedding_loss: reduction must be one of {ops.COSINE_REDUCTIONS}, got {reduction!r}')
+    return _CosineEmbed.apply(pred, target.detach(), layout, reduction)

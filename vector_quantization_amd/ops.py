@@ -754,6 +754,129 @@ def token_cross_entropy(logits: torch.Tensor, targets: torch.Tensor, start: int 
                                           weight=weight, shift=shift, reduction=reduction, want_stats=want_stats)
 
 
+# ---- fused CosineEmbeddingLoss (VQ-KD distillation: vq/algorithms/utils/losses.py:13-65) ------------------------------------
+
+COSINE_LAYOUTS = {'rows': _lib.LAYOUT_ROWS, 'map': _lib.LAYOUT_MAP}
+COSINE_REDUCTIONS = ('mean', 'sum', 'none')
+
+
+def _feature_rows(t: torch.Tensor):
+    """``t`` [..., C] as rows [R, C] read in place: (the VIEW, its row stride in elements), or a string that says why not."""
+    if t.dim() < 1 or t.dtype not in SAMPLE_DTYPES:
+        return f'{t.dtype} {tuple(t.shape)} is not float32, bfloat16 or float16 with a channel dimension'
+    C = t.shape[-1]
+    if t.numel() == 0:
+        return f'empty tensor {tuple(t.shape)}'
+    if t.stride(-1) != 1 and C > 1:
+        return 'the last dimension does not have stride 1'
+    try:
+        rows = t if t.dim() == 2 else t.view(-1, C)
+    except RuntimeError:
+        return f'shape {tuple(t.shape)} with strides {t.stride()} does not flatten to rows without a copy'
+    stride = rows.stride(0) if rows.shape[0] > 1 else max(rows.stride(0), C)
+    if stride < C:
+        return f'the rows overlap (row stride {stride} < {C})'
+    return rows, stride
+
+
+def cosine_embedding_refusal(pred: torch.Tensor, target: torch.Tensor, layout: Optional[str] = None) -> str:
+    """Why vqhip_cosine_embed_fwd would refuse this pair ('' if it would not): the clauses of its LIMITS that depend on the
+    tensors' dtypes, shapes and strides.  ``layout``: 'rows' (None: the same) - pred and target both [..., C]; 'map' - pred the
+    NCHW-contiguous [B, C, *positions], target [B, *positions, C] (or [B * P, C])."""
+    layout = layout or 'rows'
+    if layout not in COSINE_LAYOUTS:
+        return f'layout {layout!r} is neither rows nor map'
+    for name, t in (('pred', pred), ('target', target)):
+        if t.dtype not in SAMPLE_DTYPES:
+            return f'{name} is {t.dtype}, not float32, bfloat16 or float16'
+    rows = _feature_rows(target)
+    if isinstance(rows, str):
+        return f'target: {rows}'
+    R, C = rows[0].shape
+    if layout == 'rows':
+        if pred.shape != target.shape:
+            return f'pred {tuple(pred.shape)} and target {tuple(target.shape)} differ in shape'
+        prow = _feature_rows(pred)
+        if isinstance(prow, str):
+            return f'pred: {prow}'
+    else:
+        if pred.dim() < 3 or pred.shape[1] != C or pred.numel() != R * C:
+            return f'pred {tuple(pred.shape)} is not the [B, C, *positions] map of the target rows {tuple(target.shape)}'
+        if not pred.is_contiguous():
+            return f'pred with strides {pred.stride()} is not an NCHW-contiguous map'
+    if not 0 < R < (1 << 31):
+        return f'{R} rows are outside 1 .. 2^31-1'
+    return '' if C <= _lib.COSINE_EMBED_MAX_C else f'C={C} is beyond 2^16'
+
+
+def _cosine_embed_args(what: str, pred, target, layout):
+    """The arguments vqhip_cosine_embed_fwd and _bwd share; both tensors are read in place."""
+    _require_cuda(pred, target)
+    why = cosine_embedding_refusal(pred, target, layout)
+    if why:
+        raise ValueError(f'{what}: {why}')
+    trows, tstride = _feature_rows(target)
+    R, C = trows.shape
+    if (layout or 'rows') == 'rows':
+        prows, pstride = _feature_rows(pred)
+        B, P, code = R, 1, _lib.LAYOUT_ROWS
+    else:
+        prows, pstride = pred, 0
+        B, P, code = pred.shape[0], R // pred.shape[0], _lib.LAYOUT_MAP
+    head = (_ptr(prows), SAMPLE_DTYPES[pred.dtype], code, pstride, _ptr(trows), SAMPLE_DTYPES[target.dtype], tstride, B, P, C)
+    return head, R, C, (prows, trows)
+
+
+@_on_tensor_device
+def cosine_embedding_forward(pred: torch.Tensor, target: torch.Tensor, *, layout: Optional[str] = None) -> dict:
+    """vqhip_cosine_embed_fwd of include/vqhip.h on ``pred`` and ``target`` read in place, each in its own dtype: fp32 ``loss``
+    [R], ``stats`` [R, 3] = (1 / sqrt(pp tt), cos, 1 / pp) and the device scalars ``out`` [2] = (sum, mean).  ``layout``: 'rows'
+    (default; both [..., C], views with unit column stride) or 'map' (``pred`` NCHW-contiguous [B, C, *positions], ``target``
+    [B, *positions, C]).  Two launches, no copy, no synchronisation."""
+    head, R, C, keep = _cosine_embed_args('cosine_embedding_forward', pred, target, layout)
+    dev = pred.device
+    loss = torch.empty(R, dtype=torch.float32, device=dev)
+    stats = torch.empty(R, 3, dtype=torch.float32, device=dev)
+    out = torch.empty(2, dtype=torch.float32, device=dev)
+    check(_lib.lib().vqhip_cosine_embed_fwd(*head, _ptr(loss), _ptr(stats), _ptr(out), _stream()), 'vqhip_cosine_embed_fwd')
+    return dict(loss=loss, stats=stats, out=out)
+
+
+@_on_tensor_device
+def cosine_embedding_backward(pred: torch.Tensor, target: torch.Tensor, stats: torch.Tensor, g: torch.Tensor, *,
+                              layout: Optional[str] = None, mean: bool = False, out: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """vqhip_cosine_embed_bwd: the gradient over ``pred``, in its dtype, shape and layout, every element written by the one
+    launch.  ``g``: fp32, one value (sum, mean) or one per row (none); ``mean``: divide by R on the device.  ``out``: a buffer of
+    pred's shape and dtype to write into - rows layout: any view with unit column stride (the padding of its rows is not
+    touched); map layout: contiguous."""
+    head, R, C, keep = _cosine_embed_args('cosine_embedding_backward', pred, target, layout)
+    _require_cuda(stats, g, out)
+    g = g.reshape(-1).to(torch.float32).contiguous()
+    if g.numel() not in (1, R) or stats.dtype != torch.float32 or stats.shape != (R, 3) or not stats.is_contiguous():
+        raise ValueError(f'cosine_embedding_backward: g must hold 1 or {R} values and stats be contiguous fp32 [{R}, 3]')
+    grad = torch.empty(pred.shape, dtype=pred.dtype, device=pred.device) if out is None else out
+    if grad.shape != pred.shape or grad.dtype != pred.dtype:
+        raise ValueError('cosine_embedding_backward: out must have the shape and dtype of pred')
+    if (layout or 'rows') == 'rows':
+        grows = _feature_rows(grad)
+        if isinstance(grows, str):
+            raise ValueError(f'cosine_embedding_backward: out: {grows}')
+        grows, gstride = grows
+    else:
+        if not grad.is_contiguous():
+            raise ValueError('cosine_embedding_backward: out must be an NCHW-contiguous map')
+        grows, gstride = grad, 0
+    check(_lib.lib().vqhip_cosine_embed_bwd(*head, _ptr(stats), _ptr(g), 1 if g.numel() == R and R > 1 else 0, 1 if mean else 0,
+                                            _ptr(grows), gstride, _stream()), 'vqhip_cosine_embed_bwd')
+    return grad
+
+
+def cosine_embedding_loss(pred: torch.Tensor, target: torch.Tensor, reduction: str = 'mean', *, layout: Optional[str] = None):
+    """1 - cos(pred, target) per row with autograd to ``pred``: see ``functional.cosine_embedding_loss``."""
+    from . import functional
+    return functional.cosine_embedding_loss(pred, target, reduction, layout=layout)
+
+
 # ---- fused reconstruction metrics (validation: vq/runners/metrics/loss.py over vq/tasks/image_reconstruction/losses.py) -----
 
 IMAGE_DTYPES = {torch.float32: _lib.DTYPE_F32, torch.bfloat16: _lib.DTYPE_BF16, torch.float16: _lib.DTYPE_F16,

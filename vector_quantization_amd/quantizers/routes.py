@@ -13,6 +13,7 @@ shape, dtype, alignment, the probability buffer, the world size, train / eval). 
     sampler_why   fused | torch
     token_ce_why  fused | torch
     image_metrics_why  fused | torch
+    cosine_embedding_why  fused | torch
 """
 from __future__ import annotations
 
@@ -478,4 +479,23 @@ def image_metrics_why(pred: torch.Tensor, image: torch.Tensor, *, ssim: bool = T
     for name, t in (('pred', pred), ('image', image)):
         why = why or ('' if t.is_cuda else f'{name} is on device {t.device}, not on a GPU')
     why = why or ops.image_metrics_refusal(pred, image, ssim)
+    return Route('torch', why) if why else Route('fused')
+
+
+# ---- the distillation loss of VQ-KD (vector_quantization_amd/distill_losses.py) -------------------------------------------------
+
+def cosine_embedding_why(pred: torch.Tensor, target: torch.Tensor, *, layout=None, loss=None) -> Route:
+    """CosineEmbeddingLoss between the student's features and the teacher's: the launches of ``ops.cosine_embedding_loss`` on the
+    tensors as they are (``fused``), or the reference's composition around ``F.cosine_embedding_loss`` (``torch``), with the
+    first clause that refused the launches: a CPU tensor, float64 (or any dtype the kernels do not read), a target that requires
+    grad (the kernels form no gradient for it), strides that are neither rows with unit column stride nor an NCHW-contiguous
+    map, or a ``loss`` whose class overrides ``forward`` / ``forward_torch`` of ``CosineEmbeddingLoss``."""
+    from .. import distill_losses
+    why = ''
+    if loss is not None:
+        why = own(loss, distill_losses.CosineEmbeddingLoss, 'forward', 'forward_torch')
+    for name, t in (('pred', pred), ('target', target)):
+        why = why or ('' if t.is_cuda else f'{name} is on device {t.device}, not on a GPU')
+    why = why or ('the target requires grad: the fused backward forms no gradient for it' if target.requires_grad else '') \
+        or ops.cosine_embedding_refusal(pred, target, layout)
     return Route('torch', why) if why else Route('fused')

@@ -142,6 +142,16 @@ def pooled_features(quantizer, x: torch.Tensor, memo: dict):
     return features, quant, memo
 
 
+def distill_loss(loss, pred_map: torch.Tensor, target_rows: torch.Tensor) -> torch.Tensor:
+    """VQ-KD's ``r_loss`` on the decoder's feature map as it is (the distiller's ``Rearrange('b c h w -> b (h w) c')`` in front
+    of ``CosineEmbeddingLoss``, configs/vqkd/model.py:62-74, folded into the kernels): ``pred_map`` [B, C, H, W] NCHW-contiguous
+    against the teacher's ``target_rows`` [B, H * W, C].  A channels-last map already is the rows: it goes through ``loss`` itself.
+    The route and its reason are in ``loss.last_route``."""
+    if pred_map.dim() == 4 and is_token_major(pred_map) and not pred_map.is_contiguous():
+        return loss(pred_map.permute(0, 2, 3, 1).reshape(target_rows.shape), target_rows)
+    return loss.forward_map(pred_map, target_rows)
+
+
 # ---- on-disk token formats ---------------------------------------------------------------------------------------------
 
 class Tokens(TypedDict):
