@@ -137,8 +137,10 @@ int vqhip_argmin(const void *x, int x_dtype, const float *e, const void *cb, int
 int vqhip_argmin_exact(const void *x, int x_dtype, const float *e, int64_t N, int64_t K, int D, int metric,
                        int64_t *idx, float *dmin, int32_t *hist, void *ws, int64_t ws_bytes, void *stream);
 
-/* Materialise d[N,K] fp32 (memo['distance'], quantizers.py:98) for consumers that need the matrix
- * (EntropyLoss losses.py:143, MultinomialAnchor anchors.py:100).  COS: x and e already normalised. */
+/* Materialise d[N,K] fp32 (memo['distance'], quantizers.py:98) — or a row block of it, for a row slice of x: the bits do not
+ * depend on the slice.  No shipped consumer needs the whole matrix any more: EntropyLoss (losses.py:143) and MultinomialAnchor
+ * (anchors.py:100) walk bounded row blocks (vqhip_entropy_*, vqhip_col_multinomial_*); third-party code that touches
+ * memo['distance'] still gets it from here.  COS: x and e already normalised. */
 int vqhip_distance(const void *x, int x_dtype, const float *e, int64_t N, int64_t K, int D, int metric,
                    float *d, void *ws, int64_t ws_bytes, void *stream);
 
@@ -149,6 +151,61 @@ int vqhip_distance(const void *x, int x_dtype, const float *e, int64_t N, int64_
 int64_t vqhip_col_workspace_bytes(int64_t N, int64_t K, int D);
 int vqhip_col_argmin(const void *x, int x_dtype, const float *e, int64_t N, int64_t K, int D, int metric,
                      int64_t *col_idx, void *ws, int64_t ws_bytes, void *stream);
+
+/* ---- fused MultinomialAnchor (vq/algorithms/cvqvae/anchors.py:88-104) on row blocks of the distance matrix -----------------
+ * One latent per code, drawn from the softmax down the code's column of d: what `d.t().softmax(1).multinomial(1)` draws, without
+ * the [N, K] matrix, its transposed softmax, or a sort.  Caller-supplied uniforms, exact fixed-point masses, an inverse-CDF walk
+ * in row order: the draw of vqhip_sample_tokens applied down the columns of a matrix that is never stored.
+ * THE SIGN IS THE REFERENCE'S: it softmaxes +d, so FARTHER latents are likelier.  That is reproduced here, not corrected.
+ * DEFINITION  x [N, D], e [K, D], metric L2 or COS; d[n, k] = the fp32 definition of DESIGN.md §2, the bits vqhip_distance
+ *   writes (COS: both operands already normalised by the caller).  All arithmetic below is fp32 IEEE without contraction unless
+ *   it says otherwise.  For each code k:
+ *       m_k      = max_n d[n, k]
+ *       M[n, k]  = (int64) trunc(expf(fl(d[n, k] - m_k)) * 2^40)      expf at <= 1 ulp; the product is exact (formed in double)
+ *       Z_k      = sum_n M[n, k]                                      an exact integer sum; Z_k >= 2^40 (the maximal row has
+ *                                                                     mass exactly 2^40) and Z_k < 2^61 for N <= 2^20
+ *       T_k      = min(floor((double)u_k * (double)Z_k), Z_k - 1)     u fp32 [K] in [0, 1)  (a NaN or negative u counts as 0)
+ *       col_idx[k] = the first n, in increasing n, whose running sum C_n = sum_{n' <= n} M[n', k] exceeds T_k
+ *   - the inverse-CDF draw multinomial(1) makes on row k of d.t().softmax(1).  C_{N-1} = Z_k > T_k: the crossing always exists.
+ * BAD COLUMNS  a column that holds a NaN or a +inf gets col_idx[k] = -1; nothing is dereferenced out of range and no other
+ *   column is affected.  (A NaN latent row makes every column bad; a NaN codebook row exactly its own.  A distance is never -inf.)
+ * ERROR BOUND  the kernel's cumulative share C_n / Z_k differs from the exact share (float64 exp of the fp32 distances' exact
+ *   differences) by at most
+ *       VQHIP_SAMPLE_DELTA(N) = 2^-18 + N * 2^-39          (4.1e-6 at N = 2^17, 5.7e-6 at N = 2^20)
+ *   Derivation (the sampler's, with V replaced by N): expf(x) 2^40 < 1 for x < -40 ln 2 = -27.7, so a mass that is not truncated
+ *   to 0 has |d - m| < 28.  Its relative error is at most 28 * 2^-24 (the rounded difference, half an ulp of a value below 32,
+ *   carried into the exponent) + 2^-23 (expf) < 1.8e-6 = e; truncation loses less than 2^-40 per row.  A share S / Z of two such
+ *   sums, Z >= 1 in units of 2^40, is then off by at most 2 (e Z + N 2^-40) / (Z (1 - e) - N 2^-40) <= 2^-18 + N 2^-39; the fp64
+ *   product u Z and the conversion of Z add less than 2^-50.  So the picked row j satisfies
+ *       sum_{n < j} s_n / S <= u_k + delta   and   sum_{n <= j} s_n / S >= u_k - delta,   s_n = exp(d[n, k] - m_k) exactly,
+ *   and d[j, k] - m_k >= -28 (a row of zero mass is never picked).  A measurement beyond it means the kernels or this derivation
+ *   are wrong.
+ * INVARIANCE  every sum is an integer sum: the result is a pure function of (x, e, metric, u) - not of block_rows, the grid or
+ *   the run.  No float atomics (no atomics at all), no memset the caller must issue, no allocation, no synchronisation.
+ * THE WALK  the caller owns one dense fp32 [block_rows, K] tile and `ws`, and walks the row blocks b = 0 .. B - 1
+ *   (B = ceil(N / block_rows); block b is rows [r0, r0 + r), r0 = b * block_rows, r = min(block_rows, N - r0)) three times:
+ *       for each block in order:  vqhip_distance(x + r0 rows, .., r, .., tile);  vqhip_col_multinomial_max(tile, r0, ..)
+ *       for each block:           vqhip_distance(..);                            vqhip_col_multinomial_mass(tile, r0, ..)
+ *       vqhip_col_multinomial_pick(u, .., col_idx)
+ *       for each block:           vqhip_distance(..);                            vqhip_col_multinomial_resolve(tile, r0, .., col_idx)
+ *   Each d[n, k] is evaluated at most three times (B = 1: once - the tile stays).  _max takes the blocks in increasing r0 (r0 = 0
+ *   overwrites the running maximum); _mass and _resolve take them in any order.  Everything is sequential on `stream`.
+ * WORKSPACE  vqhip_col_multinomial_workspace_bytes(N, K, block_rows) = 16 K + 8 B K bytes + padding: the running maximum, the
+ *   picked block and residual target per column, and the int64 column masses of every block.  Every byte is written before it
+ *   is read.  Nothing grows with N * K but the caller's tile, whose size is the caller's choice (ops.py: 64 MiB).
+ * LIMITS (VQHIP_EINVAL before any HIP call): no null pointer; 1 <= N <= 2^20 (VQHIP_COL_MULTINOMIAL_MAX_N: keeps Z < 2^61);
+ *   1 <= K < 2^31; 1 <= block_rows <= N; r0 a multiple of block_rows below N; ws_bytes as asked for.  D and the metric are
+ *   vqhip_distance's (any D >= 1; L2 or COS - VQHIP_METRIC_COS_BF16 is the reference's bf16 matrix, not this definition). */
+#define VQHIP_COL_MULTINOMIAL_MAX_N (1ll << 20)
+int64_t vqhip_col_multinomial_workspace_bytes(int64_t N, int64_t K, int64_t block_rows);
+int vqhip_col_multinomial_max(const float *tile, int64_t r0, int64_t N, int64_t K, int64_t block_rows, void *ws, int64_t ws_bytes,
+                              void *stream);
+int vqhip_col_multinomial_mass(const float *tile, int64_t r0, int64_t N, int64_t K, int64_t block_rows, void *ws, int64_t ws_bytes,
+                               void *stream);
+int vqhip_col_multinomial_pick(const float *u /* [K] */, int64_t N, int64_t K, int64_t block_rows, void *ws, int64_t ws_bytes,
+                               int64_t *col_idx /* [K], written: -1 */, void *stream);
+int vqhip_col_multinomial_resolve(const float *tile, int64_t r0, int64_t N, int64_t K, int64_t block_rows, void *ws, int64_t ws_bytes,
+                                  int64_t *col_idx /* [K] */, void *stream);
 
 /* ---- row kernels ------------------------------------------------------------------------------------ */
 /* out[r] = |v_r|^2 in the oracle's order (64 interleaved fma partials + halving tree) */

@@ -88,6 +88,9 @@ def sample_delta(V: int) -> float:
     return 2.0 ** -18 + V * 2.0 ** -39
 
 
+COL_MULTINOMIAL_MAX_N = 1 << 20            # VQHIP_COL_MULTINOMIAL_MAX_N: rows of vqhip_col_multinomial_* (keeps a column's mass below 2^61)
+
+
 def token_ce_chain(n: int) -> float:
     """VQHIP_TOKEN_CE_CHAIN of include/vqhip.h: the longest chain of fp32 additions over n elements (a row) or n rows."""
     return float(n // 256 + 20)
@@ -171,6 +174,11 @@ SIGNATURES = {
     'vqhip_entropy_rows': (_i32, [_vp, _i64, _i64, _f32, _vp, _vp, _vp, _i32, _vp, _i64, _vp]),
     'vqhip_entropy_finish': (_i32, [_vp, _vp, _vp, _i64, _i64, _vp, _vp, _vp, _vp]),
     'vqhip_entropy_grad': (_i32, [_vp, _i64, _i64, _f32, _vp, _vp, _vp, _f32, _vp, _i32, _vp, _vp, _i32, _vp, _i64, _vp]),
+    'vqhip_col_multinomial_workspace_bytes': (_i64, [_i64, _i64, _i64]),
+    'vqhip_col_multinomial_max': (_i32, [_vp, _i64, _i64, _i64, _i64, _vp, _i64, _vp]),
+    'vqhip_col_multinomial_mass': (_i32, [_vp, _i64, _i64, _i64, _i64, _vp, _i64, _vp]),
+    'vqhip_col_multinomial_pick': (_i32, [_vp, _i64, _i64, _i64, _vp, _i64, _vp, _vp]),
+    'vqhip_col_multinomial_resolve': (_i32, [_vp, _i64, _i64, _i64, _i64, _vp, _i64, _vp, _vp]),
     'vqhip_scatter_add_rows': (_i32, [_vp, _vp, _i64, _i64, _i32, _vp, _vp]),
     'vqhip_vqkd_update': (_i32, [_vp, _vp, _vp, _i64, _i32, _f32, _i32, _vp]),
     'vqhip_cvq_update': (_i32, [_vp, _vp, _vp, _i64, _vp, _vp, _i64, _i32, _f32, _f32, _i32, _vp]),

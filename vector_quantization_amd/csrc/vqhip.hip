@@ -8,6 +8,7 @@
 #include "vqhip_kernels.h"
 #include "vqhip_fsq_kernels.h"
 #include "vqhip_entropy_kernels.h"
+#include "vqhip_col_multinomial_kernels.h"
 #include "vqhip_sample_kernels.h"
 #include "vqhip_token_ce_kernels.h"
 #include "vqhip_cosine_embed_kernels.h"
@@ -1571,6 +1572,102 @@ int vqhip_entropy_grad(float *tile, int64_t R, int64_t K, float temperature, con
     VQ_CHECK_LAUNCH("entropy_grad_kernel");
     if (!l2) return VQHIP_OK;
     return entropy_colsums(1, tile, R, K, temperature, lse, colacc, init, ws, s);
+}
+
+// ---- fused MultinomialAnchor on row blocks of the distance matrix (vqhip_col_multinomial_kernels.h) -----------------------
+struct VqColMultiWs {
+    float *colmax;       // [K] running column maximum; NaN = bad column
+    int32_t *sel;        // [K] the block that holds the column's crossing, -1 = none
+    cm_u64 *resid;       // [K] the target inside that block
+    cm_u64 *mass;        // [blocks, K] column masses per block
+    int64_t blocks, total;
+};
+
+// what every entry point refuses, and the carve of `ws` (ws may be null: sizes only)
+static int col_multinomial_setup(const char *what, int64_t N, int64_t K, int64_t R, void *ws, VqColMultiWs *w) {
+    if (N < 1 || N > VQHIP_COL_MULTINOMIAL_MAX_N) return fail(VQHIP_EINVAL, what, "N must be in 1 .. 2^20");
+    if (K < 1 || K >= (1ll << 31)) return fail(VQHIP_EINVAL, what, "K must be in 1 .. 2^31 - 1");
+    if (R < 1 || R > N) return fail(VQHIP_EINVAL, what, "block_rows must be in 1 .. N");
+    auto up = [](int64_t b) { return (b + 255) / 256 * 256; };
+    char *c = (char *)ws;
+    w->blocks = (N + R - 1) / R;                                                 // <= 2^20: blocks * K * 8 < 2^54
+    int64_t off = 0;
+    w->colmax = (float *)(c + off); off += up(K * 4);
+    w->sel = (int32_t *)(c + off); off += up(K * 4);
+    w->resid = (cm_u64 *)(c + off); off += up(K * 8);
+    w->mass = (cm_u64 *)(c + off); off += up(w->blocks * K * 8);
+    w->total = off;
+    return VQHIP_OK;
+}
+
+int64_t vqhip_col_multinomial_workspace_bytes(int64_t N, int64_t K, int64_t block_rows) {
+    VqColMultiWs w;
+    if (col_multinomial_setup("vqhip_col_multinomial_workspace_bytes", N, K, block_rows, nullptr, &w)) return 0;
+    return w.total;
+}
+
+// the checks of a call that takes a block: rows [r0, r0 + *r) with *r = min(block_rows, N - r0)
+static int col_multinomial_block(const char *what, const float *tile, int64_t r0, int64_t N, int64_t K, int64_t R, void *ws,
+                                 int64_t ws_bytes, VqColMultiWs *w, int64_t *r) {
+    if (int rc = col_multinomial_setup(what, N, K, R, ws, w)) return rc;
+    if (!tile || !ws) return fail(VQHIP_EINVAL, what, "null pointer");
+    if (r0 < 0 || r0 >= N || r0 % R != 0) return fail(VQHIP_EINVAL, what, "r0 must be a multiple of block_rows below N");
+    if (ws_bytes < w->total) {
+        char msg[160];
+        snprintf(msg, sizeof(msg), "ws too small: %lld bytes given, %lld needed", (long long)ws_bytes, (long long)w->total);
+        return fail(VQHIP_EINVAL, what, msg);
+    }
+    *r = N - r0 < R ? N - r0 : R;
+    return VQHIP_OK;
+}
+
+int vqhip_col_multinomial_max(const float *tile, int64_t r0, int64_t N, int64_t K, int64_t block_rows, void *ws, int64_t ws_bytes,
+                              void *stream) {
+    VqColMultiWs w;
+    int64_t r;
+    if (int rc = col_multinomial_block("vqhip_col_multinomial_max", tile, r0, N, K, block_rows, ws, ws_bytes, &w, &r)) return rc;
+    const unsigned grid = (unsigned)((K + VQ_CM_COLS - 1) / VQ_CM_COLS);
+    col_multinomial_max_kernel<<<grid, VQ_CM_COLS * VQ_CM_WAVES, 0, (hipStream_t)stream>>>(tile, (int)r, K, w.colmax, r0 == 0 ? 1 : 0);
+    VQ_CHECK_LAUNCH("col_multinomial_max_kernel");
+    return VQHIP_OK;
+}
+
+int vqhip_col_multinomial_mass(const float *tile, int64_t r0, int64_t N, int64_t K, int64_t block_rows, void *ws, int64_t ws_bytes,
+                               void *stream) {
+    VqColMultiWs w;
+    int64_t r;
+    if (int rc = col_multinomial_block("vqhip_col_multinomial_mass", tile, r0, N, K, block_rows, ws, ws_bytes, &w, &r)) return rc;
+    const unsigned grid = (unsigned)((K + VQ_CM_COLS - 1) / VQ_CM_COLS);
+    col_multinomial_mass_kernel<<<grid, VQ_CM_COLS * VQ_CM_WAVES, 0, (hipStream_t)stream>>>(tile, (int)r, K, w.colmax,
+                                                                                           w.mass + (r0 / block_rows) * K);
+    VQ_CHECK_LAUNCH("col_multinomial_mass_kernel");
+    return VQHIP_OK;
+}
+
+int vqhip_col_multinomial_pick(const float *u, int64_t N, int64_t K, int64_t block_rows, void *ws, int64_t ws_bytes, int64_t *col_idx,
+                               void *stream) {
+    const char *what = "vqhip_col_multinomial_pick";
+    VqColMultiWs w;
+    if (int rc = col_multinomial_setup(what, N, K, block_rows, ws, &w)) return rc;
+    if (!u || !ws || !col_idx) return fail(VQHIP_EINVAL, what, "null pointer");
+    VQ_NEED("vqhip_col_multinomial_pick: ws too small", ws_bytes, w.total);
+    col_multinomial_pick_kernel<<<(unsigned)((K + 255) / 256), 256, 0, (hipStream_t)stream>>>(w.mass, (int)w.blocks, K, w.colmax, u, w.sel,
+                                                                                              w.resid, col_idx);
+    VQ_CHECK_LAUNCH("col_multinomial_pick_kernel");
+    return VQHIP_OK;
+}
+
+int vqhip_col_multinomial_resolve(const float *tile, int64_t r0, int64_t N, int64_t K, int64_t block_rows, void *ws, int64_t ws_bytes,
+                                  int64_t *col_idx, void *stream) {
+    const char *what = "vqhip_col_multinomial_resolve";
+    VqColMultiWs w;
+    int64_t r;
+    if (int rc = col_multinomial_block(what, tile, r0, N, K, block_rows, ws, ws_bytes, &w, &r)) return rc;
+    if (!col_idx) return fail(VQHIP_EINVAL, what, "null pointer");
+    col_multinomial_resolve_kernel<<<(unsigned)((K + 63) / 64), 64, 0, (hipStream_t)stream>>>(tile, (int)r, K, (int)(r0 / block_rows), r0,
+                                                                                              w.colmax, w.sel, w.resid, col_idx);
+    VQ_CHECK_LAUNCH("col_multinomial_resolve_kernel");
+    return VQHIP_OK;
 }
 
 int vqhip_scatter_add_rows(const float *src, const int64_t *idx, int64_t N, int64_t K, int D, float *dst, void *stream) {

@@ -375,6 +375,74 @@ def entropy_loss_backward(x: torch.Tensor, e: torch.Tensor, metric, temperature:
     return gx, ge
 
 
+COL_MULTINOMIAL_MAX_N = _lib.COL_MULTINOMIAL_MAX_N     # rows of col_multinomial: a column's 2^40 fixed-point mass stays below 2^61
+
+
+def _col_multinomial_args(x, e, metric, u, block_rows):
+    """(The checks of shape, dtype and size come first and need no device: a wrong call says what is wrong on any machine.)"""
+    m = METRICS[metric]
+    if m not in (METRIC_L2, METRIC_COS):
+        raise ValueError(f"col_multinomial: metric must be 'L2' or 'Cosine', got {metric!r}")
+    x, _ = _latents(x)
+    e = _codebook(e)
+    N, D = x.shape
+    K = e.shape[0]
+    if D != e.shape[1]:
+        raise ValueError(f'latent dim {D} != codebook dim {e.shape[1]}')
+    if N < 1 or K < 1:
+        raise ValueError('col_multinomial needs N >= 1 and K >= 1')
+    if N > COL_MULTINOMIAL_MAX_N:
+        raise ValueError(f'col_multinomial: N={N} is beyond 2^20 rows')
+    if not isinstance(u, torch.Tensor) or u.dtype != torch.float32 or tuple(u.shape) != (K,):
+        got = f'{u.dtype} {tuple(u.shape)}' if isinstance(u, torch.Tensor) else type(u).__name__
+        raise ValueError(f'col_multinomial: u must be float32 [{K}] (one uniform in [0, 1) per code), got {got}')
+    if u.device != x.device:
+        raise ValueError(f'col_multinomial: u is on device {u.device}, the latents on {x.device}')
+    R = entropy_block_rows(N, K) if block_rows is None else int(block_rows)
+    if R < 1:
+        raise ValueError(f'col_multinomial: block_rows must be >= 1, got {block_rows!r}')
+    _require_cuda(x, e, u)
+    return x, e, m, u.contiguous(), N, K, D, min(R, N)
+
+
+@_on_tensor_device
+def col_multinomial(x: torch.Tensor, e: torch.Tensor, metric='L2', *, u: torch.Tensor, block_rows: Optional[int] = None) -> torch.Tensor:
+    """MultinomialAnchor indices (vq/algorithms/cvqvae/anchors.py:100) without the [N, K] matrix: for every code k one row n drawn
+    with probability softmax_n(+d[n, k]) — the reference's sign: farther latents are likelier — by the inverse-CDF walk of
+    include/vqhip.h (vqhip_col_multinomial_*) on the uniforms ``u`` fp32 [K] in [0, 1).  The rows go through one
+    [block_rows, K] fp32 tile (default: what fits ``ENTROPY_TILE_BYTES``, as ``entropy_loss``) that ``distance`` fills: once when
+    the matrix fits one tile, three times otherwise.  x, e normalised by the caller for cosine.  Returns int64 [K]; -1 for a
+    code whose column holds a NaN or a +inf.  A pure function of (x, e, metric, u): not of block_rows or the run."""
+    x, e, m, u, N, K, D, R = _col_multinomial_args(x, e, metric, u, block_rows)
+    L = _lib.lib()
+    dev = x.device
+    tile = _bytes(R * K * 4, dev)[:R * K * 4].view(torch.float32)
+    ws = _bytes(L.vqhip_col_multinomial_workspace_bytes(N, K, R), dev)
+    col_idx = torch.empty(K, dtype=torch.int64, device=dev)
+    blocks = range(0, N, R)
+    single = len(blocks) == 1                    # the tile stays: one evaluation of the distances serves all three passes
+
+    def fill(r0):
+        r = min(R, N - r0)
+        t = tile[:r * K].view(r, K)
+        distance(x[r0:r0 + r], e, m, out=t)
+        return t
+
+    t = None
+    for r0 in blocks:
+        t = fill(r0)
+        check(L.vqhip_col_multinomial_max(_ptr(t), r0, N, K, R, _ptr(ws), ws.numel(), _stream()), 'vqhip_col_multinomial_max')
+    for r0 in blocks:
+        t = t if single else fill(r0)
+        check(L.vqhip_col_multinomial_mass(_ptr(t), r0, N, K, R, _ptr(ws), ws.numel(), _stream()), 'vqhip_col_multinomial_mass')
+    check(L.vqhip_col_multinomial_pick(_ptr(u), N, K, R, _ptr(ws), ws.numel(), _ptr(col_idx), _stream()), 'vqhip_col_multinomial_pick')
+    for r0 in blocks:
+        t = t if single else fill(r0)
+        check(L.vqhip_col_multinomial_resolve(_ptr(t), r0, N, K, R, _ptr(ws), ws.numel(), _ptr(col_idx), _stream()),
+              'vqhip_col_multinomial_resolve')
+    return col_idx
+
+
 @_on_tensor_device
 def col_argmin(x: torch.Tensor, e: torch.Tensor, metric='L2') -> torch.Tensor:
     """NearestAnchor indices: for every code the nearest token (lowest token on ties)."""

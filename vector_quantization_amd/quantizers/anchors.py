@@ -68,16 +68,52 @@ class NearestAnchor(BaseAnchor):
 
 @AnchorRegistry.register_()
 class MultinomialAnchor(BaseAnchor):
-    """One latent per code drawn from softmax over the code's column of distances (anchors.py:88-104).  Needs the
-    materialised matrix (HIP distance kernel); the draw uses the device generator.  No shipped config uses it."""
+    """One latent per code drawn from softmax over the code's column of distances (anchors.py:88-104; the reference softmaxes +d:
+    farther latents are likelier, reproduced here).  No shipped config uses it.
+
+    Fused route: while ``d`` is an unmaterialised ``LazyDistance`` of metric 'L2' or 'Cosine' on a GPU, ``u = torch.rand(K)`` is
+    ONE draw from the device generator and the indices come from ``d.multinomial(u)`` — HIP kernels on one bounded [R, K]
+    row-block tile (64 MiB by default), an inverse-CDF walk down each column on exact fixed-point masses (include/vqhip.h,
+    vqhip_col_multinomial_*); the matrix, its transposed softmax and the [K, N] multinomial are never formed and the handle stays
+    unmaterialised.  With ``sync=True`` on several ranks rank 0's ``u`` is broadcast, so every rank draws the same
+    rows of the gathered latents by construction (the reference relies on equal seeds for its ``is_sync`` assert).
+    Matrix route (the reference's composition, literally): ``probabilities(d).multinomial(1)`` on the materialised matrix.
+    ``routes.multinomial_anchor_why`` decides and says why; ``last_route`` holds the decision of the last call.
+
+    Stated differences of the fused route: (1) a seeded run picks DIFFERENT rows than the matrix route — it consumes K uniforms
+    where ``multinomial`` consumes its own stream; the distribution is the same (to VQHIP_SAMPLE_DELTA(N) per cumulative share);
+    (2) a code whose column holds a NaN or a +inf keeps its own ``e[k]`` as its anchor, so the update leaves it where it is —
+    the reference's multinomial raises a device assert there.
+
+    ``fused`` (extension; configs need not name it): None (default) — the fused route wherever it applies; False — always
+    the matrix route."""
+
+    def __init__(self, *args, fused: bool | None = None, **kwargs) -> None:
+        super().__init__(*args, **kwargs)
+        if fused not in (None, False):
+            raise ValueError(f'MultinomialAnchor: fused must be None (auto) or False, got {fused!r}')
+        self._fused = fused
+        self.last_route = None
 
     @staticmethod
     def probabilities(d) -> torch.Tensor:
         return as_distance_tensor(d).detach().t().softmax(1)             # [K, N]
 
+    def _uniforms(self, K: int, device) -> torch.Tensor:
+        u = torch.rand(K, device=device)
+        if self._sync and get_world_size() > 1:
+            dist.broadcast(u, 0)
+        return u
+
     def _anchors(self, x, e, d, quant, p, memo: Memo):
-        indices = self.probabilities(d).multinomial(1).reshape(-1)
-        return ops.gather_rows(x, indices), memo
+        from . import routes
+        self.last_route = routes.multinomial_anchor_why(self, d, x)
+        if self.last_route.name != 'fused':
+            indices = self.probabilities(d).multinomial(1).reshape(-1)
+            return ops.gather_rows(x, indices), memo
+        indices = d.multinomial(self._uniforms(e.shape[0], x.device))
+        anchors = ops.gather_rows(x, indices.clamp_min(0))
+        return torch.where((indices < 0).unsqueeze(1), e.detach().to(anchors.dtype), anchors), memo
 
 
 @AnchorRegistry.register_()

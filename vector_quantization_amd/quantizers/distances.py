@@ -129,13 +129,24 @@ class LazyDistance(torch.Tensor):
         materialising it: ``_EntropyMatrix`` on the handle's operands and metric ('L2' and 'Cosine')."""
         return self._distance.entropy(self._x, self._e, temperature, self._metric, block_rows)
 
+    def exact_operands(self):
+        """(latents, codebook) as the fp32 definition consumes them (normalised for cosine): the encode's own where it left
+        them, computed otherwise — the operands of every column pass over this matrix."""
+        if self._xq is not None:
+            eq = self._eq if self._eq is not None else self._distance.exact_codebook(self._e, self._metric)
+            return self._xq, eq
+        return self._distance.exact_operands(self._x, self._e, self._metric)
+
+    def multinomial(self, u: torch.Tensor, block_rows: Optional[int] = None) -> torch.Tensor:
+        """MultinomialAnchor's indices, int64 [K]: for every code one row drawn from softmax(+d) down its column by the uniforms
+        ``u`` fp32 [K], without materialising the matrix (``BaseDistance.col_multinomial`` on the operands ``fused_argmin(0)``
+        uses; 'L2' and 'Cosine'); -1 for a code whose column holds a NaN or a +inf."""
+        xq, eq = self.exact_operands()
+        return self._distance.col_multinomial(xq, eq, u, self._metric, block_rows)
+
     def fused_argmin(self, dim: int) -> torch.Tensor:
         if dim == 0:        # NearestAnchor: d.argmin(0) — nearest latent per code
-            if self._xq is not None:
-                xq = self._xq
-                eq = self._eq if self._eq is not None else self._distance.exact_codebook(self._e, self._metric)
-            else:
-                xq, eq = self._distance.exact_operands(self._x, self._e, self._metric)
+            xq, eq = self.exact_operands()
             return ops.col_argmin(xq, eq, self._metric)
         if self._metric == self._distance.metric:
             return self._distance.argmin(self._x, self._e)
@@ -212,6 +223,15 @@ class BaseDistance(nn.Module, ABC):
         if metric == 'Cosine':
             x, e = VF.normalize(x), VF.normalize(e)
         return _EntropyMatrix.apply(x, e, metric, temperature, block_rows)
+
+    def col_multinomial(self, xq: torch.Tensor, eq: torch.Tensor, u: torch.Tensor, metric: Optional[str] = None,
+                        block_rows: Optional[int] = None) -> torch.Tensor:
+        """One row per code drawn down the columns of ``matrix`` from one bounded row-block tile (``ops.col_multinomial``);
+        ``xq``, ``eq``: the operands of the fp32 definition (``exact_operands``)."""
+        metric = metric or self.metric
+        if metric not in self.FUSED_ENTROPY_METRICS:
+            raise ValueError(f'the fused MultinomialAnchor exists for {self.FUSED_ENTROPY_METRICS}, not for {metric!r}')
+        return ops.col_multinomial(xq.reshape(-1, xq.shape[-1]), eq, metric, u=u, block_rows=block_rows)
 
     def metric_for(self, D: int) -> str:
         """The metric of a fused encode over D-dimensional rows (``metric``, unless a distance narrows it by D)."""

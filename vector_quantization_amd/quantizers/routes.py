@@ -14,6 +14,7 @@ shape, dtype, alignment, the probability buffer, the world size, train / eval). 
     token_ce_why  fused | torch
     image_metrics_why  fused | torch
     cosine_embedding_why  fused | torch
+    multinomial_anchor_why  fused | matrix
 """
 from __future__ import annotations
 
@@ -26,7 +27,7 @@ from ..utils import exchanging, get_world_size
 # (the three modules, not names out of them: each of them imports this module the same way, so neither side of the cycle reads an
 #  attribute of the other before a call, and any of the four may be imported first)
 from . import callbacks as _cb, scalar_quantizer as _sq, vector_quantizer as _vq
-from .anchors import NearestAnchor
+from .anchors import MultinomialAnchor, NearestAnchor
 from .distances import CosineDistance, L2Distance, LazyDistance
 from .losses import CodebookLoss, CommitmentLoss, VQGANLoss
 from .memo import get_memo
@@ -499,3 +500,30 @@ def cosine_embedding_why(pred: torch.Tensor, target: torch.Tensor, *, layout=Non
     why = why or ('the target requires grad: the fused backward forms no gradient for it' if target.requires_grad else '') \
         or ops.cosine_embedding_refusal(pred, target, layout)
     return Route('torch', why) if why else Route('fused')
+
+
+# ---- MultinomialAnchor of a CVQ-VAE update (vector_quantization_amd/quantizers/anchors.py) ----------------------------------------
+
+def multinomial_anchor_why(anchor, d, x: torch.Tensor) -> Route:
+    """One latent per code drawn down the columns of the distances: ``LazyDistance.multinomial`` on bounded row blocks, the
+    [N, K] matrix never formed (``fused``), or the reference's ``d.t().softmax(1).multinomial(1)`` on the materialised matrix
+    (``matrix``), with the first clause that refused the fused route: ``fused=False``, a subclass that overrides ``_anchors`` or
+    ``probabilities``, CPU tensors, a plain tensor or an already materialised handle (the caller paid for the matrix), a metric
+    whose matrix is not the fp32 definition (the bf16-autocast cosine: the reference's matrix is bf16 there), float64 latents,
+    or more rows than the fixed-point column sums hold.  No size threshold ships: where the whole matrix fits one tile - the only
+    place one could apply - the fused route was measured faster than the matrix route (profiles/col_multinomial.txt, DESIGN.md
+    §8); beyond one tile it trades time (three evaluations of the distances) for memory that does not grow with N * K."""
+    why = ('' if anchor._fused is None else 'fused=False') or own(anchor, MultinomialAnchor, '_anchors', 'probabilities') \
+        or ('' if x.is_cuda else f'the latents are on device {x.device}, not on a GPU') \
+        or ('' if isinstance(d, LazyDistance) else 'memo distance is a matrix, not the lazy handle of the fused encode: it is paid for')
+    if why:
+        return Route('matrix', why)
+    why = ('the handle is already materialised: the matrix is paid for' if d._value is not None else '') \
+        or ('' if d.is_cuda else f'the distances are on device {d.device}, not on a GPU') \
+        or ('' if d.metric in d._distance.FUSED_ENTROPY_METRICS else
+            f'metric {d.metric!r}: the reference\'s matrix is not the fp32 definition there'
+            if d.metric == 'CosineBF16' else f'{type(d._distance).__name__} has no fused column draw for metric {d.metric!r}') \
+        or ('' if x.dtype != torch.float64 and d.operands[0].dtype != torch.float64 else 'the latents are float64') \
+        or ('' if 0 < d.shape[0] <= ops.COL_MULTINOMIAL_MAX_N else f'N={d.shape[0]} is outside 1 .. 2^20') \
+        or ('' if d.dim() == 2 and x.dim() == 2 and x.shape[0] == d.shape[0] else 'the latents are not the [N, D] rows of the distances')
+    return Route('matrix', why) if why else Route('fused')
