@@ -521,6 +521,99 @@ int vqhip_cosine_embed_bwd(const void *pred, int pred_dtype, int pred_layout, in
                            const float *stats /* [R, 3] */, const float *g /* [R] or [1] */, int g_per_row, int mean,
                            void *grad, int64_t grad_row_stride, void *stream);
 
+/* ---- fused LPIPS tail: feature distance of one VGG16 layer, value and gradient ---------------------------------------------
+ * The perceptual loss of the VQGAN generator step (vq/tasks/image_reconstruction/losses.py:99-178, wired as lpips_r_loss in
+ * configs/vqgan/model.py:29 and reported as lpips_loss by configs/vqgan/runner.py:83-92).  The VGG16 convolutions stay with the
+ * framework; everything behind them - F.normalize over the channels of both feature maps, mse_loss(reduction='none'), nn.Dropout,
+ * the bias-free 1 x 1 convolution to one channel and the spatial mean - is ONE layer call here.  Forward: two launches (the
+ * pixels; the mean of each image).  Backward: one launch.  No copy of the size of the features, no atomics, no memset, no
+ * allocation and no synchronisation.  No gradient is formed for the target.
+ * INPUT   pred f and target g, both [B, C, P] (P = H W) in ONE layout: VQHIP_LAYOUT_MAP, NCHW-contiguous (channel stride P), or
+ *   VQHIP_LAYOUT_ROWS, channels-last dense (rows of C).  Each in its own dtype, VQHIP_DTYPE_F32, _BF16 or _F16; element alignment
+ *   only.  w [C] fp32, any sign.  Every element is converted to fp32 exactly; all arithmetic below is fp32 IEEE without
+ *   contraction, division and square root correctly rounded.
+ * DEFINITION  per pixel (b, p), with e = (float)1e-10 and the keep factors m_c (DROPOUT; all 1 without a seed):
+ *       nf = max(sqrt(sum_c f_c^2), e)    a_c = f_c / nf          (ATen's normalize: x / clamp_min(norm, e))
+ *       ng = max(sqrt(sum_c g_c^2), e)    b_c = g_c / ng
+ *       s(b, p) = sum_c m_c w_c (a_c - b_c)^2            value[b] = (1 / P) sum_p s(b, p)
+ *       u_c = 2 m_c w_c (a_c - b_c);   ds/df_c = (u_c - a_c sum_j u_j a_j) / nf where nf is not clamped, u_c / e where it is
+ *       grad[b, c, p] = (g_out[b] / (float)P) ds/df_c, rounded to nearest even into pred's dtype, in pred's layout.
+ *   The kernels multiply by the once-rounded reciprocals inf = 1 / nf and ing = 1 / ng where the definition divides (one more
+ *   rounding per element, counted in the bound), and form the sums over c in TWO passes over the pixel's channels inside one
+ *   launch: the norms, then the differences (the second pass re-reads what the workgroup has just read).
+ *       stats[b P + p] = (inf, ing, sum_j u_j a_j (+0 where nf is clamped), s): what the backward needs to read f and g once.
+ *       value[b] = (float)(sum_p (double)s(b, p) / (double)P): a double sum rounded once, so its error does not grow with P;
+ *       with `accumulate` the one thread that owns image b then stores value[b] + that, a plain fp32 add: the layers of one
+ *       loss are added in the order of the calls.
+ * ORDER OF EVERY SUM  Map: a workgroup owns 64 consecutive positions of one image times 4 channel groups; channel c belongs to
+ *   group c mod 4, which adds its channels in increasing c to one partial per sum (from +0, each product rounded once); the
+ *   groups add as (g0 + g1) + (g2 + g3).  Rows: 16 lanes own a pixel; its channels are cut into pieces [4 q, 4 q + 4), q < C / 4,
+ *   piece q belongs to lane q mod 16, which takes its pieces in increasing q and their elements in increasing c, then the
+ *   single channel 4 (C / 4) + lane (lane < C mod 4); the lanes add as a balanced binary tree in lane order.  The mean: partial
+ *   j = p mod 256 adds its pixels in increasing p, the 256 partials add as a balanced tree in order.
+ *   A pixel's stats and gradient are a function of C, the dtypes, w and the mask alone; value[b] of image b's pixels and P: not of
+ *   B, the other images, the address, and run to run the same bits.  The two layouts add in different orders.
+ * DROPOUT  `seed`: two uint32 on the DEVICE (null: no dropout, p is ignored); 0 <= p < 1.  Element (layer, b, c, p) is kept iff
+ *       h >= p 2^32,  h = mix(mix(seed[0] ^ lo32(i)) ^ (seed[1] + hi32(i) * 0x9E3779B9 + layer * 0x85EBCA77))     (uint32 arithmetic)
+ *       mix(h): h ^= h >> 16; h *= 0x85EBCA6B; h ^= h >> 13; h *= 0xC2B2AE35; h ^= h >> 16
+ *   for the LOGICAL index i = (b C + c) P + p, whatever the layout.  m = fl(1 / fl(1 - p)) where kept, 0 where dropped; the
+ *   product m w_c is rounded once.  The backward regenerates the mask from the same seed: none is stored.
+ *   vqhip_lpips_keep_mask writes the mask [B, C, P] (1 kept, 0 dropped) with the same device function, for tests.
+ * DEGENERATE AND NON-FINITE PIXELS  (what the fp32 evaluation of the definition gives; a pixel never affects another pixel's
+ *   stats or gradient, an image never another image's value)
+ *       the pixel holds                          a / b          s                       gradient column
+ *       f all zero (g not)                       a = 0          sum m w b_c^2           -2 m_c w_c b_c / e   (nf clamped: huge, finite)
+ *       g all zero (f not)                       b = 0          sum m w a_c^2           finite, the projected form
+ *       both all zero                            a = b = 0      0                       0
+ *       0 < |f| < e                              a = f / e      as defined              u_c / e  (no projection: the norm is the constant e)
+ *       a NaN in f or in g                       NaN            NaN                     NaN in every element
+ *       a +inf or -inf in f or in g              NaN there      NaN                     NaN in every element   (inf * (1 / inf))
+ *   A NaN s makes value[b] of ITS image NaN; the other images' values and the other pixels' gradients keep their bits.
+ * ERROR BOUND  against the exact value of the definition on the converted inputs, u = 2^-24, first order, for pixels whose
+ *   non-zero elements have magnitudes in [2^-55, 2^55] (every square is normal, no sum overflows) and whose norms are not within
+ *   N u of e (there the clamp may fall on the other side).
+ *   N = VQHIP_LPIPS_CHAIN(C) = C / 4 + 12 (integer division) bounds, in either layout, the additions one partial sum goes through
+ *   plus one for the rounding of its product: map ceil(C / 4) + 1 + 2; rows 4 ceil(C / 64) + 1 + 1 + 4.  wabs = max_c |w_c|.
+ *     a_c: sum f^2 has positive terms, N u relative; N / 2 under the root, + 1 the root, + 1 the reciprocal, + 1 the product:
+ *        E = N / 2 + 3, |a^_c - a_c| <= E u |a_c|; b_c likewise.
+ *     d_c = a_c - b_c: |d^_c - d_c| <= E u (|a_c| + |b_c|) + u |d_c|.  With |a|, |b| <= 1 and Cauchy-Schwarz,
+ *        sum_c |d_c| (|a_c| + |b_c|) <= 2 |d|, |d| = sqrt(sum d_c^2) <= 2.
+ *     s: the error of d_c^2 is 2 |d_c| times that of d_c: wabs (4 E |d| + 2 |d|^2) u; the square, m w and their product: 3 u
+ *        per term, the chain N u: wabs (N + 3) |d|^2 u.  Together wabs u (4 E |d| + (N + 5) |d|^2): PROPORTIONAL TO |d| - an identical
+ *        pair of one dtype gives exactly 0 - and with |d| <= 2 at most wabs u (8 E + 4 N + 20) = wabs u (8 N + 44).
+ *     value[b]: a mean does not exceed its largest term; the double sum adds nothing at this order, its one rounding to fp32 u of
+ *        at most 4 wabs, the accumulating add u of the sum of two layers: 8 more.
+ *        VQHIP_LPIPS_BOUND(C, wabs) = (8 N + 56) u (1 + 2^-9) wabs   for s(b, p) and for one layer's share of value[b]; the last
+ *        factors cover the second-order products.  With dropout, times 1 / (1 - p).
+ *     gradient element in fp32, before the rounding to the output dtype, per unit of |g_out[b]| / P and of 1 / (1 - p), in units
+ *        of wabs h, h = 1 / nf (1 / e where clamped):
+ *        u_c: 2 wabs times the error of d_c (<= (2 E + 2) u) plus two roundings on |d_c| <= 2: (4 E + 12) u;
+ *        sum u a: sum |a_j| err(u_j) <= (4 E + 12) u, the relative error E + 1 of each term on sum |u_j a_j| <= 4: 4 E + 4, the
+ *        chain 4 N: (8 E + 4 N + 16) u = (8 N + 40) u;  a_c sum u a: that, + (E + 1) 4: (10 N + 56) u;
+ *        the difference: (4 E + 12) + (10 N + 56) + its rounding on <= 8: (12 N + 88) u;  times inf, (N / 2 + 2) u relative on
+ *        <= 8 h, and the rounding: 4 N + 24;  times g_out[b] / P, two roundings and the product's: 24.
+ *        VQHIP_LPIPS_GRAD_BOUND(C, wabs, h) = (16 N + 136) u (1 + 2^-9) wabs h.
+ *   A measurement beyond these bounds inside the range means the kernel or this derivation is wrong.
+ * LIMITS (VQHIP_EINVAL before any HIP call): pred, target, w, stats, value (fwd) / pred, target, w, stats, g_out, grad (bwd) /
+ *   seed, out (keep_mask) not null; both dtypes one of F32 / BF16 / F16; layout one of ROWS / MAP; B, P >= 1, B P < 2^31 and
+ *   B ceil(P / 64) < 2^31; 1 <= C <= 2^16 (VQHIP_LPIPS_MAX_C); 0 <= layer <= 2^16; with a seed 0 <= p < 1. */
+#define VQHIP_LPIPS_MAX_C (1 << 16)
+#define VQHIP_LPIPS_MAX_LAYER (1 << 16)
+#define VQHIP_LPIPS_EPS 1e-10f
+#define VQHIP_LPIPS_CHAIN(C) ((double)((C) / 4 + 12))
+#define VQHIP_LPIPS_BOUND(C, wabs) \
+    ((8.0 * VQHIP_LPIPS_CHAIN(C) + 56.0) * 5.9604644775390625e-08 * 1.001953125 * (double)(wabs))
+#define VQHIP_LPIPS_GRAD_BOUND(C, wabs, h) \
+    ((16.0 * VQHIP_LPIPS_CHAIN(C) + 136.0) * 5.9604644775390625e-08 * 1.001953125 * (double)(wabs) * (double)(h))
+int vqhip_lpips_fwd(const void *pred, int pred_dtype, const void *target, int target_dtype, int layout, int64_t B, int64_t C,
+                    int64_t P, const float *w /* [C] */, const uint32_t *seed /* [2] on the device, or NULL */, float p, int64_t layer,
+                    float *stats /* [B P, 4] */, float *value /* [B] */, int accumulate, void *stream);
+int vqhip_lpips_bwd(const void *pred, int pred_dtype, const void *target, int target_dtype, int layout, int64_t B, int64_t C,
+                    int64_t P, const float *w /* [C] */, const uint32_t *seed, float p, int64_t layer, const float *stats /* [B P, 4] */,
+                    const float *g_out /* [B] */, void *grad, void *stream);
+int vqhip_lpips_keep_mask(const uint32_t *seed, float p, int64_t layer, int64_t B, int64_t C, int64_t P, uint8_t *out /* [B, C, P] */,
+                          void *stream);
+
 /* ---- fused reconstruction metrics: L1, MSE, PSNR and SSIM of a validation pass ---------------------------------------------
  * The four numbers of the reference's table per tokenizer (docs/pretrained_models.md:47-51) that come from ImageLossMetric
  * (vq/runners/metrics/loss.py) over L1Loss, MSELoss, PSNRLoss and SSIMLoss (vq/tasks/image_reconstruction/losses.py), each of

@@ -11,6 +11,7 @@ from .registries import (AnchorRegistry, InitRegistry, ModelRegistry, VQITQuanti
                          VQITQuantizerDistanceRegistry, VQITQuantizerLossRegistry, VQITQuantizerRegistry)
 from .image_losses import L1Loss, MSELoss, PSNRLoss, SSIMLoss
 from .distill_losses import CosineEmbeddingLoss
+from .perceptual_losses import LPIPSLoss
 from .sequence_losses import CausalTokenLoss, LabelSmoothingCrossEntropy, MaskedTokenLoss
 from .utils import EMA, ema
 
@@ -18,7 +19,7 @@ __all__ = [
     'BuildPreHookMixin', 'Config', 'Registry', 'RegistryMeta', 'AnchorRegistry', 'InitRegistry', 'ModelRegistry',
     'VQITQuantizerCallbackRegistry', 'VQITQuantizerDistanceRegistry', 'VQITQuantizerLossRegistry',
     'VQITQuantizerRegistry', 'EMA', 'ema', 'build_quantizer', 'CausalTokenLoss', 'LabelSmoothingCrossEntropy',
-    'MaskedTokenLoss', 'L1Loss', 'MSELoss', 'PSNRLoss', 'SSIMLoss', 'CosineEmbeddingLoss',
+    'MaskedTokenLoss', 'L1Loss', 'MSELoss', 'PSNRLoss', 'SSIMLoss', 'CosineEmbeddingLoss', 'LPIPSLoss',
 ]
 __version__ = '0.1.0'
 

@@ -130,6 +130,27 @@ def cosine_embed_grad_bound(C: int, h: float) -> float:
     return (4.0 * cosine_embed_chain(C) + 21.0) * 2.0 ** -24 * (1.0 + 2.0 ** -9) * h
 
 
+LPIPS_MAX_C = 1 << 16                      # VQHIP_LPIPS_MAX_C
+LPIPS_EPS = 1e-10                          # VQHIP_LPIPS_EPS, as the fp32 constant the kernels and ATen's normalize compare against
+
+
+def lpips_chain(C: int) -> float:
+    """VQHIP_LPIPS_CHAIN(C) of include/vqhip.h: the longest chain of fp32 additions of a pixel's sums over channels, either layout."""
+    return float(C // 4 + 12)
+
+
+def lpips_bound(C: int, wabs: float) -> float:
+    """VQHIP_LPIPS_BOUND(C, wabs): |kernel - exact| of a pixel's s and of one layer's share of an image's value of vqhip_lpips_fwd,
+    absolute; wabs = max |w|.  With dropout, times 1 / (1 - p)."""
+    return (8.0 * lpips_chain(C) + 56.0) * 2.0 ** -24 * (1.0 + 2.0 ** -9) * wabs
+
+
+def lpips_grad_bound(C: int, wabs: float, h: float) -> float:
+    """VQHIP_LPIPS_GRAD_BOUND(C, wabs, h): a gradient element in fp32, before the rounding to the output dtype, per unit of
+    |g_out[b]| / P (and of 1 / (1 - p)); h = 1 / max(|f|, 1e-10)."""
+    return (16.0 * lpips_chain(C) + 136.0) * 2.0 ** -24 * (1.0 + 2.0 ** -9) * wabs * h
+
+
 STEP_BEFORE_EXCHANGE, STEP_AFTER_EXCHANGE, STEP_ALL, STEP_PACK_SYNC = 1, 2, 3, 4
 
 # name -> (restype, argtypes); mirrors include/vqhip.h one to one
@@ -167,6 +188,9 @@ SIGNATURES = {
                                   _i64, _i64, _vp]),
     'vqhip_cosine_embed_fwd': (_i32, [_vp, _i32, _i32, _i64, _vp, _i32, _i64, _i64, _i64, _i64, _vp, _vp, _vp, _vp]),
     'vqhip_cosine_embed_bwd': (_i32, [_vp, _i32, _i32, _i64, _vp, _i32, _i64, _i64, _i64, _i64, _vp, _vp, _i32, _i32, _vp, _i64, _vp]),
+    'vqhip_lpips_fwd': (_i32, [_vp, _i32, _vp, _i32, _i32, _i64, _i64, _i64, _vp, _vp, _f32, _i64, _vp, _vp, _i32, _vp]),
+    'vqhip_lpips_bwd': (_i32, [_vp, _i32, _vp, _i32, _i32, _i64, _i64, _i64, _vp, _vp, _f32, _i64, _vp, _vp, _vp, _vp]),
+    'vqhip_lpips_keep_mask': (_i32, [_vp, _f32, _i64, _i64, _i64, _i64, _vp, _vp]),
     'vqhip_image_metrics_workspace_bytes': (_i64, [_i64, _i64, _i64, _i64]),
     'vqhip_image_metrics': (_i32, [_vp, _i32, _i32, _vp, _i32, _i32, _i64, _i64, _i64, _i64, _i32, _f64, _f64, _vp, _i64, _vp, _vp,
                                    _vp, _vp]),

@@ -12,6 +12,7 @@
 #include "vqhip_sample_kernels.h"
 #include "vqhip_token_ce_kernels.h"
 #include "vqhip_cosine_embed_kernels.h"
+#include "vqhip_lpips_kernels.h"
 #include "vqhip_image_metrics_kernels.h"
 
 static thread_local char g_err[256] = "";
@@ -548,6 +549,37 @@ static int launch_cosine_embed_bwd(const VqCoseArgs &a, int layout, const float 
         cosine_embed_map_bwd_kernel<DP, DT><<<(unsigned)((a.R + VQ_COSE_MAP_POS - 1) / VQ_COSE_MAP_POS), VQ_COSE_THREADS, 0, s>>>(
             a, stats, g, g_per_row, mean, grad);
         VQ_CHECK_LAUNCH("cosine_embed_map_bwd_kernel");
+    }
+    return VQHIP_OK;
+}
+
+// ---- fused LPIPS tail: the launches (vqhip_lpips_kernels.h) ----------------------------------------------------------------
+static unsigned lpips_grid(const VqLpipsArgs &a, int layout) {
+    return layout == VQHIP_LAYOUT_ROWS ? (unsigned)((a.B * a.P + VQ_LPIPS_ROWS - 1) / VQ_LPIPS_ROWS) : (unsigned)(a.B * a.tiles);
+}
+
+template <int DP, int DT>
+static int launch_lpips_fwd(const VqLpipsArgs &a, int layout, float *stats, float *value, int accumulate, hipStream_t s) {
+    if (layout == VQHIP_LAYOUT_ROWS) {
+        lpips_rows_fwd_kernel<DP, DT><<<lpips_grid(a, layout), VQ_LPIPS_THREADS, 0, s>>>(a, stats);
+        VQ_CHECK_LAUNCH("lpips_rows_fwd_kernel");
+    } else {
+        lpips_map_fwd_kernel<DP, DT><<<lpips_grid(a, layout), VQ_LPIPS_THREADS, 0, s>>>(a, stats);
+        VQ_CHECK_LAUNCH("lpips_map_fwd_kernel");
+    }
+    lpips_reduce_kernel<<<(unsigned)a.B, VQ_LPIPS_THREADS, 0, s>>>(stats, a.P, accumulate, value);
+    VQ_CHECK_LAUNCH("lpips_reduce_kernel");
+    return VQHIP_OK;
+}
+
+template <int DP, int DT>
+static int launch_lpips_bwd(const VqLpipsArgs &a, int layout, const float *stats, const float *g_out, void *grad, hipStream_t s) {
+    if (layout == VQHIP_LAYOUT_ROWS) {
+        lpips_rows_bwd_kernel<DP, DT><<<lpips_grid(a, layout), VQ_LPIPS_THREADS, 0, s>>>(a, stats, g_out, grad);
+        VQ_CHECK_LAUNCH("lpips_rows_bwd_kernel");
+    } else {
+        lpips_map_bwd_kernel<DP, DT><<<lpips_grid(a, layout), VQ_LPIPS_THREADS, 0, s>>>(a, stats, g_out, grad);
+        VQ_CHECK_LAUNCH("lpips_map_bwd_kernel");
     }
     return VQHIP_OK;
 }
@@ -1433,6 +1465,89 @@ int vqhip_cosine_embed_bwd(const void *pred, int pred_dtype, int pred_layout, in
 }
 #undef VQ_COSE_DISPATCH
 #undef VQ_COSE_DISPATCH_T
+
+// ---- fused LPIPS tail (vqhip_lpips_kernels.h) -------------------------------------------------------------------------------
+// what the dropout of the three entry points refuses, and its threshold and scale
+static int lpips_dropout(const char *what, const uint32_t *seed, float p, int64_t layer, VqLpipsArgs *a) {
+    if (layer < 0 || layer > VQHIP_LPIPS_MAX_LAYER) return fail(VQHIP_EINVAL, what, "layer must be in 0 .. 2^16");
+    a->seed = seed; a->layer = (uint32_t)layer; a->thr = 0u; a->scale = 1.0f;
+    if (!seed) return VQHIP_OK;
+    if (!(p >= 0.0f && p < 1.0f)) return fail(VQHIP_EINVAL, what, "p must be in [0, 1)");
+    a->thr = (uint32_t)ceil((double)p * 4294967296.0);                          // p < 1 in fp32: at most 2^32 - 256
+    a->scale = 1.0f / (1.0f - p);
+    return VQHIP_OK;
+}
+
+static int lpips_sizes(const char *what, int64_t B, int64_t C, int64_t P, VqLpipsArgs *a) {
+    const int64_t cap = 1ll << 31;
+    if (B < 1 || P < 1 || B >= cap || P >= cap || B * P >= cap) return fail(VQHIP_EINVAL, what, "B * P must be in 1 .. 2^31 - 1");
+    if (C < 1 || C > VQHIP_LPIPS_MAX_C) return fail(VQHIP_EINVAL, what, "C must be in 1 .. 2^16");
+    a->B = B; a->P = P; a->C = (int)C;
+    a->tiles = (P + VQ_LPIPS_MAP_POS - 1) / VQ_LPIPS_MAP_POS;
+    if (B * a->tiles >= cap) return fail(VQHIP_EINVAL, what, "B * ceil(P / 64) must be below 2^31");
+    return VQHIP_OK;
+}
+
+// what the forward and the backward refuse alike, and the arguments the kernels share
+static int lpips_setup(const char *what, const void *pred, int pred_dtype, const void *target, int target_dtype, int layout, int64_t B,
+                       int64_t C, int64_t P, const float *w, const uint32_t *seed, float p, int64_t layer, VqLpipsArgs *a) {
+    if (!pred || !target || !w) return fail(VQHIP_EINVAL, what, "pred, target and w are required");
+    for (int dtype : {pred_dtype, target_dtype})
+        if (dtype != VQHIP_DTYPE_F32 && dtype != VQHIP_DTYPE_BF16 && dtype != VQHIP_DTYPE_F16) return fail(VQHIP_EINVAL, what, "dtype");
+    if (layout != VQHIP_LAYOUT_ROWS && layout != VQHIP_LAYOUT_MAP) return fail(VQHIP_EINVAL, what, "layout");
+    if (int rc = lpips_sizes(what, B, C, P, a)) return rc;
+    if (int rc = lpips_dropout(what, seed, p, layer, a)) return rc;
+    a->pred = pred; a->target = target; a->w = w;
+    return VQHIP_OK;
+}
+
+#define VQ_LPIPS_DISPATCH_T(fn, DP, ...)                                                                                \
+    switch (target_dtype) {                                                                                             \
+    case VQHIP_DTYPE_F32: return fn<DP, VQHIP_DTYPE_F32>(__VA_ARGS__);                                                  \
+    case VQHIP_DTYPE_BF16: return fn<DP, VQHIP_DTYPE_BF16>(__VA_ARGS__);                                                \
+    default: return fn<DP, VQHIP_DTYPE_F16>(__VA_ARGS__);                                                               \
+    }
+#define VQ_LPIPS_DISPATCH(fn, ...)                                                                                      \
+    do {                                                                                                                \
+        switch (pred_dtype) {                                                                                           \
+        case VQHIP_DTYPE_F32: VQ_LPIPS_DISPATCH_T(fn, VQHIP_DTYPE_F32, __VA_ARGS__)                                     \
+        case VQHIP_DTYPE_BF16: VQ_LPIPS_DISPATCH_T(fn, VQHIP_DTYPE_BF16, __VA_ARGS__)                                   \
+        default: VQ_LPIPS_DISPATCH_T(fn, VQHIP_DTYPE_F16, __VA_ARGS__)                                                  \
+        }                                                                                                               \
+    } while (0)
+
+int vqhip_lpips_fwd(const void *pred, int pred_dtype, const void *target, int target_dtype, int layout, int64_t B, int64_t C,
+                    int64_t P, const float *w, const uint32_t *seed, float p, int64_t layer, float *stats, float *value,
+                    int accumulate, void *stream) {
+    VqLpipsArgs a;
+    if (int rc = lpips_setup("vqhip_lpips_fwd", pred, pred_dtype, target, target_dtype, layout, B, C, P, w, seed, p, layer, &a)) return rc;
+    VQ_REQUIRE(stats && value, "vqhip_lpips_fwd: stats and value are required");
+    VQ_LPIPS_DISPATCH(launch_lpips_fwd, a, layout, stats, value, accumulate ? 1 : 0, (hipStream_t)stream);
+}
+
+int vqhip_lpips_bwd(const void *pred, int pred_dtype, const void *target, int target_dtype, int layout, int64_t B, int64_t C,
+                    int64_t P, const float *w, const uint32_t *seed, float p, int64_t layer, const float *stats, const float *g_out,
+                    void *grad, void *stream) {
+    VqLpipsArgs a;
+    if (int rc = lpips_setup("vqhip_lpips_bwd", pred, pred_dtype, target, target_dtype, layout, B, C, P, w, seed, p, layer, &a)) return rc;
+    VQ_REQUIRE(stats && g_out && grad, "vqhip_lpips_bwd: stats, g_out and grad are required");
+    VQ_LPIPS_DISPATCH(launch_lpips_bwd, a, layout, stats, g_out, grad, (hipStream_t)stream);
+}
+#undef VQ_LPIPS_DISPATCH
+#undef VQ_LPIPS_DISPATCH_T
+
+int vqhip_lpips_keep_mask(const uint32_t *seed, float p, int64_t layer, int64_t B, int64_t C, int64_t P, uint8_t *out, void *stream) {
+    const char *what = "vqhip_lpips_keep_mask";
+    VqLpipsArgs a;
+    if (!seed || !out) return fail(VQHIP_EINVAL, what, "seed and out are required");
+    if (int rc = lpips_sizes(what, B, C, P, &a)) return rc;
+    if (int rc = lpips_dropout(what, seed, p, layer, &a)) return rc;
+    const int64_t n = B * C * P;                                                // below 2^47
+    const int64_t blocks = (n + VQ_LPIPS_THREADS - 1) / VQ_LPIPS_THREADS;
+    lpips_keep_mask_kernel<<<(unsigned)(blocks < 65536 ? blocks : 65536), VQ_LPIPS_THREADS, 0, (hipStream_t)stream>>>(seed, a.layer, a.thr, n, out);
+    VQ_CHECK_LAUNCH("lpips_keep_mask_kernel");
+    return VQHIP_OK;
+}
 
 // ---- fused reconstruction metrics (vqhip_image_metrics_kernels.h) ---------------------------------------------------------
 // what both entry points refuse; on success the number of workgroups of the first launch and the tiles along each axis

@@ -6,6 +6,7 @@ from typing import Optional
 
 import torch
 from torch.autograd import Function
+from torch.autograd.function import once_differentiable
 
 from . import ops
 
@@ -379,3 +380,48 @@ def cosine_embedding_loss(pred: torch.Tensor, target: torch.Tensor, reduction: s
     if reduction not in ops.COSINE_REDUCTIONS:
         raise ValueError(f'cosine_embedding_loss: reduction must be one of {ops.COSINE_REDUCTIONS}, got {reduction!r}')
     return _CosineEmbed.apply(pred, target.detach(), layout, reduction)
+
+
+
+class _LpipsDistance(Function):
+    """The fused LPIPS tail over the list of feature pairs (vqhip_lpips_fwd / _bwd of include/vqhip.h).  Saves the features AS GIVEN
+    (a bf16 activation stays bf16, channels-last stays channels-last: no copy), the weights and four floats per pixel; the backward
+    is one launch per layer that writes every element of that layer's gradient.  The targets and the weights get no gradient.  The
+    backward keeps nothing and changes nothing it saved: run twice on one graph it gives the same bits."""
+
+    @staticmethod
+    def forward(ctx, seed, p, n, *tensors):
+        preds, targets, weights = tensors[:n], tensors[n:2 * n], tensors[2 * n:]
+        value, stats = None, []
+        for layer, (f, g, w) in enumerate(zip(preds, targets, weights)):
+            out = ops.lpips_layer_forward(f, g, w, seed=seed, p=p, layer=layer, value=value)
+            value = out['value']
+            stats.append(out['stats'])
+        ctx.save_for_backward(*tensors, *stats, *(() if seed is None else (seed,)))
+        ctx.n, ctx.p, ctx.seeded = n, p, seed is not None
+        return value
+
+    @staticmethod
+    @once_differentiable
+    def backward(ctx, g):
+        n = ctx.n
+        saved = ctx.saved_tensors
+        preds, targets, weights, stats = saved[:n], saved[n:2 * n], saved[2 * n:3 * n], saved[3 * n:4 * n]
+        seed = saved[4 * n] if ctx.seeded else None
+        g = g.contiguous()
+        grads = [ops.lpips_layer_backward(preds[i], targets[i], weights[i], stats[i], g, seed=seed, p=ctx.p, layer=i)
+                 if ctx.needs_input_grad[3 + i] else None for i in range(n)]
+        return (None, None, None, *grads, *([None] * (2 * n)))
+
+
+def lpips_distance(pred_features, target_features, weights, seed: Optional[torch.Tensor] = None, p: float = 0.5) -> torch.Tensor:
+    """sum over the layers of mean_p sum_c m w_c (normalize(pred)_c - normalize(target)_c)^2, ``[B]`` fp32: the reference's
+    ``losses_`` before its reshape, from lists of feature maps [B, C_l, H_l, W_l] of any of the three dtypes, read in place, each
+    pair NCHW-contiguous or channels-last; ``weights``: one fp32 tensor of C_l elements per layer (the 1 x 1 convolutions').
+    ``seed``: two 32-bit words on the device switch dropout with probability ``p`` on (another stream than torch's, the same
+    distribution).  The gradient goes to the pred features only, in their dtype and layout."""
+    n = len(pred_features)
+    if n == 0 or len(target_features) != n or len(weights) != n:
+        raise ValueError(f'lpips_distance: need as many targets and weights as pred features, got {n}, {len(target_features)}, {len(weights)}')
+    return _LpipsDistance.apply(seed, float(p), n, *pred_features, *(t.detach() for t in target_features), *(w.detach() for w in weights))
+

@@ -1,6 +1,7 @@
 """The pixel losses of image reconstruction, with the reference's names and ``forward(pred_image, image)`` signature
 (vq/tasks/image_reconstruction/losses.py): ``L1Loss``, ``MSELoss``, ``PSNRLoss``, ``SSIMLoss``.  The reference uses them as
-validation metrics (configs/vqgan/runner.py:93-116); ``LPIPSLoss`` (a VGG16 with downloaded weights) is not rebuilt.
+validation metrics (configs/vqgan/runner.py:93-116).  ``LPIPSLoss``, the fifth class of that file, lives in ``perceptual_losses.py``: it
+is no column of ``ops.image_metrics`` (``column_of`` and ``is_plain`` do not claim it) and has a fused route of its own.
 
 - Float images in [0, 1], as ``dataset.decode(v) / 255`` gives them: the reference's composition with torch ops - route
   ``torch``, which also serves CPU tensors and keeps autograd for L1, MSE and PSNR.  ``SSIMLoss`` on this route is the

@@ -945,6 +945,130 @@ def cosine_embedding_loss(pred: torch.Tensor, target: torch.Tensor, reduction: s
     return functional.cosine_embedding_loss(pred, target, reduction, layout=layout)
 
 
+# ---- fused LPIPS tail (the VQGAN generator's perceptual loss: vq/tasks/image_reconstruction/losses.py:99-178) ---------------
+
+LPIPS_LAYOUTS = {'rows': _lib.LAYOUT_ROWS, 'map': _lib.LAYOUT_MAP}
+LPIPS_CHANNELS = (64, 128, 256, 512, 512)                   # the five taps of VGG16
+LPIPS_MAX_LAYER = 1 << 16
+
+
+def _lpips_layouts(t: torch.Tensor) -> tuple:
+    """The layouts of include/vqhip.h a [B, C, *positions] feature map is dense in: 'map' (NCHW-contiguous), 'rows' (channels-last)."""
+    found = ('map',) if t.is_contiguous() else ()
+    if t.dim() == 4 and t.is_contiguous(memory_format=torch.channels_last):
+        found += ('rows',)
+    return found
+
+
+def lpips_layout(pred: torch.Tensor, target: torch.Tensor):
+    """The layout both feature maps share ('map' before 'rows' where both hold, as for C == 1), None if there is none."""
+    both = [name for name in _lpips_layouts(pred) if name in _lpips_layouts(target)]
+    return both[0] if both else None
+
+
+def lpips_refusal(pred: torch.Tensor, target: torch.Tensor, weight: Optional[torch.Tensor] = None) -> str:
+    """Why vqhip_lpips_fwd would refuse this pair of feature maps ('' if it would not): the clauses of its LIMITS that depend
+    on the tensors' dtypes, shapes and strides.  ``weight``: the 1 x 1 convolution's, any shape with C elements."""
+    for name, t in (('pred', pred), ('target', target)):
+        if t.dtype not in SAMPLE_DTYPES:
+            return f'{name} is {t.dtype}, not float32, bfloat16 or float16'
+    if pred.dim() < 3 or pred.shape != target.shape:
+        return f'pred {tuple(pred.shape)} and target {tuple(target.shape)} are not two [B, C, *positions] maps of one shape'
+    if pred.numel() == 0:
+        return f'empty features {tuple(pred.shape)}'
+    for name, t in (('pred', pred), ('target', target)):
+        if not _lpips_layouts(t):
+            return f'{name} with strides {t.stride()} is neither NCHW-contiguous nor channels-last dense'
+    if lpips_layout(pred, target) is None:
+        return f'pred (strides {pred.stride()}) and target (strides {target.stride()}) differ in layout'
+    B, C = pred.shape[:2]
+    P = pred.numel() // (B * C)
+    if C > _lib.LPIPS_MAX_C:
+        return f'C={C} is beyond 2^16'
+    if B * P >= (1 << 31):
+        return f'{B * P} pixels are outside 1 .. 2^31-1'
+    if weight is not None and (weight.numel() != C or weight.dtype != torch.float32):
+        return f'the weights are {weight.dtype} {tuple(weight.shape)}, not float32 with C={C} elements'
+    return ''
+
+
+def _lpips_args(what: str, pred, target, weight, seed, p, layer):
+    """The arguments vqhip_lpips_fwd and _bwd share; both maps are read in place."""
+    _require_cuda(pred, target, weight, seed)
+    why = lpips_refusal(pred, target, weight)
+    if why:
+        raise ValueError(f'{what}: {why}')
+    if seed is not None and (seed.dtype not in (torch.int32, torch.uint32) or seed.numel() != 2 or not seed.is_contiguous()):
+        raise ValueError(f'{what}: seed must hold two contiguous 32-bit words on the device, got {seed.dtype} {tuple(seed.shape)}')
+    if seed is not None and not 0.0 <= p < 1.0:
+        raise ValueError(f'{what}: p={p!r} is outside [0, 1)')
+    if not 0 <= layer <= LPIPS_MAX_LAYER:
+        raise ValueError(f'{what}: layer={layer!r} is outside 0 .. 2^16')
+    w = weight.detach().reshape(-1)
+    w = w if w.is_contiguous() else w.contiguous()
+    B, C = pred.shape[:2]
+    P = pred.numel() // (B * C)
+    head = (_ptr(pred), SAMPLE_DTYPES[pred.dtype], _ptr(target), SAMPLE_DTYPES[target.dtype], LPIPS_LAYOUTS[lpips_layout(pred, target)],
+            B, C, P, _ptr(w), _ptr(seed), float(p), int(layer))
+    return head, B, C, P, (w,)
+
+
+@_on_tensor_device
+def lpips_layer_forward(pred: torch.Tensor, target: torch.Tensor, weight: torch.Tensor, *, seed: Optional[torch.Tensor] = None,
+                        p: float = 0.5, layer: int = 0, value: Optional[torch.Tensor] = None) -> dict:
+    """vqhip_lpips_fwd of include/vqhip.h on one layer's feature maps ``pred`` and ``target`` [B, C, *positions], read in place, each
+    in its own dtype, both NCHW-contiguous or both channels-last: fp32 ``stats`` [B, P, 4] = (1 / nf, 1 / ng, sum u a, s) per pixel
+    and ``value`` [B], the spatial mean of s.  ``value``: a buffer of earlier layers to ADD this layer onto (in place).
+    ``seed``: two 32-bit words on the device switch the dropout on, with probability ``p``; ``layer`` enters its hash.
+    Two launches, no copy, no synchronisation."""
+    head, B, C, P, keep = _lpips_args('lpips_layer_forward', pred, target, weight, seed, p, layer)
+    _require_cuda(value)
+    stats = torch.empty(B, P, 4, dtype=torch.float32, device=pred.device)
+    accumulate = value is not None
+    if accumulate and (value.dtype != torch.float32 or value.shape != (B,) or not value.is_contiguous()):
+        raise ValueError(f'lpips_layer_forward: value must be contiguous fp32 [{B}]')
+    value = value if accumulate else torch.empty(B, dtype=torch.float32, device=pred.device)
+    check(_lib.lib().vqhip_lpips_fwd(*head, _ptr(stats), _ptr(value), 1 if accumulate else 0, _stream()), 'vqhip_lpips_fwd')
+    return dict(stats=stats, value=value, s=stats[..., 3])
+
+
+@_on_tensor_device
+def lpips_layer_backward(pred: torch.Tensor, target: torch.Tensor, weight: torch.Tensor, stats: torch.Tensor, g: torch.Tensor, *,
+                         seed: Optional[torch.Tensor] = None, p: float = 0.5, layer: int = 0,
+                         out: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """vqhip_lpips_bwd: the gradient of sum_b g[b] value[b] over ``pred``, in its dtype, shape and layout, every element written
+    by the one launch.  ``g``: fp32 [B]; ``seed``, ``p``, ``layer``: those of the forward (the mask is regenerated).  ``out``: a
+    buffer of pred's shape, dtype and strides to write into."""
+    head, B, C, P, keep = _lpips_args('lpips_layer_backward', pred, target, weight, seed, p, layer)
+    _require_cuda(stats, g, out)
+    g = g.reshape(-1).to(torch.float32).contiguous()
+    if g.numel() != B or stats.dtype != torch.float32 or stats.shape != (B, P, 4) or not stats.is_contiguous():
+        raise ValueError(f'lpips_layer_backward: g must hold {B} values and stats be contiguous fp32 [{B}, {P}, 4]')
+    grad = torch.empty_like(pred) if out is None else out                       # (preserve_format: pred is dense, so its strides)
+    if grad.shape != pred.shape or grad.dtype != pred.dtype or grad.stride() != pred.stride():
+        raise ValueError('lpips_layer_backward: out must have the shape, dtype and strides of pred')
+    check(_lib.lib().vqhip_lpips_bwd(*head, _ptr(stats), _ptr(g), _ptr(grad), _stream()), 'vqhip_lpips_bwd')
+    return grad
+
+
+@_on_tensor_device
+def lpips_keep_mask(seed: torch.Tensor, p: float, layer: int, B: int, C: int, P: int) -> torch.Tensor:
+    """vqhip_lpips_keep_mask: the dropout mask uint8 [B, C, P] (1 kept, 0 dropped) the two kernels regenerate from ``seed``, by the
+    same device function - what a reference needs to be held against a seeded run."""
+    _require_cuda(seed)
+    if seed.dtype not in (torch.int32, torch.uint32) or seed.numel() != 2 or not seed.is_contiguous():
+        raise ValueError(f'lpips_keep_mask: seed must hold two contiguous 32-bit words on the device, got {seed.dtype} {tuple(seed.shape)}')
+    out = torch.empty(B, C, P, dtype=torch.uint8, device=seed.device)
+    check(_lib.lib().vqhip_lpips_keep_mask(_ptr(seed), float(p), int(layer), B, C, P, _ptr(out), _stream()), 'vqhip_lpips_keep_mask')
+    return out
+
+
+def lpips_distance(pred_features, target_features, weights, seed: Optional[torch.Tensor] = None, p: float = 0.5) -> torch.Tensor:
+    """The LPIPS distance [B] fp32 of the lists of feature maps, with autograd to the pred features: see ``functional.lpips_distance``."""
+    from . import functional
+    return functional.lpips_distance(pred_features, target_features, weights, seed, p)
+
+
 # ---- fused reconstruction metrics (validation: vq/runners/metrics/loss.py over vq/tasks/image_reconstruction/losses.py) -----
 
 IMAGE_DTYPES = {torch.float32: _lib.DTYPE_F32, torch.bfloat16: _lib.DTYPE_BF16, torch.float16: _lib.DTYPE_F16,

@@ -14,6 +14,7 @@ shape, dtype, alignment, the probability buffer, the world size, train / eval). 
     token_ce_why  fused | torch
     image_metrics_why  fused | torch
     cosine_embedding_why  fused | torch
+    lpips_why             fused | torch
     multinomial_anchor_why  fused | matrix
 """
 from __future__ import annotations
@@ -499,6 +500,33 @@ def cosine_embedding_why(pred: torch.Tensor, target: torch.Tensor, *, layout=Non
         why = why or ('' if t.is_cuda else f'{name} is on device {t.device}, not on a GPU')
     why = why or ('the target requires grad: the fused backward forms no gradient for it' if target.requires_grad else '') \
         or ops.cosine_embedding_refusal(pred, target, layout)
+    return Route('torch', why) if why else Route('fused')
+
+
+# ---- the perceptual loss of a VQGAN step (vector_quantization_amd/perceptual_losses.py) ------------------------------------------
+
+def lpips_why(loss, pred_features, target_features) -> Route:
+    """The tail of LPIPSLoss behind the VGG16 taps: the launches of ``ops.lpips_distance`` on the feature maps as they are
+    (``fused``), or the reference's normalize / mse / dropout / 1 x 1 convolution / mean (``torch``), with the first clause that
+    refused the launches: a ``loss`` whose class overrides ``forward``, ``forward_torch``, ``distance_torch`` or
+    ``extract_features`` of ``LPIPSLoss``, a CPU tensor, a target that requires grad (the kernels form no gradient for it),
+    float64 (or any dtype the kernels do not read), or strides that are neither NCHW-contiguous nor channels-last dense in both
+    maps of a layer."""
+    from .. import perceptual_losses
+    why = ''
+    if loss is not None:
+        why = own(loss, perceptual_losses.LPIPSLoss, 'forward', 'forward_torch', 'distance_torch', 'extract_features')
+        if not why and len(pred_features) != len(loss._convs):
+            why = f'{len(pred_features)} feature maps for {len(loss._convs)} convolutions'
+    if not why and (len(pred_features) == 0 or len(pred_features) != len(target_features)):
+        why = f'{len(pred_features)} pred and {len(target_features)} target feature maps'
+    for layer, (f, g) in enumerate(zip(pred_features, target_features)):
+        for name, t in (('pred', f), ('target', g)):
+            why = why or ('' if t.is_cuda else f'layer {layer}: {name} is on device {t.device}, not on a GPU')
+        why = why or ('' if not g.requires_grad else f'layer {layer}: the target requires grad: the fused backward forms no gradient for it')
+        if not why:
+            refusal = ops.lpips_refusal(f, g, None if loss is None else loss._convs[layer].weight)
+            why = f'layer {layer}: {refusal}' if refusal else ''
     return Route('torch', why) if why else Route('fused')
 
 
