@@ -614,6 +614,81 @@ int vqhip_lpips_bwd(const void *pred, int pred_dtype, const void *target, int ta
 int vqhip_lpips_keep_mask(const uint32_t *seed, float p, int64_t layer, int64_t B, int64_t C, int64_t P, uint8_t *out /* [B, C, P] */,
                           void *stream);
 
+/* ---- StyleGAN2 discriminator ops: bias-activation and the 4-tap FIR blur, forward, backward and fused ---------------------------
+ * What StyleGAN2Discriminator (vq/algorithms/vqgan/discriminators/stylegan2.py, selected by configs/vqgan/8192_stylegan2_imagenet_ddp.py
+ * and configs/llamagen/vqgan_stylegan2_imagenet_ddp.py) takes from mmcv.ops.FusedBiasLeakyReLU and mmcv.ops.upfirdn2d, restated
+ * here because mmcv is no dependency.  The convolutions stay with the framework.  No copy, no atomics, no memset, no allocation and
+ * no synchronisation; one launch per call, two where gbias is formed.
+ * INPUT   a logical [B, C, P] tensor (P = H W; a [B, C] matrix is P = 1) in VQHIP_LAYOUT_MAP (NCHW-contiguous) or VQHIP_LAYOUT_ROWS
+ *   (channels-last dense), VQHIP_DTYPE_F32, _BF16 or _F16, element alignment only; outputs in the same dtype and layout.  bias [C]
+ *   and gbias [C] are fp32.  Every element is converted to fp32 exactly; all arithmetic is fp32 IEEE without contraction; a result
+ *   is rounded to nearest even into the output dtype.
+ * DEFINITION, BIAS-ACTIVATION  (FusedBiasLeakyReLU(C): slope = 0.2, scale = 2^0.5; the kernels hold both as fp32 constants)
+ *       fwd    t = x + bias[c];   y = (t > 0 ? t : t * slope) * scale
+ *       bwd    gx = g * (y > 0 ? scale : scale * slope)   from the SAVED OUTPUT y, as mmcv's, so x is not kept;
+ *              gbias[c] = sum_{b, p} gx, over the fp32 gx before their rounding to the output dtype
+ *   A NaN in x gives NaN in y; t == 0 gives y = 0 (of t's sign), and the backward takes the slope branch there and for a NaN y
+ *   (y > 0 is false).  +-inf pass through with their sign.  The backward is linear in g: its own derivative with respect to g is
+ *   the same call on the incoming second-order gradient; the second derivative with respect to x is zero, as in mmcv.
+ * DEFINITION, FIR BLUR  (upfirdn2d(x, k, padding) with k = outer([1, 3, 3, 1]) / 64, per channel, zero padding, down factor d)
+ *       out[b, c, y, x] = sum_{i, j < 4} k[i] k[j] xpad[b, c, y d + i, x d + j],   k = (1/8, 3/8, 3/8, 1/8)  (exact in every dtype)
+ *       OH = (H + py0 + py1 - 4) / d + 1 (integer division), OW likewise; xpad has py0 zero rows in front, py1 behind, px0 / px1 columns.
+ *       bwd: the exact adjoint, gx[b, c, h, w] = sum over (y, i) with y d + i - py0 == h and (x, j) likewise of k[i] k[j] g[b, c, y, x]
+ *       (zero insertion by d, correlation with the flipped kernel, the complementary padding).  (H, W) is the blur's input plane in
+ *       both calls.  The blur is linear: the derivative of bwd is fwd.
+ *   FUSED: fwd with bias != NULL is blur(act(x + bias)), the activation applied on the way into the tile, the padding staying 0;
+ *       bwd with x and bias != NULL is gx = adjoint(g) * (x + bias[c] > 0 ? scale : scale * slope) over the SAVED INPUT x of the fused
+ *       forward, and gbias[c] = sum gx as above.
+ * ORDER OF EVERY SUM  a blur output: h(r) = ((k0 s0 + k1 s1) + k2 s2) + k3 s3 along a source row, then the same form down the four
+ *   h.  gbias: a first launch leaves one partial per SLAB and channel in ws [slabs, C] (see vqhip_stylegan2_kernels.h for who adds
+ *   what), a second adds slabs j, j + 16, .. in increasing order into 16 partials and those as a balanced tree.  Nothing depends
+ *   on the address or on timing: the same inputs give the same bits, run to run.
+ * SHAPES AND LIMITS (VQHIP_EINVAL before any HIP call)
+ *       pointer          required                      shape                 dtype
+ *       x, y, g, gx      always                        [B, C, P] / planes     the call's dtype
+ *       bias             bias_act_fwd; fused fir4      [C]                   fp32
+ *       gbias, ws        optional in bias_act_bwd      [C], [slabs, C]       fp32      (both or neither; fused fir4_bwd: required)
+ *   dtype one of F32 / BF16 / F16; layout one of ROWS / MAP; B, P >= 1; 1 <= C <= 2^16 (VQHIP_SG2_MAX_C); B C P < 2^31;
+ *   d in {1, 2}; every padding in 0 .. 3; H + py0 + py1 >= 4 and W + px0 + px1 >= 4; the tiles of one launch below 2^31;
+ *   ws_bytes >= 4 C vqhip_bias_act_slabs(..) / 4 C vqhip_fir4_slabs(..) where gbias is formed.
+ * ERROR BOUND  against the exact value of the definition on the converted inputs, u = 2^-24, first order, no overflow or underflow
+ *   in fp32; the factor 1 + 2^-9 covers the second order.
+ *     bias-activation, y and gx in fp32: the add, the slope product and the scale product round once each (3 u), the two fp32
+ *       constants are within u / 2 of 0.2 and 2^0.5 (1 u):                         VQHIP_BIAS_ACT_BOUND(y) = 4 u |y|
+ *       (gx: scale * slope rounds once, the constants, the product with g: 3 u, under the same macro).
+ *     blur, an output in fp32, a = the same blur (or adjoint) of |source|: the 16 weights sum to 1 and are formed separably, so a
+ *       term passes one rounded product and three additions per axis, 4 u along the row and 4 u down the column:
+ *                                                                                  VQHIP_FIR4_BOUND(a) = 8 u a
+ *       fused: + 4 u for the activated source (fwd, a = blur of |act|), or + 3 u for the factor (bwd, a = adjoint(|g|) factor):
+ *                                                                                  VQHIP_FIR4_ACT_BOUND(a) = 12 u a
+ *     gbias: N = VQHIP_SG2_GBIAS_CHAIN(slabs) = slabs / 16 + 80 bounds the additions a term passes: at most 64 in its thread and 8
+ *       in its workgroup's tree in the first launch, ceil(slabs / 16) + 4 in the second.  With e = 4 (bias-activation) or 12 (fused)
+ *       for the terms' own errors and sumabs = the sum of the terms' magnitudes a:   VQHIP_SG2_GBIAS_BOUND(slabs, e, sumabs) = (N + e) u sumabs
+ *     the store: half an ulp of the output dtype on top, VQHIP_SG2_STORE_U(dtype) = 0 (fp32: nothing is rounded again), 2^-8
+ *       (bf16) or 2^-11 (fp16) times |value|, plus 2^-25 absolute for fp16 (its subnormals).
+ *   A measurement beyond these bounds inside the range means the kernel or this derivation is wrong. */
+#define VQHIP_SG2_MAX_C (1 << 16)
+#define VQHIP_SG2_SLOPE 0.2
+#define VQHIP_SG2_SCALE 1.4142135623730951
+#define VQHIP_SG2_U (5.9604644775390625e-08 * 1.001953125)
+#define VQHIP_BIAS_ACT_BOUND(y) (4.0 * VQHIP_SG2_U * (double)(y))
+#define VQHIP_FIR4_BOUND(a) (8.0 * VQHIP_SG2_U * (double)(a))
+#define VQHIP_FIR4_ACT_BOUND(a) (12.0 * VQHIP_SG2_U * (double)(a))
+#define VQHIP_SG2_GBIAS_CHAIN(slabs) ((double)((slabs) / 16 + 80))
+#define VQHIP_SG2_GBIAS_BOUND(slabs, e, sumabs) ((VQHIP_SG2_GBIAS_CHAIN(slabs) + (double)(e)) * VQHIP_SG2_U * (double)(sumabs))
+#define VQHIP_SG2_STORE_U(dtype) ((dtype) == VQHIP_DTYPE_BF16 ? 0.00390625 : (dtype) == VQHIP_DTYPE_F16 ? 0.00048828125 : 0.0)
+int64_t vqhip_bias_act_slabs(int layout, int64_t B, int64_t C, int64_t P);      /* -1 for sizes the calls refuse */
+int vqhip_bias_act_fwd(const void *x, int dtype, int layout, int64_t B, int64_t C, int64_t P, const float *bias /* [C] */, void *y,
+                       void *stream);
+int vqhip_bias_act_bwd(const void *g, const void *y, int dtype, int layout, int64_t B, int64_t C, int64_t P, void *gx,
+                       float *gbias /* [C] or NULL */, float *ws, int64_t ws_bytes, void *stream);
+int64_t vqhip_fir4_slabs(int layout, int64_t B, int64_t C, int64_t H, int64_t W);  /* of the fused backward; -1 for sizes it refuses */
+int vqhip_fir4_fwd(const void *x, int dtype, int layout, int64_t B, int64_t C, int64_t H, int64_t W, int down, int py0, int py1, int px0,
+                   int px1, const float *bias /* [C], or NULL: the plain blur */, void *out /* [B, C, OH, OW] */, void *stream);
+int vqhip_fir4_bwd(const void *g /* [B, C, OH, OW] */, int dtype, int layout, int64_t B, int64_t C, int64_t H, int64_t W, int down, int py0,
+                   int py1, int px0, int px1, const void *x /* [B, C, H, W], or NULL */, const float *bias /* with x */,
+                   void *gx /* [B, C, H, W] */, float *gbias /* [C], with x */, float *ws, int64_t ws_bytes, void *stream);
+
 /* ---- fused reconstruction metrics: L1, MSE, PSNR and SSIM of a validation pass ---------------------------------------------
  * The four numbers of the reference's table per tokenizer (docs/pretrained_models.md:47-51) that come from ImageLossMetric
  * (vq/runners/metrics/loss.py) over L1Loss, MSELoss, PSNRLoss and SSIMLoss (vq/tasks/image_reconstruction/losses.py), each of

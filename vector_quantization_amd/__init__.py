@@ -8,10 +8,13 @@ re-expressed on top of that library.  There is no CPU fallback.
 from . import _lib  # noqa: F401
 from .config import BuildPreHookMixin, Config, Registry, RegistryMeta
 from .registries import (AnchorRegistry, InitRegistry, ModelRegistry, VQITQuantizerCallbackRegistry,
-                         VQITQuantizerDistanceRegistry, VQITQuantizerLossRegistry, VQITQuantizerRegistry)
+                         VQITQuantizerDistanceRegistry, VQITQuantizerLossRegistry, VQITQuantizerRegistry,
+                         VQDiscriminatorLossRegistry, VQDiscriminatorRegistry, VQGeneratorLossRegistry)
 from .image_losses import L1Loss, MSELoss, PSNRLoss, SSIMLoss
 from .distill_losses import CosineEmbeddingLoss
 from .perceptual_losses import LPIPSLoss
+from .discriminators import BaseDiscriminator, PatchGANDiscriminator, StyleGAN2Discriminator
+from .gan_losses import NonSaturatingLoss, R1GradientPenalty, VQGANDiscriminatorLoss, VQGANGeneratorLoss
 from .sequence_losses import CausalTokenLoss, LabelSmoothingCrossEntropy, MaskedTokenLoss
 from .utils import EMA, ema
 
@@ -20,6 +23,8 @@ __all__ = [
     'VQITQuantizerCallbackRegistry', 'VQITQuantizerDistanceRegistry', 'VQITQuantizerLossRegistry',
     'VQITQuantizerRegistry', 'EMA', 'ema', 'build_quantizer', 'CausalTokenLoss', 'LabelSmoothingCrossEntropy',
     'MaskedTokenLoss', 'L1Loss', 'MSELoss', 'PSNRLoss', 'SSIMLoss', 'CosineEmbeddingLoss', 'LPIPSLoss',
+    'BaseDiscriminator', 'PatchGANDiscriminator', 'StyleGAN2Discriminator', 'VQGANGeneratorLoss', 'NonSaturatingLoss',
+    'VQGANDiscriminatorLoss', 'R1GradientPenalty', 'VQDiscriminatorRegistry', 'VQGeneratorLossRegistry', 'VQDiscriminatorLossRegistry',
 ]
 __version__ = '0.1.0'
 

@@ -151,6 +151,36 @@ def lpips_grad_bound(C: int, wabs: float, h: float) -> float:
     return (16.0 * lpips_chain(C) + 136.0) * 2.0 ** -24 * (1.0 + 2.0 ** -9) * wabs * h
 
 
+SG2_MAX_C = 1 << 16                        # VQHIP_SG2_MAX_C
+SG2_SLOPE, SG2_SCALE = 0.2, 2.0 ** 0.5     # VQHIP_SG2_SLOPE, VQHIP_SG2_SCALE: the definition's constants (the kernels hold their fp32 roundings)
+SG2_U = 2.0 ** -24 * (1.0 + 2.0 ** -9)     # VQHIP_SG2_U
+
+
+def bias_act_bound(y: float) -> float:
+    """VQHIP_BIAS_ACT_BOUND(y) of include/vqhip.h: |kernel - exact| of an output (or a gx) of magnitude y, in fp32 before the store."""
+    return 4.0 * SG2_U * y
+
+
+def fir4_bound(a: float, fused: bool = False) -> float:
+    """VQHIP_FIR4_BOUND(a), or VQHIP_FIR4_ACT_BOUND(a) for the fused forms: a blur (or adjoint) output whose sources' magnitudes blur to a."""
+    return (12.0 if fused else 8.0) * SG2_U * a
+
+
+def sg2_gbias_chain(slabs: int) -> float:
+    """VQHIP_SG2_GBIAS_CHAIN(slabs): the additions one term of gbias passes through, both launches."""
+    return float(slabs // 16 + 80)
+
+
+def sg2_gbias_bound(slabs: int, e: float, sumabs: float) -> float:
+    """VQHIP_SG2_GBIAS_BOUND(slabs, e, sumabs): a gbias element; e = 4 (bias-activation) or 12 (fused blur backward)."""
+    return (sg2_gbias_chain(slabs) + e) * SG2_U * sumabs
+
+
+def sg2_store_u(dtype: int) -> float:
+    """VQHIP_SG2_STORE_U(dtype): half an ulp of the output dtype, relative (fp16 adds 2^-25 absolute)."""
+    return {DTYPE_BF16: 2.0 ** -8, DTYPE_F16: 2.0 ** -11}.get(dtype, 0.0)
+
+
 STEP_BEFORE_EXCHANGE, STEP_AFTER_EXCHANGE, STEP_ALL, STEP_PACK_SYNC = 1, 2, 3, 4
 
 # name -> (restype, argtypes); mirrors include/vqhip.h one to one
@@ -191,6 +221,12 @@ SIGNATURES = {
     'vqhip_lpips_fwd': (_i32, [_vp, _i32, _vp, _i32, _i32, _i64, _i64, _i64, _vp, _vp, _f32, _i64, _vp, _vp, _i32, _vp]),
     'vqhip_lpips_bwd': (_i32, [_vp, _i32, _vp, _i32, _i32, _i64, _i64, _i64, _vp, _vp, _f32, _i64, _vp, _vp, _vp, _vp]),
     'vqhip_lpips_keep_mask': (_i32, [_vp, _f32, _i64, _i64, _i64, _i64, _vp, _vp]),
+    'vqhip_bias_act_slabs': (_i64, [_i32, _i64, _i64, _i64]),
+    'vqhip_bias_act_fwd': (_i32, [_vp, _i32, _i32, _i64, _i64, _i64, _vp, _vp, _vp]),
+    'vqhip_bias_act_bwd': (_i32, [_vp, _vp, _i32, _i32, _i64, _i64, _i64, _vp, _vp, _vp, _i64, _vp]),
+    'vqhip_fir4_slabs': (_i64, [_i32, _i64, _i64, _i64, _i64]),
+    'vqhip_fir4_fwd': (_i32, [_vp, _i32, _i32, _i64, _i64, _i64, _i64, _i32, _i32, _i32, _i32, _i32, _vp, _vp, _vp]),
+    'vqhip_fir4_bwd': (_i32, [_vp, _i32, _i32, _i64, _i64, _i64, _i64, _i32, _i32, _i32, _i32, _i32, _vp, _vp, _vp, _vp, _vp, _i64, _vp]),
     'vqhip_image_metrics_workspace_bytes': (_i64, [_i64, _i64, _i64, _i64]),
     'vqhip_image_metrics': (_i32, [_vp, _i32, _i32, _vp, _i32, _i32, _i64, _i64, _i64, _i64, _i32, _f64, _f64, _vp, _i64, _vp, _vp,
                                    _vp, _vp]),

@@ -13,6 +13,7 @@
 #include "vqhip_token_ce_kernels.h"
 #include "vqhip_cosine_embed_kernels.h"
 #include "vqhip_lpips_kernels.h"
+#include "vqhip_stylegan2_kernels.h"
 #include "vqhip_image_metrics_kernels.h"
 
 static thread_local char g_err[256] = "";
@@ -582,6 +583,56 @@ static int launch_lpips_bwd(const VqLpipsArgs &a, int layout, const float *stats
         VQ_CHECK_LAUNCH("lpips_map_bwd_kernel");
     }
     return VQHIP_OK;
+}
+
+// ---- StyleGAN2 discriminator ops: the launches (vqhip_stylegan2_kernels.h) ---------------------------------------------------
+template <int DT>
+static int launch_bias_act_fwd(const VqBiasActArgs &a, bool rows, hipStream_t s) {
+    const int64_t pieces = (a.n + SampleElem<DT>::W - 1) / SampleElem<DT>::W;
+    const int64_t blocks = (pieces + VQ_SG2_THREADS - 1) / VQ_SG2_THREADS;
+    const unsigned grid = (unsigned)(blocks < 8192 ? blocks : 8192);
+    if (rows) bias_act_fwd_kernel<DT, true><<<grid, VQ_SG2_THREADS, 0, s>>>(a);
+    else bias_act_fwd_kernel<DT, false><<<grid, VQ_SG2_THREADS, 0, s>>>(a);
+    VQ_CHECK_LAUNCH("bias_act_fwd_kernel");
+    return VQHIP_OK;
+}
+
+static int launch_sg2_reduce(const float *ws, int64_t slabs, int C, float *gbias, hipStream_t s) {
+    sg2_reduce_kernel<<<(unsigned)((C + VQ_SG2_RED - 1) / VQ_SG2_RED), VQ_SG2_THREADS, 0, s>>>(ws, slabs, C, gbias);
+    VQ_CHECK_LAUNCH("sg2_reduce_kernel");
+    return VQHIP_OK;
+}
+
+template <int DT>
+static int launch_bias_act_bwd(const VqBiasActArgs &a, bool rows, int64_t slabs, float *gbias, hipStream_t s) {
+    if (rows) {
+        const int per = 64 * SampleElem<DT>::W;
+        bias_act_bwd_rows_kernel<DT><<<dim3((unsigned)slabs, (unsigned)((a.C + per - 1) / per)), VQ_SG2_THREADS, 0, s>>>(a);
+        VQ_CHECK_LAUNCH("bias_act_bwd_rows_kernel");
+    } else {
+        bias_act_bwd_map_kernel<DT><<<(unsigned)((int64_t)a.B * a.C * a.chunks), VQ_SG2_THREADS, 0, s>>>(a);
+        VQ_CHECK_LAUNCH("bias_act_bwd_map_kernel");
+    }
+    return gbias ? launch_sg2_reduce(a.ws, slabs, a.C, gbias, s) : VQHIP_OK;
+}
+
+template <int DT, bool ROWS, int DOWN, int FUSED>
+static int launch_fir4_one(const VqFirArgs &a, hipStream_t s) {
+    const int64_t grid = (int64_t)a.B * a.cblocks * a.tiles_y * a.tiles_x;
+    fir4_kernel<DT, ROWS, DOWN, FUSED><<<(unsigned)grid, VQ_SG2_THREADS, 0, s>>>(a);
+    VQ_CHECK_LAUNCH("fir4_kernel");
+    return VQHIP_OK;
+}
+
+template <int DT>
+static int launch_fir4(const VqFirArgs &a, bool rows, int down, int fused, hipStream_t s) {
+#define VQ_FIR_CASE(R, D, F) if (rows == R && down == D && fused == F) return launch_fir4_one<DT, R, D, F>(a, s)
+    VQ_FIR_CASE(false, 1, VQ_FIR_NONE); VQ_FIR_CASE(false, 1, VQ_FIR_ACT_IN); VQ_FIR_CASE(false, 1, VQ_FIR_MASK_OUT);
+    VQ_FIR_CASE(false, 2, VQ_FIR_NONE); VQ_FIR_CASE(false, 2, VQ_FIR_ACT_IN);
+    VQ_FIR_CASE(true, 1, VQ_FIR_NONE); VQ_FIR_CASE(true, 1, VQ_FIR_ACT_IN); VQ_FIR_CASE(true, 1, VQ_FIR_MASK_OUT);
+    VQ_FIR_CASE(true, 2, VQ_FIR_NONE); VQ_FIR_CASE(true, 2, VQ_FIR_ACT_IN);
+#undef VQ_FIR_CASE
+    return fail(VQHIP_EINVAL, "fir4", "no kernel of this form");
 }
 
 extern "C" {
@@ -1548,6 +1599,121 @@ int vqhip_lpips_keep_mask(const uint32_t *seed, float p, int64_t layer, int64_t 
     VQ_CHECK_LAUNCH("lpips_keep_mask_kernel");
     return VQHIP_OK;
 }
+
+// ---- StyleGAN2 discriminator ops (vqhip_stylegan2_kernels.h) -----------------------------------------------------------------
+#define VQ_SG2_DISPATCH(fn, ...)                                                                                        \
+    do {                                                                                                                \
+        switch (dtype) {                                                                                                \
+        case VQHIP_DTYPE_F32: return fn<VQHIP_DTYPE_F32>(__VA_ARGS__);                                                  \
+        case VQHIP_DTYPE_BF16: return fn<VQHIP_DTYPE_BF16>(__VA_ARGS__);                                                \
+        default: return fn<VQHIP_DTYPE_F16>(__VA_ARGS__);                                                               \
+        }                                                                                                               \
+    } while (0)
+
+// what every entry point of the block refuses alike
+static int sg2_common(const char *what, int dtype, int layout, int64_t B, int64_t C, int64_t P) {
+    if (dtype != VQHIP_DTYPE_F32 && dtype != VQHIP_DTYPE_BF16 && dtype != VQHIP_DTYPE_F16) return fail(VQHIP_EINVAL, what, "dtype");
+    if (layout != VQHIP_LAYOUT_ROWS && layout != VQHIP_LAYOUT_MAP) return fail(VQHIP_EINVAL, what, "layout");
+    const int64_t cap = 1ll << 31;
+    if (B < 1 || C < 1 || P < 1 || B >= cap || P >= cap || C > VQHIP_SG2_MAX_C) return fail(VQHIP_EINVAL, what, "need B, P >= 1 and 1 <= C <= 2^16");
+    if (B * P >= cap || B * P * C >= cap) return fail(VQHIP_EINVAL, what, "B * C * P must be below 2^31");
+    return VQHIP_OK;
+}
+
+// a [B, C] matrix (P == 1) is the same memory in both layouts: it takes the rows kernels
+static inline bool sg2_rows(int layout, int64_t P) { return layout == VQHIP_LAYOUT_ROWS || P == 1; }
+
+int64_t vqhip_bias_act_slabs(int layout, int64_t B, int64_t C, int64_t P) {
+    if (sg2_common("vqhip_bias_act_slabs", VQHIP_DTYPE_F32, layout, B, C, P)) return -1;
+    if (sg2_rows(layout, P)) return (B * P + VQ_SG2_ROWS_SLAB - 1) / VQ_SG2_ROWS_SLAB;
+    return B * ((P + VQ_SG2_MAP_CHUNK - 1) / VQ_SG2_MAP_CHUNK);
+}
+
+int vqhip_bias_act_fwd(const void *x, int dtype, int layout, int64_t B, int64_t C, int64_t P, const float *bias, void *y, void *stream) {
+    if (int rc = sg2_common("vqhip_bias_act_fwd", dtype, layout, B, C, P)) return rc;
+    VQ_REQUIRE(x && bias && y, "vqhip_bias_act_fwd: x, bias and y are required");
+    VqBiasActArgs a = {};
+    a.x = x; a.bias = bias; a.out = y; a.n = B * C * P; a.B = (int)B; a.C = (int)C; a.P = (int)P;
+    VQ_SG2_DISPATCH(launch_bias_act_fwd, a, sg2_rows(layout, P), (hipStream_t)stream);
+}
+
+int vqhip_bias_act_bwd(const void *g, const void *y, int dtype, int layout, int64_t B, int64_t C, int64_t P, void *gx, float *gbias,
+                       float *ws, int64_t ws_bytes, void *stream) {
+    if (int rc = sg2_common("vqhip_bias_act_bwd", dtype, layout, B, C, P)) return rc;
+    VQ_REQUIRE(g && y && gx, "vqhip_bias_act_bwd: g, y and gx are required");
+    VQ_REQUIRE(!gbias || ws, "vqhip_bias_act_bwd: gbias needs the workspace");
+    const int64_t slabs = vqhip_bias_act_slabs(layout, B, C, P);
+    if (gbias) VQ_NEED("vqhip_bias_act_bwd: ws too small", ws_bytes, slabs * C * (int64_t)sizeof(float));
+    VQ_REQUIRE(B * C * ((P + VQ_SG2_MAP_CHUNK - 1) / VQ_SG2_MAP_CHUNK) < (1ll << 31), "vqhip_bias_act_bwd: B * C * ceil(P / 4096) is beyond one launch");
+    VqBiasActArgs a = {};
+    a.x = g; a.y = y; a.out = gx; a.ws = gbias ? ws : nullptr; a.n = B * C * P; a.B = (int)B; a.C = (int)C; a.P = (int)P;
+    a.chunks = (int)((P + VQ_SG2_MAP_CHUNK - 1) / VQ_SG2_MAP_CHUNK);
+    VQ_SG2_DISPATCH(launch_bias_act_bwd, a, sg2_rows(layout, P), slabs, gbias, (hipStream_t)stream);
+}
+
+// the sizes and tiles of a blur: (H, W) the blur's INPUT plane, (OH, OW) its output; `adjoint` walks tiles of the input plane
+static int fir4_setup(const char *what, int dtype, int layout, int64_t B, int64_t C, int64_t H, int64_t W, int down, int py0, int py1,
+                      int px0, int px1, bool adjoint, VqFirArgs *a) {
+    const int64_t cap = 1ll << 31;
+    if (H < 1 || W < 1 || H >= cap || W >= cap || H * W >= cap) return fail(VQHIP_EINVAL, what, "H * W must be in 1 .. 2^31 - 1");
+    if (int rc = sg2_common(what, dtype, layout, B, C, H * W)) return rc;
+    if (down != 1 && down != 2) return fail(VQHIP_EINVAL, what, "down must be 1 or 2");
+    for (int p : {py0, py1, px0, px1})
+        if (p < 0 || p > 3) return fail(VQHIP_EINVAL, what, "every padding must be in 0 .. 3");
+    if (H + py0 + py1 < 4 || W + px0 + px1 < 4) return fail(VQHIP_EINVAL, what, "the padded plane is smaller than the 4 x 4 filter");
+    const int64_t OH = (H + py0 + py1 - 4) / down + 1, OW = (W + px0 + px1 - 4) / down + 1;
+    const bool rows = layout == VQHIP_LAYOUT_ROWS;
+    const int CB = rows ? FirTile<true>::CB : FirTile<false>::CB;
+    const int TOH = rows ? FirTile<true>::TOH : FirTile<false>::TOH, TOW = rows ? FirTile<true>::TOW : FirTile<false>::TOW;
+    a->B = (int)B; a->C = (int)C;
+    if (adjoint) {
+        a->IH = (int)OH; a->IW = (int)OW; a->OH = (int)H; a->OW = (int)W;
+        a->up = down; a->offy = 3 - py0; a->offx = 3 - px0;
+    } else {
+        a->IH = (int)H; a->IW = (int)W; a->OH = (int)OH; a->OW = (int)OW;
+        a->up = 1; a->offy = py0; a->offx = px0;
+    }
+    a->cblocks = (int)((C + CB - 1) / CB);
+    a->tiles_y = (a->OH + TOH - 1) / TOH; a->tiles_x = (a->OW + TOW - 1) / TOW;
+    if (B * a->cblocks * a->tiles_y * a->tiles_x >= cap) return fail(VQHIP_EINVAL, what, "the number of tiles is beyond one launch");
+    return VQHIP_OK;
+}
+
+int64_t vqhip_fir4_slabs(int layout, int64_t B, int64_t C, int64_t H, int64_t W) {
+    VqFirArgs a = {};
+    if (fir4_setup("vqhip_fir4_slabs", VQHIP_DTYPE_F32, layout, B, C, H, W, 1, 2, 2, 2, 2, true, &a)) return -1;
+    return B * a.tiles_y * a.tiles_x;
+}
+
+int vqhip_fir4_fwd(const void *x, int dtype, int layout, int64_t B, int64_t C, int64_t H, int64_t W, int down, int py0, int py1, int px0,
+                   int px1, const float *bias, void *out, void *stream) {
+    VqFirArgs a = {};
+    if (int rc = fir4_setup("vqhip_fir4_fwd", dtype, layout, B, C, H, W, down, py0, py1, px0, px1, false, &a)) return rc;
+    VQ_REQUIRE(x && out, "vqhip_fir4_fwd: x and out are required");
+    a.in = x; a.out = out; a.bias = bias;
+    VQ_SG2_DISPATCH(launch_fir4, a, layout == VQHIP_LAYOUT_ROWS, down, bias ? VQ_FIR_ACT_IN : VQ_FIR_NONE, (hipStream_t)stream);
+}
+
+extern "C++" {
+template <int DT>
+static int fir4_bwd_run(const VqFirArgs &a, bool rows, float *gbias, hipStream_t s) {
+    if (int rc = launch_fir4<DT>(a, rows, 1, a.x ? VQ_FIR_MASK_OUT : VQ_FIR_NONE, s)) return rc;
+    return a.x ? launch_sg2_reduce(a.ws, (int64_t)a.B * a.tiles_y * a.tiles_x, a.C, gbias, s) : VQHIP_OK;
+}
+}  // extern "C++"
+
+int vqhip_fir4_bwd(const void *g, int dtype, int layout, int64_t B, int64_t C, int64_t H, int64_t W, int down, int py0, int py1, int px0,
+                   int px1, const void *x, const float *bias, void *gx, float *gbias, float *ws, int64_t ws_bytes, void *stream) {
+    VqFirArgs a = {};
+    if (int rc = fir4_setup("vqhip_fir4_bwd", dtype, layout, B, C, H, W, down, py0, py1, px0, px1, true, &a)) return rc;
+    VQ_REQUIRE(g && gx, "vqhip_fir4_bwd: g and gx are required");
+    VQ_REQUIRE((x != nullptr) == (bias != nullptr), "vqhip_fir4_bwd: the fused form needs x and bias together");
+    VQ_REQUIRE(!x || (gbias && ws), "vqhip_fir4_bwd: the fused form needs gbias and the workspace");
+    if (x) VQ_NEED("vqhip_fir4_bwd: ws too small", ws_bytes, (int64_t)B * a.tiles_y * a.tiles_x * C * (int64_t)sizeof(float));
+    a.in = g; a.out = gx; a.x = x; a.bias = bias; a.ws = ws;
+    VQ_SG2_DISPATCH(fir4_bwd_run, a, layout == VQHIP_LAYOUT_ROWS, gbias, (hipStream_t)stream);
+}
+#undef VQ_SG2_DISPATCH
 
 // ---- fused reconstruction metrics (vqhip_image_metrics_kernels.h) ---------------------------------------------------------
 // what both entry points refuse; on success the number of workgroups of the first launch and the tiles along each axis

@@ -425,3 +425,129 @@ def lpips_distance(pred_features, target_features, weights, seed: Optional[torch
         raise ValueError(f'lpips_distance: need as many targets and weights as pred features, got {n}, {len(target_features)}, {len(weights)}')
     return _LpipsDistance.apply(seed, float(p), n, *pred_features, *(t.detach() for t in target_features), *(w.detach() for w in weights))
 
+
+# ---- StyleGAN2 discriminator ops: every backward is linear in the incoming gradient and is itself a Function, so a graph built
+#      with create_graph=True (R1GradientPenalty) differentiates through it: the second derivative with respect to x is zero ----
+
+class _BiasActBackward(Function):
+    """(gx, gbias) = vqhip_bias_act_bwd(g; y).  Its derivative with respect to g is the same call on ggx + ggbias[c]."""
+
+    @staticmethod
+    def forward(ctx, g, y, need_gbias):
+        ctx.set_materialize_grads(False)
+        ctx.save_for_backward(y)
+        gx, gbias = ops.bias_act_backward(g, y, need_gbias)
+        if gbias is None:
+            gbias = g.new_zeros(0)
+            ctx.mark_non_differentiable(gbias)
+        return gx, gbias
+
+    @staticmethod
+    def backward(ctx, ggx, ggbias):
+        y, = ctx.saved_tensors
+        if ggbias is not None and ggbias.numel():
+            shape = (1, -1) + (1,) * (y.dim() - 2)
+            term = ggbias.to(y.dtype).view(shape).expand_as(y)
+            ggx = term if ggx is None else ggx + term
+        if ggx is None:
+            return None, None, None
+        return _BiasActBackward.apply(ggx, y, False)[0], None, None
+
+
+class _BiasAct(Function):
+    """vqhip_bias_act_fwd; saves the OUTPUT only (its sign selects the branch of the backward)."""
+
+    @staticmethod
+    def forward(ctx, x, bias):
+        y = ops.bias_act(x, bias)
+        ctx.save_for_backward(y)
+        ctx.bias_dtype = bias.dtype
+        return y
+
+    @staticmethod
+    def backward(ctx, g):
+        y, = ctx.saved_tensors
+        gx, gbias = _BiasActBackward.apply(g, y, ctx.needs_input_grad[1])
+        return gx, (gbias.to(ctx.bias_dtype) if ctx.needs_input_grad[1] else None)
+
+
+def bias_act(x: torch.Tensor, bias: torch.Tensor) -> torch.Tensor:
+    """``leaky_relu(x + bias[c], 0.2) * 2**0.5`` (mmcv's FusedBiasLeakyReLU) of a [B, C] or [B, C, H, W] activation in its dtype and
+    memory format, with gradients to both; twice differentiable (the double backward is ``gg * scale * mask``)."""
+    return _BiasAct.apply(x, bias)
+
+
+class _Fir4Backward(Function):
+    """The adjoint of the blur; its derivative is the blur."""
+
+    @staticmethod
+    def forward(ctx, g, size, pad, down):
+        ctx.pad, ctx.down = pad, down
+        return ops.fir4_backward(g, size, pad, down)
+
+    @staticmethod
+    def backward(ctx, gg):
+        return _Fir4.apply(ops.sg2_dense(gg), ctx.pad, ctx.down), None, None, None
+
+
+class _Fir4(Function):
+    @staticmethod
+    def forward(ctx, x, pad, down):
+        ctx.pad, ctx.down, ctx.size = pad, down, tuple(x.shape[2:])
+        return ops.fir4(x, pad, down)
+
+    @staticmethod
+    def backward(ctx, g):
+        return _Fir4Backward.apply(g, ctx.size, ctx.pad, ctx.down), None, None
+
+
+def blur(x: torch.Tensor, pad=2, down: int = 1) -> torch.Tensor:
+    """``upfirdn2d(x, outer([1, 3, 3, 1]) / 64, padding=pad)`` keeping every ``down``-th output, with the exact adjoint as its
+    gradient; differentiable any number of times (the blur is linear)."""
+    return _Fir4.apply(x, pad, down)
+
+
+class _BiasActBlurBackward(Function):
+    """(gx, gbias) = vqhip_fir4_bwd(g; x, bias), linear in g.  Its derivative with respect to g is blur((ggx + ggbias[c]) * factor),
+    formed from three launches of the unfused kernels (a path only a create_graph=True penalty takes)."""
+
+    @staticmethod
+    def forward(ctx, g, x, bias, pad, down):
+        ctx.set_materialize_grads(False)
+        ctx.save_for_backward(x, bias)
+        ctx.pad, ctx.down = pad, down
+        return ops.fir4_backward(g, x.shape[2:], pad, down, x=x, bias=bias)
+
+    @staticmethod
+    def backward(ctx, ggx, ggbias):
+        x, bias = ctx.saved_tensors
+        if ggbias is not None:
+            term = ggbias.to(x.dtype).view(1, -1, 1, 1).expand_as(x)
+            ggx = term if ggx is None else ggx + term
+        if ggx is None:
+            return None, None, None, None, None
+        y = ops.bias_act(x, bias)                            # the sign of the activation, recomputed: nothing else was kept
+        masked = _BiasActBackward.apply(ggx, y, False)[0]
+        return _Fir4.apply(masked, ctx.pad, ctx.down), None, None, None, None
+
+
+class _BiasActBlur(Function):
+    """vqhip_fir4_fwd with a bias: blur(act(x + bias)) from one read of the convolution's output, which is what it saves."""
+
+    @staticmethod
+    def forward(ctx, x, bias, pad, down):
+        ctx.save_for_backward(x, bias)
+        ctx.pad, ctx.down = pad, down
+        return ops.fir4(x, pad, down, bias=bias)
+
+    @staticmethod
+    def backward(ctx, g):
+        x, bias = ctx.saved_tensors
+        gx, gbias = _BiasActBlurBackward.apply(g, x, bias, ctx.pad, ctx.down)
+        return gx, (gbias.to(bias.dtype) if ctx.needs_input_grad[1] else None), None, None
+
+
+def bias_act_blur(x: torch.Tensor, bias: torch.Tensor, pad=2, down: int = 1) -> torch.Tensor:
+    """``blur(bias_act(x, bias), pad, down)`` in one launch: one read of ``x``, one write of the blurred map; the backward writes
+    ``gx`` and ``gbias`` in one call from the saved ``x``.  Twice differentiable."""
+    return _BiasActBlur.apply(x, bias, pad, down)

@@ -1069,6 +1069,174 @@ def lpips_distance(pred_features, target_features, weights, seed: Optional[torch
     return functional.lpips_distance(pred_features, target_features, weights, seed, p)
 
 
+# ---- StyleGAN2 discriminator ops (vq/algorithms/vqgan/discriminators/stylegan2.py: FusedBiasLeakyReLU and upfirdn2d) ------------
+
+SG2_LAYOUTS = {'rows': _lib.LAYOUT_ROWS, 'map': _lib.LAYOUT_MAP}
+FIR4_PADS = ((2, 2), (1, 1))                                # Blur's padding for the 3 x 3 and the 1 x 1 downsampling convolution
+
+
+def sg2_layout(t: torch.Tensor):
+    """The layout of include/vqhip.h a [B, C] or [B, C, H, W] tensor is dense in: 'map' (contiguous) before 'rows' (channels-last), or None."""
+    if t.is_contiguous():
+        return 'map'
+    if t.dim() == 4 and t.is_contiguous(memory_format=torch.channels_last):
+        return 'rows'
+    return None
+
+
+def stylegan2_refusal(x: torch.Tensor, bias: Optional[torch.Tensor] = None, *, kernel_size: Optional[int] = None) -> str:
+    """Why vqhip_bias_act_* / vqhip_fir4_* would refuse this activation ('' if they would not): the clauses of their LIMITS that
+    depend on the tensor's dtype, shape and strides.  ``bias``: [C]; ``kernel_size``: of the convolution a Blur serves (3 or 1)."""
+    if x.dtype not in SAMPLE_DTYPES:
+        return f'the activation is {x.dtype}, not float32, bfloat16 or float16'
+    if x.dim() not in (2, 4):
+        return f'the activation is {x.dim()}-D, not [B, C] or [B, C, H, W]'
+    if x.numel() == 0:
+        return f'empty activation {tuple(x.shape)}'
+    if sg2_layout(x) is None:
+        return f'the activation with strides {x.stride()} is neither NCHW-contiguous nor channels-last dense'
+    if x.shape[1] > _lib.SG2_MAX_C:
+        return f'C={x.shape[1]} is beyond 2^16'
+    if x.numel() >= (1 << 31):
+        return f'{x.numel()} elements are outside 1 .. 2^31-1'
+    if bias is not None and bias.numel() != x.shape[1]:
+        return f'the bias has {bias.numel()} elements, not C={x.shape[1]}'
+    if kernel_size is not None and kernel_size not in (1, 3):
+        return f'kernel_size={kernel_size}: the blur paddings are known for 3 and 1 only'
+    return ''
+
+
+def _sg2_head(what: str, x: torch.Tensor, bias=None):
+    _require_cuda(x, bias)
+    why = stylegan2_refusal(x, bias)
+    if why:
+        raise ValueError(f'{what}: {why}')
+    B, C = x.shape[:2]
+    return SAMPLE_DTYPES[x.dtype], SG2_LAYOUTS[sg2_layout(x)], B, C, x.numel() // (B * C)
+
+
+def _sg2_bias(bias: torch.Tensor) -> torch.Tensor:
+    """The bias as the kernels read it: fp32, contiguous (a copy of C elements only where the parameter is not fp32 already)."""
+    return bias.detach().reshape(-1).to(torch.float32).contiguous()
+
+
+def sg2_dense(t: torch.Tensor) -> torch.Tensor:
+    """``t`` itself where it is dense in one of the two layouts, else a contiguous copy: autograd hands over gradients with any
+    strides (the expanded scalar of ``.sum().backward()`` has none but zeros)."""
+    return t if sg2_layout(t) is not None else t.contiguous()
+
+
+def _sg2_dense_like(t: torch.Tensor, like: torch.Tensor) -> torch.Tensor:
+    """``t`` dense in the layout the kernels read ``like`` in (a copy only where autograd handed over another memory format)."""
+    if sg2_layout(like) == 'rows':
+        return t if t.is_contiguous(memory_format=torch.channels_last) else t.contiguous(memory_format=torch.channels_last)
+    return t if t.is_contiguous() else t.contiguous()
+
+
+@_on_tensor_device
+def bias_act(x: torch.Tensor, bias: torch.Tensor) -> torch.Tensor:
+    """vqhip_bias_act_fwd: ``leaky_relu(x + bias[c], 0.2) * 2**0.5`` of a [B, C] or [B, C, H, W] activation, read in place, in its
+    dtype and memory format (NCHW or channels-last).  One launch."""
+    dtype, layout, B, C, P = _sg2_head('bias_act', x, bias)
+    b = _sg2_bias(bias)
+    y = torch.empty_like(x)
+    check(_lib.lib().vqhip_bias_act_fwd(_ptr(x), dtype, layout, B, C, P, _ptr(b), _ptr(y), _stream()), 'vqhip_bias_act_fwd')
+    return y
+
+
+@_on_tensor_device
+def bias_act_backward(g: torch.Tensor, y: torch.Tensor, need_gbias: bool = True):
+    """vqhip_bias_act_bwd: ``(gx, gbias)`` from the incoming gradient and the SAVED OUTPUT ``y`` (the sign of y selects the branch;
+    x is not kept).  ``gx`` in g's dtype and layout, ``gbias`` fp32 [C] from a fixed-order two-stage sum (None without
+    ``need_gbias``).  Linear in ``g``: the same call on a second-order gradient is its derivative."""
+    dtype, layout, B, C, P = _sg2_head('bias_act_backward', y)
+    _require_cuda(g)
+    if g.shape != y.shape or g.dtype != y.dtype:
+        raise ValueError(f'bias_act_backward: g is {g.dtype} {tuple(g.shape)}, y {y.dtype} {tuple(y.shape)}')
+    g = _sg2_dense_like(g, y)
+    gx = torch.empty_like(y)
+    gbias = ws = None
+    if need_gbias:
+        slabs = _lib.lib().vqhip_bias_act_slabs(layout, B, C, P)
+        ws = torch.empty(slabs * C, dtype=torch.float32, device=y.device)
+        gbias = torch.empty(C, dtype=torch.float32, device=y.device)
+    check(_lib.lib().vqhip_bias_act_bwd(_ptr(g), _ptr(y), dtype, layout, B, C, P, _ptr(gx), _ptr(gbias), _ptr(ws),
+                                        0 if ws is None else ws.numel() * 4, _stream()), 'vqhip_bias_act_bwd')
+    return gx, gbias
+
+
+def fir4_out_size(H: int, W: int, pad, down: int) -> tuple:
+    """(OH, OW) of the blur of an H x W plane: ``(H + py0 + py1 - 4) // down + 1``; ``pad`` = (py0, py1, px0, px1)."""
+    py0, py1, px0, px1 = pad
+    return (H + py0 + py1 - 4) // down + 1, (W + px0 + px1 - 4) // down + 1
+
+
+def _fir4_pad(what: str, pad, down: int) -> tuple:
+    pad = (pad,) * 4 if isinstance(pad, int) else tuple(pad)
+    pad = pad * 2 if len(pad) == 2 else pad                 # a symmetric (p0, p1) pair serves both axes, whichever way mmcv reads it
+    if len(pad) != 4 or any(not 0 <= int(p) <= 3 for p in pad) or down not in (1, 2):
+        raise ValueError(f'{what}: need four paddings in 0 .. 3 and down in (1, 2), got {pad!r}, {down!r}')
+    return tuple(int(p) for p in pad)
+
+
+def _fir4_like(x: torch.Tensor, shape) -> torch.Tensor:
+    fmt = torch.channels_last if sg2_layout(x) == 'rows' else torch.contiguous_format
+    return torch.empty(shape, dtype=x.dtype, device=x.device, memory_format=fmt)
+
+
+@_on_tensor_device
+def fir4(x: torch.Tensor, pad=2, down: int = 1, bias: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """vqhip_fir4_fwd: the blur ``upfirdn2d(x, outer([1, 3, 3, 1]) / 64, padding)`` of a [B, C, H, W] map per channel with zero
+    padding ``pad`` = p | (p0, p1) | (py0, py1, px0, px1), keeping every ``down``-th output (only those are computed).  With
+    ``bias`` the input passes through bias-activation on the way in: ``blur(bias_act(x, bias))`` from one read of x.  One launch."""
+    dtype, layout, B, C, P = _sg2_head('fir4', x, bias)
+    if x.dim() != 4:
+        raise ValueError(f'fir4: need a [B, C, H, W] map, got {tuple(x.shape)}')
+    pad = _fir4_pad('fir4', pad, down)
+    H, W = x.shape[2:]
+    OH, OW = fir4_out_size(H, W, pad, down)
+    if OH < 1 or OW < 1:
+        raise ValueError(f'fir4: the padded {H} x {W} plane is smaller than the filter')
+    b = None if bias is None else _sg2_bias(bias)
+    out = _fir4_like(x, (B, C, OH, OW))
+    check(_lib.lib().vqhip_fir4_fwd(_ptr(x), dtype, layout, B, C, H, W, down, *pad, _ptr(b), _ptr(out), _stream()), 'vqhip_fir4_fwd')
+    return out
+
+
+@_on_tensor_device
+def fir4_backward(g: torch.Tensor, size, pad=2, down: int = 1, x: Optional[torch.Tensor] = None, bias: Optional[torch.Tensor] = None):
+    """vqhip_fir4_bwd: the exact adjoint of ``fir4`` for an input plane of ``size`` = (H, W): ``gx`` [B, C, H, W] in g's dtype and
+    layout.  With ``x`` and ``bias`` (the saved input of the fused forward) returns ``(gx, gbias)``:
+    ``gx = adjoint(g) * scale * (x + bias > 0 ? 1 : slope)`` and its per-channel sum, fp32 [C], in a fixed order."""
+    if g.dim() != 4 or (x is None) != (bias is None):
+        raise ValueError('fir4_backward: need a [B, C, OH, OW] gradient, and x and bias together or neither')
+    _require_cuda(g, x)
+    if x is not None and sg2_layout(x) is None:
+        raise ValueError(f'fir4_backward: x with strides {x.stride()} is neither NCHW-contiguous nor channels-last dense')
+    g = sg2_dense(g) if x is None else _sg2_dense_like(g, x)                    # (in x's layout for the fused form)
+    dtype, layout, B, C, _ = _sg2_head('fir4_backward', g)
+    pad = _fir4_pad('fir4_backward', pad, down)
+    H, W = (int(v) for v in size)
+    if tuple(g.shape[2:]) != fir4_out_size(H, W, pad, down):
+        raise ValueError(f'fir4_backward: g is {tuple(g.shape)}, the blur of a {H} x {W} plane gives {fir4_out_size(H, W, pad, down)}')
+    gbias = ws = b = None
+    if x is not None:
+        _require_cuda(bias)
+        if x.dtype != g.dtype or tuple(x.shape) != (B, C, H, W):
+            raise ValueError(f'fir4_backward: x must be a dense {g.dtype} [{B}, {C}, {H}, {W}] map')
+        layout = SG2_LAYOUTS[sg2_layout(x)]
+        b = _sg2_bias(bias)
+        slabs = _lib.lib().vqhip_fir4_slabs(layout, B, C, H, W)
+        ws = torch.empty(slabs * C, dtype=torch.float32, device=g.device)
+        gbias = torch.empty(C, dtype=torch.float32, device=g.device)
+    gx = _fir4_like(g if x is None else x, (B, C, H, W))
+    if gx.numel() >= (1 << 31):
+        raise ValueError(f'fir4_backward: {gx.numel()} elements are outside 1 .. 2^31-1')
+    check(_lib.lib().vqhip_fir4_bwd(_ptr(g), dtype, layout, B, C, H, W, down, *pad, _ptr(x), _ptr(b), _ptr(gx), _ptr(gbias), _ptr(ws),
+                                    0 if ws is None else ws.numel() * 4, _stream()), 'vqhip_fir4_bwd')
+    return gx if x is None else (gx, gbias)
+
+
 # ---- fused reconstruction metrics (validation: vq/runners/metrics/loss.py over vq/tasks/image_reconstruction/losses.py) -----
 
 IMAGE_DTYPES = {torch.float32: _lib.DTYPE_F32, torch.bfloat16: _lib.DTYPE_BF16, torch.float16: _lib.DTYPE_F16,

@@ -15,6 +15,7 @@ shape, dtype, alignment, the probability buffer, the world size, train / eval). 
     image_metrics_why  fused | torch
     cosine_embedding_why  fused | torch
     lpips_why             fused | torch
+    stylegan2_why         fused | torch
     multinomial_anchor_why  fused | matrix
 """
 from __future__ import annotations
@@ -527,6 +528,30 @@ def lpips_why(loss, pred_features, target_features) -> Route:
         if not why:
             refusal = ops.lpips_refusal(f, g, None if loss is None else loss._convs[layer].weight)
             why = f'layer {layer}: {refusal}' if refusal else ''
+    return Route('torch', why) if why else Route('fused')
+
+
+# ---- the StyleGAN2 discriminator of a VQGAN step (vector_quantization_amd/discriminators.py) ------------------------------------
+
+def stylegan2_why(module, x: torch.Tensor) -> Route:
+    """The bias-activations and blurs of ``StyleGAN2Discriminator`` (or of one of its layers): the HIP kernels of
+    ``functional.bias_act`` / ``blur`` / ``bias_act_blur`` on the activations as they are (``fused``), or the same definitions in
+    plain torch (``torch``), with the first clause that refused the kernels: ``fused=False`` on the module, a class that overrides
+    ``forward``, a Blur for a kernel size other than 3 or 1 (its paddings are not known here), a CPU tensor, float64 (or any dtype
+    the kernels do not read), strides that are neither NCHW-contiguous nor channels-last dense.  No shape is sent to ``torch``
+    for speed: profiles/stylegan2.txt has the measurements."""
+    from .. import discriminators
+    why = ''
+    if module is not None:
+        why = '' if getattr(module, 'fused', True) else 'fused=False'
+        if not why and isinstance(module, discriminators.StyleGAN2Discriminator):
+            why = own(module, discriminators.StyleGAN2Discriminator, 'forward')
+        for m in ([] if why else module.modules()):
+            if isinstance(m, discriminators.Blur) and m._kernel_size not in (1, 3):
+                why = f'a Blur for kernel_size={m._kernel_size}: the paddings are known for 3 and 1 only'
+                break
+    why = why or ('' if x.is_cuda else f'the input is on device {x.device}, not on a GPU')
+    why = why or ops.stylegan2_refusal(x)
     return Route('torch', why) if why else Route('fused')
 
 
