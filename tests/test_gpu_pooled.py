@@ -1,6 +1,8 @@
 """Pooled code features on the MI355X: tokens [B, *] -> [B, D] mean of the decoded rows in one launch, held bit for bit to the
 numpy restatement of the contract (tests/pooled_ref.py), to the float64 mean within the derived bound, and — through the
 modules — to `decode` + mean, whose [B*HW, D] matrix it must not allocate."""
+import gc
+
 import numpy as np
 import pytest
 import torch
@@ -277,6 +279,7 @@ def test_the_decoded_matrix_is_never_allocated():
     matrix = B * HW * D * 4
 
     def peak_over_baseline(fn):
+        gc.collect()                 # garbage of earlier tests freed DURING fn would lower the peak over the baseline
         torch.cuda.synchronize()
         torch.cuda.empty_cache()
         torch.cuda.reset_peak_memory_stats()
