@@ -689,6 +689,65 @@ int vqhip_fir4_bwd(const void *g /* [B, C, OH, OW] */, int dtype, int layout, in
                    int py1, int px0, int px1, const void *x /* [B, C, H, W], or NULL */, const float *bias /* with x */,
                    void *gx /* [B, C, H, W] */, float *gbias /* [C], with x */, float *ws, int64_t ws_bytes, void *stream);
 
+/* ---- GroupNorm with an optional fused SiLU, forward and backward ----------------------------------------------------------------
+ * The step in front of every convolution of VQGANEncoder / VQGANDecoder (vq/algorithms/vqgan/autoencoder.py: GroupNorm(32, C, 1e-6)
+ * followed by SiLU; GroupNorm alone in Attention).  No copy, no atomics, no memset, no allocation and no synchronisation.  One launch
+ * where a group fits one workgroup (n <= 8192), two otherwise; the backward adds the two launches of the dgamma / dbeta second stage.
+ * INPUT   a logical [B, C, P] tensor (P = H W) in VQHIP_LAYOUT_MAP (NCHW-contiguous: a group is one contiguous run) or
+ *   VQHIP_LAYOUT_ROWS (channels-last dense: a group is C / G adjacent channels at every position), VQHIP_DTYPE_F32, _BF16 or _F16,
+ *   element alignment only; y and gx in the same dtype and layout.  gamma, beta, dgamma, dbeta [C] and stats [B G 2] are fp32.
+ *   Every element is converted to fp32 exactly; all arithmetic is fp32 IEEE without contraction; a result is rounded to nearest
+ *   even into the output dtype.
+ * DEFINITION  for image b and group g, over the n = (C / G) P values of the group:
+ *       mean = sum x / n;   var = sum (x - mean)^2 / n  (biased);   rstd = 1 / sqrt(var + eps)
+ *       xh = (x - mean) rstd;   u = xh gamma[c] + beta[c];   y = u  (act 0)   or   y = u sigmoid(u)  (act 1, SiLU)
+ *       stats[2 (b G + g)] = mean, stats[2 (b G + g) + 1] = rstd
+ *   The variance is a second pass over the values a workgroup holds in registers, about that chunk's own mean; chunks recombine
+ *   as M2 = sum_c (M2_c + n_c (mean_c - mean)^2), every term non-negative.  E[x^2] - mean^2 is never formed.
+ *       bwd    d = 1 (act 0) or s (1 + u (1 - s)), s = sigmoid(u), recomputed from x and stats;   gu = g d;   t = gu gamma[c]
+ *              gx = rstd (t - mean_grp(t) - xh mean_grp(t xh));   dgamma[c] = sum_{b, p} gu xh;   dbeta[c] = sum_{b, p} gu
+ *   Nothing of the activation's size is kept besides x.  A NaN or an infinity in a group makes that group's y NaN and touches no
+ *   other group.  A constant group has var = 0 and y = act(beta) within the bound below.
+ * ORDER OF EVERY SUM  fixed by the shape alone (vqhip_group_norm_kernels.h says who adds what): the same inputs give the same
+ *   bits of y, stats, gx, dgamma and dbeta, run to run.
+ * LAUNCH SHAPE  n <= 2048: one wave per group, four groups per workgroup.  2048 < n <= 8192: one workgroup per group.  Beyond:
+ *   S = ceil(n / 8192) workgroups per group leave partials in ws; a second launch combines them and writes the result (the
+ *   configs' first layer at B = 8 has 256 groups of 262144 values: 8192 workgroups instead of 256).
+ * SHAPES AND LIMITS (VQHIP_EINVAL before any HIP call, and no launch)  dtype one of F32 / BF16 / F16; layout one of ROWS / MAP;
+ *   B, C, P, G >= 1; C a multiple of G; B, C, P < 2^31; B C P no overflow of int64; n < 2^31; B G S < 2^31; act 0 or 1; eps >= 0
+ *   and finite; every pointer required; ws_bytes >= vqhip_group_norm_ws_bytes(..) (-1 for sizes the calls refuse), in both calls.
+ * ERROR BOUND  against the exact value of the definition on the converted inputs; u0 = VQHIP_GN_U = 2^-24 (1 + 2^-9); first order
+ *   in u0 except where a square is written; no overflow in fp32 and no underflow of exp(-u).  All quantities are magnitudes.
+ *     N = VQHIP_GN_CHAIN(n) = n / 2^21 + 56 bounds the roundings a value passes into a group's sum: 32 in its thread, 6 in the
+ *       wave, 2 across waves, one product and ceil(S / 256) + 8 additions across chunks, two divisions.
+ *     mean: within N u0 mabs, mabs = the group's mean of |x|.  q = VQHIP_GN_Q(n, mabs, rstd) = N u0 mabs rstd is that error in
+ *       units of the deviation: the part no fp32 algorithm escapes when |mean| >> sigma.
+ *     rstd: M2 adds non-negative terms, each from one subtraction and one product: relative (N + 4) u0.  Inside a chunk
+ *       sum (x - m)^2 = sum (x - mean_c)^2 + n_c (m - mean_c)^2 exactly, so the chunk mean's error enters squared; between chunks
+ *       the means' errors dm enter as 4 sigma dm + 4 dm^2.  With sigma rstd <= 1, and 3 u0 for the addition of eps, the root and
+ *       the division, and 3 u0 reserved for the subtraction and products of xh and u:
+ *                                       rho = VQHIP_GN_RHO(n, q) = (N / 2 + 8) u0 + 2 q + 2 q^2
+ *     xh:  E_xh = xh rho + q.      u:  E_u = gamma E_xh + 2 u0 u.
+ *     y:   act 0: E_u.   act 1: 1.1 E_u + 8 u0 y   (|SiLU'| <= 1.1; exp, the addition, the division and the product: 8 u0).
+ *     d:   E_d = 0 (act 0) or 0.5 E_u + 10 u0  (|SiLU''| <= 0.5).      t:  E_t = g gamma E_d + 2 u0 t.
+ *     m1 = mean_grp(t): E_1 = N u0 mean_grp(t) + mean_grp(E_t).   m2 = mean_grp(t xh): E_2 = (N + 1) u0 mean_grp(t xh) + mean_grp(E_t xh + t E_xh).
+ *     gx:  E_gx = rstd (E_t + E_1 + xh E_2 + m2 E_xh + 4 u0 (t + m1 + xh m2)) + rho gx.
+ *     dgamma[c]: (M + 2) u0 sum(gu xh) + sum(E_gu xh + gu E_xh), dbeta[c]: M u0 sum(gu) + sum(E_gu), with E_gu = g E_d + u0 gu and
+ *       M = VQHIP_SG2_GBIAS_CHAIN(slabs), slabs = B S (at most 32 + 8 additions in the first launch, the second stage above).
+ *     the store: VQHIP_SG2_STORE_U(dtype) on top, as for the StyleGAN2 ops.
+ *   A measurement beyond these bounds inside the range means the kernel or this derivation is wrong. */
+#define VQHIP_GN_U (5.9604644775390625e-08 * 1.001953125)
+#define VQHIP_GN_CHAIN(n) ((double)((n) / 2097152 + 56))
+#define VQHIP_GN_Q(n, mabs, rstd) (VQHIP_GN_CHAIN(n) * VQHIP_GN_U * (double)(mabs) * (double)(rstd))
+#define VQHIP_GN_RHO(n, q) ((VQHIP_GN_CHAIN(n) / 2.0 + 8.0) * VQHIP_GN_U + 2.0 * (double)(q) + 2.0 * (double)(q) * (double)(q))
+int64_t vqhip_group_norm_ws_bytes(int layout, int64_t B, int64_t C, int64_t P, int64_t G);   /* -1 for sizes the calls refuse */
+int vqhip_group_norm_fwd(const void *x, int dtype, int layout, int64_t B, int64_t C, int64_t P, int64_t G, const float *gamma /* [C] */,
+                         const float *beta /* [C] */, float eps, int act, void *y, float *stats /* [B G 2] */, float *ws, int64_t ws_bytes,
+                         void *stream);
+int vqhip_group_norm_bwd(const void *g, const void *x, int dtype, int layout, int64_t B, int64_t C, int64_t P, int64_t G,
+                         const float *gamma, const float *beta, const float *stats, int act, void *gx, float *dgamma /* [C] */,
+                         float *dbeta /* [C] */, float *ws, int64_t ws_bytes, void *stream);
+
 /* ---- fused reconstruction metrics: L1, MSE, PSNR and SSIM of a validation pass ---------------------------------------------
  * The four numbers of the reference's table per tokenizer (docs/pretrained_models.md:47-51) that come from ImageLossMetric
  * (vq/runners/metrics/loss.py) over L1Loss, MSELoss, PSNRLoss and SSIMLoss (vq/tasks/image_reconstruction/losses.py), each of

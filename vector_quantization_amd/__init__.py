@@ -9,11 +9,13 @@ from . import _lib  # noqa: F401
 from .config import BuildPreHookMixin, Config, Registry, RegistryMeta
 from .registries import (AnchorRegistry, InitRegistry, ModelRegistry, VQITQuantizerCallbackRegistry,
                          VQITQuantizerDistanceRegistry, VQITQuantizerLossRegistry, VQITQuantizerRegistry,
-                         VQDiscriminatorLossRegistry, VQDiscriminatorRegistry, VQGeneratorLossRegistry)
+                         VQDiscriminatorLossRegistry, VQDiscriminatorRegistry, VQGeneratorLossRegistry,
+                         VQDecoderRegistry, VQEncoderRegistry)
 from .image_losses import L1Loss, MSELoss, PSNRLoss, SSIMLoss
 from .distill_losses import CosineEmbeddingLoss
 from .perceptual_losses import LPIPSLoss
 from .discriminators import BaseDiscriminator, PatchGANDiscriminator, StyleGAN2Discriminator
+from .autoencoders import BaseDecoder, BaseEncoder, VQGANDecoder, VQGANEncoder
 from .gan_losses import NonSaturatingLoss, R1GradientPenalty, VQGANDiscriminatorLoss, VQGANGeneratorLoss
 from .sequence_losses import CausalTokenLoss, LabelSmoothingCrossEntropy, MaskedTokenLoss
 from .utils import EMA, ema
@@ -25,6 +27,7 @@ __all__ = [
     'MaskedTokenLoss', 'L1Loss', 'MSELoss', 'PSNRLoss', 'SSIMLoss', 'CosineEmbeddingLoss', 'LPIPSLoss',
     'BaseDiscriminator', 'PatchGANDiscriminator', 'StyleGAN2Discriminator', 'VQGANGeneratorLoss', 'NonSaturatingLoss',
     'VQGANDiscriminatorLoss', 'R1GradientPenalty', 'VQDiscriminatorRegistry', 'VQGeneratorLossRegistry', 'VQDiscriminatorLossRegistry',
+    'BaseEncoder', 'BaseDecoder', 'VQGANEncoder', 'VQGANDecoder', 'VQEncoderRegistry', 'VQDecoderRegistry',
 ]
 __version__ = '0.1.0'
 

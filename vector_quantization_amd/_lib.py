@@ -181,6 +181,60 @@ def sg2_store_u(dtype: int) -> float:
     return {DTYPE_BF16: 2.0 ** -8, DTYPE_F16: 2.0 ** -11}.get(dtype, 0.0)
 
 
+GN_U = SG2_U                               # VQHIP_GN_U
+GN_SMALL, GN_CHUNK = 2048, 8192            # a wave per group up to GN_SMALL values; beyond GN_CHUNK a group is split over workgroups
+
+
+def gn_chain(n: int) -> float:
+    """VQHIP_GN_CHAIN(n) of include/vqhip.h: the roundings a value passes on the way into a sum over a group of n."""
+    return float(n // 2097152 + 56)
+
+
+def gn_q(n: int, mabs, rstd):
+    """VQHIP_GN_Q(n, mabs, rstd): the error of the group's mean in units of the deviation; mabs = the group's mean of |x|."""
+    return gn_chain(n) * GN_U * mabs * rstd
+
+
+def gn_rho(n: int, q):
+    """VQHIP_GN_RHO(n, q): the relative error of rstd (with the roundings of xh and u reserved)."""
+    return (gn_chain(n) / 2.0 + 8.0) * GN_U + 2.0 * q + 2.0 * q * q
+
+
+def gn_xhat_bound(n: int, q, xh):
+    """E_xh of include/vqhip.h for a normalised value of magnitude xh."""
+    return xh * gn_rho(n, q) + q
+
+
+def gn_u_bound(n: int, q, xh, gamma, u):
+    """E_u: the affine value u = xh gamma + beta, from the magnitudes of xh, gamma and u."""
+    return gamma * gn_xhat_bound(n, q, xh) + 2.0 * GN_U * u
+
+
+def gn_y_bound(n: int, q, xh, gamma, u, y, act: int):
+    """|kernel y - exact y| in fp32, before the store: E_u, or 1.1 E_u + 8 u0 |y| behind the SiLU."""
+    e = gn_u_bound(n, q, xh, gamma, u)
+    return 1.1 * e + 8.0 * GN_U * y if act else e
+
+
+def gn_d_bound(n: int, q, xh, gamma, u, act: int):
+    """E_d: the derivative of the activation, 0 without one."""
+    return 0.5 * gn_u_bound(n, q, xh, gamma, u) + 10.0 * GN_U if act else 0.0 * xh
+
+
+def gn_gx_bound(n: int, q, rstd, xh, e_t, t, m1, m2, mean_t, mean_txh, mean_e_t, mean_e_txh, gx):
+    """E_gx of include/vqhip.h.  e_t = g gamma E_d + 2 u0 t per value; mean_* are the group's means of t, t xh, e_t and of
+    e_t xh + t E_xh; m1, m2 the magnitudes of the two group means of the definition."""
+    N = gn_chain(n)
+    e1 = N * GN_U * mean_t + mean_e_t
+    e2 = (N + 1.0) * GN_U * mean_txh + mean_e_txh
+    return rstd * (e_t + e1 + xh * e2 + m2 * gn_xhat_bound(n, q, xh) + 4.0 * GN_U * (t + m1 + xh * m2)) + gn_rho(n, q) * gx
+
+
+def gn_param_bound(slabs: int, extra: float, sumabs, sum_err):
+    """dgamma (extra = 2) or dbeta (extra = 0): (M + extra) u0 sum|terms| + the sum of the terms' own errors."""
+    return (sg2_gbias_chain(slabs) + extra) * GN_U * sumabs + sum_err
+
+
 STEP_BEFORE_EXCHANGE, STEP_AFTER_EXCHANGE, STEP_ALL, STEP_PACK_SYNC = 1, 2, 3, 4
 
 # name -> (restype, argtypes); mirrors include/vqhip.h one to one
@@ -227,6 +281,9 @@ SIGNATURES = {
     'vqhip_fir4_slabs': (_i64, [_i32, _i64, _i64, _i64, _i64]),
     'vqhip_fir4_fwd': (_i32, [_vp, _i32, _i32, _i64, _i64, _i64, _i64, _i32, _i32, _i32, _i32, _i32, _vp, _vp, _vp]),
     'vqhip_fir4_bwd': (_i32, [_vp, _i32, _i32, _i64, _i64, _i64, _i64, _i32, _i32, _i32, _i32, _i32, _vp, _vp, _vp, _vp, _vp, _i64, _vp]),
+    'vqhip_group_norm_ws_bytes': (_i64, [_i32, _i64, _i64, _i64, _i64]),
+    'vqhip_group_norm_fwd': (_i32, [_vp, _i32, _i32, _i64, _i64, _i64, _i64, _vp, _vp, _f32, _i32, _vp, _vp, _vp, _i64, _vp]),
+    'vqhip_group_norm_bwd': (_i32, [_vp, _vp, _i32, _i32, _i64, _i64, _i64, _i64, _vp, _vp, _vp, _i32, _vp, _vp, _vp, _vp, _i64, _vp]),
     'vqhip_image_metrics_workspace_bytes': (_i64, [_i64, _i64, _i64, _i64]),
     'vqhip_image_metrics': (_i32, [_vp, _i32, _i32, _vp, _i32, _i32, _i64, _i64, _i64, _i64, _i32, _f64, _f64, _vp, _i64, _vp, _vp,
                                    _vp, _vp]),

@@ -14,6 +14,7 @@
 #include "vqhip_cosine_embed_kernels.h"
 #include "vqhip_lpips_kernels.h"
 #include "vqhip_stylegan2_kernels.h"
+#include "vqhip_group_norm_kernels.h"
 #include "vqhip_image_metrics_kernels.h"
 
 static thread_local char g_err[256] = "";
@@ -633,6 +634,48 @@ static int launch_fir4(const VqFirArgs &a, bool rows, int down, int fused, hipSt
     VQ_FIR_CASE(true, 2, VQ_FIR_NONE); VQ_FIR_CASE(true, 2, VQ_FIR_ACT_IN);
 #undef VQ_FIR_CASE
     return fail(VQHIP_EINVAL, "fir4", "no kernel of this form");
+}
+
+// ---- GroupNorm (+ SiLU): the launches (vqhip_group_norm_kernels.h) -------------------------------------------------------------
+template <int DT, bool ROWS, int PW>
+static int launch_gn_one(const VqGnArgs &a, int T, bool bwd, hipStream_t s) {
+    const unsigned grid = (unsigned)(T == 64 ? (a.units + 3) / 4 : a.units);
+    if (T == 64) {
+        if (bwd) gn_bwd_kernel<DT, ROWS, PW, 64><<<grid, VQ_GN_THREADS, 0, s>>>(a);
+        else gn_fwd_kernel<DT, ROWS, PW, 64><<<grid, VQ_GN_THREADS, 0, s>>>(a);
+    } else {
+        if (bwd) gn_bwd_kernel<DT, ROWS, PW, 256><<<grid, VQ_GN_THREADS, 0, s>>>(a);
+        else gn_fwd_kernel<DT, ROWS, PW, 256><<<grid, VQ_GN_THREADS, 0, s>>>(a);
+    }
+    VQ_CHECK_LAUNCH(bwd ? "gn_bwd_kernel" : "gn_fwd_kernel");
+    return VQHIP_OK;
+}
+
+// the piece of the rows layout: the widest of 16 bytes, 8 bytes or one element that divides the channels of a group
+template <int DT>
+static int launch_gn(const VqGnArgs &a, bool rows, int T, bool bwd, hipStream_t s) {
+    constexpr int W = SampleElem<DT>::W;
+    if (!rows) return launch_gn_one<DT, false, W>(a, T, bwd, s);
+    if (a.cpg % W == 0) return launch_gn_one<DT, true, W>(a, T, bwd, s);
+    if (W == 8 && a.cpg % 4 == 0) return launch_gn_one<DT, true, 4>(a, T, bwd, s);
+    return launch_gn_one<DT, true, 1>(a, T, bwd, s);
+}
+
+// one launch where a group is one chunk; else the partials, and behind the launch boundary their combination and the result
+template <int DT>
+static int gn_run(VqGnArgs a, bool rows, int T, bool bwd, int64_t slabs, float *dgamma, float *dbeta, hipStream_t s) {
+    if (a.S == 1) {
+        a.phase = VQ_GN_ALL;
+        if (int rc = launch_gn<DT>(a, rows, T, bwd, s)) return rc;
+    } else {
+        a.phase = VQ_GN_PART;
+        if (int rc = launch_gn<DT>(a, rows, T, bwd, s)) return rc;
+        a.phase = VQ_GN_APPLY;
+        if (int rc = launch_gn<DT>(a, rows, T, bwd, s)) return rc;
+    }
+    if (!bwd) return VQHIP_OK;
+    if (int rc = launch_sg2_reduce(a.ws_dg, slabs, a.C, dgamma, s)) return rc;
+    return launch_sg2_reduce(a.ws_db, slabs, a.C, dbeta, s);
 }
 
 extern "C" {
@@ -1712,6 +1755,72 @@ int vqhip_fir4_bwd(const void *g, int dtype, int layout, int64_t B, int64_t C, i
     if (x) VQ_NEED("vqhip_fir4_bwd: ws too small", ws_bytes, (int64_t)B * a.tiles_y * a.tiles_x * C * (int64_t)sizeof(float));
     a.in = g; a.out = gx; a.x = x; a.bias = bias; a.ws = ws;
     VQ_SG2_DISPATCH(fir4_bwd_run, a, layout == VQHIP_LAYOUT_ROWS, gbias, (hipStream_t)stream);
+}
+// ---- GroupNorm (+ SiLU) (vqhip_group_norm_kernels.h) ---------------------------------------------------------------------------
+struct VqGnPlan {
+    int64_t n, S, units, slabs, ws_floats;
+    int T;
+};
+
+// what the three entry points refuse alike; on success the launch shape
+static int gn_plan(const char *what, int dtype, int layout, int64_t B, int64_t C, int64_t P, int64_t G, VqGnPlan *pl) {
+    if (dtype != VQHIP_DTYPE_F32 && dtype != VQHIP_DTYPE_BF16 && dtype != VQHIP_DTYPE_F16) return fail(VQHIP_EINVAL, what, "dtype");
+    if (layout != VQHIP_LAYOUT_ROWS && layout != VQHIP_LAYOUT_MAP) return fail(VQHIP_EINVAL, what, "layout");
+    if (B < 1 || C < 1 || P < 1 || G < 1) return fail(VQHIP_EINVAL, what, "B, C, P and G must be positive");
+    if (C % G != 0) return fail(VQHIP_EINVAL, what, "C must be a multiple of G");
+    const int64_t cap = 1ll << 31;
+    if (B >= cap || C >= cap || P >= cap) return fail(VQHIP_EINVAL, what, "B, C and P must be below 2^31");
+    if (B * C > INT64_MAX / P / 8) return fail(VQHIP_EINVAL, what, "B * C * P overflows");     // (8: bytes and the workspace's floats)
+    pl->n = (C / G) * P;
+    if (pl->n >= cap) return fail(VQHIP_EINVAL, what, "a group must hold fewer than 2^31 values");
+    pl->T = pl->n <= VQ_GN_SMALL ? 64 : 256;
+    pl->S = pl->T == 64 ? 1 : (pl->n + VQ_GN_CHUNK - 1) / VQ_GN_CHUNK;
+    pl->units = B * G * pl->S;
+    if (pl->units >= cap) return fail(VQHIP_EINVAL, what, "B * G * ceil(n / 8192) is beyond one launch");
+    pl->slabs = B * pl->S;
+    pl->ws_floats = 2 * pl->units + 2 * pl->slabs * C;
+    return VQHIP_OK;
+}
+
+int64_t vqhip_group_norm_ws_bytes(int layout, int64_t B, int64_t C, int64_t P, int64_t G) {
+    VqGnPlan pl;
+    if (gn_plan("vqhip_group_norm_ws_bytes", VQHIP_DTYPE_F32, layout, B, C, P, G, &pl)) return -1;
+    return pl.ws_floats * (int64_t)sizeof(float);
+}
+
+static void gn_fill(VqGnArgs *a, const VqGnPlan &pl, int64_t B, int64_t C, int64_t P, int64_t G, float *ws) {
+    a->units = pl.units; a->n = (uint32_t)pl.n;
+    a->B = (int)B; a->C = (int)C; a->P = (int)P; a->G = (int)G; a->cpg = (int)(C / G); a->S = (int)pl.S;
+    a->ws_grp = ws; a->ws_dg = ws + 2 * pl.units; a->ws_db = a->ws_dg + pl.slabs * C;
+}
+
+int vqhip_group_norm_fwd(const void *x, int dtype, int layout, int64_t B, int64_t C, int64_t P, int64_t G, const float *gamma,
+                         const float *beta, float eps, int act, void *y, float *stats, float *ws, int64_t ws_bytes, void *stream) {
+    VqGnPlan pl;
+    if (int rc = gn_plan("vqhip_group_norm_fwd", dtype, layout, B, C, P, G, &pl)) return rc;
+    VQ_REQUIRE(act == 0 || act == 1, "vqhip_group_norm_fwd: act must be 0 (none) or 1 (SiLU)");
+    VQ_REQUIRE(eps >= 0.0f && eps < INFINITY, "vqhip_group_norm_fwd: eps must be finite and not negative");
+    VQ_REQUIRE(x && gamma && beta && y && stats && ws, "vqhip_group_norm_fwd: x, gamma, beta, y, stats and ws are required");
+    VQ_NEED("vqhip_group_norm_fwd: ws too small", ws_bytes, pl.ws_floats * (int64_t)sizeof(float));
+    VqGnArgs a = {};
+    gn_fill(&a, pl, B, C, P, G, ws);
+    a.x = x; a.out = y; a.gamma = gamma; a.beta = beta; a.stats = stats; a.eps = eps; a.act = act;
+    VQ_SG2_DISPATCH(gn_run, a, layout == VQHIP_LAYOUT_ROWS, pl.T, false, pl.slabs, nullptr, nullptr, (hipStream_t)stream);
+}
+
+int vqhip_group_norm_bwd(const void *g, const void *x, int dtype, int layout, int64_t B, int64_t C, int64_t P, int64_t G,
+                         const float *gamma, const float *beta, const float *stats, int act, void *gx, float *dgamma, float *dbeta,
+                         float *ws, int64_t ws_bytes, void *stream) {
+    VqGnPlan pl;
+    if (int rc = gn_plan("vqhip_group_norm_bwd", dtype, layout, B, C, P, G, &pl)) return rc;
+    VQ_REQUIRE(act == 0 || act == 1, "vqhip_group_norm_bwd: act must be 0 (none) or 1 (SiLU)");
+    VQ_REQUIRE(g && x && gamma && beta && stats && gx && dgamma && dbeta && ws,
+               "vqhip_group_norm_bwd: g, x, gamma, beta, stats, gx, dgamma, dbeta and ws are required");
+    VQ_NEED("vqhip_group_norm_bwd: ws too small", ws_bytes, pl.ws_floats * (int64_t)sizeof(float));
+    VqGnArgs a = {};
+    gn_fill(&a, pl, B, C, P, G, ws);
+    a.x = x; a.g = g; a.out = gx; a.gamma = gamma; a.beta = beta; a.stats = const_cast<float *>(stats); a.act = act;
+    VQ_SG2_DISPATCH(gn_run, a, layout == VQHIP_LAYOUT_ROWS, pl.T, true, pl.slabs, dgamma, dbeta, (hipStream_t)stream);
 }
 #undef VQ_SG2_DISPATCH
 

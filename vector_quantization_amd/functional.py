@@ -551,3 +551,43 @@ def bias_act_blur(x: torch.Tensor, bias: torch.Tensor, pad=2, down: int = 1) -> 
     """``blur(bias_act(x, bias), pad, down)`` in one launch: one read of ``x``, one write of the blurred map; the backward writes
     ``gx`` and ``gbias`` in one call from the saved ``x``.  Twice differentiable."""
     return _BiasActBlur.apply(x, bias, pad, down)
+
+
+# ---- GroupNorm (+ SiLU) of the VQGAN encoder and decoder: one read and one write forward; the backward recomputes the affine
+#      value and the SiLU derivative from x and the saved [B, G, 2] statistics, so nothing activation-sized is kept besides x ----
+
+class _GroupNorm(Function):
+    """vqhip_group_norm_fwd / _bwd.  Nothing in a generator step differentiates it twice: the backward is once differentiable."""
+
+    @staticmethod
+    def forward(ctx, x, weight, bias, num_groups, eps, act):
+        y, stats = ops.group_norm(x, num_groups, weight, bias, eps, act)
+        ctx.save_for_backward(x, weight, bias, stats)
+        ctx.num_groups, ctx.act = num_groups, act
+        return y
+
+    @staticmethod
+    @once_differentiable
+    def backward(ctx, g):
+        x, weight, bias, stats = ctx.saved_tensors
+        gx, dgamma, dbeta = ops.group_norm_backward(g, x, stats, ctx.num_groups, weight, bias, ctx.act)
+        return (gx if ctx.needs_input_grad[0] else None, dgamma.to(weight.dtype).view_as(weight) if ctx.needs_input_grad[1] else None,
+                dbeta.to(bias.dtype).view_as(bias) if ctx.needs_input_grad[2] else None, None, None, None)
+
+
+def group_norm_torch(x: torch.Tensor, num_groups: int, weight: torch.Tensor, bias: torch.Tensor, eps: float = 1e-6, act=None) -> torch.Tensor:
+    """The same definition with ``F.group_norm`` and ``F.silu``: CPU tensors, float64, layouts that are not dense."""
+    y = torch.nn.functional.group_norm(x, num_groups, weight, bias, eps)
+    return torch.nn.functional.silu(y) if act == 'silu' else y
+
+
+def group_norm(x: torch.Tensor, num_groups: int, weight: torch.Tensor, bias: torch.Tensor, eps: float = 1e-6, act=None) -> torch.Tensor:
+    """``act(group_norm(x, num_groups, weight, bias, eps))`` with ``act`` None or 'silu', of a [B, C, ...] activation in its dtype
+    and memory format: one launch reads x and writes y (two where a group is split over workgroups), fp32 arithmetic whatever the
+    dtype, gradients to x, weight and bias.  A CPU tensor, float64 or a layout that is neither NCHW-contiguous nor channels-last
+    dense computes the same definition in torch."""
+    if act not in ops.GROUP_NORM_ACTS:
+        raise ValueError(f'group_norm: act={act!r} is neither None nor \'silu\'')
+    if not x.is_cuda or ops.group_norm_refusal(x, num_groups):
+        return group_norm_torch(x, num_groups, weight, bias, eps, act)
+    return _GroupNorm.apply(x, weight, bias, int(num_groups), float(eps), act)

@@ -1237,6 +1237,85 @@ def fir4_backward(g: torch.Tensor, size, pad=2, down: int = 1, x: Optional[torch
     return gx if x is None else (gx, gbias)
 
 
+# ---- GroupNorm (+ SiLU) of the VQGAN encoder and decoder (vq/algorithms/vqgan/autoencoder.py) ---------------------------------
+
+GROUP_NORM_ACTS = {None: 0, 'silu': 1}
+
+
+def group_norm_refusal(x: torch.Tensor, num_groups: int) -> str:
+    """Why vqhip_group_norm_* would refuse this activation ('' if they would not): the clauses of their LIMITS that depend on the
+    tensor's dtype, shape and strides."""
+    if x.dtype not in SAMPLE_DTYPES:
+        return f'the activation is {x.dtype}, not float32, bfloat16 or float16'
+    if x.dim() < 2:
+        return f'the activation is {x.dim()}-D, not [B, C, ...]'
+    if x.numel() == 0:
+        return f'empty activation {tuple(x.shape)}'
+    if num_groups < 1 or x.shape[1] % num_groups:
+        return f'C={x.shape[1]} is no multiple of num_groups={num_groups}'
+    if sg2_layout(x) is None:
+        return f'the activation with strides {x.stride()} is neither NCHW-contiguous nor channels-last dense'
+    if x.numel() // (x.shape[0] * num_groups) >= (1 << 31):
+        return f'a group of {x.numel() // (x.shape[0] * num_groups)} values is outside 1 .. 2^31-1'
+    return ''
+
+
+def _gn_head(what: str, x: torch.Tensor, num_groups: int, weight: torch.Tensor, bias: torch.Tensor, act):
+    _require_cuda(x, weight, bias)
+    why = group_norm_refusal(x, num_groups)
+    if not why and act not in GROUP_NORM_ACTS:
+        why = f'act={act!r} is neither None nor \'silu\''
+    if not why and (weight.numel() != x.shape[1] or bias.numel() != x.shape[1]):
+        why = f'weight and bias have {weight.numel()} and {bias.numel()} elements, not C={x.shape[1]}'
+    if why:
+        raise ValueError(f'{what}: {why}')
+    B, C = x.shape[:2]
+    P = x.numel() // (B * C)
+    layout = SG2_LAYOUTS[sg2_layout(x)]
+    ws_bytes = _lib.lib().vqhip_group_norm_ws_bytes(layout, B, C, P, num_groups)
+    if ws_bytes < 0:
+        raise ValueError(f'{what}: {tuple(x.shape)} in {num_groups} groups is beyond the sizes of vqhip_group_norm_*')
+    ws = torch.empty(ws_bytes // 4, dtype=torch.float32, device=x.device)
+    return SAMPLE_DTYPES[x.dtype], layout, B, C, P, ws
+
+
+@_on_tensor_device
+def group_norm(x: torch.Tensor, num_groups: int, weight: torch.Tensor, bias: torch.Tensor, eps: float = 1e-6, act=None):
+    """vqhip_group_norm_fwd: ``(y, stats)`` for ``y = act(group_norm(x) * weight[c] + bias[c])`` of a [B, C, ...] activation read in
+    place, in its dtype and memory format (NCHW or channels-last); ``act``: None or 'silu'.  ``stats`` [B, G, 2] fp32 holds each
+    group's mean and 1 / sqrt(var + eps), what the backward reads.  One launch, two where a group is split over workgroups."""
+    dtype, layout, B, C, P, ws = _gn_head('group_norm', x, num_groups, weight, bias, act)
+    w, b = _sg2_bias(weight), _sg2_bias(bias)
+    y = torch.empty_like(x)
+    stats = torch.empty(B, num_groups, 2, dtype=torch.float32, device=x.device)
+    check(_lib.lib().vqhip_group_norm_fwd(_ptr(x), dtype, layout, B, C, P, num_groups, _ptr(w), _ptr(b), float(eps), GROUP_NORM_ACTS[act],
+                                          _ptr(y), _ptr(stats), _ptr(ws), ws.numel() * 4, _stream()), 'vqhip_group_norm_fwd')
+    return y, stats
+
+
+@_on_tensor_device
+def group_norm_backward(g: torch.Tensor, x: torch.Tensor, stats: torch.Tensor, num_groups: int, weight: torch.Tensor, bias: torch.Tensor,
+                        act=None):
+    """vqhip_group_norm_bwd: ``(gx, dgamma, dbeta)`` from the incoming gradient, the saved input and the forward's ``stats``; the
+    affine value and the SiLU derivative are recomputed.  ``gx`` in x's dtype and layout, ``dgamma`` and ``dbeta`` fp32 [C] from a
+    fixed-order two-stage sum."""
+    dtype, layout, B, C, P, ws = _gn_head('group_norm_backward', x, num_groups, weight, bias, act)
+    _require_cuda(g, stats)
+    if g.shape != x.shape or g.dtype != x.dtype:
+        raise ValueError(f'group_norm_backward: g is {g.dtype} {tuple(g.shape)}, x {x.dtype} {tuple(x.shape)}')
+    if stats.dtype != torch.float32 or stats.numel() != B * num_groups * 2 or not stats.is_contiguous():
+        raise ValueError(f'group_norm_backward: stats must be the contiguous fp32 [{B}, {num_groups}, 2] of the forward')
+    g = _sg2_dense_like(g, x)
+    w, b = _sg2_bias(weight), _sg2_bias(bias)
+    gx = torch.empty_like(x)
+    dgamma = torch.empty(C, dtype=torch.float32, device=x.device)
+    dbeta = torch.empty(C, dtype=torch.float32, device=x.device)
+    check(_lib.lib().vqhip_group_norm_bwd(_ptr(g), _ptr(x), dtype, layout, B, C, P, num_groups, _ptr(w), _ptr(b), _ptr(stats),
+                                          GROUP_NORM_ACTS[act], _ptr(gx), _ptr(dgamma), _ptr(dbeta), _ptr(ws), ws.numel() * 4, _stream()),
+          'vqhip_group_norm_bwd')
+    return gx, dgamma, dbeta
+
+
 # ---- fused reconstruction metrics (validation: vq/runners/metrics/loss.py over vq/tasks/image_reconstruction/losses.py) -----
 
 IMAGE_DTYPES = {torch.float32: _lib.DTYPE_F32, torch.bfloat16: _lib.DTYPE_BF16, torch.float16: _lib.DTYPE_F16,

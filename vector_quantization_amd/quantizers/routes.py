@@ -16,6 +16,7 @@ shape, dtype, alignment, the probability buffer, the world size, train / eval). 
     cosine_embedding_why  fused | torch
     lpips_why             fused | torch
     stylegan2_why         fused | torch
+    group_norm_why        fused | torch
     multinomial_anchor_why  fused | matrix
 """
 from __future__ import annotations
@@ -552,6 +553,28 @@ def stylegan2_why(module, x: torch.Tensor) -> Route:
                 break
     why = why or ('' if x.is_cuda else f'the input is on device {x.device}, not on a GPU')
     why = why or ops.stylegan2_refusal(x)
+    return Route('torch', why) if why else Route('fused')
+
+
+# ---- the GroupNorm (+ SiLU) sites of VQGANEncoder / VQGANDecoder (vector_quantization_amd/autoencoders.py) --------------------------
+
+def group_norm_why(module, x: torch.Tensor, num_groups: int = 32) -> Route:
+    """The ``GroupNorm -> SiLU`` sites of ``VQGANEncoder`` / ``VQGANDecoder`` (or of one of their blocks): the HIP kernels of
+    ``functional.group_norm`` on the activations as they are (``fused``), or ``F.group_norm`` and ``F.silu`` (``torch``), with the
+    first clause that refused the kernels: ``fused=False`` on the module, a class that overrides ``forward``, a CPU tensor, float64
+    (or any dtype the kernels do not read), strides that are neither NCHW-contiguous nor channels-last dense.  The decision is
+    taken on the module's input; every site repeats the tensor clauses on its own activation (``functional.group_norm``)."""
+    from .. import autoencoders
+    why = ''
+    if module is not None:
+        why = '' if getattr(module, 'fused', True) else 'fused=False'
+        if not why and isinstance(module, autoencoders.VQGANMixin):
+            why = own(module, autoencoders.VQGANMixin, 'forward')
+    why = why or ('' if x.is_cuda else f'the input is on device {x.device}, not on a GPU')
+    if not why and x.dtype not in ops.SAMPLE_DTYPES:
+        why = f'the input is {x.dtype}, not float32, bfloat16 or float16'
+    if not why and ops.sg2_layout(x) is None:
+        why = f'the input with strides {x.stride()} is neither NCHW-contiguous nor channels-last dense'
     return Route('torch', why) if why else Route('fused')
 
 

@@ -1,6 +1,6 @@
 """Registry hierarchy of the quantizer path, same names as the reference
 (vq/registries.py:18-35, vq/tasks/image_tokenization/registries.py:11-16, .../runners/registries.py:11-16,
-vq/tasks/image_tokenization/models/registries.py, vq/models/registries.py:20, vq/tasks/image_reconstruction/registries.py:16,
+vq/tasks/image_tokenization/models/registries.py, vq/models/registries.py:12-20, vq/tasks/image_reconstruction/registries.py:16,
 vq/runners/registries.py:15, vq/algorithms/vqgan/registries.py:8, vq/algorithms/vqgan/losses/registries.py:9-14,
 .../quantizers/registries.py:9-14, vq/algorithms/vq/distances.py:19-20, vq/algorithms/cvqvae/registries.py:8)."""
 from .config import Registry
@@ -62,6 +62,14 @@ class VQLossRegistry(VQRegistry):
 
 class VQIRLossRegistry(VQModelRegistry, VQLossRegistry):
     """The losses of image reconstruction (vq/tasks/image_reconstruction/losses.py): image_losses.py."""
+
+
+class VQEncoderRegistry(VQModelRegistry):
+    """The encoders of a tokenizer (vq/models/registries.py:12): autoencoders.py."""
+
+
+class VQDecoderRegistry(VQModelRegistry):
+    """The decoders of a tokenizer (vq/models/registries.py:16): autoencoders.py."""
 
 
 class VQDiscriminatorRegistry(VQModelRegistry):
