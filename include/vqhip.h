@@ -57,7 +57,8 @@ extern "C" {
 #define VQHIP_DTYPE_F32 0
 #define VQHIP_DTYPE_BF16 1
 /* (2 and 3 are the token dtypes VQHIP_DTYPE_I32 / VQHIP_DTYPE_I64, defined with the FSQ entry points below) */
-#define VQHIP_DTYPE_F16 4   /* logits of vqhip_sample_tokens only: every other entry point takes F32 or BF16 rows */
+#define VQHIP_DTYPE_F16 4   /* the sampler, token cross-entropy and the activation ops (cosine embedding, LPIPS, StyleGAN2,
+                             * GroupNorm, image metrics) read it; the quantizer core and FSQ take F32 or BF16 rows only */
 
 #define VQHIP_OK 0
 #define VQHIP_EINVAL (-22)      /* bad argument (null pointer, unsupported D, ...) */

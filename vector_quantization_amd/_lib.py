@@ -15,7 +15,7 @@ LIB_PATH = os.environ.get('VQHIP_LIB') or os.path.join(_HERE, 'libvqhip.so')   #
 ABI_VERSION = 600          # VQHIP_VERSION of include/vqhip.h this binding was written against
 METRIC_L2, METRIC_COS, METRIC_COS_BF16 = 0, 1, 5
 DTYPE_F32, DTYPE_BF16 = 0, 1
-DTYPE_F16 = 4                              # logits of vqhip_sample_tokens only (2 and 3 are the token dtypes below)
+DTYPE_F16 = 4                              # sampler, token CE and the activation ops; not the quantizer core or FSQ (2, 3: below)
 DTYPE_I32, DTYPE_I64 = 2, 3                # token dtypes of vqhip_fsq_decode
 DTYPE_U8 = 5                               # images of vqhip_image_metrics only
 IMAGE_NCHW, IMAGE_NHWC = 0, 1              # layouts of vqhip_image_metrics

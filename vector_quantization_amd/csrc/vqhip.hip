@@ -44,6 +44,7 @@ static int fail(int code, const char *what, const char *detail = "") {
 // on), the knobs and the per-device attribute cache are atomics.
 #include <atomic>
 #include <mutex>
+#include <type_traits>
 #include <vector>
 static std::atomic<bool> g_prof_on{false};
 static std::mutex g_prof_mu;
@@ -103,10 +104,23 @@ static int ensure_dyn_lds(const void *kern, size_t bytes, LdsCache &set) {
 #define VQ_REQUIRE(cond, text) do { if (!(cond)) return fail(VQHIP_EINVAL, text); } while (0)
 static inline bool vq_public_metric(int m) { return m == VQHIP_METRIC_L2 || m == VQHIP_METRIC_COS || m == VQHIP_METRIC_COS_BF16; }
 static inline bool vq_row_dtype(int t) { return t == VQHIP_DTYPE_F32 || t == VQHIP_DTYPE_BF16; }
+static inline bool vq_float_dtype(int t) { return vq_row_dtype(t) || t == VQHIP_DTYPE_F16; }       // what the activation ops read
+static inline bool vq_dense_layout(int l) { return l == VQHIP_LAYOUT_ROWS || l == VQHIP_LAYOUT_MAP; }
 static inline bool vq_fits_i31(int64_t N, int64_t K) { return N < (1ll << 31) && K < (1ll << 31); }
 
 static inline int waves_grid(int64_t rows, int waves_per_block) {
     return (int)((rows + waves_per_block - 1) / waves_per_block);
+}
+
+// A float dtype that vq_float_dtype has let through, as a template argument: `fn` is a generic lambda, `decltype(its parameter)
+// ::value` the constant.  Two dtypes nest two calls.  Anything but F32 and BF16 goes to F16.
+template <class Fn>
+static int vq_with_dtype(int dtype, Fn &&fn) {
+    switch (dtype) {
+    case VQHIP_DTYPE_F32: return fn(std::integral_constant<int, VQHIP_DTYPE_F32>{});
+    case VQHIP_DTYPE_BF16: return fn(std::integral_constant<int, VQHIP_DTYPE_BF16>{});
+    default: return fn(std::integral_constant<int, VQHIP_DTYPE_F16>{});
+    }
 }
 
 // ---- proposal-pass dispatch ------------------------------------------------------------------------
@@ -634,6 +648,13 @@ static int launch_fir4(const VqFirArgs &a, bool rows, int down, int fused, hipSt
     VQ_FIR_CASE(true, 2, VQ_FIR_NONE); VQ_FIR_CASE(true, 2, VQ_FIR_ACT_IN);
 #undef VQ_FIR_CASE
     return fail(VQHIP_EINVAL, "fir4", "no kernel of this form");
+}
+
+// the adjoint blur; in the fused form (a.x) it masks on the way out and the bias gradient follows from its slabs
+template <int DT>
+static int fir4_bwd_run(const VqFirArgs &a, bool rows, float *gbias, hipStream_t s) {
+    if (int rc = launch_fir4<DT>(a, rows, 1, a.x ? VQ_FIR_MASK_OUT : VQ_FIR_NONE, s)) return rc;
+    return a.x ? launch_sg2_reduce(a.ws, (int64_t)a.B * a.tiles_y * a.tiles_x, a.C, gbias, s) : VQHIP_OK;
 }
 
 // ---- GroupNorm (+ SiLU): the launches (vqhip_group_norm_kernels.h) -------------------------------------------------------------
@@ -1420,7 +1441,7 @@ int vqhip_sample_tokens(const void *logits, int dtype, int64_t R, int64_t row_st
                         int cfg, float temperature, int top_k, float top_p, const float *u, int64_t *tokens,
                         vqhip_sample_cut_t *cut, void *stream) {
     VQ_REQUIRE(logits && u && tokens, "vqhip_sample_tokens: logits, u and tokens are required");
-    VQ_REQUIRE(dtype == VQHIP_DTYPE_F32 || dtype == VQHIP_DTYPE_BF16 || dtype == VQHIP_DTYPE_F16, "vqhip_sample_tokens: dtype");
+    VQ_REQUIRE(vq_float_dtype(dtype), "vqhip_sample_tokens: dtype");
     VQ_REQUIRE(R >= 1 && R < (1ll << 31), "vqhip_sample_tokens: R must be in 1 .. 2^31 - 1");
     VQ_REQUIRE(!cfg || R % 2 == 0, "vqhip_sample_tokens: R must be even under CFG");
     VQ_REQUIRE(start >= 0 && start < end && end <= row_stride, "vqhip_sample_tokens: need 0 <= start < end <= row_stride");
@@ -1438,12 +1459,7 @@ int vqhip_sample_tokens(const void *logits, int dtype, int64_t R, int64_t row_st
     a.use_top_p = (top_p >= 0.0f && top_p <= 1.0f) ? 1 : 0;
     a.one_minus_p = 1.0 - (double)top_p;
     a.u = u; a.tokens = tokens; a.cut = cut;
-    hipStream_t s = (hipStream_t)stream;
-    switch (dtype) {
-    case VQHIP_DTYPE_F32: return launch_sample<VQHIP_DTYPE_F32>(a, s);
-    case VQHIP_DTYPE_BF16: return launch_sample<VQHIP_DTYPE_BF16>(a, s);
-    default: return launch_sample<VQHIP_DTYPE_F16>(a, s);
-    }
+    return vq_with_dtype(dtype, [&](auto dt) { return launch_sample<decltype(dt)::value>(a, (hipStream_t)stream); });
 }
 
 // ---- fused token cross-entropy (vqhip_token_ce_kernels.h) -----------------------------------------------------------------
@@ -1452,7 +1468,7 @@ static int token_ce_setup(const char *what, const void *logits, int dtype, int64
                           const void *targets, int target_dtype, int64_t shift_len, int64_t ignore_index, float eps,
                           const float *weight, VqCeArgs *a) {
     if (!logits || !targets) return fail(VQHIP_EINVAL, what, "logits and targets are required");
-    if (dtype != VQHIP_DTYPE_F32 && dtype != VQHIP_DTYPE_BF16 && dtype != VQHIP_DTYPE_F16) return fail(VQHIP_EINVAL, what, "dtype");
+    if (!vq_float_dtype(dtype)) return fail(VQHIP_EINVAL, what, "dtype");
     if (target_dtype != VQHIP_DTYPE_I32 && target_dtype != VQHIP_DTYPE_I64) return fail(VQHIP_EINVAL, what, "target_dtype");
     if (R < 1 || R >= (1ll << 31)) return fail(VQHIP_EINVAL, what, "R must be in 1 .. 2^31 - 1");
     if (!(start >= 0 && start < end && end <= row_stride)) return fail(VQHIP_EINVAL, what, "need 0 <= start < end <= row_stride");
@@ -1468,16 +1484,6 @@ static int token_ce_setup(const char *what, const void *logits, int dtype, int64
     return VQHIP_OK;
 }
 
-#define VQ_TOKEN_CE_DISPATCH(fn, ...)                                                                                   \
-    do {                                                                                                                \
-        const bool i64__ = target_dtype == VQHIP_DTYPE_I64;                                                             \
-        switch (dtype) {                                                                                                \
-        case VQHIP_DTYPE_F32: return i64__ ? fn<VQHIP_DTYPE_F32, true>(__VA_ARGS__) : fn<VQHIP_DTYPE_F32, false>(__VA_ARGS__);      \
-        case VQHIP_DTYPE_BF16: return i64__ ? fn<VQHIP_DTYPE_BF16, true>(__VA_ARGS__) : fn<VQHIP_DTYPE_BF16, false>(__VA_ARGS__);   \
-        default: return i64__ ? fn<VQHIP_DTYPE_F16, true>(__VA_ARGS__) : fn<VQHIP_DTYPE_F16, false>(__VA_ARGS__);                  \
-        }                                                                                                               \
-    } while (0)
-
 int vqhip_token_ce_fwd(const void *logits, int dtype, int64_t R, int64_t row_stride, int64_t start, int64_t end, const void *targets,
                        int target_dtype, int64_t shift_len, int64_t ignore_index, float label_smoothing, const float *weight,
                        float *loss, float *lse, int32_t *hit, float *out, void *stream) {
@@ -1485,7 +1491,12 @@ int vqhip_token_ce_fwd(const void *logits, int dtype, int64_t R, int64_t row_str
     if (int rc = token_ce_setup("vqhip_token_ce_fwd", logits, dtype, R, row_stride, start, end, targets, target_dtype, shift_len,
                                 ignore_index, label_smoothing, weight, &a)) return rc;
     VQ_REQUIRE(loss && lse && out, "vqhip_token_ce_fwd: loss, lse and out are required");
-    VQ_TOKEN_CE_DISPATCH(launch_token_ce_fwd, a, loss, lse, hit, out, (hipStream_t)stream);
+    hipStream_t s = (hipStream_t)stream;
+    return vq_with_dtype(dtype, [&](auto dt) {
+        constexpr int DT = decltype(dt)::value;
+        return target_dtype == VQHIP_DTYPE_I64 ? launch_token_ce_fwd<DT, true>(a, loss, lse, hit, out, s)
+                                               : launch_token_ce_fwd<DT, false>(a, loss, lse, hit, out, s);
+    });
 }
 
 int vqhip_token_ce_bwd(const void *logits, int dtype, int64_t R, int64_t row_stride, int64_t start, int64_t end, const void *targets,
@@ -1497,9 +1508,13 @@ int vqhip_token_ce_bwd(const void *logits, int dtype, int64_t R, int64_t row_str
                                 ignore_index, label_smoothing, weight, &a)) return rc;
     VQ_REQUIRE(lse && g && grad, "vqhip_token_ce_bwd: lse, g and grad are required");
     VQ_REQUIRE(end <= cols && cols <= row_stride_out && cols < (1ll << 31), "vqhip_token_ce_bwd: need end <= cols <= row_stride_out, cols < 2^31");
-    VQ_TOKEN_CE_DISPATCH(launch_token_ce_bwd, a, lse, g, g_per_row ? 1 : 0, wsum, grad, (int)cols, row_stride_out, (hipStream_t)stream);
+    hipStream_t s = (hipStream_t)stream;
+    return vq_with_dtype(dtype, [&](auto dt) {
+        constexpr int DT = decltype(dt)::value;
+        return target_dtype == VQHIP_DTYPE_I64 ? launch_token_ce_bwd<DT, true>(a, lse, g, g_per_row ? 1 : 0, wsum, grad, (int)cols, row_stride_out, s)
+                                               : launch_token_ce_bwd<DT, false>(a, lse, g, g_per_row ? 1 : 0, wsum, grad, (int)cols, row_stride_out, s);
+    });
 }
-#undef VQ_TOKEN_CE_DISPATCH
 
 // ---- fused CosineEmbeddingLoss (vqhip_cosine_embed_kernels.h) --------------------------------------------------------------
 // what the two entry points refuse alike, and the arguments the kernels share
@@ -1507,9 +1522,8 @@ static int cosine_embed_setup(const char *what, const void *pred, int pred_dtype
                               const void *target, int target_dtype, int64_t target_row_stride, int64_t B, int64_t P, int64_t C,
                               VqCoseArgs *a) {
     if (!pred || !target) return fail(VQHIP_EINVAL, what, "pred and target are required");
-    for (int dtype : {pred_dtype, target_dtype})
-        if (dtype != VQHIP_DTYPE_F32 && dtype != VQHIP_DTYPE_BF16 && dtype != VQHIP_DTYPE_F16) return fail(VQHIP_EINVAL, what, "dtype");
-    if (pred_layout != VQHIP_LAYOUT_ROWS && pred_layout != VQHIP_LAYOUT_MAP) return fail(VQHIP_EINVAL, what, "pred_layout");
+    if (!vq_float_dtype(pred_dtype) || !vq_float_dtype(target_dtype)) return fail(VQHIP_EINVAL, what, "dtype");
+    if (!vq_dense_layout(pred_layout)) return fail(VQHIP_EINVAL, what, "pred_layout");
     const int64_t cap = 1ll << 31;
     if (B < 1 || P < 1 || B >= cap || P >= cap || B * P >= cap) return fail(VQHIP_EINVAL, what, "R = B * P must be in 1 .. 2^31 - 1");
     if (C < 1 || C > VQHIP_COSINE_EMBED_MAX_C) return fail(VQHIP_EINVAL, what, "C must be in 1 .. 2^16");
@@ -1521,21 +1535,6 @@ static int cosine_embed_setup(const char *what, const void *pred, int pred_dtype
     return VQHIP_OK;
 }
 
-#define VQ_COSE_DISPATCH_T(fn, DP, ...)                                                                                 \
-    switch (target_dtype) {                                                                                             \
-    case VQHIP_DTYPE_F32: return fn<DP, VQHIP_DTYPE_F32>(__VA_ARGS__);                                                  \
-    case VQHIP_DTYPE_BF16: return fn<DP, VQHIP_DTYPE_BF16>(__VA_ARGS__);                                                \
-    default: return fn<DP, VQHIP_DTYPE_F16>(__VA_ARGS__);                                                               \
-    }
-#define VQ_COSE_DISPATCH(fn, ...)                                                                                       \
-    do {                                                                                                                \
-        switch (pred_dtype) {                                                                                           \
-        case VQHIP_DTYPE_F32: VQ_COSE_DISPATCH_T(fn, VQHIP_DTYPE_F32, __VA_ARGS__)                                      \
-        case VQHIP_DTYPE_BF16: VQ_COSE_DISPATCH_T(fn, VQHIP_DTYPE_BF16, __VA_ARGS__)                                    \
-        default: VQ_COSE_DISPATCH_T(fn, VQHIP_DTYPE_F16, __VA_ARGS__)                                                   \
-        }                                                                                                               \
-    } while (0)
-
 int vqhip_cosine_embed_fwd(const void *pred, int pred_dtype, int pred_layout, int64_t pred_row_stride, const void *target,
                            int target_dtype, int64_t target_row_stride, int64_t B, int64_t P, int64_t C, float *loss, float *stats,
                            float *out, void *stream) {
@@ -1543,7 +1542,9 @@ int vqhip_cosine_embed_fwd(const void *pred, int pred_dtype, int pred_layout, in
     if (int rc = cosine_embed_setup("vqhip_cosine_embed_fwd", pred, pred_dtype, pred_layout, pred_row_stride, target, target_dtype,
                                     target_row_stride, B, P, C, &a)) return rc;
     VQ_REQUIRE(loss && stats && out, "vqhip_cosine_embed_fwd: loss, stats and out are required");
-    VQ_COSE_DISPATCH(launch_cosine_embed_fwd, a, pred_layout, loss, stats, out, (hipStream_t)stream);
+    return vq_with_dtype(pred_dtype, [&](auto dp) { return vq_with_dtype(target_dtype, [&](auto dt) {
+        return launch_cosine_embed_fwd<decltype(dp)::value, decltype(dt)::value>(a, pred_layout, loss, stats, out, (hipStream_t)stream);
+    }); });
 }
 
 int vqhip_cosine_embed_bwd(const void *pred, int pred_dtype, int pred_layout, int64_t pred_row_stride, const void *target,
@@ -1554,11 +1555,11 @@ int vqhip_cosine_embed_bwd(const void *pred, int pred_dtype, int pred_layout, in
                                     target_row_stride, B, P, C, &a)) return rc;
     VQ_REQUIRE(stats && g && grad, "vqhip_cosine_embed_bwd: stats, g and grad are required");
     VQ_REQUIRE(pred_layout != VQHIP_LAYOUT_ROWS || grad_row_stride >= C, "vqhip_cosine_embed_bwd: the row stride of grad is below C");
-    VQ_COSE_DISPATCH(launch_cosine_embed_bwd, a, pred_layout, stats, g, g_per_row ? 1 : 0, mean ? 1 : 0, grad, grad_row_stride,
-                     (hipStream_t)stream);
+    return vq_with_dtype(pred_dtype, [&](auto dp) { return vq_with_dtype(target_dtype, [&](auto dt) {
+        return launch_cosine_embed_bwd<decltype(dp)::value, decltype(dt)::value>(a, pred_layout, stats, g, g_per_row ? 1 : 0, mean ? 1 : 0, grad,
+                                                                                 grad_row_stride, (hipStream_t)stream);
+    }); });
 }
-#undef VQ_COSE_DISPATCH
-#undef VQ_COSE_DISPATCH_T
 
 // ---- fused LPIPS tail (vqhip_lpips_kernels.h) -------------------------------------------------------------------------------
 // what the dropout of the three entry points refuses, and its threshold and scale
@@ -1586,29 +1587,13 @@ static int lpips_sizes(const char *what, int64_t B, int64_t C, int64_t P, VqLpip
 static int lpips_setup(const char *what, const void *pred, int pred_dtype, const void *target, int target_dtype, int layout, int64_t B,
                        int64_t C, int64_t P, const float *w, const uint32_t *seed, float p, int64_t layer, VqLpipsArgs *a) {
     if (!pred || !target || !w) return fail(VQHIP_EINVAL, what, "pred, target and w are required");
-    for (int dtype : {pred_dtype, target_dtype})
-        if (dtype != VQHIP_DTYPE_F32 && dtype != VQHIP_DTYPE_BF16 && dtype != VQHIP_DTYPE_F16) return fail(VQHIP_EINVAL, what, "dtype");
-    if (layout != VQHIP_LAYOUT_ROWS && layout != VQHIP_LAYOUT_MAP) return fail(VQHIP_EINVAL, what, "layout");
+    if (!vq_float_dtype(pred_dtype) || !vq_float_dtype(target_dtype)) return fail(VQHIP_EINVAL, what, "dtype");
+    if (!vq_dense_layout(layout)) return fail(VQHIP_EINVAL, what, "layout");
     if (int rc = lpips_sizes(what, B, C, P, a)) return rc;
     if (int rc = lpips_dropout(what, seed, p, layer, a)) return rc;
     a->pred = pred; a->target = target; a->w = w;
     return VQHIP_OK;
 }
-
-#define VQ_LPIPS_DISPATCH_T(fn, DP, ...)                                                                                \
-    switch (target_dtype) {                                                                                             \
-    case VQHIP_DTYPE_F32: return fn<DP, VQHIP_DTYPE_F32>(__VA_ARGS__);                                                  \
-    case VQHIP_DTYPE_BF16: return fn<DP, VQHIP_DTYPE_BF16>(__VA_ARGS__);                                                \
-    default: return fn<DP, VQHIP_DTYPE_F16>(__VA_ARGS__);                                                               \
-    }
-#define VQ_LPIPS_DISPATCH(fn, ...)                                                                                      \
-    do {                                                                                                                \
-        switch (pred_dtype) {                                                                                           \
-        case VQHIP_DTYPE_F32: VQ_LPIPS_DISPATCH_T(fn, VQHIP_DTYPE_F32, __VA_ARGS__)                                     \
-        case VQHIP_DTYPE_BF16: VQ_LPIPS_DISPATCH_T(fn, VQHIP_DTYPE_BF16, __VA_ARGS__)                                   \
-        default: VQ_LPIPS_DISPATCH_T(fn, VQHIP_DTYPE_F16, __VA_ARGS__)                                                  \
-        }                                                                                                               \
-    } while (0)
 
 int vqhip_lpips_fwd(const void *pred, int pred_dtype, const void *target, int target_dtype, int layout, int64_t B, int64_t C,
                     int64_t P, const float *w, const uint32_t *seed, float p, int64_t layer, float *stats, float *value,
@@ -1616,7 +1601,9 @@ int vqhip_lpips_fwd(const void *pred, int pred_dtype, const void *target, int ta
     VqLpipsArgs a;
     if (int rc = lpips_setup("vqhip_lpips_fwd", pred, pred_dtype, target, target_dtype, layout, B, C, P, w, seed, p, layer, &a)) return rc;
     VQ_REQUIRE(stats && value, "vqhip_lpips_fwd: stats and value are required");
-    VQ_LPIPS_DISPATCH(launch_lpips_fwd, a, layout, stats, value, accumulate ? 1 : 0, (hipStream_t)stream);
+    return vq_with_dtype(pred_dtype, [&](auto dp) { return vq_with_dtype(target_dtype, [&](auto dt) {
+        return launch_lpips_fwd<decltype(dp)::value, decltype(dt)::value>(a, layout, stats, value, accumulate ? 1 : 0, (hipStream_t)stream);
+    }); });
 }
 
 int vqhip_lpips_bwd(const void *pred, int pred_dtype, const void *target, int target_dtype, int layout, int64_t B, int64_t C,
@@ -1625,10 +1612,10 @@ int vqhip_lpips_bwd(const void *pred, int pred_dtype, const void *target, int ta
     VqLpipsArgs a;
     if (int rc = lpips_setup("vqhip_lpips_bwd", pred, pred_dtype, target, target_dtype, layout, B, C, P, w, seed, p, layer, &a)) return rc;
     VQ_REQUIRE(stats && g_out && grad, "vqhip_lpips_bwd: stats, g_out and grad are required");
-    VQ_LPIPS_DISPATCH(launch_lpips_bwd, a, layout, stats, g_out, grad, (hipStream_t)stream);
+    return vq_with_dtype(pred_dtype, [&](auto dp) { return vq_with_dtype(target_dtype, [&](auto dt) {
+        return launch_lpips_bwd<decltype(dp)::value, decltype(dt)::value>(a, layout, stats, g_out, grad, (hipStream_t)stream);
+    }); });
 }
-#undef VQ_LPIPS_DISPATCH
-#undef VQ_LPIPS_DISPATCH_T
 
 int vqhip_lpips_keep_mask(const uint32_t *seed, float p, int64_t layer, int64_t B, int64_t C, int64_t P, uint8_t *out, void *stream) {
     const char *what = "vqhip_lpips_keep_mask";
@@ -1644,19 +1631,10 @@ int vqhip_lpips_keep_mask(const uint32_t *seed, float p, int64_t layer, int64_t 
 }
 
 // ---- StyleGAN2 discriminator ops (vqhip_stylegan2_kernels.h) -----------------------------------------------------------------
-#define VQ_SG2_DISPATCH(fn, ...)                                                                                        \
-    do {                                                                                                                \
-        switch (dtype) {                                                                                                \
-        case VQHIP_DTYPE_F32: return fn<VQHIP_DTYPE_F32>(__VA_ARGS__);                                                  \
-        case VQHIP_DTYPE_BF16: return fn<VQHIP_DTYPE_BF16>(__VA_ARGS__);                                                \
-        default: return fn<VQHIP_DTYPE_F16>(__VA_ARGS__);                                                               \
-        }                                                                                                               \
-    } while (0)
-
 // what every entry point of the block refuses alike
 static int sg2_common(const char *what, int dtype, int layout, int64_t B, int64_t C, int64_t P) {
-    if (dtype != VQHIP_DTYPE_F32 && dtype != VQHIP_DTYPE_BF16 && dtype != VQHIP_DTYPE_F16) return fail(VQHIP_EINVAL, what, "dtype");
-    if (layout != VQHIP_LAYOUT_ROWS && layout != VQHIP_LAYOUT_MAP) return fail(VQHIP_EINVAL, what, "layout");
+    if (!vq_float_dtype(dtype)) return fail(VQHIP_EINVAL, what, "dtype");
+    if (!vq_dense_layout(layout)) return fail(VQHIP_EINVAL, what, "layout");
     const int64_t cap = 1ll << 31;
     if (B < 1 || C < 1 || P < 1 || B >= cap || P >= cap || C > VQHIP_SG2_MAX_C) return fail(VQHIP_EINVAL, what, "need B, P >= 1 and 1 <= C <= 2^16");
     if (B * P >= cap || B * P * C >= cap) return fail(VQHIP_EINVAL, what, "B * C * P must be below 2^31");
@@ -1677,7 +1655,7 @@ int vqhip_bias_act_fwd(const void *x, int dtype, int layout, int64_t B, int64_t 
     VQ_REQUIRE(x && bias && y, "vqhip_bias_act_fwd: x, bias and y are required");
     VqBiasActArgs a = {};
     a.x = x; a.bias = bias; a.out = y; a.n = B * C * P; a.B = (int)B; a.C = (int)C; a.P = (int)P;
-    VQ_SG2_DISPATCH(launch_bias_act_fwd, a, sg2_rows(layout, P), (hipStream_t)stream);
+    return vq_with_dtype(dtype, [&](auto dt) { return launch_bias_act_fwd<decltype(dt)::value>(a, sg2_rows(layout, P), (hipStream_t)stream); });
 }
 
 int vqhip_bias_act_bwd(const void *g, const void *y, int dtype, int layout, int64_t B, int64_t C, int64_t P, void *gx, float *gbias,
@@ -1691,7 +1669,9 @@ int vqhip_bias_act_bwd(const void *g, const void *y, int dtype, int layout, int6
     VqBiasActArgs a = {};
     a.x = g; a.y = y; a.out = gx; a.ws = gbias ? ws : nullptr; a.n = B * C * P; a.B = (int)B; a.C = (int)C; a.P = (int)P;
     a.chunks = (int)((P + VQ_SG2_MAP_CHUNK - 1) / VQ_SG2_MAP_CHUNK);
-    VQ_SG2_DISPATCH(launch_bias_act_bwd, a, sg2_rows(layout, P), slabs, gbias, (hipStream_t)stream);
+    return vq_with_dtype(dtype, [&](auto dt) {
+        return launch_bias_act_bwd<decltype(dt)::value>(a, sg2_rows(layout, P), slabs, gbias, (hipStream_t)stream);
+    });
 }
 
 // the sizes and tiles of a blur: (H, W) the blur's INPUT plane, (OH, OW) its output; `adjoint` walks tiles of the input plane
@@ -1734,16 +1714,10 @@ int vqhip_fir4_fwd(const void *x, int dtype, int layout, int64_t B, int64_t C, i
     if (int rc = fir4_setup("vqhip_fir4_fwd", dtype, layout, B, C, H, W, down, py0, py1, px0, px1, false, &a)) return rc;
     VQ_REQUIRE(x && out, "vqhip_fir4_fwd: x and out are required");
     a.in = x; a.out = out; a.bias = bias;
-    VQ_SG2_DISPATCH(launch_fir4, a, layout == VQHIP_LAYOUT_ROWS, down, bias ? VQ_FIR_ACT_IN : VQ_FIR_NONE, (hipStream_t)stream);
+    return vq_with_dtype(dtype, [&](auto dt) {
+        return launch_fir4<decltype(dt)::value>(a, layout == VQHIP_LAYOUT_ROWS, down, bias ? VQ_FIR_ACT_IN : VQ_FIR_NONE, (hipStream_t)stream);
+    });
 }
-
-extern "C++" {
-template <int DT>
-static int fir4_bwd_run(const VqFirArgs &a, bool rows, float *gbias, hipStream_t s) {
-    if (int rc = launch_fir4<DT>(a, rows, 1, a.x ? VQ_FIR_MASK_OUT : VQ_FIR_NONE, s)) return rc;
-    return a.x ? launch_sg2_reduce(a.ws, (int64_t)a.B * a.tiles_y * a.tiles_x, a.C, gbias, s) : VQHIP_OK;
-}
-}  // extern "C++"
 
 int vqhip_fir4_bwd(const void *g, int dtype, int layout, int64_t B, int64_t C, int64_t H, int64_t W, int down, int py0, int py1, int px0,
                    int px1, const void *x, const float *bias, void *gx, float *gbias, float *ws, int64_t ws_bytes, void *stream) {
@@ -1754,8 +1728,9 @@ int vqhip_fir4_bwd(const void *g, int dtype, int layout, int64_t B, int64_t C, i
     VQ_REQUIRE(!x || (gbias && ws), "vqhip_fir4_bwd: the fused form needs gbias and the workspace");
     if (x) VQ_NEED("vqhip_fir4_bwd: ws too small", ws_bytes, (int64_t)B * a.tiles_y * a.tiles_x * C * (int64_t)sizeof(float));
     a.in = g; a.out = gx; a.x = x; a.bias = bias; a.ws = ws;
-    VQ_SG2_DISPATCH(fir4_bwd_run, a, layout == VQHIP_LAYOUT_ROWS, gbias, (hipStream_t)stream);
+    return vq_with_dtype(dtype, [&](auto dt) { return fir4_bwd_run<decltype(dt)::value>(a, layout == VQHIP_LAYOUT_ROWS, gbias, (hipStream_t)stream); });
 }
+
 // ---- GroupNorm (+ SiLU) (vqhip_group_norm_kernels.h) ---------------------------------------------------------------------------
 struct VqGnPlan {
     int64_t n, S, units, slabs, ws_floats;
@@ -1764,8 +1739,8 @@ struct VqGnPlan {
 
 // what the three entry points refuse alike; on success the launch shape
 static int gn_plan(const char *what, int dtype, int layout, int64_t B, int64_t C, int64_t P, int64_t G, VqGnPlan *pl) {
-    if (dtype != VQHIP_DTYPE_F32 && dtype != VQHIP_DTYPE_BF16 && dtype != VQHIP_DTYPE_F16) return fail(VQHIP_EINVAL, what, "dtype");
-    if (layout != VQHIP_LAYOUT_ROWS && layout != VQHIP_LAYOUT_MAP) return fail(VQHIP_EINVAL, what, "layout");
+    if (!vq_float_dtype(dtype)) return fail(VQHIP_EINVAL, what, "dtype");
+    if (!vq_dense_layout(layout)) return fail(VQHIP_EINVAL, what, "layout");
     if (B < 1 || C < 1 || P < 1 || G < 1) return fail(VQHIP_EINVAL, what, "B, C, P and G must be positive");
     if (C % G != 0) return fail(VQHIP_EINVAL, what, "C must be a multiple of G");
     const int64_t cap = 1ll << 31;
@@ -1805,7 +1780,9 @@ int vqhip_group_norm_fwd(const void *x, int dtype, int layout, int64_t B, int64_
     VqGnArgs a = {};
     gn_fill(&a, pl, B, C, P, G, ws);
     a.x = x; a.out = y; a.gamma = gamma; a.beta = beta; a.stats = stats; a.eps = eps; a.act = act;
-    VQ_SG2_DISPATCH(gn_run, a, layout == VQHIP_LAYOUT_ROWS, pl.T, false, pl.slabs, nullptr, nullptr, (hipStream_t)stream);
+    return vq_with_dtype(dtype, [&](auto dt) {
+        return gn_run<decltype(dt)::value>(a, layout == VQHIP_LAYOUT_ROWS, pl.T, false, pl.slabs, nullptr, nullptr, (hipStream_t)stream);
+    });
 }
 
 int vqhip_group_norm_bwd(const void *g, const void *x, int dtype, int layout, int64_t B, int64_t C, int64_t P, int64_t G,
@@ -1820,9 +1797,10 @@ int vqhip_group_norm_bwd(const void *g, const void *x, int dtype, int layout, in
     VqGnArgs a = {};
     gn_fill(&a, pl, B, C, P, G, ws);
     a.x = x; a.g = g; a.out = gx; a.gamma = gamma; a.beta = beta; a.stats = const_cast<float *>(stats); a.act = act;
-    VQ_SG2_DISPATCH(gn_run, a, layout == VQHIP_LAYOUT_ROWS, pl.T, true, pl.slabs, dgamma, dbeta, (hipStream_t)stream);
+    return vq_with_dtype(dtype, [&](auto dt) {
+        return gn_run<decltype(dt)::value>(a, layout == VQHIP_LAYOUT_ROWS, pl.T, true, pl.slabs, dgamma, dbeta, (hipStream_t)stream);
+    });
 }
-#undef VQ_SG2_DISPATCH
 
 // ---- fused reconstruction metrics (vqhip_image_metrics_kernels.h) ---------------------------------------------------------
 // what both entry points refuse; on success the number of workgroups of the first launch and the tiles along each axis
@@ -1847,7 +1825,7 @@ int64_t vqhip_image_metrics_workspace_bytes(int64_t B, int64_t C, int64_t H, int
 
 static int image_metrics_side(const char *what, const void *p, int dtype, int layout, int64_t C, int64_t H, int64_t W, VqImSide *s) {
     if (!p) return fail(VQHIP_EINVAL, what, "pred and image are required");
-    if (dtype != VQHIP_DTYPE_F32 && dtype != VQHIP_DTYPE_BF16 && dtype != VQHIP_DTYPE_F16 && dtype != VQHIP_DTYPE_U8) return fail(VQHIP_EINVAL, what, "dtype");
+    if (!vq_float_dtype(dtype) && dtype != VQHIP_DTYPE_U8) return fail(VQHIP_EINVAL, what, "dtype");
     if (layout != VQHIP_IMAGE_NCHW && layout != VQHIP_IMAGE_NHWC) return fail(VQHIP_EINVAL, what, "layout");
     s->p = p; s->dtype = dtype; s->sb = C * H * W;
     if (layout == VQHIP_IMAGE_NCHW) { s->sc = H * W; s->sy = W; s->sx = 1; }

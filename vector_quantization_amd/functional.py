@@ -487,7 +487,7 @@ class _Fir4Backward(Function):
 
     @staticmethod
     def backward(ctx, gg):
-        return _Fir4.apply(ops.sg2_dense(gg), ctx.pad, ctx.down), None, None, None
+        return _Fir4.apply(ops.dense(gg), ctx.pad, ctx.down), None, None, None
 
 
 class _Fir4(Function):

@@ -684,32 +684,110 @@ def fsq_decode(quant: torch.Tensor, q: _lib.FsqConstants, map_shape: Optional[tu
     return z
 
 
+# ---- what the op families below decide alike about a tensor: float dtype, dense layout, row view, small arguments -----------
+
+FLOAT_DTYPES = {torch.float32: _lib.DTYPE_F32, torch.bfloat16: _lib.DTYPE_BF16, torch.float16: _lib.DTYPE_F16}
+IMAGE_DTYPES = {**FLOAT_DTYPES, torch.uint8: _lib.DTYPE_U8}
+LAYOUTS = {'rows': _lib.LAYOUT_ROWS, 'map': _lib.LAYOUT_MAP}              # channels-last dense / NCHW-contiguous
+IMAGE_LAYOUTS = {'rows': _lib.IMAGE_NHWC, 'map': _lib.IMAGE_NCHW}         # the same two in vqhip_image_metrics' enum (codes reversed)
+
+
+def float_dtype_refusal(name: str, t: torch.Tensor) -> str:
+    """'' for fp32 / bf16 / fp16, else the sentence that says so; ``name`` is the subject with its verb ('pred is')."""
+    return '' if t.dtype in FLOAT_DTYPES else f'{name} {t.dtype}, not float32, bfloat16 or float16'
+
+
+def dense_layouts(t: torch.Tensor) -> tuple:
+    """The layouts of include/vqhip.h ``t`` is dense in: 'map' (contiguous: NCHW, [B, C], ...) before 'rows' (4-D channels-last)."""
+    found = ('map',) if t.is_contiguous() else ()
+    if t.dim() == 4 and t.is_contiguous(memory_format=torch.channels_last):
+        found += ('rows',)
+    return found
+
+
+def dense_layout(t: torch.Tensor):
+    """The first of ``dense_layouts(t)`` ('map' where both hold, as for C == 1), None where there is none."""
+    found = dense_layouts(t)
+    return found[0] if found else None
+
+
+def dense_refusal(name: str, t: torch.Tensor) -> str:
+    """'' where ``t`` is dense in one of the two layouts, else the sentence that says so."""
+    return '' if dense_layouts(t) else f'{name} with strides {t.stride()} is neither NCHW-contiguous nor channels-last dense'
+
+
+def dense(t: torch.Tensor) -> torch.Tensor:
+    """``t`` itself where it is dense in one of the two layouts, else a contiguous copy: autograd hands over gradients with any
+    strides (the expanded scalar of ``.sum().backward()`` has none but zeros)."""
+    return t if dense_layouts(t) else t.contiguous()
+
+
+def _dense_like(t: torch.Tensor, like: torch.Tensor) -> torch.Tensor:
+    """``t`` dense in the layout the kernels read ``like`` in (a copy only where autograd handed over another memory format)."""
+    if dense_layout(like) == 'rows':
+        return t if t.is_contiguous(memory_format=torch.channels_last) else t.contiguous(memory_format=torch.channels_last)
+    return t if t.is_contiguous() else t.contiguous()
+
+
+def _empty_like(x: torch.Tensor, shape) -> torch.Tensor:
+    """An uninitialised [B, C, H, W] tensor of ``shape`` in the dtype and dense layout of ``x``."""
+    fmt = torch.channels_last if dense_layout(x) == 'rows' else torch.contiguous_format
+    return torch.empty(shape, dtype=x.dtype, device=x.device, memory_format=fmt)
+
+
+def row_view(t: torch.Tensor, name: str):
+    """``t`` [..., C] as rows [R, C] read in place: (the VIEW, its row stride in elements), or a string that says why not - no float
+    dtype, a strided last dimension, leading dimensions that flatten only by a copy, rows that overlap.  Never a copy.  Nothing
+    follows a single row, so its stride counts as at least C.  An empty tensor passes (R = 0 is the caller's to refuse)."""
+    if t.dim() < 1 or t.dtype not in FLOAT_DTYPES:
+        return f'{name}: {t.dtype} {tuple(t.shape)} is not float32, bfloat16 or float16 with at least one dimension'
+    C = t.shape[-1]
+    if t.stride(-1) != 1 and C > 1:
+        return f'the last dimension of {name} does not have stride 1'
+    try:
+        rows = t if t.dim() == 2 else t.view(-1, C)
+    except RuntimeError:
+        return f'{name}: shape {tuple(t.shape)} with strides {t.stride()} does not flatten to rows without a copy'
+    stride = rows.stride(0) if rows.shape[0] > 1 else max(rows.stride(0), C)
+    if stride < C:
+        return f'the rows of {name} overlap (row stride {stride} < {C})'
+    return rows, stride
+
+
+def _refuse(what: str, why: str) -> None:
+    if why:
+        raise ValueError(f'{what}: {why}')
+
+
+def _grad_values(g: torch.Tensor, R: int):
+    """The incoming gradient as the kernels read it: (fp32, flat, contiguous; 1 where it holds one value per row of R > 1 rows)."""
+    g = g.reshape(-1).to(torch.float32).contiguous()
+    return g, 1 if g.numel() == R and R > 1 else 0
+
+
+def _fp32_vector(p: torch.Tensor) -> torch.Tensor:
+    """A parameter as the kernels read it: fp32, flat, contiguous (a copy of its few elements only where it is not that already)."""
+    return p.detach().reshape(-1).to(torch.float32).contiguous()
+
+
+def _seed_refusal(seed: torch.Tensor) -> str:
+    ok = seed.dtype in (torch.int32, torch.uint32) and seed.numel() == 2 and seed.is_contiguous()
+    return '' if ok else f'seed must hold two contiguous 32-bit words on the device, got {seed.dtype} {tuple(seed.shape)}'
+
+
 # ---- fused token sampler (stage-2 generation, vq/tasks/sequence_modeling/models/samplers.py) -----------------------------
 
-SAMPLE_DTYPES = {torch.float32: _lib.DTYPE_F32, torch.bfloat16: _lib.DTYPE_BF16, torch.float16: _lib.DTYPE_F16}
 SAMPLE_MAX_V = 1 << 20
 
 
 def _logit_rows(what: str, logits: torch.Tensor, start: int, end: int):
     """``logits`` [..., V_total] as the kernels read it in place: (rows [R, V_total] as a VIEW, R, the row stride in elements).
-    ValueError where that takes a copy, the last dimension is strided, the rows overlap or [start, end) is not inside it."""
-    if logits.dim() < 1 or logits.dtype not in SAMPLE_DTYPES:
-        raise ValueError(f'{what}: logits must be fp32, bf16 or fp16 with at least one dimension, got {logits.dtype} {tuple(logits.shape)}')
-    shape = logits.shape
-    try:
-        rows = logits if logits.dim() == 2 else logits.view(-1, shape[-1])       # never a copy: the logits are read in place
-    except RuntimeError:
-        raise ValueError(f'{what}: logits of shape {tuple(shape)} and strides {logits.stride()} do not flatten to rows '
-                         'without a copy') from None
-    if not 0 <= start < end <= shape[-1]:
-        raise ValueError(f'{what}: need 0 <= start < end <= {shape[-1]} (the last dimension), got [{start}, {end})')
-    if rows.stride(1) != 1 and rows.shape[1] > 1:
-        raise ValueError(f'{what}: the last dimension of the logits must have stride 1')
-    R = rows.shape[0]
-    stride = rows.stride(0) if R > 1 else max(rows.stride(0), rows.shape[1])
-    if stride < rows.shape[1]:
-        raise ValueError(f'{what}: rows of the logits overlap')
-    return rows, R, stride
+    ValueError where ``row_view`` has a reason or [start, end) is not inside the last dimension."""
+    view = row_view(logits, 'the logits')
+    if not isinstance(view, str) and not 0 <= start < end <= logits.shape[-1]:
+        view = f'need 0 <= start < end <= {logits.shape[-1]} (the last dimension), got [{start}, {end})'
+    _refuse(what, view if isinstance(view, str) else '')
+    return view[0], view[0].shape[0], view[1]
 
 
 @_on_tensor_device
@@ -734,7 +812,7 @@ def sample_tokens(logits: torch.Tensor, start: int, end: int, *, u: torch.Tensor
     tokens = torch.empty(R, dtype=torch.int64, device=logits.device)
     cut = torch.empty(Ro, 6, dtype=torch.int32, device=logits.device) if want_cut else None
     # the library checks the limits (R, the slice, V <= 2^20, temperature, alpha) before any HIP call
-    check(_lib.lib().vqhip_sample_tokens(_ptr(rows), SAMPLE_DTYPES[logits.dtype], R, stride, int(start), int(end),
+    check(_lib.lib().vqhip_sample_tokens(_ptr(rows), FLOAT_DTYPES[logits.dtype], R, stride, int(start), int(end),
                                          float(cfg_alpha) if cfg else 0.0, 1 if cfg else 0, float(temperature), int(top_k),
                                          float(top_p), _ptr(u), _ptr(tokens), _ptr(cut), _stream()), 'vqhip_sample_tokens')
     tokens = tokens.reshape(shape[:-1])
@@ -769,8 +847,8 @@ def _token_ce_args(what: str, logits, targets, start, end, label_smoothing, igno
     if weight is not None:
         if weight.numel() != R:
             raise ValueError(f'{what}: weight must have one value per row ({R}), got {tuple(weight.shape)}')
-        weight = weight.reshape(-1).to(torch.float32).contiguous()
-    head = (_ptr(rows), SAMPLE_DTYPES[logits.dtype], R, stride, int(start), int(end), _ptr(targets), TOKEN_DTYPES[targets.dtype],
+        weight = _fp32_vector(weight)
+    head = (_ptr(rows), FLOAT_DTYPES[logits.dtype], R, stride, int(start), int(end), _ptr(targets), TOKEN_DTYPES[targets.dtype],
             int(logits.shape[-2]) if shift else 0, int(ignore_index), float(label_smoothing), _ptr(weight))
     return head, R, (rows, targets, weight)
 
@@ -800,15 +878,15 @@ def token_ce_backward(logits: torch.Tensor, targets: torch.Tensor, lse: torch.Te
     ``weight_sum``: the device scalar W of the forward for the mean, None otherwise.  ``out``: a buffer to write into."""
     head, R, keep = _token_ce_args('token_ce_backward', logits, targets, start, end, label_smoothing, ignore_index, weight, shift)
     _require_cuda(lse, g, weight_sum, out)
-    g = g.reshape(-1).to(torch.float32).contiguous()
+    g, per_row = _grad_values(g, R)
     if g.numel() not in (1, R) or lse.dtype != torch.float32 or lse.numel() != R or not lse.is_contiguous():
         raise ValueError(f'token_ce_backward: g must hold 1 or {R} values and lse {R} contiguous fp32 values')
     Vt = logits.shape[-1]
     grad = torch.empty(logits.shape, dtype=logits.dtype, device=logits.device) if out is None else out
     if grad.shape != logits.shape or grad.dtype != logits.dtype or not grad.is_contiguous():
         raise ValueError('token_ce_backward: out must be contiguous, of the shape and dtype of the logits')
-    check(_lib.lib().vqhip_token_ce_bwd(*head, _ptr(lse), _ptr(g), 1 if g.numel() == R and R > 1 else 0, _ptr(weight_sum),
-                                        _ptr(grad), Vt, Vt, _stream()), 'vqhip_token_ce_bwd')
+    check(_lib.lib().vqhip_token_ce_bwd(*head, _ptr(lse), _ptr(g), per_row, _ptr(weight_sum), _ptr(grad), Vt, Vt, _stream()),
+          'vqhip_token_ce_bwd')
     return grad
 
 
@@ -824,27 +902,7 @@ def token_cross_entropy(logits: torch.Tensor, targets: torch.Tensor, start: int 
 
 # ---- fused CosineEmbeddingLoss (VQ-KD distillation: vq/algorithms/utils/losses.py:13-65) ------------------------------------
 
-COSINE_LAYOUTS = {'rows': _lib.LAYOUT_ROWS, 'map': _lib.LAYOUT_MAP}
 COSINE_REDUCTIONS = ('mean', 'sum', 'none')
-
-
-def _feature_rows(t: torch.Tensor):
-    """``t`` [..., C] as rows [R, C] read in place: (the VIEW, its row stride in elements), or a string that says why not."""
-    if t.dim() < 1 or t.dtype not in SAMPLE_DTYPES:
-        return f'{t.dtype} {tuple(t.shape)} is not float32, bfloat16 or float16 with a channel dimension'
-    C = t.shape[-1]
-    if t.numel() == 0:
-        return f'empty tensor {tuple(t.shape)}'
-    if t.stride(-1) != 1 and C > 1:
-        return 'the last dimension does not have stride 1'
-    try:
-        rows = t if t.dim() == 2 else t.view(-1, C)
-    except RuntimeError:
-        return f'shape {tuple(t.shape)} with strides {t.stride()} does not flatten to rows without a copy'
-    stride = rows.stride(0) if rows.shape[0] > 1 else max(rows.stride(0), C)
-    if stride < C:
-        return f'the rows overlap (row stride {stride} < {C})'
-    return rows, stride
 
 
 def cosine_embedding_refusal(pred: torch.Tensor, target: torch.Tensor, layout: Optional[str] = None) -> str:
@@ -852,21 +910,23 @@ def cosine_embedding_refusal(pred: torch.Tensor, target: torch.Tensor, layout: O
     tensors' dtypes, shapes and strides.  ``layout``: 'rows' (None: the same) - pred and target both [..., C]; 'map' - pred the
     NCHW-contiguous [B, C, *positions], target [B, *positions, C] (or [B * P, C])."""
     layout = layout or 'rows'
-    if layout not in COSINE_LAYOUTS:
+    if layout not in LAYOUTS:
         return f'layout {layout!r} is neither rows nor map'
-    for name, t in (('pred', pred), ('target', target)):
-        if t.dtype not in SAMPLE_DTYPES:
-            return f'{name} is {t.dtype}, not float32, bfloat16 or float16'
-    rows = _feature_rows(target)
+    why = float_dtype_refusal('pred is', pred) or float_dtype_refusal('target is', target)
+    if why:
+        return why
+    if target.numel() == 0:                                                     # (row_view lets R = 0 pass)
+        return f'target: empty tensor {tuple(target.shape)}'
+    rows = row_view(target, 'target')
     if isinstance(rows, str):
-        return f'target: {rows}'
+        return rows
     R, C = rows[0].shape
     if layout == 'rows':
         if pred.shape != target.shape:
             return f'pred {tuple(pred.shape)} and target {tuple(target.shape)} differ in shape'
-        prow = _feature_rows(pred)
+        prow = row_view(pred, 'pred')
         if isinstance(prow, str):
-            return f'pred: {prow}'
+            return prow
     else:
         if pred.dim() < 3 or pred.shape[1] != C or pred.numel() != R * C:
             return f'pred {tuple(pred.shape)} is not the [B, C, *positions] map of the target rows {tuple(target.shape)}'
@@ -880,18 +940,17 @@ def cosine_embedding_refusal(pred: torch.Tensor, target: torch.Tensor, layout: O
 def _cosine_embed_args(what: str, pred, target, layout):
     """The arguments vqhip_cosine_embed_fwd and _bwd share; both tensors are read in place."""
     _require_cuda(pred, target)
-    why = cosine_embedding_refusal(pred, target, layout)
-    if why:
-        raise ValueError(f'{what}: {why}')
-    trows, tstride = _feature_rows(target)
+    _refuse(what, cosine_embedding_refusal(pred, target, layout))
+    layout = layout or 'rows'
+    trows, tstride = row_view(target, 'target')
     R, C = trows.shape
-    if (layout or 'rows') == 'rows':
-        prows, pstride = _feature_rows(pred)
-        B, P, code = R, 1, _lib.LAYOUT_ROWS
+    if layout == 'rows':
+        prows, pstride = row_view(pred, 'pred')
+        B, P = R, 1
     else:
         prows, pstride = pred, 0
-        B, P, code = pred.shape[0], R // pred.shape[0], _lib.LAYOUT_MAP
-    head = (_ptr(prows), SAMPLE_DTYPES[pred.dtype], code, pstride, _ptr(trows), SAMPLE_DTYPES[target.dtype], tstride, B, P, C)
+        B, P = pred.shape[0], R // pred.shape[0]
+    head = (_ptr(prows), FLOAT_DTYPES[pred.dtype], LAYOUTS[layout], pstride, _ptr(trows), FLOAT_DTYPES[target.dtype], tstride, B, P, C)
     return head, R, C, (prows, trows)
 
 
@@ -919,23 +978,21 @@ def cosine_embedding_backward(pred: torch.Tensor, target: torch.Tensor, stats: t
     touched); map layout: contiguous."""
     head, R, C, keep = _cosine_embed_args('cosine_embedding_backward', pred, target, layout)
     _require_cuda(stats, g, out)
-    g = g.reshape(-1).to(torch.float32).contiguous()
+    g, per_row = _grad_values(g, R)
     if g.numel() not in (1, R) or stats.dtype != torch.float32 or stats.shape != (R, 3) or not stats.is_contiguous():
         raise ValueError(f'cosine_embedding_backward: g must hold 1 or {R} values and stats be contiguous fp32 [{R}, 3]')
     grad = torch.empty(pred.shape, dtype=pred.dtype, device=pred.device) if out is None else out
     if grad.shape != pred.shape or grad.dtype != pred.dtype:
         raise ValueError('cosine_embedding_backward: out must have the shape and dtype of pred')
     if (layout or 'rows') == 'rows':
-        grows = _feature_rows(grad)
-        if isinstance(grows, str):
-            raise ValueError(f'cosine_embedding_backward: out: {grows}')
+        grows = row_view(grad, 'out')
+        _refuse('cosine_embedding_backward', grows if isinstance(grows, str) else '')
         grows, gstride = grows
     else:
-        if not grad.is_contiguous():
-            raise ValueError('cosine_embedding_backward: out must be an NCHW-contiguous map')
+        _refuse('cosine_embedding_backward', '' if grad.is_contiguous() else 'out must be an NCHW-contiguous map')
         grows, gstride = grad, 0
-    check(_lib.lib().vqhip_cosine_embed_bwd(*head, _ptr(stats), _ptr(g), 1 if g.numel() == R and R > 1 else 0, 1 if mean else 0,
-                                            _ptr(grows), gstride, _stream()), 'vqhip_cosine_embed_bwd')
+    check(_lib.lib().vqhip_cosine_embed_bwd(*head, _ptr(stats), _ptr(g), per_row, 1 if mean else 0, _ptr(grows), gstride, _stream()),
+          'vqhip_cosine_embed_bwd')
     return grad
 
 
@@ -947,38 +1004,29 @@ def cosine_embedding_loss(pred: torch.Tensor, target: torch.Tensor, reduction: s
 
 # ---- fused LPIPS tail (the VQGAN generator's perceptual loss: vq/tasks/image_reconstruction/losses.py:99-178) ---------------
 
-LPIPS_LAYOUTS = {'rows': _lib.LAYOUT_ROWS, 'map': _lib.LAYOUT_MAP}
 LPIPS_CHANNELS = (64, 128, 256, 512, 512)                   # the five taps of VGG16
 LPIPS_MAX_LAYER = 1 << 16
 
 
-def _lpips_layouts(t: torch.Tensor) -> tuple:
-    """The layouts of include/vqhip.h a [B, C, *positions] feature map is dense in: 'map' (NCHW-contiguous), 'rows' (channels-last)."""
-    found = ('map',) if t.is_contiguous() else ()
-    if t.dim() == 4 and t.is_contiguous(memory_format=torch.channels_last):
-        found += ('rows',)
-    return found
-
-
 def lpips_layout(pred: torch.Tensor, target: torch.Tensor):
     """The layout both feature maps share ('map' before 'rows' where both hold, as for C == 1), None if there is none."""
-    both = [name for name in _lpips_layouts(pred) if name in _lpips_layouts(target)]
+    both = [name for name in dense_layouts(pred) if name in dense_layouts(target)]
     return both[0] if both else None
 
 
 def lpips_refusal(pred: torch.Tensor, target: torch.Tensor, weight: Optional[torch.Tensor] = None) -> str:
     """Why vqhip_lpips_fwd would refuse this pair of feature maps ('' if it would not): the clauses of its LIMITS that depend
     on the tensors' dtypes, shapes and strides.  ``weight``: the 1 x 1 convolution's, any shape with C elements."""
-    for name, t in (('pred', pred), ('target', target)):
-        if t.dtype not in SAMPLE_DTYPES:
-            return f'{name} is {t.dtype}, not float32, bfloat16 or float16'
+    why = float_dtype_refusal('pred is', pred) or float_dtype_refusal('target is', target)
+    if why:
+        return why
     if pred.dim() < 3 or pred.shape != target.shape:
         return f'pred {tuple(pred.shape)} and target {tuple(target.shape)} are not two [B, C, *positions] maps of one shape'
     if pred.numel() == 0:
         return f'empty features {tuple(pred.shape)}'
-    for name, t in (('pred', pred), ('target', target)):
-        if not _lpips_layouts(t):
-            return f'{name} with strides {t.stride()} is neither NCHW-contiguous nor channels-last dense'
+    why = dense_refusal('pred', pred) or dense_refusal('target', target)
+    if why:
+        return why
     if lpips_layout(pred, target) is None:
         return f'pred (strides {pred.stride()}) and target (strides {target.stride()}) differ in layout'
     B, C = pred.shape[:2]
@@ -995,20 +1043,14 @@ def lpips_refusal(pred: torch.Tensor, target: torch.Tensor, weight: Optional[tor
 def _lpips_args(what: str, pred, target, weight, seed, p, layer):
     """The arguments vqhip_lpips_fwd and _bwd share; both maps are read in place."""
     _require_cuda(pred, target, weight, seed)
-    why = lpips_refusal(pred, target, weight)
-    if why:
-        raise ValueError(f'{what}: {why}')
-    if seed is not None and (seed.dtype not in (torch.int32, torch.uint32) or seed.numel() != 2 or not seed.is_contiguous()):
-        raise ValueError(f'{what}: seed must hold two contiguous 32-bit words on the device, got {seed.dtype} {tuple(seed.shape)}')
-    if seed is not None and not 0.0 <= p < 1.0:
-        raise ValueError(f'{what}: p={p!r} is outside [0, 1)')
-    if not 0 <= layer <= LPIPS_MAX_LAYER:
-        raise ValueError(f'{what}: layer={layer!r} is outside 0 .. 2^16')
-    w = weight.detach().reshape(-1)
-    w = w if w.is_contiguous() else w.contiguous()
+    _refuse(what, lpips_refusal(pred, target, weight))
+    if seed is not None:
+        _refuse(what, _seed_refusal(seed) or ('' if 0.0 <= p < 1.0 else f'p={p!r} is outside [0, 1)'))
+    _refuse(what, '' if 0 <= layer <= LPIPS_MAX_LAYER else f'layer={layer!r} is outside 0 .. 2^16')
+    w = _fp32_vector(weight)
     B, C = pred.shape[:2]
     P = pred.numel() // (B * C)
-    head = (_ptr(pred), SAMPLE_DTYPES[pred.dtype], _ptr(target), SAMPLE_DTYPES[target.dtype], LPIPS_LAYOUTS[lpips_layout(pred, target)],
+    head = (_ptr(pred), FLOAT_DTYPES[pred.dtype], _ptr(target), FLOAT_DTYPES[target.dtype], LAYOUTS[lpips_layout(pred, target)],
             B, C, P, _ptr(w), _ptr(seed), float(p), int(layer))
     return head, B, C, P, (w,)
 
@@ -1041,7 +1083,7 @@ def lpips_layer_backward(pred: torch.Tensor, target: torch.Tensor, weight: torch
     buffer of pred's shape, dtype and strides to write into."""
     head, B, C, P, keep = _lpips_args('lpips_layer_backward', pred, target, weight, seed, p, layer)
     _require_cuda(stats, g, out)
-    g = g.reshape(-1).to(torch.float32).contiguous()
+    g, _ = _grad_values(g, B)
     if g.numel() != B or stats.dtype != torch.float32 or stats.shape != (B, P, 4) or not stats.is_contiguous():
         raise ValueError(f'lpips_layer_backward: g must hold {B} values and stats be contiguous fp32 [{B}, {P}, 4]')
     grad = torch.empty_like(pred) if out is None else out                       # (preserve_format: pred is dense, so its strides)
@@ -1056,8 +1098,7 @@ def lpips_keep_mask(seed: torch.Tensor, p: float, layer: int, B: int, C: int, P:
     """vqhip_lpips_keep_mask: the dropout mask uint8 [B, C, P] (1 kept, 0 dropped) the two kernels regenerate from ``seed``, by the
     same device function - what a reference needs to be held against a seeded run."""
     _require_cuda(seed)
-    if seed.dtype not in (torch.int32, torch.uint32) or seed.numel() != 2 or not seed.is_contiguous():
-        raise ValueError(f'lpips_keep_mask: seed must hold two contiguous 32-bit words on the device, got {seed.dtype} {tuple(seed.shape)}')
+    _refuse('lpips_keep_mask', _seed_refusal(seed))
     out = torch.empty(B, C, P, dtype=torch.uint8, device=seed.device)
     check(_lib.lib().vqhip_lpips_keep_mask(_ptr(seed), float(p), int(layer), B, C, P, _ptr(out), _stream()), 'vqhip_lpips_keep_mask')
     return out
@@ -1071,30 +1112,17 @@ def lpips_distance(pred_features, target_features, weights, seed: Optional[torch
 
 # ---- StyleGAN2 discriminator ops (vq/algorithms/vqgan/discriminators/stylegan2.py: FusedBiasLeakyReLU and upfirdn2d) ------------
 
-SG2_LAYOUTS = {'rows': _lib.LAYOUT_ROWS, 'map': _lib.LAYOUT_MAP}
 FIR4_PADS = ((2, 2), (1, 1))                                # Blur's padding for the 3 x 3 and the 1 x 1 downsampling convolution
-
-
-def sg2_layout(t: torch.Tensor):
-    """The layout of include/vqhip.h a [B, C] or [B, C, H, W] tensor is dense in: 'map' (contiguous) before 'rows' (channels-last), or None."""
-    if t.is_contiguous():
-        return 'map'
-    if t.dim() == 4 and t.is_contiguous(memory_format=torch.channels_last):
-        return 'rows'
-    return None
 
 
 def stylegan2_refusal(x: torch.Tensor, bias: Optional[torch.Tensor] = None, *, kernel_size: Optional[int] = None) -> str:
     """Why vqhip_bias_act_* / vqhip_fir4_* would refuse this activation ('' if they would not): the clauses of their LIMITS that
     depend on the tensor's dtype, shape and strides.  ``bias``: [C]; ``kernel_size``: of the convolution a Blur serves (3 or 1)."""
-    if x.dtype not in SAMPLE_DTYPES:
-        return f'the activation is {x.dtype}, not float32, bfloat16 or float16'
-    if x.dim() not in (2, 4):
-        return f'the activation is {x.dim()}-D, not [B, C] or [B, C, H, W]'
-    if x.numel() == 0:
-        return f'empty activation {tuple(x.shape)}'
-    if sg2_layout(x) is None:
-        return f'the activation with strides {x.stride()} is neither NCHW-contiguous nor channels-last dense'
+    why = float_dtype_refusal('the activation is', x) \
+        or ('' if x.dim() in (2, 4) else f'the activation is {x.dim()}-D, not [B, C] or [B, C, H, W]') \
+        or ('' if x.numel() else f'empty activation {tuple(x.shape)}') or dense_refusal('the activation', x)
+    if why:
+        return why
     if x.shape[1] > _lib.SG2_MAX_C:
         return f'C={x.shape[1]} is beyond 2^16'
     if x.numel() >= (1 << 31):
@@ -1108,29 +1136,9 @@ def stylegan2_refusal(x: torch.Tensor, bias: Optional[torch.Tensor] = None, *, k
 
 def _sg2_head(what: str, x: torch.Tensor, bias=None):
     _require_cuda(x, bias)
-    why = stylegan2_refusal(x, bias)
-    if why:
-        raise ValueError(f'{what}: {why}')
+    _refuse(what, stylegan2_refusal(x, bias))
     B, C = x.shape[:2]
-    return SAMPLE_DTYPES[x.dtype], SG2_LAYOUTS[sg2_layout(x)], B, C, x.numel() // (B * C)
-
-
-def _sg2_bias(bias: torch.Tensor) -> torch.Tensor:
-    """The bias as the kernels read it: fp32, contiguous (a copy of C elements only where the parameter is not fp32 already)."""
-    return bias.detach().reshape(-1).to(torch.float32).contiguous()
-
-
-def sg2_dense(t: torch.Tensor) -> torch.Tensor:
-    """``t`` itself where it is dense in one of the two layouts, else a contiguous copy: autograd hands over gradients with any
-    strides (the expanded scalar of ``.sum().backward()`` has none but zeros)."""
-    return t if sg2_layout(t) is not None else t.contiguous()
-
-
-def _sg2_dense_like(t: torch.Tensor, like: torch.Tensor) -> torch.Tensor:
-    """``t`` dense in the layout the kernels read ``like`` in (a copy only where autograd handed over another memory format)."""
-    if sg2_layout(like) == 'rows':
-        return t if t.is_contiguous(memory_format=torch.channels_last) else t.contiguous(memory_format=torch.channels_last)
-    return t if t.is_contiguous() else t.contiguous()
+    return FLOAT_DTYPES[x.dtype], LAYOUTS[dense_layout(x)], B, C, x.numel() // (B * C)
 
 
 @_on_tensor_device
@@ -1138,7 +1146,7 @@ def bias_act(x: torch.Tensor, bias: torch.Tensor) -> torch.Tensor:
     """vqhip_bias_act_fwd: ``leaky_relu(x + bias[c], 0.2) * 2**0.5`` of a [B, C] or [B, C, H, W] activation, read in place, in its
     dtype and memory format (NCHW or channels-last).  One launch."""
     dtype, layout, B, C, P = _sg2_head('bias_act', x, bias)
-    b = _sg2_bias(bias)
+    b = _fp32_vector(bias)
     y = torch.empty_like(x)
     check(_lib.lib().vqhip_bias_act_fwd(_ptr(x), dtype, layout, B, C, P, _ptr(b), _ptr(y), _stream()), 'vqhip_bias_act_fwd')
     return y
@@ -1153,7 +1161,7 @@ def bias_act_backward(g: torch.Tensor, y: torch.Tensor, need_gbias: bool = True)
     _require_cuda(g)
     if g.shape != y.shape or g.dtype != y.dtype:
         raise ValueError(f'bias_act_backward: g is {g.dtype} {tuple(g.shape)}, y {y.dtype} {tuple(y.shape)}')
-    g = _sg2_dense_like(g, y)
+    g = _dense_like(g, y)
     gx = torch.empty_like(y)
     gbias = ws = None
     if need_gbias:
@@ -1179,11 +1187,6 @@ def _fir4_pad(what: str, pad, down: int) -> tuple:
     return tuple(int(p) for p in pad)
 
 
-def _fir4_like(x: torch.Tensor, shape) -> torch.Tensor:
-    fmt = torch.channels_last if sg2_layout(x) == 'rows' else torch.contiguous_format
-    return torch.empty(shape, dtype=x.dtype, device=x.device, memory_format=fmt)
-
-
 @_on_tensor_device
 def fir4(x: torch.Tensor, pad=2, down: int = 1, bias: Optional[torch.Tensor] = None) -> torch.Tensor:
     """vqhip_fir4_fwd: the blur ``upfirdn2d(x, outer([1, 3, 3, 1]) / 64, padding)`` of a [B, C, H, W] map per channel with zero
@@ -1197,8 +1200,8 @@ def fir4(x: torch.Tensor, pad=2, down: int = 1, bias: Optional[torch.Tensor] = N
     OH, OW = fir4_out_size(H, W, pad, down)
     if OH < 1 or OW < 1:
         raise ValueError(f'fir4: the padded {H} x {W} plane is smaller than the filter')
-    b = None if bias is None else _sg2_bias(bias)
-    out = _fir4_like(x, (B, C, OH, OW))
+    b = None if bias is None else _fp32_vector(bias)
+    out = _empty_like(x, (B, C, OH, OW))
     check(_lib.lib().vqhip_fir4_fwd(_ptr(x), dtype, layout, B, C, H, W, down, *pad, _ptr(b), _ptr(out), _stream()), 'vqhip_fir4_fwd')
     return out
 
@@ -1211,9 +1214,9 @@ def fir4_backward(g: torch.Tensor, size, pad=2, down: int = 1, x: Optional[torch
     if g.dim() != 4 or (x is None) != (bias is None):
         raise ValueError('fir4_backward: need a [B, C, OH, OW] gradient, and x and bias together or neither')
     _require_cuda(g, x)
-    if x is not None and sg2_layout(x) is None:
-        raise ValueError(f'fir4_backward: x with strides {x.stride()} is neither NCHW-contiguous nor channels-last dense')
-    g = sg2_dense(g) if x is None else _sg2_dense_like(g, x)                    # (in x's layout for the fused form)
+    if x is not None:
+        _refuse('fir4_backward', dense_refusal('x', x))
+    g = dense(g) if x is None else _dense_like(g, x)                            # (in x's layout for the fused form)
     dtype, layout, B, C, _ = _sg2_head('fir4_backward', g)
     pad = _fir4_pad('fir4_backward', pad, down)
     H, W = (int(v) for v in size)
@@ -1224,12 +1227,12 @@ def fir4_backward(g: torch.Tensor, size, pad=2, down: int = 1, x: Optional[torch
         _require_cuda(bias)
         if x.dtype != g.dtype or tuple(x.shape) != (B, C, H, W):
             raise ValueError(f'fir4_backward: x must be a dense {g.dtype} [{B}, {C}, {H}, {W}] map')
-        layout = SG2_LAYOUTS[sg2_layout(x)]
-        b = _sg2_bias(bias)
+        layout = LAYOUTS[dense_layout(x)]
+        b = _fp32_vector(bias)
         slabs = _lib.lib().vqhip_fir4_slabs(layout, B, C, H, W)
         ws = torch.empty(slabs * C, dtype=torch.float32, device=g.device)
         gbias = torch.empty(C, dtype=torch.float32, device=g.device)
-    gx = _fir4_like(g if x is None else x, (B, C, H, W))
+    gx = _empty_like(g if x is None else x, (B, C, H, W))
     if gx.numel() >= (1 << 31):
         raise ValueError(f'fir4_backward: {gx.numel()} elements are outside 1 .. 2^31-1')
     check(_lib.lib().vqhip_fir4_bwd(_ptr(g), dtype, layout, B, C, H, W, down, *pad, _ptr(x), _ptr(b), _ptr(gx), _ptr(gbias), _ptr(ws),
@@ -1245,19 +1248,13 @@ GROUP_NORM_ACTS = {None: 0, 'silu': 1}
 def group_norm_refusal(x: torch.Tensor, num_groups: int) -> str:
     """Why vqhip_group_norm_* would refuse this activation ('' if they would not): the clauses of their LIMITS that depend on the
     tensor's dtype, shape and strides."""
-    if x.dtype not in SAMPLE_DTYPES:
-        return f'the activation is {x.dtype}, not float32, bfloat16 or float16'
-    if x.dim() < 2:
-        return f'the activation is {x.dim()}-D, not [B, C, ...]'
-    if x.numel() == 0:
-        return f'empty activation {tuple(x.shape)}'
-    if num_groups < 1 or x.shape[1] % num_groups:
-        return f'C={x.shape[1]} is no multiple of num_groups={num_groups}'
-    if sg2_layout(x) is None:
-        return f'the activation with strides {x.stride()} is neither NCHW-contiguous nor channels-last dense'
-    if x.numel() // (x.shape[0] * num_groups) >= (1 << 31):
-        return f'a group of {x.numel() // (x.shape[0] * num_groups)} values is outside 1 .. 2^31-1'
-    return ''
+    return float_dtype_refusal('the activation is', x) \
+        or ('' if x.dim() >= 2 else f'the activation is {x.dim()}-D, not [B, C, ...]') \
+        or ('' if x.numel() else f'empty activation {tuple(x.shape)}') \
+        or ('' if num_groups >= 1 and x.shape[1] % num_groups == 0 else f'C={x.shape[1]} is no multiple of num_groups={num_groups}') \
+        or dense_refusal('the activation', x) \
+        or ('' if x.numel() // (x.shape[0] * num_groups) < (1 << 31) else
+            f'a group of {x.numel() // (x.shape[0] * num_groups)} values is outside 1 .. 2^31-1')
 
 
 def _gn_head(what: str, x: torch.Tensor, num_groups: int, weight: torch.Tensor, bias: torch.Tensor, act):
@@ -1267,16 +1264,15 @@ def _gn_head(what: str, x: torch.Tensor, num_groups: int, weight: torch.Tensor, 
         why = f'act={act!r} is neither None nor \'silu\''
     if not why and (weight.numel() != x.shape[1] or bias.numel() != x.shape[1]):
         why = f'weight and bias have {weight.numel()} and {bias.numel()} elements, not C={x.shape[1]}'
-    if why:
-        raise ValueError(f'{what}: {why}')
+    _refuse(what, why)
     B, C = x.shape[:2]
     P = x.numel() // (B * C)
-    layout = SG2_LAYOUTS[sg2_layout(x)]
+    layout = LAYOUTS[dense_layout(x)]
     ws_bytes = _lib.lib().vqhip_group_norm_ws_bytes(layout, B, C, P, num_groups)
     if ws_bytes < 0:
         raise ValueError(f'{what}: {tuple(x.shape)} in {num_groups} groups is beyond the sizes of vqhip_group_norm_*')
     ws = torch.empty(ws_bytes // 4, dtype=torch.float32, device=x.device)
-    return SAMPLE_DTYPES[x.dtype], layout, B, C, P, ws
+    return FLOAT_DTYPES[x.dtype], layout, B, C, P, ws
 
 
 @_on_tensor_device
@@ -1285,7 +1281,7 @@ def group_norm(x: torch.Tensor, num_groups: int, weight: torch.Tensor, bias: tor
     place, in its dtype and memory format (NCHW or channels-last); ``act``: None or 'silu'.  ``stats`` [B, G, 2] fp32 holds each
     group's mean and 1 / sqrt(var + eps), what the backward reads.  One launch, two where a group is split over workgroups."""
     dtype, layout, B, C, P, ws = _gn_head('group_norm', x, num_groups, weight, bias, act)
-    w, b = _sg2_bias(weight), _sg2_bias(bias)
+    w, b = _fp32_vector(weight), _fp32_vector(bias)
     y = torch.empty_like(x)
     stats = torch.empty(B, num_groups, 2, dtype=torch.float32, device=x.device)
     check(_lib.lib().vqhip_group_norm_fwd(_ptr(x), dtype, layout, B, C, P, num_groups, _ptr(w), _ptr(b), float(eps), GROUP_NORM_ACTS[act],
@@ -1305,8 +1301,8 @@ def group_norm_backward(g: torch.Tensor, x: torch.Tensor, stats: torch.Tensor, n
         raise ValueError(f'group_norm_backward: g is {g.dtype} {tuple(g.shape)}, x {x.dtype} {tuple(x.shape)}')
     if stats.dtype != torch.float32 or stats.numel() != B * num_groups * 2 or not stats.is_contiguous():
         raise ValueError(f'group_norm_backward: stats must be the contiguous fp32 [{B}, {num_groups}, 2] of the forward')
-    g = _sg2_dense_like(g, x)
-    w, b = _sg2_bias(weight), _sg2_bias(bias)
+    g = _dense_like(g, x)
+    w, b = _fp32_vector(weight), _fp32_vector(bias)
     gx = torch.empty_like(x)
     dgamma = torch.empty(C, dtype=torch.float32, device=x.device)
     dbeta = torch.empty(C, dtype=torch.float32, device=x.device)
@@ -1318,19 +1314,8 @@ def group_norm_backward(g: torch.Tensor, x: torch.Tensor, stats: torch.Tensor, n
 
 # ---- fused reconstruction metrics (validation: vq/runners/metrics/loss.py over vq/tasks/image_reconstruction/losses.py) -----
 
-IMAGE_DTYPES = {torch.float32: _lib.DTYPE_F32, torch.bfloat16: _lib.DTYPE_BF16, torch.float16: _lib.DTYPE_F16,
-                torch.uint8: _lib.DTYPE_U8}
 IMAGE_METRIC_COLUMNS = ('l1', 'mse', 'psnr', 'ssim')
 SSIM_C1, SSIM_C2 = (0.01 * 1) ** 2, (0.03 * 1) ** 2           # scikit-image's (K1 * data_range) ** 2, (K2 * data_range) ** 2
-
-
-def image_layout(t: torch.Tensor):
-    """IMAGE_NCHW / IMAGE_NHWC of include/vqhip.h for a dense [B, C, H, W] tensor, None for any other arrangement."""
-    if t.is_contiguous():
-        return _lib.IMAGE_NCHW
-    if t.dim() == 4 and t.is_contiguous(memory_format=torch.channels_last):
-        return _lib.IMAGE_NHWC
-    return None
 
 
 def image_metrics_refusal(pred: torch.Tensor, image: torch.Tensor, ssim: bool = True) -> str:
@@ -1342,9 +1327,9 @@ def image_metrics_refusal(pred: torch.Tensor, image: torch.Tensor, ssim: bool = 
             return f'{name} is {t.dtype}, not float32, bfloat16, float16 or uint8'
     if pred.numel() == 0:
         return f'empty images {tuple(pred.shape)}'
-    for name, t in (('pred', pred), ('image', image)):
-        if image_layout(t) is None:
-            return f'{name} with strides {t.stride()} is neither NCHW-contiguous nor channels-last dense'
+    why = dense_refusal('pred', pred) or dense_refusal('image', image)
+    if why:
+        return why
     B, C, H, W = pred.shape
     if ssim and (H < 7 or W < 7):
         return f'SSIM needs H >= 7 and W >= 7 (a 7 x 7 window), got {H} x {W}'
@@ -1360,9 +1345,7 @@ def image_metrics(pred: torch.Tensor, image: torch.Tensor, *, ssim: bool = True)
     fp32 ``l1``, ``mse``, ``psnr``, ``ssim`` [B] (columns of ``values32``), float64 ``values64`` [B, 4], int64 ``abs_sum`` and
     ``sq_sum`` [B].  Two launches, no copy of an image, no synchronisation.  ``ssim=False``: the ssim column is NaN and any
     H, W >= 1 is taken.  ValueError for what the library refuses."""
-    why = image_metrics_refusal(pred, image, ssim)
-    if why:
-        raise ValueError(f'image_metrics: {why}')
+    _refuse('image_metrics', image_metrics_refusal(pred, image, ssim))
     _require_cuda(pred, image)
     B, C, H, W = pred.shape
     L, dev = _lib.lib(), pred.device
@@ -1371,8 +1354,8 @@ def image_metrics(pred: torch.Tensor, image: torch.Tensor, *, ssim: bool = True)
     values64 = torch.empty(B, 4, dtype=torch.float64, device=dev)
     values32 = torch.empty(B, 4, dtype=torch.float32, device=dev)
     sums = torch.empty(B, 2, dtype=torch.int64, device=dev)
-    rc = L.vqhip_image_metrics(_ptr(pred), IMAGE_DTYPES[pred.dtype], image_layout(pred), _ptr(image), IMAGE_DTYPES[image.dtype],
-                               image_layout(image), B, C, H, W, 1 if ssim else 0, SSIM_C1, SSIM_C2, _ptr(ws), ws_bytes,
+    rc = L.vqhip_image_metrics(_ptr(pred), IMAGE_DTYPES[pred.dtype], IMAGE_LAYOUTS[dense_layout(pred)], _ptr(image),
+                               IMAGE_DTYPES[image.dtype], IMAGE_LAYOUTS[dense_layout(image)], B, C, H, W, 1 if ssim else 0, SSIM_C1, SSIM_C2, _ptr(ws), ws_bytes,
                                _ptr(values64), _ptr(values32), _ptr(sums), _stream())
     if rc == -22:                                                              # VQHIP_EINVAL
         raise ValueError(f'image_metrics: {L.vqhip_last_error().decode()}')

@@ -120,9 +120,9 @@ class LPIPSLoss(BaseReconstructLoss):
     def forward(self, pred_image: torch.Tensor, image: torch.Tensor) -> torch.Tensor:
         from .quantizers import routes
         assert pred_image.shape == image.shape
-        if pred_image.dim() == 4 and ops.image_layout(pred_image) is not None and ops.image_layout(image) != ops.image_layout(pred_image):
+        if pred_image.dim() == 4 and ops.dense_layout(pred_image) is not None and ops.dense_layout(image) != ops.dense_layout(pred_image):
             # three channels: a small copy that lets both feature stacks come out in one memory format
-            nhwc = ops.image_layout(pred_image) == ops._lib.IMAGE_NHWC
+            nhwc = ops.dense_layout(pred_image) == 'rows'
             image = image.contiguous(memory_format=torch.channels_last if nhwc else torch.contiguous_format)
         pred_features = self.extract_features(pred_image)
         with torch.no_grad():

@@ -401,40 +401,30 @@ def sampler_arguments(s) -> str:
     return '' if ok else f'temperature={t!r} is not a finite number > 0'
 
 
+def device_logits(logits: torch.Tensor) -> str:
+    """The logits are on a device, in a float dtype, with a last dimension of unit stride."""
+    return ('' if logits.is_cuda else f'the logits are on device {logits.device}, not on a GPU') \
+        or ('' if logits.dim() >= 1 and (logits.stride(-1) == 1 or logits.shape[-1] == 1) else 'the last dimension of the logits does not have stride 1') \
+        or ops.float_dtype_refusal('the logits are', logits)
+
+
 def sampler_rows(logits: torch.Tensor, start: int, end: int) -> str:
-    """[..., V_total] is rows of ONE stride that do not overlap, read as a view, and [start, end) lies inside the last dimension."""
+    """[start, end) lies inside the last dimension, and [..., V_total] is rows of ONE stride that do not overlap, read as a view
+    (``ops.row_view``; behind ``device_logits`` its reason is one of those two)."""
     if not 0 <= start < end <= logits.shape[-1]:
         return f'[{start}, {end}) is not a non-empty slice of the last dimension ({logits.shape[-1]})'
     if end - start > ops.SAMPLE_MAX_V:
         return f'V={end - start} is beyond 2^20'
-    if not _flattens(logits):
-        return 'the leading dimensions of the logits do not flatten without a copy'
-    rows = logits if logits.dim() == 2 else logits.view(-1, logits.shape[-1])
-    if rows.shape[0] > 1 and rows.stride(0) < rows.shape[1]:
-        return f'the rows of the logits overlap (row stride {rows.stride(0)} < {rows.shape[1]})'
-    return ''
+    view = ops.row_view(logits, 'the logits')
+    return view if isinstance(view, str) else ''
 
 
 def sampler_why(sampler, logits: torch.Tensor, start: int = 0, end=None) -> Route:
     """A sampler step: ONE launch of ``ops.sample_tokens`` on the logits as they are (``fused``), or the reference's composition
     with torch ops (``torch``), with the first clause that refused the launch."""
     end = logits.shape[-1] if end is None else end
-    why = ('' if logits.is_cuda else f'the logits are on device {logits.device}, not on a GPU') \
-        or ('' if logits.dim() >= 1 and (logits.stride(-1) == 1 or logits.shape[-1] == 1) else 'the last dimension of the logits does not have stride 1') \
-        or ('' if logits.dtype in ops.SAMPLE_DTYPES else f'the logits are {logits.dtype}, not float32, bfloat16 or float16') \
-        or sampler_config(sampler) or sampler_arguments(sampler) or sampler_rows(logits, start, end)
+    why = device_logits(logits) or sampler_config(sampler) or sampler_arguments(sampler) or sampler_rows(logits, start, end)
     return Route('torch', why) if why else Route('fused')
-
-
-def _flattens(x: torch.Tensor) -> bool:
-    """[..., V] is [-1, V] rows with ONE row stride, as a view."""
-    if x.dim() <= 2:
-        return True
-    try:
-        x.view(-1, x.shape[-1])
-        return True
-    except RuntimeError:
-        return False
 
 
 # ---- the token cross-entropy of stage-2 training (vector_quantization_amd/sequence_losses.py) -----------------------------
@@ -457,10 +447,7 @@ def token_ce_why(logits: torch.Tensor, targets: torch.Tensor, start: int = 0, en
     """A stage-2 loss: the fused launches of ``ops.token_cross_entropy`` on the logits as they are (``fused``), or the reference's
     composition with log_softmax / gather (``torch``), with the first clause that refused the launches."""
     end = logits.shape[-1] if end is None else end
-    why = ('' if logits.is_cuda else f'the logits are on device {logits.device}, not on a GPU') \
-        or ('' if logits.dim() >= 1 and (logits.stride(-1) == 1 or logits.shape[-1] == 1) else 'the last dimension of the logits does not have stride 1') \
-        or ('' if logits.dtype in ops.SAMPLE_DTYPES else f'the logits are {logits.dtype}, not float32, bfloat16 or float16') \
-        or sampler_rows(logits, start, end) or token_ce_targets(logits, targets, shift) \
+    why = device_logits(logits) or sampler_rows(logits, start, end) or token_ce_targets(logits, targets, shift) \
         or ('' if 0.0 <= label_smoothing < 1.0 else f'label_smoothing={label_smoothing!r} is outside [0, 1)') \
         or ('' if weight is None or weight.numel() == targets.numel() else f'the weights are {tuple(weight.shape)}, not one per row')
     return Route('torch', why) if why else Route('fused')
@@ -570,11 +557,8 @@ def group_norm_why(module, x: torch.Tensor, num_groups: int = 32) -> Route:
         why = '' if getattr(module, 'fused', True) else 'fused=False'
         if not why and isinstance(module, autoencoders.VQGANMixin):
             why = own(module, autoencoders.VQGANMixin, 'forward')
-    why = why or ('' if x.is_cuda else f'the input is on device {x.device}, not on a GPU')
-    if not why and x.dtype not in ops.SAMPLE_DTYPES:
-        why = f'the input is {x.dtype}, not float32, bfloat16 or float16'
-    if not why and ops.sg2_layout(x) is None:
-        why = f'the input with strides {x.stride()} is neither NCHW-contiguous nor channels-last dense'
+    why = why or ('' if x.is_cuda else f'the input is on device {x.device}, not on a GPU') \
+        or ops.float_dtype_refusal('the input is', x) or ops.dense_refusal('the input', x)
     return Route('torch', why) if why else Route('fused')
 
 
