@@ -749,6 +749,94 @@ int vqhip_group_norm_bwd(const void *g, const void *x, int dtype, int layout, in
                          const float *gamma, const float *beta, const float *stats, int act, void *gx, float *dgamma /* [C] */,
                          float *dbeta /* [C] */, float *ws, int64_t ws_bytes, void *stream);
 
+/* ---- the row ops of VQKDEncoder / VQKDDecoder: residual add + LayerNorm, bias + GELU / tanh, forward and backward --------------------
+ * Everything between the GEMMs and the attention core of the pre-norm ViT of vq/algorithms/vqkd/autoencoder.py.  No copy, no atomics,
+ * no memset, no allocation and no synchronisation.  Rows [R, D], dense (row stride D), element alignment only.  Every element is
+ * converted to fp32 exactly; all arithmetic is fp32 IEEE without contraction; a result is rounded to nearest even into its dtype.
+ * ADD + LAYER NORM
+ *       fwd    s = round_to_x_dtype(x + res)  (res == NULL: s = x, sum_out is not written);   sum_out = s
+ *              mean = sum s / D;   var = sum (s - mean)^2 / D  (biased, second pass from registers);   rstd = 1 / sqrt(var + eps)
+ *              y = ((s - mean) rstd) gamma[c] + beta[c]  in y_dtype;   stats[2 r] = mean, stats[2 r + 1] = rstd
+ *       bwd    xh = (s - mean) rstd from the saved s and stats;   t = g gamma[c]
+ *              gx = rstd (t - mean_row(t) - xh mean_row(t xh)) + g_skip  (g_skip == NULL: nothing is added)
+ *              dgamma[c] = sum_r g xh;   dbeta[c] = sum_r g
+ *   s is what torch's `x + branch` leaves behind, bit for bit; the norm reads the ROUNDED s, as torch's LayerNorm would.
+ *   Dtypes (x, res, y):  (F32, F32, F32)  (F32, BF16, BF16)  (F32, F16, F16)  (BF16, BF16, BF16)  (F16, F16, F16).  sum_out has x's dtype.  The
+ *   two mixed rows are autocast: the residual stream stays fp32, the branch arrives in the autocast dtype and y leaves in it - an fp32
+ *   layer norm rounded once, as by the linear that follows torch's.  res_dtype is read only where res != NULL.  Backward:
+ *   s, g_skip and gx have the forward's x dtype (s_dtype), g the forward's y dtype (g_dtype); dgamma, dbeta, stats, gamma, beta fp32.
+ *   A NaN or an infinity in a row makes that row's y (and gx) NaN and touches no other row.  A constant row has var = 0 and y = beta
+ *   within the bound below.
+ * ROW BIAS-ACTIVATION   t = x + bias[c];   y = act(t)
+ *       act VQHIP_ROW_ACT_GELU   y = (t / 2) (1 + erf(t / 2^0.5))             d = (1 + erf(t / 2^0.5)) / 2 + t exp(-t^2 / 2) / (2 pi)^0.5
+ *       act VQHIP_ROW_ACT_TANH   y = tanh(t)                                  d = 1 - tanh(t)^2
+ *       bwd    gx = g d, recomputed from x and bias (y is not kept);   dbias[c] = sum_r of the fp32 gx  (dbias == NULL: not formed)
+ *   x, y, g and gx in the call's one dtype; bias and dbias fp32.  An element's result depends on that element alone: a NaN stays
+ *   where it is.
+ * ORDER OF EVERY SUM  fixed by the shape alone (vqhip_vit_kernels.h says who adds what): the same inputs give the same bits of
+ *   every output, run to run.
+ * LAUNCH SHAPE  add + layer norm, a piece = 8 elements where all tensors are 16-bit and D % 8 == 0, else 4 where D % 4 == 0, else 1:
+ *   D <= 2048: one wave per row, four rows per workgroup;  2048 < D <= 8192: one workgroup per row.  The backward gives a
+ *   workgroup a slab of 16 rows and leaves its column sums in ws [2, slabs, D]; two launches of the second stage follow.
+ *   Row bias-activation: forward one launch over 16-byte pieces of the flat tensor, a thread per piece up to 8192 workgroups of
+ *   256 threads = 2 097 152 pieces (8.4 M fp32 or 16.8 M 16-bit elements); beyond that the grid stays at 8192 workgroups and
+ *   every thread strides through pieces q, q + 2 097 152, ..  Backward a workgroup per 256 rows x 64 pieces, column sums in ws
+ *   [slabs, D], one launch of the second stage.
+ * SHAPES AND LIMITS (VQHIP_EINVAL before any HIP call, and no launch)  1 <= R <= VQHIP_VIT_MAX_R = 2^24 (no launch of more than 2^32
+ *   threads: the widest is 256 threads per row); 1 <= D <= VQHIP_VIT_MAX_D = 8192; R D < 2^31; a dtype
+ *   combination outside the table; res != NULL with res_dtype != y_dtype; res without sum_out; eps negative or not finite; act not 0
+ *   or 1; a NULL among x, gamma, beta, y, stats (fwd), g, s, gamma, stats, gx, dgamma, dbeta, ws (bwd), x, bias, y (act fwd), g, x, bias,
+ *   gx (act bwd); dbias without ws; ws_bytes < 8 D vqhip_add_layer_norm_slabs(..) / 4 D vqhip_row_bias_act_slabs(..) (-1 for sizes
+ *   the calls refuse).
+ * ERROR BOUND  against the exact value of the definition on the converted inputs (for the norm: on the rounded s); u0 = VQHIP_GN_U.
+ *   add + layer norm: a row is a group of n = D of the group norm, act 0, summed by the same code, so its bounds hold as they stand:
+ *     mean within VQHIP_GN_CHAIN(D) u0 mabs, rstd within VQHIP_GN_RHO(D, q) rstd, y within E_u, gx within E_gx; the addition of g_skip
+ *     rounds once more:  E_gx' = E_gx + u0 |gx + g_skip|.  dgamma / dbeta: the group norm's, with M = VQHIP_SG2_GBIAS_CHAIN(slabs),
+ *     slabs = ceil(R / 16) (a term passes at most 16 additions in its thread and 2 across teams in the first launch).  s itself is
+ *     exact: one correctly rounded addition.
+ *   row bias-activation: the one thing that cannot be derived is the accuracy of the device library's erff, tanhf and expf.  No
+ *     document shipped with the toolchain states it, so each was measured once on an MI355X against the float64 function over
+ *     every fp32 value of erff [-6, 6], tanhf [-12, 12], expf [-88, 0] (tools/measure_libm_ulp.hip; profiles/vqkd_autoencoder.txt):
+ *     1.5098, 1.4052 and 0.8907 ulp.  The constants are twice that, rounded up: L_erf = VQHIP_VIT_ERF_ULPS = 3.02, L_tanh =
+ *     VQHIP_VIT_TANH_ULPS = 2.82, L_exp = VQHIP_VIT_EXP_ULPS = 1.79.  An ulp of a result of magnitude at most 1 is at most 2 u0 absolute
+ *     and at most 2 u0 relative.
+ *     GELU, y: t carries u0 |t|; z = t c with c within u0 / 2 of 2^-0.5: relative 2.5 u0; |z erf'(z)| <= 0.49, so erf(z) is within
+ *       (1.3 + 2 L_erf) u0 absolute; h = 1 + erf rounds once (2 u0); y = (t / 2) h rounds once:
+ *                               VQHIP_ROW_GELU_BOUND(t, y) = ((3 + L_erf) |t| + 2 |y|) u0         (absolute in |t|: 1 + erf cancels for t < 0)
+ *     GELU, d: h / 2 within (1.7 + L_erf) u0; w = -t^2 / 2 is within 3 u0 |w|, exp(w) relative 3 u0 |w| + 2 L_exp u0, the constant and two
+ *       products 3.5 u0; |t| phi(t) <= 0.242 and |w t| phi(t) <= 0.231 give (1.8 + 0.5 L_exp) u0; the sum rounds once (|d| <= 1.13):
+ *                               VQHIP_ROW_GELU_GRAD_BOUND = (5 + L_erf + L_exp / 2) u0                                      (absolute)
+ *     tanh, y: |t tanh'(t)| <= |tanh(t)|, so t's rounding costs u0 |y|:   VQHIP_ROW_TANH_BOUND(y) = (1 + 2 L_tanh) u0 |y|
+ *     tanh, d: y^2 within (3 + 4 L_tanh) u0 y^2, the subtraction rounds once:
+ *                               VQHIP_ROW_TANH_GRAD_BOUND(y, d) = ((3 + 4 L_tanh) y^2 + |d|) u0
+ *     gx = g d: |g| E_d + u0 |gx|.   dbias[c]: M u0 sum |gx| + sum E_gx, M = VQHIP_SG2_GBIAS_CHAIN(slabs), slabs = ceil(R / 256).
+ *     Both y bounds carry VQHIP_VIT_TINY = 2^-148 absolute: a subnormal t loses up to half a subnormal ulp in t / 2 and in t c.
+ *   the store: VQHIP_SG2_STORE_U(dtype) on top, as for the StyleGAN2 ops.
+ *   A measurement beyond these bounds inside the range means the kernel or this derivation is wrong. */
+#define VQHIP_VIT_MAX_D 8192
+#define VQHIP_VIT_MAX_R (1 << 24)
+#define VQHIP_ROW_ACT_GELU 0
+#define VQHIP_ROW_ACT_TANH 1
+#define VQHIP_VIT_ERF_ULPS 3.02
+#define VQHIP_VIT_TANH_ULPS 2.82
+#define VQHIP_VIT_EXP_ULPS 1.79
+#define VQHIP_VIT_TINY 2.8025969286496341e-45
+#define VQHIP_ROW_GELU_BOUND(t, y) (((3.0 + VQHIP_VIT_ERF_ULPS) * (double)(t) + 2.0 * (double)(y)) * VQHIP_GN_U + VQHIP_VIT_TINY)
+#define VQHIP_ROW_GELU_GRAD_BOUND ((5.0 + VQHIP_VIT_ERF_ULPS + VQHIP_VIT_EXP_ULPS / 2.0) * VQHIP_GN_U)
+#define VQHIP_ROW_TANH_BOUND(y) ((1.0 + 2.0 * VQHIP_VIT_TANH_ULPS) * VQHIP_GN_U * (double)(y) + VQHIP_VIT_TINY)
+#define VQHIP_ROW_TANH_GRAD_BOUND(y, d) (((3.0 + 4.0 * VQHIP_VIT_TANH_ULPS) * (double)(y) * (double)(y) + (double)(d)) * VQHIP_GN_U)
+int64_t vqhip_add_layer_norm_slabs(int64_t R, int64_t D);                       /* -1 for sizes the calls refuse */
+int vqhip_add_layer_norm_fwd(const void *x, int x_dtype, const void *res /* or NULL */, int res_dtype, int64_t R, int64_t D,
+                             const float *gamma /* [D] */, const float *beta /* [D] */, float eps, void *sum_out /* with res */, void *y,
+                             int y_dtype, float *stats /* [R, 2] */, void *stream);
+int vqhip_add_layer_norm_bwd(const void *g, int g_dtype, const void *s, int s_dtype, const void *g_skip /* or NULL */, int64_t R, int64_t D,
+                             const float *gamma, const float *stats, void *gx, float *dgamma /* [D] */, float *dbeta /* [D] */, float *ws,
+                             int64_t ws_bytes, void *stream);
+int64_t vqhip_row_bias_act_slabs(int64_t R, int64_t D);                         /* -1 for sizes the calls refuse */
+int vqhip_row_bias_act_fwd(const void *x, int dtype, int64_t R, int64_t D, const float *bias /* [D] */, int act, void *y, void *stream);
+int vqhip_row_bias_act_bwd(const void *g, const void *x, int dtype, int64_t R, int64_t D, const float *bias, int act, void *gx,
+                           float *dbias /* [D] or NULL */, float *ws, int64_t ws_bytes, void *stream);
+
 /* ---- fused reconstruction metrics: L1, MSE, PSNR and SSIM of a validation pass ---------------------------------------------
  * The four numbers of the reference's table per tokenizer (docs/pretrained_models.md:47-51) that come from ImageLossMetric
  * (vq/runners/metrics/loss.py) over L1Loss, MSELoss, PSNRLoss and SSIMLoss (vq/tasks/image_reconstruction/losses.py), each of

@@ -16,6 +16,7 @@ from .distill_losses import CosineEmbeddingLoss
 from .perceptual_losses import LPIPSLoss
 from .discriminators import BaseDiscriminator, PatchGANDiscriminator, StyleGAN2Discriminator
 from .autoencoders import BaseDecoder, BaseEncoder, VQGANDecoder, VQGANEncoder
+from .vqkd_autoencoders import VQKDDecoder, VQKDEncoder
 from .gan_losses import NonSaturatingLoss, R1GradientPenalty, VQGANDiscriminatorLoss, VQGANGeneratorLoss
 from .sequence_losses import CausalTokenLoss, LabelSmoothingCrossEntropy, MaskedTokenLoss
 from .utils import EMA, ema
@@ -27,7 +28,7 @@ __all__ = [
     'MaskedTokenLoss', 'L1Loss', 'MSELoss', 'PSNRLoss', 'SSIMLoss', 'CosineEmbeddingLoss', 'LPIPSLoss',
     'BaseDiscriminator', 'PatchGANDiscriminator', 'StyleGAN2Discriminator', 'VQGANGeneratorLoss', 'NonSaturatingLoss',
     'VQGANDiscriminatorLoss', 'R1GradientPenalty', 'VQDiscriminatorRegistry', 'VQGeneratorLossRegistry', 'VQDiscriminatorLossRegistry',
-    'BaseEncoder', 'BaseDecoder', 'VQGANEncoder', 'VQGANDecoder', 'VQEncoderRegistry', 'VQDecoderRegistry',
+    'BaseEncoder', 'BaseDecoder', 'VQGANEncoder', 'VQGANDecoder', 'VQKDEncoder', 'VQKDDecoder', 'VQEncoderRegistry', 'VQDecoderRegistry',
 ]
 __version__ = '0.1.0'
 

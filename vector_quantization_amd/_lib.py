@@ -235,6 +235,40 @@ def gn_param_bound(slabs: int, extra: float, sumabs, sum_err):
     return (sg2_gbias_chain(slabs) + extra) * GN_U * sumabs + sum_err
 
 
+VIT_MAX_D = 8192                           # VQHIP_VIT_MAX_D: the widest row of vqhip_add_layer_norm_* / vqhip_row_bias_act_*
+VIT_MAX_R = 1 << 24                        # VQHIP_VIT_MAX_R: their most rows (no launch of more than 2^32 threads)
+ROW_ACT_GRID_PIECES = 8192 * 256           # 16-byte pieces the row bias-activation forward covers with a thread each; beyond: grid-stride
+LN_SLAB, ROW_ACT_SLAB = 16, 256            # rows per workgroup of the two backwards (the slabs of their column sums)
+ROW_ACT_GELU, ROW_ACT_TANH = 0, 1          # VQHIP_ROW_ACT_*
+# VQHIP_VIT_*_ULPS: twice the measured accuracy of the device erff / tanhf / expf (include/vqhip.h; profiles/vqkd_autoencoder.txt)
+VIT_ERF_ULPS, VIT_TANH_ULPS, VIT_EXP_ULPS = 3.02, 2.82, 1.79
+VIT_TINY = 2.0 ** -148                     # VQHIP_VIT_TINY
+
+
+def ln_gx_bound(e_gx, gx_total):
+    """E_gx' of include/vqhip.h: the group norm's E_gx (n = D, act 0) and the one rounding of the addition of g_skip."""
+    return e_gx + GN_U * gx_total
+
+
+def row_act_bound(act: int, t, y):
+    """VQHIP_ROW_GELU_BOUND(t, y) / VQHIP_ROW_TANH_BOUND(y): |kernel y - exact y| in fp32, before the store; magnitudes."""
+    if act == ROW_ACT_GELU:
+        return ((3.0 + VIT_ERF_ULPS) * t + 2.0 * y) * GN_U + VIT_TINY
+    return (1.0 + 2.0 * VIT_TANH_ULPS) * GN_U * y + VIT_TINY
+
+
+def row_act_grad_bound(act: int, y, d):
+    """VQHIP_ROW_GELU_GRAD_BOUND / VQHIP_ROW_TANH_GRAD_BOUND(y, d): the derivative d of the activation, absolute."""
+    if act == ROW_ACT_GELU:
+        return (5.0 + VIT_ERF_ULPS + VIT_EXP_ULPS / 2.0) * GN_U + 0.0 * d
+    return ((3.0 + 4.0 * VIT_TANH_ULPS) * y * y + d) * GN_U
+
+
+def row_act_gx_bound(act: int, g, y, d, gx):
+    """gx = g d: |g| E_d + u0 |gx|."""
+    return g * row_act_grad_bound(act, y, d) + GN_U * gx
+
+
 STEP_BEFORE_EXCHANGE, STEP_AFTER_EXCHANGE, STEP_ALL, STEP_PACK_SYNC = 1, 2, 3, 4
 
 # name -> (restype, argtypes); mirrors include/vqhip.h one to one
@@ -284,6 +318,12 @@ SIGNATURES = {
     'vqhip_group_norm_ws_bytes': (_i64, [_i32, _i64, _i64, _i64, _i64]),
     'vqhip_group_norm_fwd': (_i32, [_vp, _i32, _i32, _i64, _i64, _i64, _i64, _vp, _vp, _f32, _i32, _vp, _vp, _vp, _i64, _vp]),
     'vqhip_group_norm_bwd': (_i32, [_vp, _vp, _i32, _i32, _i64, _i64, _i64, _i64, _vp, _vp, _vp, _i32, _vp, _vp, _vp, _vp, _i64, _vp]),
+    'vqhip_add_layer_norm_slabs': (_i64, [_i64, _i64]),
+    'vqhip_add_layer_norm_fwd': (_i32, [_vp, _i32, _vp, _i32, _i64, _i64, _vp, _vp, _f32, _vp, _vp, _i32, _vp, _vp]),
+    'vqhip_add_layer_norm_bwd': (_i32, [_vp, _i32, _vp, _i32, _vp, _i64, _i64, _vp, _vp, _vp, _vp, _vp, _vp, _i64, _vp]),
+    'vqhip_row_bias_act_slabs': (_i64, [_i64, _i64]),
+    'vqhip_row_bias_act_fwd': (_i32, [_vp, _i32, _i64, _i64, _vp, _i32, _vp, _vp]),
+    'vqhip_row_bias_act_bwd': (_i32, [_vp, _vp, _i32, _i64, _i64, _vp, _i32, _vp, _vp, _vp, _i64, _vp]),
     'vqhip_image_metrics_workspace_bytes': (_i64, [_i64, _i64, _i64, _i64]),
     'vqhip_image_metrics': (_i32, [_vp, _i32, _i32, _vp, _i32, _i32, _i64, _i64, _i64, _i64, _i32, _f64, _f64, _vp, _i64, _vp, _vp,
                                    _vp, _vp]),

@@ -15,6 +15,7 @@
 #include "vqhip_lpips_kernels.h"
 #include "vqhip_stylegan2_kernels.h"
 #include "vqhip_group_norm_kernels.h"
+#include "vqhip_vit_kernels.h"
 #include "vqhip_image_metrics_kernels.h"
 
 static thread_local char g_err[256] = "";
@@ -697,6 +698,52 @@ static int gn_run(VqGnArgs a, bool rows, int T, bool bwd, int64_t slabs, float *
     if (!bwd) return VQHIP_OK;
     if (int rc = launch_sg2_reduce(a.ws_dg, slabs, a.C, dgamma, s)) return rc;
     return launch_sg2_reduce(a.ws_db, slabs, a.C, dbeta, s);
+}
+
+// ---- the row ops of the VQ-KD networks: the launches (vqhip_vit_kernels.h) ---------------------------------------------------------
+template <int XDT, int YDT, int PW>
+static int launch_ln_one(const VqLnArgs &a, bool bwd, hipStream_t s) {
+    if (a.D <= VQ_GN_SMALL) {
+        if (bwd) ln_bwd_kernel<XDT, YDT, PW, 64><<<(unsigned)((a.R + VQ_LN_SLAB - 1) / VQ_LN_SLAB), VQ_LN_THREADS, 0, s>>>(a);
+        else ln_fwd_kernel<XDT, YDT, PW, 64><<<(unsigned)((a.R + 3) / 4), VQ_LN_THREADS, 0, s>>>(a);
+    } else {
+        if (bwd) ln_bwd_kernel<XDT, YDT, PW, 256><<<(unsigned)((a.R + VQ_LN_SLAB - 1) / VQ_LN_SLAB), VQ_LN_THREADS, 0, s>>>(a);
+        else ln_fwd_kernel<XDT, YDT, PW, 256><<<(unsigned)a.R, VQ_LN_THREADS, 0, s>>>(a);
+    }
+    VQ_CHECK_LAUNCH(bwd ? "ln_bwd_kernel" : "ln_fwd_kernel");
+    return VQHIP_OK;
+}
+
+// the piece: 16 bytes of the narrowest dtype where they divide the row, else four elements, else one
+template <int XDT, int YDT>
+static int launch_ln(const VqLnArgs &a, bool bwd, hipStream_t s) {
+    if constexpr (XDT == YDT || XDT == VQHIP_DTYPE_F32) {
+        if constexpr (XDT != VQHIP_DTYPE_F32)
+            if (a.D % 8 == 0) return launch_ln_one<XDT, YDT, 8>(a, bwd, s);
+        if (a.D % 4 == 0) return launch_ln_one<XDT, YDT, 4>(a, bwd, s);
+        return launch_ln_one<XDT, YDT, 1>(a, bwd, s);
+    } else {
+        return fail(VQHIP_EINVAL, "add_layer_norm", "no kernel of this dtype combination");
+    }
+}
+
+template <int DT>
+static int launch_row_act(const VqRowActArgs &a, int act, bool bwd, int64_t slabs, float *dbias, hipStream_t s) {
+    if (!bwd) {
+        const int64_t pieces = (a.R * a.D + SampleElem<DT>::W - 1) / SampleElem<DT>::W;
+        const int64_t blocks = (pieces + VQ_SG2_THREADS - 1) / VQ_SG2_THREADS;
+        const unsigned grid = (unsigned)(blocks < 8192 ? blocks : 8192);
+        if (act == VQHIP_ROW_ACT_GELU) row_act_fwd_kernel<DT, VQHIP_ROW_ACT_GELU><<<grid, VQ_SG2_THREADS, 0, s>>>(a);
+        else row_act_fwd_kernel<DT, VQHIP_ROW_ACT_TANH><<<grid, VQ_SG2_THREADS, 0, s>>>(a);
+        VQ_CHECK_LAUNCH("row_act_fwd_kernel");
+        return VQHIP_OK;
+    }
+    const int per = 64 * SampleElem<DT>::W;
+    const dim3 grid((unsigned)slabs, (unsigned)((a.D + per - 1) / per));
+    if (act == VQHIP_ROW_ACT_GELU) row_act_bwd_kernel<DT, VQHIP_ROW_ACT_GELU><<<grid, VQ_SG2_THREADS, 0, s>>>(a);
+    else row_act_bwd_kernel<DT, VQHIP_ROW_ACT_TANH><<<grid, VQ_SG2_THREADS, 0, s>>>(a);
+    VQ_CHECK_LAUNCH("row_act_bwd_kernel");
+    return dbias ? launch_sg2_reduce(a.ws, slabs, a.D, dbias, s) : VQHIP_OK;
 }
 
 extern "C" {
@@ -1800,6 +1847,88 @@ int vqhip_group_norm_bwd(const void *g, const void *x, int dtype, int layout, in
     return vq_with_dtype(dtype, [&](auto dt) {
         return gn_run<decltype(dt)::value>(a, layout == VQHIP_LAYOUT_ROWS, pl.T, true, pl.slabs, dgamma, dbeta, (hipStream_t)stream);
     });
+}
+
+// ---- the row ops of the VQ-KD networks (vqhip_vit_kernels.h) ---------------------------------------------------------------------
+// what the six entry points refuse alike about the rows
+static int vit_rows(const char *what, int64_t R, int64_t D) {
+    if (R < 1 || R > VQHIP_VIT_MAX_R || D < 1 || D > VQHIP_VIT_MAX_D) return fail(VQHIP_EINVAL, what, "need 1 <= R <= 2^24 and 1 <= D <= 8192");
+    if (R > ((1ll << 31) - 1) / D) return fail(VQHIP_EINVAL, what, "R * D must be below 2^31");
+    return VQHIP_OK;
+}
+
+// (x, y): the same float dtype, or fp32 x with a 16-bit y (autocast); res, where given, in y's dtype
+static inline bool vit_ln_pair(int x_dtype, int y_dtype) {
+    return vq_float_dtype(x_dtype) && vq_float_dtype(y_dtype) && (x_dtype == y_dtype || x_dtype == VQHIP_DTYPE_F32);
+}
+
+int64_t vqhip_add_layer_norm_slabs(int64_t R, int64_t D) {
+    if (vit_rows("vqhip_add_layer_norm_slabs", R, D)) return -1;
+    return (R + VQ_LN_SLAB - 1) / VQ_LN_SLAB;
+}
+
+int vqhip_add_layer_norm_fwd(const void *x, int x_dtype, const void *res, int res_dtype, int64_t R, int64_t D, const float *gamma,
+                             const float *beta, float eps, void *sum_out, void *y, int y_dtype, float *stats, void *stream) {
+    if (int rc = vit_rows("vqhip_add_layer_norm_fwd", R, D)) return rc;
+    VQ_REQUIRE(vit_ln_pair(x_dtype, y_dtype), "vqhip_add_layer_norm_fwd: (x, y) must be one float dtype, or fp32 x with a bf16 or fp16 y");
+    VQ_REQUIRE(!res || res_dtype == y_dtype, "vqhip_add_layer_norm_fwd: res must have y's dtype");
+    VQ_REQUIRE(eps >= 0.0f && eps < INFINITY, "vqhip_add_layer_norm_fwd: eps must be finite and not negative");
+    VQ_REQUIRE(x && gamma && beta && y && stats, "vqhip_add_layer_norm_fwd: x, gamma, beta, y and stats are required");
+    VQ_REQUIRE(!res || sum_out, "vqhip_add_layer_norm_fwd: res needs sum_out");
+    VqLnArgs a = {};
+    a.x = x; a.res = res; a.sum_out = sum_out; a.out = y; a.gamma = gamma; a.beta = beta; a.stats = stats; a.R = R; a.D = (int)D; a.eps = eps;
+    return vq_with_dtype(x_dtype, [&](auto dx) { return vq_with_dtype(y_dtype, [&](auto dy) {
+        return launch_ln<decltype(dx)::value, decltype(dy)::value>(a, false, (hipStream_t)stream);
+    }); });
+}
+
+int vqhip_add_layer_norm_bwd(const void *g, int g_dtype, const void *s, int s_dtype, const void *g_skip, int64_t R, int64_t D,
+                             const float *gamma, const float *stats, void *gx, float *dgamma, float *dbeta, float *ws, int64_t ws_bytes,
+                             void *stream) {
+    if (int rc = vit_rows("vqhip_add_layer_norm_bwd", R, D)) return rc;
+    VQ_REQUIRE(vit_ln_pair(s_dtype, g_dtype), "vqhip_add_layer_norm_bwd: (s, g) must be one float dtype, or fp32 s with a bf16 or fp16 g");
+    VQ_REQUIRE(g && s && gamma && stats && gx && dgamma && dbeta && ws,
+               "vqhip_add_layer_norm_bwd: g, s, gamma, stats, gx, dgamma, dbeta and ws are required");
+    const int64_t slabs = (R + VQ_LN_SLAB - 1) / VQ_LN_SLAB;
+    VQ_NEED("vqhip_add_layer_norm_bwd: ws too small", ws_bytes, 2 * slabs * D * (int64_t)sizeof(float));
+    VqLnArgs a = {};
+    a.x = s; a.res = g_skip; a.g = g; a.out = gx; a.gamma = gamma; a.stats = const_cast<float *>(stats); a.R = R; a.D = (int)D;
+    a.ws_dg = ws; a.ws_db = ws + slabs * D;
+    const hipStream_t st = (hipStream_t)stream;
+    if (int rc = vq_with_dtype(s_dtype, [&](auto dx) { return vq_with_dtype(g_dtype, [&](auto dy) {
+            return launch_ln<decltype(dx)::value, decltype(dy)::value>(a, true, st);
+        }); })) return rc;
+    if (int rc = launch_sg2_reduce(a.ws_dg, slabs, a.D, dgamma, st)) return rc;
+    return launch_sg2_reduce(a.ws_db, slabs, a.D, dbeta, st);
+}
+
+int64_t vqhip_row_bias_act_slabs(int64_t R, int64_t D) {
+    if (vit_rows("vqhip_row_bias_act_slabs", R, D)) return -1;
+    return (R + VQ_SG2_ROWS_SLAB - 1) / VQ_SG2_ROWS_SLAB;
+}
+
+int vqhip_row_bias_act_fwd(const void *x, int dtype, int64_t R, int64_t D, const float *bias, int act, void *y, void *stream) {
+    if (int rc = vit_rows("vqhip_row_bias_act_fwd", R, D)) return rc;
+    VQ_REQUIRE(vq_float_dtype(dtype), "vqhip_row_bias_act_fwd: dtype");
+    VQ_REQUIRE(act == VQHIP_ROW_ACT_GELU || act == VQHIP_ROW_ACT_TANH, "vqhip_row_bias_act_fwd: act must be 0 (GELU) or 1 (tanh)");
+    VQ_REQUIRE(x && bias && y, "vqhip_row_bias_act_fwd: x, bias and y are required");
+    VqRowActArgs a = {};
+    a.x = x; a.bias = bias; a.out = y; a.R = R; a.D = (int)D;
+    return vq_with_dtype(dtype, [&](auto dt) { return launch_row_act<decltype(dt)::value>(a, act, false, 0, nullptr, (hipStream_t)stream); });
+}
+
+int vqhip_row_bias_act_bwd(const void *g, const void *x, int dtype, int64_t R, int64_t D, const float *bias, int act, void *gx,
+                           float *dbias, float *ws, int64_t ws_bytes, void *stream) {
+    if (int rc = vit_rows("vqhip_row_bias_act_bwd", R, D)) return rc;
+    VQ_REQUIRE(vq_float_dtype(dtype), "vqhip_row_bias_act_bwd: dtype");
+    VQ_REQUIRE(act == VQHIP_ROW_ACT_GELU || act == VQHIP_ROW_ACT_TANH, "vqhip_row_bias_act_bwd: act must be 0 (GELU) or 1 (tanh)");
+    VQ_REQUIRE(g && x && bias && gx, "vqhip_row_bias_act_bwd: g, x, bias and gx are required");
+    VQ_REQUIRE(!dbias || ws, "vqhip_row_bias_act_bwd: dbias needs the workspace");
+    const int64_t slabs = (R + VQ_SG2_ROWS_SLAB - 1) / VQ_SG2_ROWS_SLAB;
+    if (dbias) VQ_NEED("vqhip_row_bias_act_bwd: ws too small", ws_bytes, slabs * D * (int64_t)sizeof(float));
+    VqRowActArgs a = {};
+    a.x = x; a.g = g; a.bias = bias; a.out = gx; a.ws = dbias ? ws : nullptr; a.R = R; a.D = (int)D;
+    return vq_with_dtype(dtype, [&](auto dt) { return launch_row_act<decltype(dt)::value>(a, act, true, slabs, dbias, (hipStream_t)stream); });
 }
 
 // ---- fused reconstruction metrics (vqhip_image_metrics_kernels.h) ---------------------------------------------------------

@@ -134,6 +134,26 @@ __device__ __forceinline__ float gn_team_sum(float v, float *red /* [4] in LDS *
     return v;
 }
 
+// mean and M2 = sum (x - mean)^2 of the nc values a team holds in registers (FORWARD above; shared with the row norm of
+// vqhip_vit_kernels.h): a value counts where its piece has it (e < cnt[k])
+template <int T, int NP, int PW>
+__device__ __forceinline__ void gn_mean_m2(const float (&xv)[NP][PW], const int (&cnt)[NP], float nc, float *red, float &mean, float &m2) {
+    float acc = 0.0f;
+#pragma unroll
+    for (int k = 0; k < NP; ++k)
+#pragma unroll
+        for (int e = 0; e < PW; ++e)
+            if (e < cnt[k]) acc = acc + xv[k][e];
+    mean = gn_team_sum<T>(acc, red) / nc;
+    acc = 0.0f;
+#pragma unroll
+    for (int k = 0; k < NP; ++k)
+#pragma unroll
+        for (int e = 0; e < PW; ++e)
+            if (e < cnt[k]) { const float d = xv[k][e] - mean; acc = acc + d * d; }
+    m2 = gn_team_sum<T>(acc, red);
+}
+
 __device__ __forceinline__ float gn_sigmoid(float u) { return 1.0f / (1.0f + expf(-u)); }
 
 // values of chunk c of a group of n
@@ -181,21 +201,7 @@ __global__ __launch_bounds__(VQ_GN_THREADS) void gn_fwd_kernel(VqGnArgs a) {
     }
     float mean, m2;
     if (a.phase != VQ_GN_APPLY) {
-        float acc = 0.0f;
-#pragma unroll
-        for (int k = 0; k < NP; ++k)
-#pragma unroll
-            for (int e = 0; e < PW; ++e)
-                if (e < cnt[k]) acc = acc + xv[k][e];
-        const float nc = a.S == 1 ? (float)a.n : gn_chunk_count(a.n, tm.s);
-        mean = gn_team_sum<T>(acc, red) / nc;
-        acc = 0.0f;
-#pragma unroll
-        for (int k = 0; k < NP; ++k)
-#pragma unroll
-            for (int e = 0; e < PW; ++e)
-                if (e < cnt[k]) { const float d = xv[k][e] - mean; acc = acc + d * d; }
-        m2 = gn_team_sum<T>(acc, red);
+        gn_mean_m2<T, NP, PW>(xv, cnt, a.S == 1 ? (float)a.n : gn_chunk_count(a.n, tm.s), red, mean, m2);
         if (a.phase == VQ_GN_PART) {
             if (tm.t == 0) { a.ws_grp[tm.unit * 2] = mean; a.ws_grp[tm.unit * 2 + 1] = m2; }
             return;

@@ -591,3 +591,109 @@ def group_norm(x: torch.Tensor, num_groups: int, weight: torch.Tensor, bias: tor
     if not x.is_cuda or ops.group_norm_refusal(x, num_groups):
         return group_norm_torch(x, num_groups, weight, bias, eps, act)
     return _GroupNorm.apply(x, weight, bias, int(num_groups), float(eps), act)
+
+
+# ---- the row ops of VQKDEncoder / VQKDDecoder: the residual add folded into the LayerNorm that follows it, and bias + GELU / tanh.
+#      The norm keeps the sum s and two floats per row; the activation keeps its input: both backwards recompute the rest ----
+
+class _AddLayerNorm(Function):
+    """vqhip_add_layer_norm_fwd / _bwd.  Outputs (s, y) with a branch to add, (y,) without; the gradient arriving at s is the
+    kernel's g_skip."""
+
+    @staticmethod
+    def forward(ctx, x, res, weight, bias, eps, out_dtype):
+        s, y, stats = ops.add_layer_norm(x, res, weight, bias, eps, out_dtype)
+        ctx.save_for_backward(s, weight, stats)
+        ctx.set_materialize_grads(False)
+        ctx.res_dtype = None if res is None else res.dtype
+        ctx.bias_dtype = bias.dtype
+        return (y,) if res is None else (s, y)
+
+    @staticmethod
+    @once_differentiable
+    def backward(ctx, *grads):
+        s, weight, stats = ctx.saved_tensors
+        g_s, g_y = (None, grads[0]) if ctx.res_dtype is None else grads
+        if g_y is None:                                                         # y took no part in the loss: the add alone
+            gx, dgamma, dbeta = g_s, None, None
+        else:
+            skip = None if g_s is None else g_s.to(s.dtype).contiguous()
+            gx, dgamma, dbeta = ops.add_layer_norm_backward(g_y.contiguous(), s, stats, weight, skip)
+        need = ctx.needs_input_grad
+        return (gx if need[0] else None,
+                gx.to(ctx.res_dtype) if need[1] and gx is not None and ctx.res_dtype is not None else None,
+                dgamma.to(weight.dtype).view_as(weight) if need[2] and dgamma is not None else None,
+                dbeta.to(ctx.bias_dtype).view_as(weight) if need[3] and dbeta is not None else None, None, None)
+
+
+def add_layer_norm_torch(x: torch.Tensor, res: Optional[torch.Tensor], weight: torch.Tensor, bias: torch.Tensor, eps: float = 1e-6,
+                         out_dtype=None):
+    """The same definition in the reference's lines, ``x = x + branch`` and ``norm(x)``: CPU tensors, float64, ``fused=False``."""
+    s = x if res is None else x + res
+    y = torch.nn.functional.layer_norm(s, (s.shape[-1],), weight, bias, eps)
+    return s, (y if out_dtype is None else y.to(out_dtype))
+
+
+def _vit_refusal(x: torch.Tensor) -> str:
+    """Why the row kernels would not read ``x`` (made contiguous) in place: device, dtype, shape."""
+    return ('' if x.is_cuda else f'the rows are on device {x.device}, not on a GPU') or ops.float_dtype_refusal('the rows are', x) \
+        or ops.vit_rows_refusal('x', x.contiguous())
+
+
+def add_layer_norm(x: torch.Tensor, res: Optional[torch.Tensor], weight: torch.Tensor, bias: torch.Tensor, eps: float = 1e-6,
+                   out_dtype=None, *, strict: bool = False):
+    """``(s, y)`` with ``s = x + res`` (``x`` itself where ``res`` is None) in x's dtype and ``y = layer_norm(s, weight, bias, eps)``
+    in ``out_dtype`` (default: res's dtype, else x's): one launch reads x and res and writes s and y, fp32 arithmetic whatever the
+    dtypes, gradients to x, res, weight and bias.  fp32 x with a bf16 / fp16 res and y is the autocast case.  A CPU tensor, float64
+    or a dtype combination the kernels do not read computes the same definition in torch - or, with ``strict`` (a module that
+    has reported the fused route), raises with the reason."""
+    y_dtype = out_dtype or (x.dtype if res is None else res.dtype)
+    why = _vit_refusal(x) or ops.ln_pair_refusal(x, y_dtype) \
+        or ('' if res is None or (res.dtype == y_dtype and res.shape == x.shape) else
+            f'res is {res.dtype} {tuple(res.shape)}, not {y_dtype} {tuple(x.shape)}')
+    if why:
+        if strict:
+            raise ValueError(f'add_layer_norm: {why}')
+        return add_layer_norm_torch(x, res, weight, bias, eps, out_dtype)
+    x, res = x.contiguous(), None if res is None else res.contiguous()
+    out = _AddLayerNorm.apply(x, res, weight, bias, float(eps), y_dtype)
+    return (x, out[0]) if res is None else out
+
+
+ROW_ACTS_TORCH = {'gelu': torch.nn.functional.gelu, 'tanh': torch.tanh}
+
+
+class _RowBiasAct(Function):
+    """vqhip_row_bias_act_fwd / _bwd; saves the INPUT and the bias (the backward recomputes the derivative)."""
+
+    @staticmethod
+    def forward(ctx, x, bias, act):
+        ctx.save_for_backward(x, bias)
+        ctx.act = act
+        return ops.row_bias_act(x, bias, act)
+
+    @staticmethod
+    @once_differentiable
+    def backward(ctx, g):
+        x, bias = ctx.saved_tensors
+        gx, dbias = ops.row_bias_act_backward(g.contiguous(), x, bias, ctx.act, ctx.needs_input_grad[1])
+        return gx if ctx.needs_input_grad[0] else None, None if dbias is None else dbias.to(bias.dtype).view_as(bias), None
+
+
+def row_bias_act_torch(x: torch.Tensor, bias: torch.Tensor, act='gelu') -> torch.Tensor:
+    """The same definition in torch: the bias a ``Linear`` would have added, in x's dtype, then ``F.gelu`` / ``torch.tanh``."""
+    return ROW_ACTS_TORCH[act](x + bias.to(x.dtype))
+
+
+def row_bias_act(x: torch.Tensor, bias: torch.Tensor, act='gelu', *, strict: bool = False) -> torch.Tensor:
+    """``act(x + bias)`` of rows [..., D] with ``act`` 'gelu' (the erf form, ``nn.GELU()``) or 'tanh', in x's dtype: one launch, and a
+    backward that writes ``gx`` and the bias gradient in one pass from the saved ``x``.  A CPU tensor, float64 or rows the kernels
+    do not read compute the same definition in torch - or, with ``strict``, raise with the reason."""
+    if act not in ROW_ACTS_TORCH:
+        raise ValueError(f'row_bias_act: act={act!r} is neither \'gelu\' nor \'tanh\'')
+    why = _vit_refusal(x)
+    if why:
+        if strict:
+            raise ValueError(f'row_bias_act: {why}')
+        return row_bias_act_torch(x, bias, act)
+    return _RowBiasAct.apply(x.contiguous(), bias, act)

@@ -1312,6 +1312,144 @@ def group_norm_backward(g: torch.Tensor, x: torch.Tensor, stats: torch.Tensor, n
     return gx, dgamma, dbeta
 
 
+# ---- the row ops of VQKDEncoder / VQKDDecoder (vq/algorithms/vqkd/autoencoder.py): add + LayerNorm, bias + GELU / tanh -------------
+
+ROW_ACTS = {'gelu': _lib.ROW_ACT_GELU, 'tanh': _lib.ROW_ACT_TANH}
+
+
+def vit_rows_refusal(name: str, t: torch.Tensor) -> str:
+    """Why vqhip_add_layer_norm_* / vqhip_row_bias_act_* would refuse ``t`` [..., D] ('' if they would not): the clauses of their
+    LIMITS that depend on the tensor's dtype, shape and strides.  Rows must be dense: no copy is made here."""
+    rows = row_view(t, name)
+    if isinstance(rows, str):
+        return rows
+    rows, stride = rows
+    R, D = rows.shape
+    return ('' if R >= 1 and D >= 1 else f'{name} {tuple(t.shape)} is empty') \
+        or ('' if stride == D else f'the rows of {name} are not dense (row stride {stride}, D={D})') \
+        or ('' if D <= _lib.VIT_MAX_D else f'D={D} is beyond {_lib.VIT_MAX_D}') \
+        or ('' if R <= _lib.VIT_MAX_R else f'R={R} rows are beyond 2^24') \
+        or ('' if R * D < (1 << 31) else f'{R * D} elements are outside 1 .. 2^31-1')
+
+
+def _vit_rows(what: str, name: str, t: torch.Tensor):
+    _require_cuda(t)
+    _refuse(what, vit_rows_refusal(name, t))
+    return row_view(t, name)[0]
+
+
+def ln_pair_refusal(x: torch.Tensor, y_dtype) -> str:
+    """'' where (x's dtype, the dtype of res, y and g) is a row of the table of include/vqhip.h, else the sentence that says so."""
+    ok = y_dtype in FLOAT_DTYPES and (y_dtype == x.dtype or x.dtype == torch.float32)
+    return '' if ok else f'x is {x.dtype} and the other side {y_dtype}: need one float dtype, or float32 x with bfloat16 or float16'
+
+
+@_on_tensor_device
+def add_layer_norm(x: torch.Tensor, res: Optional[torch.Tensor], weight: torch.Tensor, bias: torch.Tensor, eps: float = 1e-6,
+                   out_dtype=None):
+    """vqhip_add_layer_norm_fwd: ``(s, y, stats)`` with ``s = x + res`` in x's dtype (``x`` itself where ``res`` is None),
+    ``y = layer_norm(s) * weight + bias`` in ``out_dtype`` (default: res's dtype, else x's) and ``stats`` [R, 2] fp32 (each row's
+    mean and 1 / sqrt(var + eps)).  Rows [..., D] read in place; fp32 x with a bf16 / fp16 res and y is the autocast case.  One launch."""
+    xr = _vit_rows('add_layer_norm', 'x', x)
+    out_dtype = out_dtype or (x.dtype if res is None else res.dtype)
+    why = ln_pair_refusal(x, out_dtype)
+    rr = None
+    if not why and res is not None:
+        why = ('' if res.shape == x.shape and res.dtype == out_dtype else
+               f'res is {res.dtype} {tuple(res.shape)}, not {out_dtype} {tuple(x.shape)}') or vit_rows_refusal('res', res)
+        _require_cuda(res)
+    R, D = xr.shape
+    if not why and (weight.numel() != D or bias.numel() != D):
+        why = f'weight and bias have {weight.numel()} and {bias.numel()} elements, not D={D}'
+    _refuse('add_layer_norm', why)
+    _require_cuda(weight, bias)
+    if res is not None:
+        rr = row_view(res, 'res')[0]
+    w, b = _fp32_vector(weight), _fp32_vector(bias)
+    s = x if res is None else torch.empty_like(xr).view(x.shape)
+    y = torch.empty(x.shape, dtype=out_dtype, device=x.device)
+    stats = torch.empty(R, 2, dtype=torch.float32, device=x.device)
+    check(_lib.lib().vqhip_add_layer_norm_fwd(_ptr(xr), FLOAT_DTYPES[x.dtype], _ptr(rr), FLOAT_DTYPES[out_dtype], R, D, _ptr(w), _ptr(b),
+                                              float(eps), None if res is None else _ptr(s), _ptr(y), FLOAT_DTYPES[out_dtype], _ptr(stats),
+                                              _stream()), 'vqhip_add_layer_norm_fwd')
+    return s, y, stats
+
+
+@_on_tensor_device
+def add_layer_norm_backward(g: torch.Tensor, s: torch.Tensor, stats: torch.Tensor, weight: torch.Tensor,
+                            g_skip: Optional[torch.Tensor] = None):
+    """vqhip_add_layer_norm_bwd: ``(gx, dgamma, dbeta)`` from the gradient ``g`` arriving at y, the saved sum ``s`` and the
+    forward's ``stats``; ``g_skip``, the gradient arriving at s itself, is added in the same pass.  ``gx`` in s's dtype (it is the
+    gradient of x and, cast, of res), ``dgamma`` and ``dbeta`` fp32 [D] from a fixed-order two-stage sum."""
+    sr = _vit_rows('add_layer_norm_backward', 's', s)
+    R, D = sr.shape
+    why = ln_pair_refusal(s, g.dtype) or ('' if g.shape == s.shape else f'g is {tuple(g.shape)}, s {tuple(s.shape)}') \
+        or vit_rows_refusal('g', g)
+    if not why and g_skip is not None:
+        why = ('' if g_skip.shape == s.shape and g_skip.dtype == s.dtype else
+               f'g_skip is {g_skip.dtype} {tuple(g_skip.shape)}, not {s.dtype} {tuple(s.shape)}') or vit_rows_refusal('g_skip', g_skip)
+    if not why and (stats.dtype != torch.float32 or stats.numel() != 2 * R or not stats.is_contiguous()):
+        why = f'stats must be the contiguous fp32 [{R}, 2] of the forward'
+    if not why and weight.numel() != D:
+        why = f'weight has {weight.numel()} elements, not D={D}'
+    _refuse('add_layer_norm_backward', why)
+    _require_cuda(g, g_skip, stats, weight)
+    w = _fp32_vector(weight)
+    gr = row_view(g, 'g')[0]
+    kr = None if g_skip is None else row_view(g_skip, 'g_skip')[0]
+    gx = torch.empty_like(sr).view(s.shape)
+    slabs = _lib.lib().vqhip_add_layer_norm_slabs(R, D)
+    ws = torch.empty(2 * slabs * D, dtype=torch.float32, device=s.device)
+    dgamma = torch.empty(D, dtype=torch.float32, device=s.device)
+    dbeta = torch.empty(D, dtype=torch.float32, device=s.device)
+    check(_lib.lib().vqhip_add_layer_norm_bwd(_ptr(gr), FLOAT_DTYPES[g.dtype], _ptr(sr), FLOAT_DTYPES[s.dtype], _ptr(kr), R, D, _ptr(w),
+                                              _ptr(stats), _ptr(gx), _ptr(dgamma), _ptr(dbeta), _ptr(ws), ws.numel() * 4, _stream()),
+          'vqhip_add_layer_norm_bwd')
+    return gx, dgamma, dbeta
+
+
+def _row_act_head(what: str, x: torch.Tensor, bias: torch.Tensor, act):
+    xr = _vit_rows(what, 'x', x)
+    why = ('' if act in ROW_ACTS else f'act={act!r} is neither \'gelu\' nor \'tanh\'') \
+        or ('' if bias.numel() == xr.shape[1] else f'the bias has {bias.numel()} elements, not D={xr.shape[1]}')
+    _refuse(what, why)
+    _require_cuda(bias)
+    return xr, _fp32_vector(bias)
+
+
+@_on_tensor_device
+def row_bias_act(x: torch.Tensor, bias: torch.Tensor, act='gelu') -> torch.Tensor:
+    """vqhip_row_bias_act_fwd: ``act(x + bias)`` of rows [..., D] read in place, in x's dtype; ``act``: 'gelu' (the erf form) or
+    'tanh'.  One launch."""
+    xr, b = _row_act_head('row_bias_act', x, bias, act)
+    y = torch.empty_like(xr).view(x.shape)
+    check(_lib.lib().vqhip_row_bias_act_fwd(_ptr(xr), FLOAT_DTYPES[x.dtype], *xr.shape, _ptr(b), ROW_ACTS[act], _ptr(y), _stream()),
+          'vqhip_row_bias_act_fwd')
+    return y
+
+
+@_on_tensor_device
+def row_bias_act_backward(g: torch.Tensor, x: torch.Tensor, bias: torch.Tensor, act='gelu', need_dbias: bool = True):
+    """vqhip_row_bias_act_bwd: ``(gx, dbias)`` from the incoming gradient and the SAVED INPUT ``x`` and ``bias`` (the derivative
+    is recomputed; y is not kept).  ``gx`` in x's dtype, ``dbias`` fp32 [D] from a fixed-order two-stage sum (None without
+    ``need_dbias``)."""
+    xr, b = _row_act_head('row_bias_act_backward', x, bias, act)
+    _refuse('row_bias_act_backward', ('' if g.shape == x.shape and g.dtype == x.dtype else
+                                      f'g is {g.dtype} {tuple(g.shape)}, x {x.dtype} {tuple(x.shape)}') or vit_rows_refusal('g', g))
+    _require_cuda(g)
+    gr = row_view(g, 'g')[0]
+    R, D = xr.shape
+    gx = torch.empty_like(xr).view(x.shape)
+    dbias = ws = None
+    if need_dbias:
+        slabs = _lib.lib().vqhip_row_bias_act_slabs(R, D)
+        ws = torch.empty(slabs * D, dtype=torch.float32, device=x.device)
+        dbias = torch.empty(D, dtype=torch.float32, device=x.device)
+    check(_lib.lib().vqhip_row_bias_act_bwd(_ptr(gr), _ptr(xr), FLOAT_DTYPES[x.dtype], R, D, _ptr(b), ROW_ACTS[act], _ptr(gx), _ptr(dbias),
+                                            _ptr(ws), 0 if ws is None else ws.numel() * 4, _stream()), 'vqhip_row_bias_act_bwd')
+    return gx, dbias
+
+
 # ---- fused reconstruction metrics (validation: vq/runners/metrics/loss.py over vq/tasks/image_reconstruction/losses.py) -----
 
 IMAGE_METRIC_COLUMNS = ('l1', 'mse', 'psnr', 'ssim')
