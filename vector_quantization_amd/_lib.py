@@ -2,11 +2,18 @@
 
 The library is built in-tree by ``vector_quantization_amd/csrc/build.sh`` (hipcc, gfx950).  There is no
 CPU or PyTorch fallback: if the shared object is missing or a call fails, an exception is raised.
+
+The prototypes are not written down here: ``SIGNATURES`` is read from include/vqhip.h at import (``parse_header``), so a new
+entry point is its declaration in the header and its caller.  What a regex cannot derive stays a copy in this file - the five
+``Structure`` layouts, the numeric constants and the ``VQHIP_*_BOUND`` family as Python functions - and every such copy is
+held to the header by tests/test_binding_header_cpu.py, which compiles a C probe against it.  ``ABI_VERSION`` is
+hand-written on purpose.
 """
 from __future__ import annotations
 
 import ctypes
 import os
+import re
 import subprocess
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
@@ -271,125 +278,54 @@ def row_act_gx_bound(act: int, g, y, d, gx):
 
 STEP_BEFORE_EXCHANGE, STEP_AFTER_EXCHANGE, STEP_ALL, STEP_PACK_SYNC = 1, 2, 3, 4
 
-# name -> (restype, argtypes); mirrors include/vqhip.h one to one
-SIGNATURES = {
-    'vqhip_version': (_i32, []),
-    'vqhip_last_error': (ctypes.c_char_p, []),
-    'vqhip_codebook_bytes': (_i64, [_i64, _i32]),
-    'vqhip_codebook_exact_offset': (_i64, [_i64, _i32]),
-    'vqhip_encode': (_i32, [_vp, _i32, _vp, _i64, _i64, _i32, _i32, _vp, _i64, _vp, _vp, _vp, _vp, _i64, _vp]),
-    'vqhip_encode_ex': (_i32, [_vp, _i32, _vp, _i64, _i64, _i32, _i32, _vp, _i64, _vp, _vp, _vp, _vp, _i64, _i32, _vp]),
-    'vqhip_encode_map': (_i32, [_vp, _i32, _vp, _i64, _i64, _i64, _i32, _i32, _vp, _i64, _vp, _vp, _vp, _vp, _vp, _i64, _i32, _vp]),
-    'vqhip_gather_ste_map': (_i32, [_vp, _i32, _vp, _vp, _i64, _i64, _i32, _vp, _vp, _f32, _vp, _vp]),
-    'vqhip_workspace_bytes': (_i64, [_i64, _i64, _i32]),
-    'vqhip_col_workspace_bytes': (_i64, [_i64, _i64, _i32]),
-    'vqhip_codebook_prepare': (_i32, [_vp, _i64, _i32, _i32, _vp, _i64, _vp]),
-    'vqhip_argmin': (_i32, [_vp, _i32, _vp, _vp, _i64, _i64, _i64, _i32, _i32, _vp, _vp, _vp, _i64, _vp]),
-    'vqhip_argmin_exact': (_i32, [_vp, _i32, _vp, _i64, _i64, _i32, _i32, _vp, _vp, _vp, _vp, _i64, _vp]),
-    'vqhip_distance': (_i32, [_vp, _i32, _vp, _i64, _i64, _i32, _i32, _vp, _vp, _i64, _vp]),
-    'vqhip_col_argmin': (_i32, [_vp, _i32, _vp, _i64, _i64, _i32, _i32, _vp, _vp, _i64, _vp]),
-    'vqhip_row_sqnorm': (_i32, [_vp, _i32, _i64, _i32, _vp, _vp]),
-    'vqhip_normalize_rows': (_i32, [_vp, _i32, _i64, _i32, _f32, _vp, _vp]),
-    'vqhip_gather_ste_loss': (_i32, [_vp, _i32, _vp, _vp, _i64, _i32, _vp, _vp, _vp, _vp]),
-    'vqhip_gather_ste_mse': (_i32, [_vp, _i32, _vp, _vp, _i64, _i32, _vp, _vp, _vp, _f32, _vp, _vp]),
-    'vqhip_hist': (_i32, [_vp, _i64, _i64, _vp, _vp]),
-    'vqhip_hist_i32': (_i32, [_vp, _i64, _i64, _vp, _vp]),
-    'vqhip_fsq_encode': (_i32, [ctypes.POINTER(FsqConstants), _vp, _i32, _i32, _i64, _i64, _vp, _vp, _i32, _vp, _vp, _vp]),
-    'vqhip_fsq_backward': (_i32, [ctypes.POINTER(FsqConstants), _vp, _i32, _i32, _i64, _i64, _vp, _vp, _vp]),
-    'vqhip_fsq_decode': (_i32, [ctypes.POINTER(FsqConstants), _vp, _i32, _i32, _i64, _i64, _vp, _vp]),
-    'vqhip_decode_pool': (_i32, [_vp, _i64, _i32, _vp, _i32, _i64, _i64, _vp, _vp]),
-    'vqhip_decode_pool_bwd': (_i32, [_vp, _vp, _i32, _i64, _i64, _i64, _i32, _vp, _vp]),
-    'vqhip_fsq_decode_pool': (_i32, [ctypes.POINTER(FsqConstants), _vp, _i32, _i64, _i64, _vp, _vp]),
-    'vqhip_sample_tokens': (_i32, [_vp, _i32, _i64, _i64, _i64, _i64, _f32, _i32, _f32, _i32, _f32, _vp, _vp, _vp, _vp]),
-    'vqhip_token_ce_fwd': (_i32, [_vp, _i32, _i64, _i64, _i64, _i64, _vp, _i32, _i64, _i64, _f32, _vp, _vp, _vp, _vp, _vp, _vp]),
-    'vqhip_token_ce_bwd': (_i32, [_vp, _i32, _i64, _i64, _i64, _i64, _vp, _i32, _i64, _i64, _f32, _vp, _vp, _vp, _i32, _vp, _vp,
-                                  _i64, _i64, _vp]),
-    'vqhip_cosine_embed_fwd': (_i32, [_vp, _i32, _i32, _i64, _vp, _i32, _i64, _i64, _i64, _i64, _vp, _vp, _vp, _vp]),
-    'vqhip_cosine_embed_bwd': (_i32, [_vp, _i32, _i32, _i64, _vp, _i32, _i64, _i64, _i64, _i64, _vp, _vp, _i32, _i32, _vp, _i64, _vp]),
-    'vqhip_lpips_fwd': (_i32, [_vp, _i32, _vp, _i32, _i32, _i64, _i64, _i64, _vp, _vp, _f32, _i64, _vp, _vp, _i32, _vp]),
-    'vqhip_lpips_bwd': (_i32, [_vp, _i32, _vp, _i32, _i32, _i64, _i64, _i64, _vp, _vp, _f32, _i64, _vp, _vp, _vp, _vp]),
-    'vqhip_lpips_keep_mask': (_i32, [_vp, _f32, _i64, _i64, _i64, _i64, _vp, _vp]),
-    'vqhip_bias_act_slabs': (_i64, [_i32, _i64, _i64, _i64]),
-    'vqhip_bias_act_fwd': (_i32, [_vp, _i32, _i32, _i64, _i64, _i64, _vp, _vp, _vp]),
-    'vqhip_bias_act_bwd': (_i32, [_vp, _vp, _i32, _i32, _i64, _i64, _i64, _vp, _vp, _vp, _i64, _vp]),
-    'vqhip_fir4_slabs': (_i64, [_i32, _i64, _i64, _i64, _i64]),
-    'vqhip_fir4_fwd': (_i32, [_vp, _i32, _i32, _i64, _i64, _i64, _i64, _i32, _i32, _i32, _i32, _i32, _vp, _vp, _vp]),
-    'vqhip_fir4_bwd': (_i32, [_vp, _i32, _i32, _i64, _i64, _i64, _i64, _i32, _i32, _i32, _i32, _i32, _vp, _vp, _vp, _vp, _vp, _i64, _vp]),
-    'vqhip_group_norm_ws_bytes': (_i64, [_i32, _i64, _i64, _i64, _i64]),
-    'vqhip_group_norm_fwd': (_i32, [_vp, _i32, _i32, _i64, _i64, _i64, _i64, _vp, _vp, _f32, _i32, _vp, _vp, _vp, _i64, _vp]),
-    'vqhip_group_norm_bwd': (_i32, [_vp, _vp, _i32, _i32, _i64, _i64, _i64, _i64, _vp, _vp, _vp, _i32, _vp, _vp, _vp, _vp, _i64, _vp]),
-    'vqhip_add_layer_norm_slabs': (_i64, [_i64, _i64]),
-    'vqhip_add_layer_norm_fwd': (_i32, [_vp, _i32, _vp, _i32, _i64, _i64, _vp, _vp, _f32, _vp, _vp, _i32, _vp, _vp]),
-    'vqhip_add_layer_norm_bwd': (_i32, [_vp, _i32, _vp, _i32, _vp, _i64, _i64, _vp, _vp, _vp, _vp, _vp, _vp, _i64, _vp]),
-    'vqhip_row_bias_act_slabs': (_i64, [_i64, _i64]),
-    'vqhip_row_bias_act_fwd': (_i32, [_vp, _i32, _i64, _i64, _vp, _i32, _vp, _vp]),
-    'vqhip_row_bias_act_bwd': (_i32, [_vp, _vp, _i32, _i64, _i64, _vp, _i32, _vp, _vp, _vp, _i64, _vp]),
-    'vqhip_image_metrics_workspace_bytes': (_i64, [_i64, _i64, _i64, _i64]),
-    'vqhip_image_metrics': (_i32, [_vp, _i32, _i32, _vp, _i32, _i32, _i64, _i64, _i64, _i64, _i32, _f64, _f64, _vp, _i64, _vp, _vp,
-                                   _vp, _vp]),
-    'vqhip_entropy_workspace_bytes': (_i64, [_i64, _i64]),
-    'vqhip_entropy_rows': (_i32, [_vp, _i64, _i64, _f32, _vp, _vp, _vp, _i32, _vp, _i64, _vp]),
-    'vqhip_entropy_finish': (_i32, [_vp, _vp, _vp, _i64, _i64, _vp, _vp, _vp, _vp]),
-    'vqhip_entropy_grad': (_i32, [_vp, _i64, _i64, _f32, _vp, _vp, _vp, _f32, _vp, _i32, _vp, _vp, _i32, _vp, _i64, _vp]),
-    'vqhip_col_multinomial_workspace_bytes': (_i64, [_i64, _i64, _i64]),
-    'vqhip_col_multinomial_max': (_i32, [_vp, _i64, _i64, _i64, _i64, _vp, _i64, _vp]),
-    'vqhip_col_multinomial_mass': (_i32, [_vp, _i64, _i64, _i64, _i64, _vp, _i64, _vp]),
-    'vqhip_col_multinomial_pick': (_i32, [_vp, _i64, _i64, _i64, _vp, _i64, _vp, _vp]),
-    'vqhip_col_multinomial_resolve': (_i32, [_vp, _i64, _i64, _i64, _i64, _vp, _i64, _vp, _vp]),
-    'vqhip_scatter_add_rows': (_i32, [_vp, _vp, _i64, _i64, _i32, _vp, _vp]),
-    'vqhip_vqkd_update': (_i32, [_vp, _vp, _vp, _i64, _i32, _f32, _i32, _vp]),
-    'vqhip_cvq_update': (_i32, [_vp, _vp, _vp, _i64, _vp, _vp, _i64, _i32, _f32, _f32, _i32, _vp]),
-    'vqhip_gather_rows': (_i32, [_vp, _i32, _vp, _i64, _i32, _vp, _vp]),
-    'vqhip_diff': (_i32, [_vp, _i32, _vp, _i32, _i64, _f32, _vp, _vp, _vp, _vp]),
-    'vqhip_vq_backward': (_i32, [_vp, _i32, _vp, _vp, _i64, _i32, _vp, _vp, _vp, _vp, _vp, _vp]),
-    'vqhip_vq_backward_ex': (_i32, [_vp, _i32, _vp, _vp, _i64, _i32, _vp, _vp, _vp, _vp, _f32, _vp, _vp, _vp]),
-    'vqhip_vq_backward_map': (_i32, [_vp, _i32, _vp, _vp, _i64, _i64, _i32, _vp, _vp, _vp, _f32, _vp, _i32, _vp]),
-    'vqhip_ste': (_i32, [_vp, _i32, _vp, _i64, _vp, _vp]),
-    'vqhip_normalize_rows_bwd': (_i32, [_vp, _i32, _vp, _i64, _i32, _f32, _vp, _vp]),
-    'vqhip_transpose': (_i32, [_vp, _vp, _i32, _i64, _i32, _i32, _vp]),
-    'vqhip_codebook_metrics': (_i32, [_vp, _i64, _vp, _vp]),
-    'vqhip_argmin_stats': (_i32, [_vp, _vp, _vp]),
-    'vqhip_cvq_step': (_i32, [_vp, _vp, _vp, _vp, _vp, _i64, _vp, _i32, _vp, _i64, _i32, _f32, _f32, _vp]),
-    'vqhip_cvq_decay': (_i32, [_vp, _i64, _f32, _f32, _vp, _vp]),
-    'vqhip_cvq_update_rows': (_i32, [_vp, _vp, _vp, _vp, _i64, _i64, _i32, _f32, _f32, _vp]),
-    'vqhip_pack_floats': (_i64, [_i64, _i64, _i32]),
-    'vqhip_pack_counts': (_i32, [_vp, _i32, _i64, _i64, _vp, _vp]),
-    'vqhip_unpack_counts': (_i32, [_vp, _i64, _vp, _vp]),
-    'vqhip_cvq_rows': (_i32, [_vp, _i64, _f32, _f32, _vp, _vp, _vp, _vp]),
-    'vqhip_col_rows_workspace_bytes': (_i64, [_i64, _i64, _i32]),
-    'vqhip_col_argmin_rows': (_i32, [_vp, _i32, _vp, _vp, _vp, _i64, _i64, _i64, _i32, _i32, _vp, _vp, _i64, _vp]),
-    'vqhip_cvq_pack': (_i32, [_vp, _i64, _vp, _i32, _vp, _vp, _i64, _i64, _i32, _vp, _vp]),
-    'vqhip_cvq_forward_ws_bytes': (_i64, [_i64, _i64, _i32, _i64]),
-    'vqhip_cvq_forward': (_i32, [ctypes.POINTER(CvqForwardArgs), _vp]),
-    'vqhip_vqkd_forward_ws_bytes': (_i64, [_i64, _i64, _i32]),
-    'vqhip_vqkd_forward': (_i32, [ctypes.POINTER(VqkdForwardArgs), _vp]),
-    'vqhip_vq_forward': (_i32, [ctypes.POINTER(VqForwardArgs), _vp]),
-    'vqhip_vqkd_backward': (_i32, [_vp, _i32, _vp, _vp, _vp, _i64, _i32, _vp, _vp, _vp, _vp]),
-    'vqhip_cvq_apply': (_i32, [_vp, _vp, _vp, _vp, _vp, _i64, _vp, _i32, _vp, _vp, _i32, _vp, _i64, _i64, _i32, _f32, _f32, _vp]),
-    'vqhip_cvq_col_keys': (_i32, [_vp, _i32, _vp, _vp, _vp, _i64, _vp, _i64, _i64, _i32, _i32, _i32, _vp, _vp]),
-    'vqhip_cvq_pack_sync': (_i32, [_vp, _i64, _vp, _i32, _vp, _vp, _i64, _i32, _i64, _i32, _vp, _vp]),
-    'vqhip_allreduce_min_i64': (_i32, [_vp, _i64, _vp, _vp]),
-    'vqhip_order_workspace_bytes': (_i64, [_i64, _i64]),
-    'vqhip_token_order': (_i32, [_vp, _i64, _i64, _vp, _vp, _vp, _vp, _i64, _vp]),
-    'vqhip_segsum_workspace_bytes': (_i64, [_i64, _i32]),
-    'vqhip_segsum_rows': (_i32, [_vp, _vp, _vp, _vp, _i64, _i64, _i32, _vp, _vp, _i64, _vp]),
-    'vqhip_vq_backward_w_ordered': (_i32, [_vp, _i32, _vp, _vp, _vp, _vp, _i64, _i64, _i32, _vp, _vp, _vp, _i64, _vp]),
-    'vqhip_debug_proposal_scores': (_i32, [_vp, _i32, _vp, _i64, _i64, _i32, _i32, _vp, _vp, _vp, _vp, _i64, _vp]),
-    'vqhip_rccl_load': (_i32, [ctypes.c_char_p]),
-    'vqhip_rccl_unique_id': (_i32, [_vp]),
-    'vqhip_rccl_comm_init': (_i32, [ctypes.POINTER(_vp), _i32, _vp, _i32]),
-    'vqhip_rccl_comm_destroy': (_i32, [_vp]),
-    'vqhip_allreduce_packed': (_i32, [_vp, _i64, _vp, _vp]),
-    'vqhip_profile_enable': (_i32, [_i32]),
-    'vqhip_set_tuning': (_i32, [_i32, _i32]),
-    'vqhip_profile_collect': (_i32, [ctypes.POINTER(ctypes.c_double), ctypes.POINTER(ctypes.c_int64)]),
-}
-
-_lib = None
-
 
 class VqhipError(RuntimeError):
     pass
+
+
+HEADER_PATH = os.path.join(_HERE, os.pardir, 'include', 'vqhip.h')
+# the header's typedef names -> their ctypes layouts above (the only structs a prototype may point to)
+STRUCTS = {'vqhip_cvq_forward_t': CvqForwardArgs, 'vqhip_vqkd_forward_t': VqkdForwardArgs, 'vqhip_vq_forward_t': VqForwardArgs,
+           'vqhip_fsq_t': FsqConstants, 'vqhip_sample_cut_t': SampleCut}
+_DEVICE_STRUCTS = {'vqhip_sample_cut_t'}   # an array the kernel writes on the DEVICE: callers pass its address, as for any buffer
+_SCALARS = {'int': _i32, 'int32_t': _i32, 'int64_t': _i64, 'float': _f32, 'double': _f64}
+
+
+def _ctype(c_type: str, fn: str):
+    """The ctypes type of one parameter or return type of a prototype: the scalars above, ``const char *``, a pointer to one
+    of STRUCTS, any other pointer as c_void_p.  Anything else is refused by name: at import, not at a launch."""
+    t = re.sub(r'\bconst\b|\s+', '', c_type)
+    if t in _SCALARS:
+        return _SCALARS[t]
+    if t == 'char*':
+        return ctypes.c_char_p
+    if t.endswith('*') and t[:-1] in STRUCTS:
+        return _vp if t[:-1] in _DEVICE_STRUCTS else ctypes.POINTER(STRUCTS[t[:-1]])
+    if t.endswith('*') and not re.fullmatch(r'vqhip_\w+_t\*', t):
+        return _vp
+    raise VqhipError(f'include/vqhip.h: {fn}: no ctypes rule for the type "{" ".join(c_type.split())}"')
+
+
+def parse_header(text: str) -> dict:
+    """name -> (restype, [argtypes]) of every ``ret vqhip_name(params);`` in the text of a C header."""
+    text = re.sub(r'/\*.*?\*/|//[^\n]*', ' ', text.replace('\\\n', ' '), flags=re.S)
+    text = re.sub(r'(?m)^[ \t]*#.*$', '', text)
+    out = {}
+    for ret, name, params in re.findall(r'([A-Za-z_][\w\s*]*?)\b(vqhip_[a-z0-9_]+)\s*\(([^()]*)\)\s*;', text):
+        params = [] if params.strip() == 'void' else [p.strip() for p in params.split(',')]
+        # a parameter is its type and then its name
+        out[name] = (_ctype(ret, name), [_ctype(re.sub(r'(?<=[\s*])\w+$', '', p), name) for p in params])
+    unread = set(re.findall(r'\b(vqhip_[a-z0-9_]+)\s*\(', text)) - set(out)
+    if unread:
+        raise VqhipError(f'include/vqhip.h: not read as prototypes: {sorted(unread)}')
+    return out
+
+
+# name -> (restype, [argtypes]): derived from the prototypes of include/vqhip.h, which is the only place they are written
+with open(HEADER_PATH) as _f:
+    SIGNATURES = parse_header(_f.read())
+
+_lib = None
 
 
 def build(verbose: bool = False) -> str:
