@@ -26,7 +26,13 @@
  *   ordered sums         K <= 32768, D % 4 == 0, ceil(N/1024) * K < 2^31 (vqhip_token_order and the two sums built on it)
  *   packed exchange      <= 256 ranks (count pieces stay exact in fp32), per-rank counts < 2^31, token count < 2^48
  *   vqhip_transpose      B <= 65535 per launch
- *   alignment            every buffer pointer 16-byte aligned (hipMalloc / torch allocations are); rows dense, no padding
+ *   alignment            every buffer pointer 16-byte aligned (hipMalloc / torch allocations are); rows dense, no padding.
+ *                        The entry points that state "element alignment only" below (sampler, token cross-entropy, cosine
+ *                        embedding, LPIPS, bias-activation / FIR, GroupNorm, the ViT row ops, image metrics) mean it for every
+ *                        pointer they take except `ws`: the small vectors are read and written element by element (u, targets,
+ *                        weight, lse, g, weight_sum, stats, seed, g_out, bias, gamma, beta; tokens, cut, loss, hit, out, value,
+ *                        the fp32 column sums), and an output tensor needs the alignment of its element type as an input does:
+ *                        no result bit depends on an address.  Workspaces keep the 16 bytes.
  *   device               all pointers belong to the device `stream` was created on, which is the current HIP device
  */
 #ifndef VQHIP_H_

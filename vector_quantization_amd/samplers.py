@@ -10,6 +10,8 @@ composition written with torch ops otherwise (CPU tensors among them); the decis
 Randomness: the fused draw consumes one uniform per output row.  They come from the device's default generator in blocks of
 ``UNIFORM_BLOCK`` steps (``torch.rand(256, Ro)``), kept in the module and refilled when used up or when the number of rows
 changes, so a step is one launch and a seeded run repeats itself.  ``memo['u']`` (fp32 [Ro]), if present, is used instead.
+Inside a graph capture (``torch.cuda.graph``) the block is left alone and ``torch.rand(Ro)`` is captured with the launch, so
+every replay draws new uniforms; a static ``memo['u']`` the caller refills between replays works as in eager mode.
 The torch route draws with ``multinomial`` like the reference, or by the same inverse CDF when ``memo['u']`` is given.
 """
 from __future__ import annotations
@@ -79,6 +81,10 @@ class _Sampler(nn.Module):
         u = memo.get('u') if hasattr(memo, 'get') else None
         if u is not None:
             return u.to(device, torch.float32).reshape(-1).contiguous()
+        if device.type == 'cuda' and torch.cuda.is_current_stream_capturing():
+            # a row of the module's block would be baked into the graph and every replay would draw from the same uniforms:
+            # draw inside the capture, where torch's generator hands each replay its own Philox offset
+            return torch.rand(Ro, device=device, dtype=torch.float32)
         block = getattr(self, '_u_block', None)
         if block is None or block.shape[1] != Ro or block.device != device or self._u_next >= block.shape[0]:
             block = torch.rand(UNIFORM_BLOCK, Ro, device=device, dtype=torch.float32)
