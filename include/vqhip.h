@@ -696,7 +696,7 @@ int vqhip_fir4_bwd(const void *g /* [B, C, OH, OW] */, int dtype, int layout, in
                    int py1, int px0, int px1, const void *x /* [B, C, H, W], or NULL */, const float *bias /* with x */,
                    void *gx /* [B, C, H, W] */, float *gbias /* [C], with x */, float *ws, int64_t ws_bytes, void *stream);
 
-/* ---- GroupNorm with an optional fused SiLU, forward and backward ----------------------------------------------------------------
+/* ---- GroupNorm / BatchNorm with an optional fused SiLU / LeakyReLU, forward and backward ----------------------------------------------------------------
  * The step in front of every convolution of VQGANEncoder / VQGANDecoder (vq/algorithms/vqgan/autoencoder.py: GroupNorm(32, C, 1e-6)
  * followed by SiLU; GroupNorm alone in Attention).  No copy, no atomics, no memset, no allocation and no synchronisation.  One launch
  * where a group fits one workgroup (n <= 8192), two otherwise; the backward adds the two launches of the dgamma / dbeta second stage.
@@ -721,8 +721,8 @@ int vqhip_fir4_bwd(const void *g /* [B, C, OH, OW] */, int dtype, int layout, in
  *   S = ceil(n / 8192) workgroups per group leave partials in ws; a second launch combines them and writes the result (the
  *   configs' first layer at B = 8 has 256 groups of 262144 values: 8192 workgroups instead of 256).
  * SHAPES AND LIMITS (VQHIP_EINVAL before any HIP call, and no launch)  dtype one of F32 / BF16 / F16; layout one of ROWS / MAP;
- *   B, C, P, G >= 1; C a multiple of G; B, C, P < 2^31; B C P no overflow of int64; n < 2^31; B G S < 2^31; act 0 or 1; eps >= 0
- *   and finite; every pointer required; ws_bytes >= vqhip_group_norm_ws_bytes(..) (-1 for sizes the calls refuse), in both calls.
+ *   B, C, P, G >= 1 (or G == VQHIP_GN_BATCH: BATCH STATISTICS below); C a multiple of G; B, C, P < 2^31; B C P no overflow of
+ *   int64; n < 2^31; B G S < 2^31; act 0 or 1 (with VQHIP_GN_BATCH also 2: LEAKY RELU below); eps >= 0 and finite; every pointer required; ws_bytes >= vqhip_group_norm_ws_bytes(..) (-1 for sizes the calls refuse), in both calls.
  * ERROR BOUND  against the exact value of the definition on the converted inputs; u0 = VQHIP_GN_U = 2^-24 (1 + 2^-9); first order
  *   in u0 except where a square is written; no overflow in fp32 and no underflow of exp(-u).  All quantities are magnitudes.
  *     N = VQHIP_GN_CHAIN(n) = n / 2^21 + 56 bounds the roundings a value passes into a group's sum: 32 in its thread, 6 in the
@@ -742,7 +742,46 @@ int vqhip_fir4_bwd(const void *g /* [B, C, OH, OW] */, int dtype, int layout, in
  *     dgamma[c]: (M + 2) u0 sum(gu xh) + sum(E_gu xh + gu E_xh), dbeta[c]: M u0 sum(gu) + sum(E_gu), with E_gu = g E_d + u0 gu and
  *       M = VQHIP_SG2_GBIAS_CHAIN(slabs), slabs = B S (at most 32 + 8 additions in the first launch, the second stage above).
  *     the store: VQHIP_SG2_STORE_U(dtype) on top, as for the StyleGAN2 ops.
- *   A measurement beyond these bounds inside the range means the kernel or this derivation is wrong. */
+ *   A measurement beyond these bounds inside the range means the kernel or this derivation is wrong.
+ *
+ * LEAKY RELU  act == VQHIP_GN_ACT_LEAKY (2), valid with G == VQHIP_GN_BATCH only (with G >= 1 it stays VQHIP_EINVAL, as every
+ *   earlier version of this header answers it): y = u for u > 0, otherwise VQHIP_GN_LEAKY_SLOPE u (0.2, held as its
+ *   fp32 rounding); the backward's factor is d = 1 for u > 0, otherwise the slope, so u == 0 takes the slope as F.leaky_relu does.
+ *   The backward recomputes u from x and stats with the very instruction sequence of the forward (no contraction): both directions
+ *   agree on the branch.  Bound: E_y = E_u + 2 u0 y (the product and the rounding of the slope).  E_d = 0 wherever |u| > E_u;
+ *   within E_u of zero the branch of the exact u is undetermined, d may be either of the two values, and no bound on t, gx,
+ *   dgamma or dbeta is stated for such an element.
+ *
+ * BATCH STATISTICS  G == VQHIP_GN_BATCH (-2; G == 0 and G == -1 stay VQHIP_EINVAL, as every earlier version of this header answers
+ *   them): BatchNorm2d in training mode, the step between the convolutions of
+ *   PatchGANDiscriminator (vq/algorithms/vqgan/discriminators/: Conv2d -> BatchNorm2d -> LeakyReLU(0.2)).
+ *   DEFINITION  one group per channel, spanning all B images: n = B P.  mean, the biased var, rstd, xh, u and y as above with the
+ *     sums over (b, p) of channel c; stats is [C, 2]: stats[2 c] = mean, stats[2 c + 1] = rstd.  vqhip_group_norm_fwd also leaves
+ *     ws[c] = mean and ws[C + c] = M2 / (n - 1), the UNBIASED variance, for c < C: an output of the call, what the host's
+ *     running statistics take (no cancellation of 1 / rstd^2 - eps).  The rest of ws is scratch.
+ *       bwd    gu = g d;   dbeta[c] = sum gu;   dgamma[c] = sum gu xh;   gx = gamma[c] rstd (gu - dbeta / n - xh dgamma / n),
+ *              evaluated as rstd ((t - m1) - xh m2) with t = gu gamma[c], m1 = dbeta gamma[c] / n, m2 = dgamma gamma[c] / n.
+ *     The channel sums are the parameter gradients: there is no dgamma / dbeta second stage.  A NaN or an infinity in a channel
+ *     makes that channel's y NaN and touches no other channel.  A constant channel has var = 0 and y = act(beta) within the bound.
+ *   ORDER OF EVERY SUM  fixed by the shape and the dtype alone: the same inputs give the same bits of y, stats, the block, gx,
+ *     dgamma and dbeta, run to run.  No atomics, no memset, no allocation, no synchronisation.
+ *   LAUNCH SHAPE  MAP: a channel's B runs of P values are cut into chunks of 8192; S = ceil(n / 8192) workgroups per channel.
+ *     ROWS: a workgroup takes 8 PW adjacent channels (PW = the widest of 16 bytes, 8 bytes or one element that divides C) and a slab
+ *     of 1024 / PW positions; S = ceil(n PW / 1024).  S == 1 (MAP: n <= 8192; ROWS: n <= 1024 / PW): one launch.  S > 1: three -
+ *     the chunks' partials (n_c, mean_c, M2_c; backward: sum gu, sum gu xh; n_c is a function of the shape and is not stored) go to
+ *     ws; one workgroup per channel combines them in a fixed order, M2 = sum_c (M2_c + n_c (mean_c - mean)^2), and writes stats and
+ *     the block (backward: dgamma and dbeta, once); the last writes y (gx).  The configs' sites at B = 8, [8, 128, 64, 64],
+ *     [8, 256, 32, 32] and [8, 512, 31, 31], are 512, 256 and 512 workgroups in NCHW.
+ *   SHAPES AND LIMITS  as above with B G S read as C S (S of the 16-bit dtypes, the larger), and n >= 2: one value per channel is
+ *     VQHIP_EINVAL (torch raises in training).  vqhip_group_norm_ws_bytes(layout, B, C, P, VQHIP_GN_BATCH) >= 8 C covers every dtype.
+ *   ERROR BOUND  the one above with n = B P: every value's path into a sum stays within VQHIP_GN_CHAIN(n) roundings
+ *     (vqhip_group_norm_kernels.h counts them).  mean, rstd, xh, u, y, d, t, m1, m2 and gx as above (mean_grp = the channel's mean);
+ *     the block's mean within N u0 mabs, its variance within 2 VQHIP_GN_RHO(n, q) (var + eps) n / (n - 1) (rho halves the error
+ *     of M2 under the root; here it is whole);  dgamma[c]: (N + 2) u0 sum(gu xh) + sum(E_gu xh + gu E_xh), dbeta[c]: N u0 sum(gu) + sum(E_gu),
+ *     N = VQHIP_GN_CHAIN(n) in place of the second stage's M. */
+#define VQHIP_GN_BATCH (-2)               /* G: batch statistics, one group per channel over all images */
+#define VQHIP_GN_ACT_LEAKY 2              /* act: LeakyReLU(VQHIP_GN_LEAKY_SLOPE) */
+#define VQHIP_GN_LEAKY_SLOPE 0.2f
 #define VQHIP_GN_U (5.9604644775390625e-08 * 1.001953125)
 #define VQHIP_GN_CHAIN(n) ((double)((n) / 2097152 + 56))
 #define VQHIP_GN_Q(n, mabs, rstd) (VQHIP_GN_CHAIN(n) * VQHIP_GN_U * (double)(mabs) * (double)(rstd))

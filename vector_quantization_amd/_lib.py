@@ -190,6 +190,8 @@ def sg2_store_u(dtype: int) -> float:
 
 GN_U = SG2_U                               # VQHIP_GN_U
 GN_SMALL, GN_CHUNK = 2048, 8192            # a wave per group up to GN_SMALL values; beyond GN_CHUNK a group is split over workgroups
+GN_BATCH = -2                              # VQHIP_GN_BATCH: the G of batch statistics (one group per channel over all images)
+GN_ACT_LEAKY, GN_LEAKY_SLOPE = 2, 0.2      # VQHIP_GN_ACT_LEAKY, VQHIP_GN_LEAKY_SLOPE (the kernels hold the slope's fp32 rounding)
 
 
 def gn_chain(n: int) -> float:

@@ -700,6 +700,42 @@ static int gn_run(VqGnArgs a, bool rows, int T, bool bwd, int64_t slabs, float *
     return launch_sg2_reduce(a.ws_db, slabs, a.C, dbeta, s);
 }
 
+// batch statistics: one launch where a channel is one chunk; else the partials, their combination, the result
+template <int DT, int PW>
+static int launch_bn_one(const VqBnArgs &a, bool rows, bool bwd, unsigned grid, hipStream_t s) {
+    if (rows) {
+        if (bwd) bn_rows_bwd_kernel<DT, PW><<<grid, VQ_GN_THREADS, 0, s>>>(a);
+        else bn_rows_fwd_kernel<DT, PW><<<grid, VQ_GN_THREADS, 0, s>>>(a);
+    } else {
+        if (bwd) bn_map_bwd_kernel<DT, PW><<<grid, VQ_GN_THREADS, 0, s>>>(a);
+        else bn_map_fwd_kernel<DT, PW><<<grid, VQ_GN_THREADS, 0, s>>>(a);
+    }
+    VQ_CHECK_LAUNCH(bwd ? "bn_bwd_kernel" : "bn_fwd_kernel");
+    return VQHIP_OK;
+}
+
+template <int DT>
+static int launch_bn(const VqBnArgs &a, bool rows, int pw, bool bwd, unsigned grid, hipStream_t s) {
+    constexpr int W = SampleElem<DT>::W;
+    if (!rows || pw == W) return launch_bn_one<DT, W>(a, rows, bwd, grid, s);
+    if (W == 8 && pw == 4) return launch_bn_one<DT, 4>(a, rows, bwd, grid, s);
+    return launch_bn_one<DT, 1>(a, rows, bwd, grid, s);
+}
+
+template <int DT>
+static int bn_run(VqBnArgs a, bool rows, int pw, bool bwd, unsigned grid, hipStream_t s) {
+    if (a.S == 1) {
+        a.phase = VQ_GN_ALL;
+        return launch_bn<DT>(a, rows, pw, bwd, grid, s);
+    }
+    a.phase = VQ_GN_PART;
+    if (int rc = launch_bn<DT>(a, rows, pw, bwd, grid, s)) return rc;
+    bn_combine_kernel<<<(unsigned)a.C, VQ_GN_THREADS, 0, s>>>(a, bwd ? 1 : 0);
+    VQ_CHECK_LAUNCH("bn_combine_kernel");
+    a.phase = VQ_GN_APPLY;
+    return launch_bn<DT>(a, rows, pw, bwd, grid, s);
+}
+
 // ---- the row ops of the VQ-KD networks: the launches (vqhip_vit_kernels.h) ---------------------------------------------------------
 template <int XDT, int YDT, int PW>
 static int launch_ln_one(const VqLnArgs &a, bool bwd, hipStream_t s) {
@@ -1782,17 +1818,45 @@ int vqhip_fir4_bwd(const void *g, int dtype, int layout, int64_t B, int64_t C, i
 struct VqGnPlan {
     int64_t n, S, units, slabs, ws_floats;
     int T;
+    int pw;                                     // batch statistics: the piece (elements); units = workgroups of a launch
 };
+
+// the piece of the rows layout in batch mode: the widest of 16 bytes, 8 bytes or one element that divides C
+static int bn_rows_pw(int dtype, int64_t C) {
+    const int W = dtype == VQHIP_DTYPE_F32 ? 4 : 8;
+    return C % W == 0 ? W : (W == 8 && C % 4 == 0 ? 4 : 1);
+}
+
+// G == VQHIP_GN_BATCH, behind the clauses every mode shares: a channel over all images
+static int bn_plan(const char *what, int dtype, int layout, int64_t B, int64_t C, int64_t P, VqGnPlan *pl) {
+    const int64_t cap = 1ll << 31;
+    pl->n = B * P;
+    if (pl->n >= cap) return fail(VQHIP_EINVAL, what, "a channel must hold fewer than 2^31 values over the batch");
+    if (pl->n < 2) return fail(VQHIP_EINVAL, what, "batch statistics need more than one value per channel");
+    const bool rows = layout == VQHIP_LAYOUT_ROWS;
+    pl->pw = rows ? bn_rows_pw(dtype, C) : (dtype == VQHIP_DTYPE_F32 ? 4 : 8);
+    const int64_t chunk = rows ? 1024 / pl->pw : VQ_GN_CHUNK;
+    const int64_t chunk_ws = rows ? 1024 / bn_rows_pw(VQHIP_DTYPE_BF16, C) : VQ_GN_CHUNK;      // the workspace serves every dtype
+    pl->S = (pl->n + chunk - 1) / chunk;
+    const int64_t S_ws = (pl->n + chunk_ws - 1) / chunk_ws;
+    if (C * S_ws >= cap) return fail(VQHIP_EINVAL, what, "C * S is beyond one launch");
+    pl->units = (rows ? (C + VQ_BN_LX * pl->pw - 1) / (VQ_BN_LX * pl->pw) : C) * pl->S;
+    pl->slabs = 0; pl->T = VQ_GN_THREADS;
+    pl->ws_floats = 2 * C + 2 * C * S_ws;
+    return VQHIP_OK;
+}
 
 // what the three entry points refuse alike; on success the launch shape
 static int gn_plan(const char *what, int dtype, int layout, int64_t B, int64_t C, int64_t P, int64_t G, VqGnPlan *pl) {
     if (!vq_float_dtype(dtype)) return fail(VQHIP_EINVAL, what, "dtype");
     if (!vq_dense_layout(layout)) return fail(VQHIP_EINVAL, what, "layout");
-    if (B < 1 || C < 1 || P < 1 || G < 1) return fail(VQHIP_EINVAL, what, "B, C, P and G must be positive");
-    if (C % G != 0) return fail(VQHIP_EINVAL, what, "C must be a multiple of G");
+    if (B < 1 || C < 1 || P < 1 || (G < 1 && G != VQHIP_GN_BATCH)) return fail(VQHIP_EINVAL, what, "B, C and P must be positive, G positive or VQHIP_GN_BATCH");
+    if (G != VQHIP_GN_BATCH && C % G != 0) return fail(VQHIP_EINVAL, what, "C must be a multiple of G");
     const int64_t cap = 1ll << 31;
     if (B >= cap || C >= cap || P >= cap) return fail(VQHIP_EINVAL, what, "B, C and P must be below 2^31");
     if (B * C > INT64_MAX / P / 8) return fail(VQHIP_EINVAL, what, "B * C * P overflows");     // (8: bytes and the workspace's floats)
+    pl->pw = 0;
+    if (G == VQHIP_GN_BATCH) return bn_plan(what, dtype, layout, B, C, P, pl);
     pl->n = (C / G) * P;
     if (pl->n >= cap) return fail(VQHIP_EINVAL, what, "a group must hold fewer than 2^31 values");
     pl->T = pl->n <= VQ_GN_SMALL ? 64 : 256;
@@ -1806,8 +1870,14 @@ static int gn_plan(const char *what, int dtype, int layout, int64_t B, int64_t C
 
 int64_t vqhip_group_norm_ws_bytes(int layout, int64_t B, int64_t C, int64_t P, int64_t G) {
     VqGnPlan pl;
-    if (gn_plan("vqhip_group_norm_ws_bytes", VQHIP_DTYPE_F32, layout, B, C, P, G, &pl)) return -1;
+    if (gn_plan("vqhip_group_norm_ws_bytes", VQHIP_DTYPE_BF16, layout, B, C, P, G, &pl)) return -1;   // (batch mode: the dtype of the most chunks)
     return pl.ws_floats * (int64_t)sizeof(float);
+}
+
+static void bn_fill(VqBnArgs *a, const VqGnPlan &pl, int layout, int64_t B, int64_t C, int64_t P, float *ws) {
+    a->n = (uint32_t)pl.n; a->chunk = layout == VQHIP_LAYOUT_ROWS ? 1024u / (uint32_t)pl.pw : (uint32_t)VQ_GN_CHUNK;
+    a->B = (int)B; a->C = (int)C; a->P = (int)P; a->S = (int)pl.S;
+    a->mv = ws; a->part = ws + 2 * C;
 }
 
 static void gn_fill(VqGnArgs *a, const VqGnPlan &pl, int64_t B, int64_t C, int64_t P, int64_t G, float *ws) {
@@ -1820,10 +1890,19 @@ int vqhip_group_norm_fwd(const void *x, int dtype, int layout, int64_t B, int64_
                          const float *beta, float eps, int act, void *y, float *stats, float *ws, int64_t ws_bytes, void *stream) {
     VqGnPlan pl;
     if (int rc = gn_plan("vqhip_group_norm_fwd", dtype, layout, B, C, P, G, &pl)) return rc;
-    VQ_REQUIRE(act == 0 || act == 1, "vqhip_group_norm_fwd: act must be 0 (none) or 1 (SiLU)");
+    VQ_REQUIRE(act == 0 || act == 1 || (act == VQHIP_GN_ACT_LEAKY && G == VQHIP_GN_BATCH),
+               "vqhip_group_norm_fwd: act must be 0 (none) or 1 (SiLU), with batch statistics also 2 (LeakyReLU)");
     VQ_REQUIRE(eps >= 0.0f && eps < INFINITY, "vqhip_group_norm_fwd: eps must be finite and not negative");
     VQ_REQUIRE(x && gamma && beta && y && stats && ws, "vqhip_group_norm_fwd: x, gamma, beta, y, stats and ws are required");
     VQ_NEED("vqhip_group_norm_fwd: ws too small", ws_bytes, pl.ws_floats * (int64_t)sizeof(float));
+    if (G == VQHIP_GN_BATCH) {
+        VqBnArgs a = {};
+        bn_fill(&a, pl, layout, B, C, P, ws);
+        a.x = x; a.out = y; a.gamma = gamma; a.beta = beta; a.stats = stats; a.eps = eps; a.act = act;
+        return vq_with_dtype(dtype, [&](auto dt) {
+            return bn_run<decltype(dt)::value>(a, layout == VQHIP_LAYOUT_ROWS, pl.pw, false, (unsigned)pl.units, (hipStream_t)stream);
+        });
+    }
     VqGnArgs a = {};
     gn_fill(&a, pl, B, C, P, G, ws);
     a.x = x; a.out = y; a.gamma = gamma; a.beta = beta; a.stats = stats; a.eps = eps; a.act = act;
@@ -1837,10 +1916,20 @@ int vqhip_group_norm_bwd(const void *g, const void *x, int dtype, int layout, in
                          float *ws, int64_t ws_bytes, void *stream) {
     VqGnPlan pl;
     if (int rc = gn_plan("vqhip_group_norm_bwd", dtype, layout, B, C, P, G, &pl)) return rc;
-    VQ_REQUIRE(act == 0 || act == 1, "vqhip_group_norm_bwd: act must be 0 (none) or 1 (SiLU)");
+    VQ_REQUIRE(act == 0 || act == 1 || (act == VQHIP_GN_ACT_LEAKY && G == VQHIP_GN_BATCH),
+               "vqhip_group_norm_bwd: act must be 0 (none) or 1 (SiLU), with batch statistics also 2 (LeakyReLU)");
     VQ_REQUIRE(g && x && gamma && beta && stats && gx && dgamma && dbeta && ws,
                "vqhip_group_norm_bwd: g, x, gamma, beta, stats, gx, dgamma, dbeta and ws are required");
     VQ_NEED("vqhip_group_norm_bwd: ws too small", ws_bytes, pl.ws_floats * (int64_t)sizeof(float));
+    if (G == VQHIP_GN_BATCH) {
+        VqBnArgs a = {};
+        bn_fill(&a, pl, layout, B, C, P, ws);
+        a.x = x; a.g = g; a.out = gx; a.gamma = gamma; a.beta = beta; a.stats = const_cast<float *>(stats); a.act = act;
+        a.dgamma = dgamma; a.dbeta = dbeta;
+        return vq_with_dtype(dtype, [&](auto dt) {
+            return bn_run<decltype(dt)::value>(a, layout == VQHIP_LAYOUT_ROWS, pl.pw, true, (unsigned)pl.units, (hipStream_t)stream);
+        });
+    }
     VqGnArgs a = {};
     gn_fill(&a, pl, B, C, P, G, ws);
     a.x = x; a.g = g; a.out = gx; a.gamma = gamma; a.beta = beta; a.stats = const_cast<float *>(stats); a.act = act;

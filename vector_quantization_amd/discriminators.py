@@ -55,11 +55,17 @@ class BaseDiscriminator(nn.Module):
 @VQDiscriminatorRegistry.register_()
 class PatchGANDiscriminator(BaseDiscriminator):
     """The pix2pix patch discriminator: ``depth`` stride-2 convolutions, one stride-1, one to a single channel; batch norm on all but
-    the first and the last.  Module indices under ``_discriminator`` as in the reference, so its checkpoints load."""
+    the first and the last.  Module indices under ``_discriminator`` as in the reference, so its checkpoints load.
+
+    Route ``fused`` (``routes.patchgan_why``): every adjacent ``BatchNorm2d, LeakyReLU(0.2)`` pair in training mode is one
+    ``functional.batch_norm(..., act='leaky_relu')`` - the HIP kernels of include/vqhip.h with batch statistics, the same
+    parameters and buffers.  Route ``torch``, and any site the kernels refuse (eval mode, so ``R1GradientPenalty``): the modules
+    as they are.  The convolutions and the first layer's LeakyReLU stay with torch on both routes."""
 
     def __init__(self, *args, in_channels: int = 3, width: int = 64, depth: int = 3, kernel_size: int = 4, padding: int = 1,
-                 **kwargs) -> None:
+                 fused: bool = True, **kwargs) -> None:
         super().__init__(*args, **kwargs)
+        self.fused = fused
         mults = [1] + [min(2 ** n, 8) for n in range(1, depth + 1)]
         layers = [nn.Conv2d(in_channels, width, kernel_size, 2, padding), nn.LeakyReLU(0.2, True)]
         for n in range(1, depth + 1):
@@ -79,7 +85,28 @@ class PatchGANDiscriminator(BaseDiscriminator):
         return False
 
     def forward(self, image: torch.Tensor) -> torch.Tensor:
-        return self._discriminator(image)
+        from .quantizers import routes
+        self.last_route = route = routes.patchgan_why(self, image)
+        if route.name != 'fused':
+            return self._discriminator(image)
+        layers, x, k, refused, taken = list(self._discriminator), image, 0, [], 0
+        while k < len(layers):
+            m, act = layers[k], layers[k + 1] if k + 1 < len(layers) else None
+            if isinstance(m, nn.BatchNorm2d) and isinstance(act, nn.LeakyReLU):
+                site = routes.patchgan_why(m, x)
+                if site.name == 'fused' and act.negative_slope != NEGATIVE_SLOPE:
+                    site = routes.Route('torch', f'negative_slope={act.negative_slope}, the kernels hold {NEGATIVE_SLOPE}')
+                if site.name == 'fused':
+                    x = functional.batch_norm(x, m.running_mean, m.running_var, m.weight, m.bias, True, m.momentum, m.eps,
+                                              'leaky_relu', m.num_batches_tracked)
+                    k, taken = k + 2, taken + 1
+                    continue
+                refused.append(site.why)
+            x = m(x)
+            k += 1
+        if not taken and refused:
+            self.last_route = routes.Route('torch', refused[0])
+        return x
 
 
 class _Equalized(nn.Module):

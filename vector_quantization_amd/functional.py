@@ -586,11 +586,83 @@ def group_norm(x: torch.Tensor, num_groups: int, weight: torch.Tensor, bias: tor
     and memory format: one launch reads x and writes y (two where a group is split over workgroups), fp32 arithmetic whatever the
     dtype, gradients to x, weight and bias.  A CPU tensor, float64 or a layout that is neither NCHW-contiguous nor channels-last
     dense computes the same definition in torch."""
-    if act not in ops.GROUP_NORM_ACTS:
+    if act not in (None, 'silu'):                                               # ('leaky_relu' is fused behind batch statistics only)
         raise ValueError(f'group_norm: act={act!r} is neither None nor \'silu\'')
     if not x.is_cuda or ops.group_norm_refusal(x, num_groups):
         return group_norm_torch(x, num_groups, weight, bias, eps, act)
     return _GroupNorm.apply(x, weight, bias, int(num_groups), float(eps), act)
+
+
+# ---- BatchNorm2d (+ LeakyReLU) of PatchGANDiscriminator in training mode: two reads and one write forward; the backward recomputes
+#      the affine value and the branch from x and the saved [C, 2] statistics, so nothing activation-sized is kept besides x ----
+
+class _BatchNorm(Function):
+    """vqhip_group_norm_fwd / _bwd with batch statistics.  Outputs (y, mean, unbiased_var); the last two are the call's block, not
+    differentiable.  Nothing in a discriminator step differentiates it twice (R1GradientPenalty runs in eval mode, on the torch
+    route): the backward is once differentiable."""
+
+    @staticmethod
+    def forward(ctx, x, weight, bias, eps, act):
+        y, stats, mean, var = ops.batch_norm(x, weight, bias, eps, act)
+        ctx.save_for_backward(x, weight, bias, stats)
+        ctx.act = act
+        ctx.mark_non_differentiable(mean, var)
+        return y, mean, var
+
+    @staticmethod
+    @once_differentiable
+    def backward(ctx, g, _gmean, _gvar):
+        x, weight, bias, stats = ctx.saved_tensors
+        gx, dgamma, dbeta = ops.batch_norm_backward(g, x, stats, weight, bias, ctx.act)
+        return (gx if ctx.needs_input_grad[0] else None, dgamma.to(weight.dtype).view_as(weight) if ctx.needs_input_grad[1] else None,
+                dbeta.to(bias.dtype).view_as(bias) if ctx.needs_input_grad[2] else None, None, None)
+
+
+def batch_norm_torch(x: torch.Tensor, running_mean, running_var, weight, bias, training: bool = True, momentum=0.1, eps: float = 1e-5,
+                     act=None) -> torch.Tensor:
+    """The same definition with ``F.batch_norm`` and ``F.leaky_relu(., 0.2)``: eval mode, CPU tensors, float64, layouts that are not
+    dense, a module without running statistics or affine parameters.  Twice differentiable."""
+    y = torch.nn.functional.batch_norm(x, running_mean, running_var, weight, bias, training, momentum, eps)
+    return torch.nn.functional.leaky_relu(y, 0.2) if act == 'leaky_relu' else y
+
+
+def batch_norm_refusal(x: torch.Tensor, running_mean, running_var, weight, bias, training: bool, momentum) -> str:
+    """Why one batch-norm site goes to torch ('' if it does not): the clauses of ``routes.patchgan_why`` that belong to a site."""
+    if not training:
+        return 'eval mode: the running statistics normalise, there is no kernel for that'
+    if momentum is None:
+        return 'momentum=None: the cumulative average needs the counter on the host'
+    if running_mean is None or running_var is None:
+        return 'track_running_stats=False'
+    if weight is None or bias is None:
+        return 'affine=False'
+    return ('' if x.is_cuda else f'the activation is on device {x.device}, not on a GPU') or ops.group_norm_refusal(x, 0)
+
+
+def batch_norm(x: torch.Tensor, running_mean: torch.Tensor, running_var: torch.Tensor, weight: torch.Tensor, bias: torch.Tensor,
+               training: bool = True, momentum=0.1, eps: float = 1e-5, act=None, num_batches_tracked=None) -> torch.Tensor:
+    """``act(batch_norm(x))`` with ``act`` None or 'leaky_relu' (slope 0.2), of a [B, C, ...] activation in its dtype and memory
+    format, as ``nn.BatchNorm2d`` computes it: in training mode from the statistics of this batch, fp32 arithmetic whatever the
+    dtype, gradients to x, weight and bias (once differentiable); ``running_mean`` / ``running_var`` move by ``momentum`` towards the
+    batch's mean and unbiased variance in one ``torch._foreach_lerp_`` and ``num_batches_tracked`` (if given) grows by one - no
+    host synchronisation, so the step can be captured in a graph.  Whatever ``batch_norm_refusal`` names computes the same
+    definition in torch."""
+    if act not in (None, 'leaky_relu'):
+        raise ValueError(f'batch_norm: act={act!r} is neither None nor \'leaky_relu\'')
+    if batch_norm_refusal(x, running_mean, running_var, weight, bias, training, momentum):
+        if training and num_batches_tracked is not None:
+            num_batches_tracked.add_(1)
+        if momentum is None:                                                    # the cumulative average of nn.BatchNorm2d
+            if training and num_batches_tracked is None:
+                raise ValueError('batch_norm: momentum=None needs num_batches_tracked')
+            momentum = 1.0 / float(num_batches_tracked) if training else 0.0
+        return batch_norm_torch(x, running_mean, running_var, weight, bias, training, momentum, eps, act)
+    y, mean, var = _BatchNorm.apply(x, weight, bias, float(eps), act)
+    with torch.no_grad():
+        torch._foreach_lerp_([running_mean, running_var], [mean.to(running_mean.dtype), var.to(running_var.dtype)], float(momentum))
+        if num_batches_tracked is not None:
+            num_batches_tracked.add_(1)
+    return y
 
 
 # ---- the row ops of VQKDEncoder / VQKDDecoder: the residual add folded into the LayerNorm that follows it, and bias + GELU / tanh.

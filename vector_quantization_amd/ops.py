@@ -1242,33 +1242,40 @@ def fir4_backward(g: torch.Tensor, size, pad=2, down: int = 1, x: Optional[torch
 
 # ---- GroupNorm (+ SiLU) of the VQGAN encoder and decoder (vq/algorithms/vqgan/autoencoder.py) ---------------------------------
 
-GROUP_NORM_ACTS = {None: 0, 'silu': 1}
+GROUP_NORM_ACTS = {None: 0, 'silu': 1, 'leaky_relu': _lib.GN_ACT_LEAKY}      # 'leaky_relu': slope 0.2 (VQHIP_GN_LEAKY_SLOPE)
 
 
 def group_norm_refusal(x: torch.Tensor, num_groups: int) -> str:
     """Why vqhip_group_norm_* would refuse this activation ('' if they would not): the clauses of their LIMITS that depend on the
-    tensor's dtype, shape and strides."""
-    return float_dtype_refusal('the activation is', x) \
+    tensor's dtype, shape and strides.  ``num_groups=0`` is batch statistics (VQHIP_GN_BATCH at the ABI): one group per channel over
+    all images."""
+    why = float_dtype_refusal('the activation is', x) \
         or ('' if x.dim() >= 2 else f'the activation is {x.dim()}-D, not [B, C, ...]') \
-        or ('' if x.numel() else f'empty activation {tuple(x.shape)}') \
-        or ('' if num_groups >= 1 and x.shape[1] % num_groups == 0 else f'C={x.shape[1]} is no multiple of num_groups={num_groups}') \
-        or dense_refusal('the activation', x) \
-        or ('' if x.numel() // (x.shape[0] * num_groups) < (1 << 31) else
-            f'a group of {x.numel() // (x.shape[0] * num_groups)} values is outside 1 .. 2^31-1')
+        or ('' if x.numel() else f'empty activation {tuple(x.shape)}')
+    if why or num_groups != 0:
+        return why \
+            or ('' if num_groups >= 1 and x.shape[1] % num_groups == 0 else f'C={x.shape[1]} is no multiple of num_groups={num_groups}') \
+            or dense_refusal('the activation', x) \
+            or ('' if x.numel() // (x.shape[0] * num_groups) < (1 << 31) else
+                f'a group of {x.numel() // (x.shape[0] * num_groups)} values is outside 1 .. 2^31-1')
+    n = x.numel() // x.shape[1]
+    return dense_refusal('the activation', x) or ('' if 2 <= n < (1 << 31) else f'a channel of {n} values over the batch is outside 2 .. 2^31-1')
 
 
 def _gn_head(what: str, x: torch.Tensor, num_groups: int, weight: torch.Tensor, bias: torch.Tensor, act):
     _require_cuda(x, weight, bias)
     why = group_norm_refusal(x, num_groups)
     if not why and act not in GROUP_NORM_ACTS:
-        why = f'act={act!r} is neither None nor \'silu\''
+        why = f'act={act!r} is none of None, \'silu\', \'leaky_relu\''
+    if not why and act == 'leaky_relu' and num_groups != 0:
+        why = 'act=\'leaky_relu\' is fused behind batch statistics (num_groups=0) only'
     if not why and (weight.numel() != x.shape[1] or bias.numel() != x.shape[1]):
         why = f'weight and bias have {weight.numel()} and {bias.numel()} elements, not C={x.shape[1]}'
     _refuse(what, why)
     B, C = x.shape[:2]
     P = x.numel() // (B * C)
     layout = LAYOUTS[dense_layout(x)]
-    ws_bytes = _lib.lib().vqhip_group_norm_ws_bytes(layout, B, C, P, num_groups)
+    ws_bytes = _lib.lib().vqhip_group_norm_ws_bytes(layout, B, C, P, num_groups or _lib.GN_BATCH)
     if ws_bytes < 0:
         raise ValueError(f'{what}: {tuple(x.shape)} in {num_groups} groups is beyond the sizes of vqhip_group_norm_*')
     ws = torch.empty(ws_bytes // 4, dtype=torch.float32, device=x.device)
@@ -1279,14 +1286,20 @@ def _gn_head(what: str, x: torch.Tensor, num_groups: int, weight: torch.Tensor, 
 def group_norm(x: torch.Tensor, num_groups: int, weight: torch.Tensor, bias: torch.Tensor, eps: float = 1e-6, act=None):
     """vqhip_group_norm_fwd: ``(y, stats)`` for ``y = act(group_norm(x) * weight[c] + bias[c])`` of a [B, C, ...] activation read in
     place, in its dtype and memory format (NCHW or channels-last); ``act``: None or 'silu'.  ``stats`` [B, G, 2] fp32 holds each
-    group's mean and 1 / sqrt(var + eps), what the backward reads.  One launch, two where a group is split over workgroups."""
+    group's mean and 1 / sqrt(var + eps), what the backward reads.  One launch, two where a group is split over workgroups.
+    ``num_groups=0``: batch statistics, ``stats`` [C, 2], ``act`` also 'leaky_relu' (slope 0.2); ``batch_norm`` returns the
+    call's block of means and unbiased variances as well."""
+    return _group_norm(x, num_groups, weight, bias, eps, act)[:2]
+
+
+def _group_norm(x, num_groups, weight, bias, eps, act):
     dtype, layout, B, C, P, ws = _gn_head('group_norm', x, num_groups, weight, bias, act)
     w, b = _fp32_vector(weight), _fp32_vector(bias)
     y = torch.empty_like(x)
-    stats = torch.empty(B, num_groups, 2, dtype=torch.float32, device=x.device)
-    check(_lib.lib().vqhip_group_norm_fwd(_ptr(x), dtype, layout, B, C, P, num_groups, _ptr(w), _ptr(b), float(eps), GROUP_NORM_ACTS[act],
+    stats = torch.empty((B, num_groups, 2) if num_groups else (C, 2), dtype=torch.float32, device=x.device)
+    check(_lib.lib().vqhip_group_norm_fwd(_ptr(x), dtype, layout, B, C, P, num_groups or _lib.GN_BATCH, _ptr(w), _ptr(b), float(eps), GROUP_NORM_ACTS[act],
                                           _ptr(y), _ptr(stats), _ptr(ws), ws.numel() * 4, _stream()), 'vqhip_group_norm_fwd')
-    return y, stats
+    return y, stats, ws
 
 
 @_on_tensor_device
@@ -1299,17 +1312,34 @@ def group_norm_backward(g: torch.Tensor, x: torch.Tensor, stats: torch.Tensor, n
     _require_cuda(g, stats)
     if g.shape != x.shape or g.dtype != x.dtype:
         raise ValueError(f'group_norm_backward: g is {g.dtype} {tuple(g.shape)}, x {x.dtype} {tuple(x.shape)}')
-    if stats.dtype != torch.float32 or stats.numel() != B * num_groups * 2 or not stats.is_contiguous():
-        raise ValueError(f'group_norm_backward: stats must be the contiguous fp32 [{B}, {num_groups}, 2] of the forward')
+    if stats.dtype != torch.float32 or stats.numel() != (B * num_groups if num_groups else C) * 2 or not stats.is_contiguous():
+        raise ValueError(f'group_norm_backward: stats must be the contiguous fp32 '
+                         f'{[B, num_groups, 2] if num_groups else [C, 2]} of the forward')
     g = _dense_like(g, x)
     w, b = _fp32_vector(weight), _fp32_vector(bias)
     gx = torch.empty_like(x)
     dgamma = torch.empty(C, dtype=torch.float32, device=x.device)
     dbeta = torch.empty(C, dtype=torch.float32, device=x.device)
-    check(_lib.lib().vqhip_group_norm_bwd(_ptr(g), _ptr(x), dtype, layout, B, C, P, num_groups, _ptr(w), _ptr(b), _ptr(stats),
+    check(_lib.lib().vqhip_group_norm_bwd(_ptr(g), _ptr(x), dtype, layout, B, C, P, num_groups or _lib.GN_BATCH, _ptr(w), _ptr(b), _ptr(stats),
                                           GROUP_NORM_ACTS[act], _ptr(gx), _ptr(dgamma), _ptr(dbeta), _ptr(ws), ws.numel() * 4, _stream()),
           'vqhip_group_norm_bwd')
     return gx, dgamma, dbeta
+
+
+@_on_tensor_device
+def batch_norm(x: torch.Tensor, weight: torch.Tensor, bias: torch.Tensor, eps: float = 1e-5, act=None):
+    """vqhip_group_norm_fwd with G = VQHIP_GN_BATCH: ``(y, stats, mean, unbiased_var)`` for ``y = act(batch_norm(x) * weight[c] +
+    bias[c])`` with the statistics of this batch (training mode), of a [B, C, ...] activation read in place.  ``stats`` [C, 2] fp32
+    (mean, 1 / sqrt(var + eps)) is what the backward reads; ``mean`` and ``unbiased_var`` [C] are views of the call's workspace,
+    what the running statistics take.  One launch where a workgroup holds a channel, three otherwise."""
+    y, stats, ws = _group_norm(x, 0, weight, bias, eps, act)
+    C = x.shape[1]
+    return y, stats, ws[:C], ws[C:2 * C]
+
+
+def batch_norm_backward(g: torch.Tensor, x: torch.Tensor, stats: torch.Tensor, weight: torch.Tensor, bias: torch.Tensor, act=None):
+    """vqhip_group_norm_bwd with G = VQHIP_GN_BATCH: ``(gx, dgamma, dbeta)``; the channel sums are the parameter gradients."""
+    return group_norm_backward(g, x, stats, 0, weight, bias, act)
 
 
 # ---- the row ops of VQKDEncoder / VQKDDecoder (vq/algorithms/vqkd/autoencoder.py): add + LayerNorm, bias + GELU / tanh -------------

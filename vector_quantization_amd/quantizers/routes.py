@@ -16,6 +16,7 @@ shape, dtype, alignment, the probability buffer, the world size, train / eval). 
     cosine_embedding_why  fused | torch
     lpips_why             fused | torch
     stylegan2_why         fused | torch
+    patchgan_why          fused | torch
     group_norm_why        fused | torch
     vit_why               fused | torch
     multinomial_anchor_why  fused | matrix
@@ -541,6 +542,30 @@ def stylegan2_why(module, x: torch.Tensor) -> Route:
                 break
     why = why or ('' if x.is_cuda else f'the input is on device {x.device}, not on a GPU')
     why = why or ops.stylegan2_refusal(x)
+    return Route('torch', why) if why else Route('fused')
+
+
+def patchgan_why(module, x: torch.Tensor) -> Route:
+    """The ``BatchNorm2d -> LeakyReLU(0.2)`` sites of ``PatchGANDiscriminator``: the HIP kernels of ``functional.batch_norm`` on the
+    activations as they are (``fused``), or the modules themselves (``torch``), with the first clause that refused the kernels.
+    For the discriminator, on its input: ``fused=False`` on the module, a class that overrides ``forward``, a CPU tensor, float64
+    (or any dtype the kernels do not read), strides that are neither NCHW-contiguous nor channels-last dense.  For one
+    ``BatchNorm2d`` of it, on its own activation: eval mode (what ``R1GradientPenalty`` sets, whose ``create_graph=True`` so keeps
+    working through torch), ``momentum=None`` (the cumulative average needs the counter on the host),
+    ``track_running_stats=False``, ``affine=False``, one value per channel, and the tensor clauses again.  No shape is sent to
+    ``torch`` for speed: profiles/batch_norm.txt has the measurements."""
+    from .. import discriminators, functional
+    if isinstance(module, torch.nn.modules.batchnorm._BatchNorm):
+        why = functional.batch_norm_refusal(x, module.running_mean, module.running_var, module.weight, module.bias, module.training,
+                                            module.momentum)
+        return Route('torch', why) if why else Route('fused')
+    why = ''
+    if module is not None:
+        why = '' if getattr(module, 'fused', True) else 'fused=False'
+        if not why and isinstance(module, discriminators.PatchGANDiscriminator):
+            why = own(module, discriminators.PatchGANDiscriminator, 'forward')
+    why = why or ('' if x.is_cuda else f'the input is on device {x.device}, not on a GPU') \
+        or ops.float_dtype_refusal('the input is', x) or ops.dense_refusal('the input', x)
     return Route('torch', why) if why else Route('fused')
 
 
