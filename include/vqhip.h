@@ -818,6 +818,31 @@ int vqhip_group_norm_bwd(const void *g, const void *x, int dtype, int layout, in
  *       bwd    gx = g d, recomputed from x and bias (y is not kept);   dbias[c] = sum_r of the fp32 gx  (dbias == NULL: not formed)
  *   x, y, g and gx in the call's one dtype; bias and dbias fp32.  An element's result depends on that element alone: a NaN stays
  *   where it is.
+ * ADD + RMS NORM  the mode of the two add + layer norm calls with beta == NULL (fwd) / dbeta == NULL (bwd): the norms of
+ *   LlamaTransformer (transformers' LlamaRMSNorm), each with the residual add in front of it folded in.
+ *       fwd    s = round_to_x_dtype(x + res)  (res == NULL: s = x, sum_out is not written);   sum_out = s
+ *              ms = sum s^2 / D;   rstd = 1 / sqrt(ms + eps);   y = (s rstd) gamma[c]  in fp32, rounded once into y_dtype
+ *              stats[2 r] = 0, stats[2 r + 1] = rstd
+ *       bwd    xh = s rstd from the saved s and stats;   t = g gamma[c]
+ *              gx = rstd (t - xh mean_row(t xh)) + g_skip  (g_skip == NULL: nothing is added);   dgamma[c] = sum_r g xh
+ *   dbeta is not written, and the second half of ws is not touched (ws_bytes is held to the same size).  The two calls are
+ *   independent: no call sees both beta and dbeta, so a forward in one mode followed by a backward in the other is not refused - it
+ *   is the caller's to pair them (vector_quantization_amd/ops.py does).  The dtype table, the sum_out rule, the g_skip rule, the slab
+ *   workspace, the order of the sums, the limits on R and D and the launch shapes are the layer norm's.  A NaN in a row makes that
+ *   row's y (and gx) NaN; an infinity makes ms infinite and rstd = 0, so y is 0 at the row's finite elements and NaN at the infinite
+ *   one (gx: NaN); neither touches another row.  An all-zero row has ms = 0 and y = 0 (eps > 0).
+ *   transformers' LlamaRMSNorm rounds s rstd to the input dtype BEFORE the product with gamma where the stream is 16-bit; this mode
+ *   does not: it rounds once, at the end.  Under bf16 autocast the stream is fp32 and the two definitions coincide.
+ * SWIGLU  act == VQHIP_ROW_ACT_SWIGLU (3; 2 stays VQHIP_EINVAL, as every earlier version of this header answers it) of the two row
+ *   bias-activation calls: the gated MLP of LlamaTransformer behind ONE GEMM against cat(gate_proj.weight, up_proj.weight).
+ *   D is the OUTPUT width F.  x is [R, 2 F] dense, gate = x[:, :F], up = x[:, F:];  y and g are [R, F];  gx is [R, 2 F].
+ *       fwd    y = silu(gate) up,   silu(a) = a / (1 + exp(-a)) for a >= 0,  a exp(a) / (1 + exp(a)) for a < 0
+ *       bwd    sg = sigmoid(a), recomputed from x (y is not kept):   gx[:, :F] = g up sg (1 + a (1 - sg));   gx[:, F:] = g silu(a)
+ *   fp32 from the exactly converted inputs, each result rounded once.  Both directions evaluate ONE exponential per element,
+ *   e = expf(max(-|a|, -88)): expf sees [-88, 0] only, the range VQHIP_VIT_EXP_ULPS was measured over; sigmoid and 1 - sigmoid are
+ *   1 / (1 + e) and e / (1 + e) (a >= 0; exchanged for a < 0), so no subtraction cancels.  bias, dbias and ws must be NULL
+ *   (a model with mlp_bias=True takes the torch route).  An element's result depends on its own (gate, up) pair (and g) alone: a NaN
+ *   or an infinity stays in its element (backward: in the two elements of its pair).  Alignment is by element only.
  * ORDER OF EVERY SUM  fixed by the shape alone (vqhip_vit_kernels.h says who adds what): the same inputs give the same bits of
  *   every output, run to run.
  * LAUNCH SHAPE  add + layer norm, a piece = 8 elements where all tensors are 16-bit and D % 8 == 0, else 4 where D % 4 == 0, else 1:
@@ -826,13 +851,15 @@ int vqhip_group_norm_bwd(const void *g, const void *x, int dtype, int layout, in
  *   Row bias-activation: forward one launch over 16-byte pieces of the flat tensor, a thread per piece up to 8192 workgroups of
  *   256 threads = 2 097 152 pieces (8.4 M fp32 or 16.8 M 16-bit elements); beyond that the grid stays at 8192 workgroups and
  *   every thread strides through pieces q, q + 2 097 152, ..  Backward a workgroup per 256 rows x 64 pieces, column sums in ws
- *   [slabs, D], one launch of the second stage.
+ *   [slabs, D], one launch of the second stage.  SwiGLU, both directions: one launch over the 16-byte pieces of the flat [R, F]
+ *   side on the forward's grid; a piece that crosses a row end (F % 4 != 0, or F % 8 != 0 in a 16-bit dtype) goes element by element.
  * SHAPES AND LIMITS (VQHIP_EINVAL before any HIP call, and no launch)  1 <= R <= VQHIP_VIT_MAX_R = 2^24 (no launch of more than 2^32
  *   threads: the widest is 256 threads per row); 1 <= D <= VQHIP_VIT_MAX_D = 8192; R D < 2^31; a dtype
  *   combination outside the table; res != NULL with res_dtype != y_dtype; res without sum_out; eps negative or not finite; act not 0
  *   or 1; a NULL among x, gamma, beta, y, stats (fwd), g, s, gamma, stats, gx, dgamma, dbeta, ws (bwd), x, bias, y (act fwd), g, x, bias,
  *   gx (act bwd); dbias without ws; ws_bytes < 8 D vqhip_add_layer_norm_slabs(..) / 4 D vqhip_row_bias_act_slabs(..) (-1 for sizes
- *   the calls refuse).
+ *   the calls refuse).  RMS mode: beta (fwd) and dbeta (bwd) are NULL and every other pointer stays required.  SwiGLU:
+ *   R 2 D >= 2^31; a bias, a dbias or a ws that is not NULL; a NULL among x, y (fwd), g, x, gx (bwd).  act 2 is refused.
  * ERROR BOUND  against the exact value of the definition on the converted inputs (for the norm: on the rounded s); u0 = VQHIP_GN_U.
  *   add + layer norm: a row is a group of n = D of the group norm, act 0, summed by the same code, so its bounds hold as they stand:
  *     mean within VQHIP_GN_CHAIN(D) u0 mabs, rstd within VQHIP_GN_RHO(D, q) rstd, y within E_u, gx within E_gx; the addition of g_skip
@@ -856,12 +883,31 @@ int vqhip_group_norm_bwd(const void *g, const void *x, int dtype, int layout, in
  *                               VQHIP_ROW_TANH_GRAD_BOUND(y, d) = ((3 + 4 L_tanh) y^2 + |d|) u0
  *     gx = g d: |g| E_d + u0 |gx|.   dbias[c]: M u0 sum |gx| + sum E_gx, M = VQHIP_SG2_GBIAS_CHAIN(slabs), slabs = ceil(R / 256).
  *     Both y bounds carry VQHIP_VIT_TINY = 2^-148 absolute: a subnormal t loses up to half a subnormal ulp in t / 2 and in t c.
+ *   add + RMS norm: the layer norm's derivation with no mean, so q = 0 and every m1 term is absent; N = VQHIP_GN_CHAIN(D).
+ *     ms adds D non-negative terms of one product each: relative (N + 1) u0; half of that under the root, 3 u0 for the addition of
+ *     eps, the root and the division, and 3 u0 reserved for the products of xh and y:   rho = VQHIP_GN_RHO(D, 0) = (N / 2 + 8) u0.
+ *     rstd: within rho rstd.      xh: E_xh = rho |xh|.      y: E_y = |gamma| E_xh + 2 u0 |y|.
+ *     t = g gamma: E_t = 2 u0 |t|.   m2 = mean_row(t xh): E_2 = (N + 1) u0 mean_row(|t xh|) + mean_row(E_t |xh| + |t| E_xh).
+ *     gx: E_gx = rstd (E_t + |xh| E_2 + |m2| E_xh + 4 u0 (|t| + |xh m2|)) + rho |gx|;   with g_skip: E_gx' = E_gx + u0 |gx + g_skip|.
+ *     dgamma[c]: (M + 2) u0 sum |g xh| + sum (u0 |g xh| + |g| E_xh), M = VQHIP_SG2_GBIAS_CHAIN(slabs), slabs = ceil(R / 16).
+ *     (These are the group norm's E_u, E_gx and dgamma formulas evaluated at q = 0, beta = 0, m1 = 0, act 0.)
+ *   SwiGLU: L = VQHIP_VIT_EXP_ULPS, so e = expf(..) is within 2 L u0 e; den = 1 + e rounds once and e / (1 + e) <= 1 / 2:
+ *     relative (L + 1) u0.  a >= 0: s = a / den, (L + 2) u0 |s|.  a < 0: a e carries (2 L + 1) u0, the division one more: (3 L + 3) u0 |s|.
+ *       silu:  E_s = (3 L + 3) u0 |s|.        y = s up rounds once:        E_y = (3 L + 4) u0 |y|
+ *     sg and qc = 1 - sg are 1 / den or e / den: relative (3 L + 2) u0.  a qc: (3 L + 3) u0 |a| qc;  w = 1 + a qc rounds once; d = sg w
+ *     rounds once; sg |a| qc = |a sigmoid'(a)| <= 0.224:
+ *       d:     E_d = ((3 L + 3) |a| sg (1 - sg) + (3 L + 4) |d|) u0                                                   (absolute)
+ *       gx gate = (g up) d:  |g up| E_d + 2 u0 |gx|.        gx up = g s:  |g| E_s + u0 |gx|.
+ *     Underflow: where e, a e or a result is subnormal an absolute term takes the place of a relative one, VQHIP_VIT_TINY (1 + (1 + |a|) |f|)
+ *     with f = up (y), g up (gx gate), g (gx up): L + 1 subnormal ulps of s per unit of |a|, and half of one for the result itself.
+ *     |a| > 88: the held argument leaves e within exp(-88) < 2^-126 of exp(-|a|):  2^-126 (1 + |a|) |f| more, the same f.
  *   the store: VQHIP_SG2_STORE_U(dtype) on top, as for the StyleGAN2 ops.
  *   A measurement beyond these bounds inside the range means the kernel or this derivation is wrong. */
 #define VQHIP_VIT_MAX_D 8192
 #define VQHIP_VIT_MAX_R (1 << 24)
 #define VQHIP_ROW_ACT_GELU 0
 #define VQHIP_ROW_ACT_TANH 1
+#define VQHIP_ROW_ACT_SWIGLU 3            /* x = (gate | up) [R, 2 D]; 2 is not an activation */
 #define VQHIP_VIT_ERF_ULPS 3.02
 #define VQHIP_VIT_TANH_ULPS 2.82
 #define VQHIP_VIT_EXP_ULPS 1.79
@@ -872,13 +918,14 @@ int vqhip_group_norm_bwd(const void *g, const void *x, int dtype, int layout, in
 #define VQHIP_ROW_TANH_GRAD_BOUND(y, d) (((3.0 + 4.0 * VQHIP_VIT_TANH_ULPS) * (double)(y) * (double)(y) + (double)(d)) * VQHIP_GN_U)
 int64_t vqhip_add_layer_norm_slabs(int64_t R, int64_t D);                       /* -1 for sizes the calls refuse */
 int vqhip_add_layer_norm_fwd(const void *x, int x_dtype, const void *res /* or NULL */, int res_dtype, int64_t R, int64_t D,
-                             const float *gamma /* [D] */, const float *beta /* [D] */, float eps, void *sum_out /* with res */, void *y,
+                             const float *gamma /* [D] */, const float *beta /* [D], or NULL: RMS */, float eps, void *sum_out /* with res */, void *y,
                              int y_dtype, float *stats /* [R, 2] */, void *stream);
 int vqhip_add_layer_norm_bwd(const void *g, int g_dtype, const void *s, int s_dtype, const void *g_skip /* or NULL */, int64_t R, int64_t D,
-                             const float *gamma, const float *stats, void *gx, float *dgamma /* [D] */, float *dbeta /* [D] */, float *ws,
+                             const float *gamma, const float *stats, void *gx, float *dgamma /* [D] */, float *dbeta /* [D], or NULL: RMS */, float *ws,
                              int64_t ws_bytes, void *stream);
 int64_t vqhip_row_bias_act_slabs(int64_t R, int64_t D);                         /* -1 for sizes the calls refuse */
-int vqhip_row_bias_act_fwd(const void *x, int dtype, int64_t R, int64_t D, const float *bias /* [D] */, int act, void *y, void *stream);
+int vqhip_row_bias_act_fwd(const void *x, int dtype, int64_t R, int64_t D, const float *bias /* [D]; SwiGLU: NULL */, int act, void *y,
+                           void *stream);
 int vqhip_row_bias_act_bwd(const void *g, const void *x, int dtype, int64_t R, int64_t D, const float *bias, int act, void *gx,
                            float *dbias /* [D] or NULL */, float *ws, int64_t ws_bytes, void *stream);
 

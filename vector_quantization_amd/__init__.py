@@ -10,7 +10,7 @@ from .config import BuildPreHookMixin, Config, Registry, RegistryMeta
 from .registries import (AnchorRegistry, InitRegistry, ModelRegistry, VQITQuantizerCallbackRegistry,
                          VQITQuantizerDistanceRegistry, VQITQuantizerLossRegistry, VQITQuantizerRegistry,
                          VQDiscriminatorLossRegistry, VQDiscriminatorRegistry, VQGeneratorLossRegistry,
-                         VQDecoderRegistry, VQEncoderRegistry)
+                         VQDecoderRegistry, VQEncoderRegistry, VQSMSamplerRegistry, VQSMTransformerRegistry)
 from .image_losses import L1Loss, MSELoss, PSNRLoss, SSIMLoss
 from .distill_losses import CosineEmbeddingLoss
 from .perceptual_losses import LPIPSLoss
@@ -19,6 +19,7 @@ from .autoencoders import BaseDecoder, BaseEncoder, VQGANDecoder, VQGANEncoder
 from .vqkd_autoencoders import VQKDDecoder, VQKDEncoder
 from .gan_losses import NonSaturatingLoss, R1GradientPenalty, VQGANDiscriminatorLoss, VQGANGeneratorLoss
 from .sequence_losses import CausalTokenLoss, LabelSmoothingCrossEntropy, MaskedTokenLoss
+from .transformers import BaseTransformer, HFTransformer, LlamaTransformer
 from .utils import EMA, ema
 
 __all__ = [
@@ -29,6 +30,7 @@ __all__ = [
     'BaseDiscriminator', 'PatchGANDiscriminator', 'StyleGAN2Discriminator', 'VQGANGeneratorLoss', 'NonSaturatingLoss',
     'VQGANDiscriminatorLoss', 'R1GradientPenalty', 'VQDiscriminatorRegistry', 'VQGeneratorLossRegistry', 'VQDiscriminatorLossRegistry',
     'BaseEncoder', 'BaseDecoder', 'VQGANEncoder', 'VQGANDecoder', 'VQKDEncoder', 'VQKDDecoder', 'VQEncoderRegistry', 'VQDecoderRegistry',
+    'BaseTransformer', 'HFTransformer', 'LlamaTransformer', 'VQSMSamplerRegistry', 'VQSMTransformerRegistry',
 ]
 __version__ = '0.1.0'
 

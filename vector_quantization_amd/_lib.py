@@ -249,6 +249,8 @@ VIT_MAX_R = 1 << 24                        # VQHIP_VIT_MAX_R: their most rows (n
 ROW_ACT_GRID_PIECES = 8192 * 256           # 16-byte pieces the row bias-activation forward covers with a thread each; beyond: grid-stride
 LN_SLAB, ROW_ACT_SLAB = 16, 256            # rows per workgroup of the two backwards (the slabs of their column sums)
 ROW_ACT_GELU, ROW_ACT_TANH = 0, 1          # VQHIP_ROW_ACT_*
+ROW_ACT_SWIGLU = 3                         # VQHIP_ROW_ACT_SWIGLU: x = (gate | up) [R, 2 D]; 2 is not an activation
+SWIGLU_CLAMP = 88.0                        # the exponential of the SwiGLU mode sees max(-|a|, -88)
 # VQHIP_VIT_*_ULPS: twice the measured accuracy of the device erff / tanhf / expf (include/vqhip.h; profiles/vqkd_autoencoder.txt)
 VIT_ERF_ULPS, VIT_TANH_ULPS, VIT_EXP_ULPS = 3.02, 2.82, 1.79
 VIT_TINY = 2.0 ** -148                     # VQHIP_VIT_TINY
@@ -276,6 +278,46 @@ def row_act_grad_bound(act: int, y, d):
 def row_act_gx_bound(act: int, g, y, d, gx):
     """gx = g d: |g| E_d + u0 |gx|."""
     return g * row_act_grad_bound(act, y, d) + GN_U * gx
+
+
+def rms_y_bound(D: int, xh, gamma, y):
+    """E_y of the RMS mode of include/vqhip.h: the group norm's E_u at q = 0 (no mean) and beta = 0."""
+    return gn_u_bound(D, 0.0, xh, gamma, y)
+
+
+def rms_gx_bound(D: int, rstd, xh, t, m2, mean_txh, mean_e_txh, gx):
+    """E_gx of the RMS mode: the group norm's at q = 0 with every m1 term absent; E_t = 2 u0 |t|; mean_e_txh = the row's mean of
+    E_t |xh| + |t| E_xh."""
+    return gn_gx_bound(D, 0.0, rstd, xh, 2.0 * GN_U * t, t, 0.0, m2, 0.0, mean_txh, 0.0, mean_e_txh, gx)
+
+
+def swiglu_floor(a, f):
+    """The absolute terms of the SwiGLU bounds for a gate of magnitude a and a factor of magnitude f (up, g up or g): the
+    subnormal results, and the exponential's argument held at -88."""
+    held = 2.0 ** -126 * (1.0 + a) * f
+    return VIT_TINY * (1.0 + (1.0 + a) * f) + held * (a > SWIGLU_CLAMP)
+
+
+def swiglu_silu_bound(s):
+    """E_s of include/vqhip.h: silu(a) of magnitude s, relative part."""
+    return (3.0 * VIT_EXP_ULPS + 3.0) * GN_U * s
+
+
+def swiglu_bound(a, up, y):
+    """E_y of the SwiGLU mode: |kernel y - exact y| in fp32, before the store; magnitudes."""
+    return (3.0 * VIT_EXP_ULPS + 4.0) * GN_U * y + swiglu_floor(a, up)
+
+
+def swiglu_grad_bound(a, sg, d):
+    """E_d: the factor d = sg (1 + a (1 - sg)) of the gate's gradient, absolute; magnitudes, sg = sigmoid of the signed gate."""
+    return ((3.0 * VIT_EXP_ULPS + 3.0) * a * sg * (1.0 - sg) + (3.0 * VIT_EXP_ULPS + 4.0) * d) * GN_U
+
+
+def swiglu_gx_bounds(a, sg, d, s, g, up, gx_gate, gx_up):
+    """(E of gx[:, :F], E of gx[:, F:]) of the SwiGLU backward."""
+    gu = g * up
+    return (gu * swiglu_grad_bound(a, sg, d) + 2.0 * GN_U * gx_gate + swiglu_floor(a, gu),
+            g * swiglu_silu_bound(s) + GN_U * gx_up + swiglu_floor(a, g))
 
 
 STEP_BEFORE_EXCHANGE, STEP_AFTER_EXCHANGE, STEP_ALL, STEP_PACK_SYNC = 1, 2, 3, 4

@@ -737,27 +737,27 @@ static int bn_run(VqBnArgs a, bool rows, int pw, bool bwd, unsigned grid, hipStr
 }
 
 // ---- the row ops of the VQ-KD networks: the launches (vqhip_vit_kernels.h) ---------------------------------------------------------
-template <int XDT, int YDT, int PW>
+template <int XDT, int YDT, int PW, bool RMS>
 static int launch_ln_one(const VqLnArgs &a, bool bwd, hipStream_t s) {
     if (a.D <= VQ_GN_SMALL) {
-        if (bwd) ln_bwd_kernel<XDT, YDT, PW, 64><<<(unsigned)((a.R + VQ_LN_SLAB - 1) / VQ_LN_SLAB), VQ_LN_THREADS, 0, s>>>(a);
-        else ln_fwd_kernel<XDT, YDT, PW, 64><<<(unsigned)((a.R + 3) / 4), VQ_LN_THREADS, 0, s>>>(a);
+        if (bwd) ln_bwd_kernel<XDT, YDT, PW, 64, RMS><<<(unsigned)((a.R + VQ_LN_SLAB - 1) / VQ_LN_SLAB), VQ_LN_THREADS, 0, s>>>(a);
+        else ln_fwd_kernel<XDT, YDT, PW, 64, RMS><<<(unsigned)((a.R + 3) / 4), VQ_LN_THREADS, 0, s>>>(a);
     } else {
-        if (bwd) ln_bwd_kernel<XDT, YDT, PW, 256><<<(unsigned)((a.R + VQ_LN_SLAB - 1) / VQ_LN_SLAB), VQ_LN_THREADS, 0, s>>>(a);
-        else ln_fwd_kernel<XDT, YDT, PW, 256><<<(unsigned)a.R, VQ_LN_THREADS, 0, s>>>(a);
+        if (bwd) ln_bwd_kernel<XDT, YDT, PW, 256, RMS><<<(unsigned)((a.R + VQ_LN_SLAB - 1) / VQ_LN_SLAB), VQ_LN_THREADS, 0, s>>>(a);
+        else ln_fwd_kernel<XDT, YDT, PW, 256, RMS><<<(unsigned)a.R, VQ_LN_THREADS, 0, s>>>(a);
     }
     VQ_CHECK_LAUNCH(bwd ? "ln_bwd_kernel" : "ln_fwd_kernel");
     return VQHIP_OK;
 }
 
 // the piece: 16 bytes of the narrowest dtype where they divide the row, else four elements, else one
-template <int XDT, int YDT>
+template <int XDT, int YDT, bool RMS>
 static int launch_ln(const VqLnArgs &a, bool bwd, hipStream_t s) {
     if constexpr (XDT == YDT || XDT == VQHIP_DTYPE_F32) {
         if constexpr (XDT != VQHIP_DTYPE_F32)
-            if (a.D % 8 == 0) return launch_ln_one<XDT, YDT, 8>(a, bwd, s);
-        if (a.D % 4 == 0) return launch_ln_one<XDT, YDT, 4>(a, bwd, s);
-        return launch_ln_one<XDT, YDT, 1>(a, bwd, s);
+            if (a.D % 8 == 0) return launch_ln_one<XDT, YDT, 8, RMS>(a, bwd, s);
+        if (a.D % 4 == 0) return launch_ln_one<XDT, YDT, 4, RMS>(a, bwd, s);
+        return launch_ln_one<XDT, YDT, 1, RMS>(a, bwd, s);
     } else {
         return fail(VQHIP_EINVAL, "add_layer_norm", "no kernel of this dtype combination");
     }
@@ -765,6 +765,15 @@ static int launch_ln(const VqLnArgs &a, bool bwd, hipStream_t s) {
 
 template <int DT>
 static int launch_row_act(const VqRowActArgs &a, int act, bool bwd, int64_t slabs, float *dbias, hipStream_t s) {
+    if (act == VQHIP_ROW_ACT_SWIGLU) {                                          // both directions: the forward's grid over the [R, F] side
+        const int64_t pieces = (a.R * a.D + SampleElem<DT>::W - 1) / SampleElem<DT>::W;
+        const int64_t blocks = (pieces + VQ_SG2_THREADS - 1) / VQ_SG2_THREADS;
+        const unsigned grid = (unsigned)(blocks < 8192 ? blocks : 8192);
+        if (bwd) swiglu_kernel<DT, true><<<grid, VQ_SG2_THREADS, 0, s>>>(a);
+        else swiglu_kernel<DT, false><<<grid, VQ_SG2_THREADS, 0, s>>>(a);
+        VQ_CHECK_LAUNCH("swiglu_kernel");
+        return VQHIP_OK;
+    }
     if (!bwd) {
         const int64_t pieces = (a.R * a.D + SampleElem<DT>::W - 1) / SampleElem<DT>::W;
         const int64_t blocks = (pieces + VQ_SG2_THREADS - 1) / VQ_SG2_THREADS;
@@ -1962,12 +1971,13 @@ int vqhip_add_layer_norm_fwd(const void *x, int x_dtype, const void *res, int re
     VQ_REQUIRE(vit_ln_pair(x_dtype, y_dtype), "vqhip_add_layer_norm_fwd: (x, y) must be one float dtype, or fp32 x with a bf16 or fp16 y");
     VQ_REQUIRE(!res || res_dtype == y_dtype, "vqhip_add_layer_norm_fwd: res must have y's dtype");
     VQ_REQUIRE(eps >= 0.0f && eps < INFINITY, "vqhip_add_layer_norm_fwd: eps must be finite and not negative");
-    VQ_REQUIRE(x && gamma && beta && y && stats, "vqhip_add_layer_norm_fwd: x, gamma, beta, y and stats are required");
+    VQ_REQUIRE(x && gamma && y && stats, "vqhip_add_layer_norm_fwd: x, gamma, y and stats are required (beta == NULL: RMS mode)");
     VQ_REQUIRE(!res || sum_out, "vqhip_add_layer_norm_fwd: res needs sum_out");
     VqLnArgs a = {};
     a.x = x; a.res = res; a.sum_out = sum_out; a.out = y; a.gamma = gamma; a.beta = beta; a.stats = stats; a.R = R; a.D = (int)D; a.eps = eps;
     return vq_with_dtype(x_dtype, [&](auto dx) { return vq_with_dtype(y_dtype, [&](auto dy) {
-        return launch_ln<decltype(dx)::value, decltype(dy)::value>(a, false, (hipStream_t)stream);
+        if (!beta) return launch_ln<decltype(dx)::value, decltype(dy)::value, true>(a, false, (hipStream_t)stream);
+        return launch_ln<decltype(dx)::value, decltype(dy)::value, false>(a, false, (hipStream_t)stream);
     }); });
 }
 
@@ -1976,19 +1986,27 @@ int vqhip_add_layer_norm_bwd(const void *g, int g_dtype, const void *s, int s_dt
                              void *stream) {
     if (int rc = vit_rows("vqhip_add_layer_norm_bwd", R, D)) return rc;
     VQ_REQUIRE(vit_ln_pair(s_dtype, g_dtype), "vqhip_add_layer_norm_bwd: (s, g) must be one float dtype, or fp32 s with a bf16 or fp16 g");
-    VQ_REQUIRE(g && s && gamma && stats && gx && dgamma && dbeta && ws,
-               "vqhip_add_layer_norm_bwd: g, s, gamma, stats, gx, dgamma, dbeta and ws are required");
+    VQ_REQUIRE(g && s && gamma && stats && gx && dgamma && ws,
+               "vqhip_add_layer_norm_bwd: g, s, gamma, stats, gx, dgamma and ws are required (dbeta == NULL: RMS mode)");
     const int64_t slabs = (R + VQ_LN_SLAB - 1) / VQ_LN_SLAB;
     VQ_NEED("vqhip_add_layer_norm_bwd: ws too small", ws_bytes, 2 * slabs * D * (int64_t)sizeof(float));
     VqLnArgs a = {};
     a.x = s; a.res = g_skip; a.g = g; a.out = gx; a.gamma = gamma; a.stats = const_cast<float *>(stats); a.R = R; a.D = (int)D;
-    a.ws_dg = ws; a.ws_db = ws + slabs * D;
+    a.ws_dg = ws; a.ws_db = ws + slabs * D;                                     // (RMS mode leaves the second half alone)
     const hipStream_t st = (hipStream_t)stream;
     if (int rc = vq_with_dtype(s_dtype, [&](auto dx) { return vq_with_dtype(g_dtype, [&](auto dy) {
-            return launch_ln<decltype(dx)::value, decltype(dy)::value>(a, true, st);
+            if (!dbeta) return launch_ln<decltype(dx)::value, decltype(dy)::value, true>(a, true, st);
+            return launch_ln<decltype(dx)::value, decltype(dy)::value, false>(a, true, st);
         }); })) return rc;
     if (int rc = launch_sg2_reduce(a.ws_dg, slabs, a.D, dgamma, st)) return rc;
-    return launch_sg2_reduce(a.ws_db, slabs, a.D, dbeta, st);
+    return dbeta ? launch_sg2_reduce(a.ws_db, slabs, a.D, dbeta, st) : VQHIP_OK;
+}
+
+// what act == VQHIP_ROW_ACT_SWIGLU refuses on top of vit_rows: x is [R, 2 D] and there is no bias
+static int swiglu_rows(const char *what, int64_t R, int64_t D, const void *bias, const void *dbias, const void *ws) {
+    if (R > ((1ll << 31) - 1) / (2 * D)) return fail(VQHIP_EINVAL, what, "SwiGLU: R * 2 D must be below 2^31");
+    if (bias || dbias || ws) return fail(VQHIP_EINVAL, what, "SwiGLU has no bias: bias, dbias and ws must be NULL");
+    return VQHIP_OK;
 }
 
 int64_t vqhip_row_bias_act_slabs(int64_t R, int64_t D) {
@@ -1999,8 +2017,14 @@ int64_t vqhip_row_bias_act_slabs(int64_t R, int64_t D) {
 int vqhip_row_bias_act_fwd(const void *x, int dtype, int64_t R, int64_t D, const float *bias, int act, void *y, void *stream) {
     if (int rc = vit_rows("vqhip_row_bias_act_fwd", R, D)) return rc;
     VQ_REQUIRE(vq_float_dtype(dtype), "vqhip_row_bias_act_fwd: dtype");
-    VQ_REQUIRE(act == VQHIP_ROW_ACT_GELU || act == VQHIP_ROW_ACT_TANH, "vqhip_row_bias_act_fwd: act must be 0 (GELU) or 1 (tanh)");
-    VQ_REQUIRE(x && bias && y, "vqhip_row_bias_act_fwd: x, bias and y are required");
+    VQ_REQUIRE(act == VQHIP_ROW_ACT_GELU || act == VQHIP_ROW_ACT_TANH || act == VQHIP_ROW_ACT_SWIGLU,
+               "vqhip_row_bias_act_fwd: act must be 0 (GELU), 1 (tanh) or 3 (SwiGLU)");
+    if (act == VQHIP_ROW_ACT_SWIGLU) {
+        if (int rc = swiglu_rows("vqhip_row_bias_act_fwd", R, D, bias, nullptr, nullptr)) return rc;
+        VQ_REQUIRE(x && y, "vqhip_row_bias_act_fwd: x and y are required");
+    } else {
+        VQ_REQUIRE(x && bias && y, "vqhip_row_bias_act_fwd: x, bias and y are required");
+    }
     VqRowActArgs a = {};
     a.x = x; a.bias = bias; a.out = y; a.R = R; a.D = (int)D;
     return vq_with_dtype(dtype, [&](auto dt) { return launch_row_act<decltype(dt)::value>(a, act, false, 0, nullptr, (hipStream_t)stream); });
@@ -2010,8 +2034,14 @@ int vqhip_row_bias_act_bwd(const void *g, const void *x, int dtype, int64_t R, i
                            float *dbias, float *ws, int64_t ws_bytes, void *stream) {
     if (int rc = vit_rows("vqhip_row_bias_act_bwd", R, D)) return rc;
     VQ_REQUIRE(vq_float_dtype(dtype), "vqhip_row_bias_act_bwd: dtype");
-    VQ_REQUIRE(act == VQHIP_ROW_ACT_GELU || act == VQHIP_ROW_ACT_TANH, "vqhip_row_bias_act_bwd: act must be 0 (GELU) or 1 (tanh)");
-    VQ_REQUIRE(g && x && bias && gx, "vqhip_row_bias_act_bwd: g, x, bias and gx are required");
+    VQ_REQUIRE(act == VQHIP_ROW_ACT_GELU || act == VQHIP_ROW_ACT_TANH || act == VQHIP_ROW_ACT_SWIGLU,
+               "vqhip_row_bias_act_bwd: act must be 0 (GELU), 1 (tanh) or 3 (SwiGLU)");
+    if (act == VQHIP_ROW_ACT_SWIGLU) {
+        if (int rc = swiglu_rows("vqhip_row_bias_act_bwd", R, D, bias, dbias, ws)) return rc;
+        VQ_REQUIRE(g && x && gx, "vqhip_row_bias_act_bwd: g, x and gx are required");
+    } else {
+        VQ_REQUIRE(g && x && bias && gx, "vqhip_row_bias_act_bwd: g, x, bias and gx are required");
+    }
     VQ_REQUIRE(!dbias || ws, "vqhip_row_bias_act_bwd: dbias needs the workspace");
     const int64_t slabs = (R + VQ_SG2_ROWS_SLAB - 1) / VQ_SG2_ROWS_SLAB;
     if (dbias) VQ_NEED("vqhip_row_bias_act_bwd: ws too small", ws_bytes, slabs * D * (int64_t)sizeof(float));

@@ -670,15 +670,18 @@ def batch_norm(x: torch.Tensor, running_mean: torch.Tensor, running_var: torch.T
 
 class _AddLayerNorm(Function):
     """vqhip_add_layer_norm_fwd / _bwd.  Outputs (s, y) with a branch to add, (y,) without; the gradient arriving at s is the
-    kernel's g_skip."""
+    kernel's g_skip.  ``bias`` None is the RMS mode, forward and backward."""
 
     @staticmethod
     def forward(ctx, x, res, weight, bias, eps, out_dtype):
-        s, y, stats = ops.add_layer_norm(x, res, weight, bias, eps, out_dtype)
+        if bias is None:
+            s, y, stats = ops.add_rms_norm(x, res, weight, eps, out_dtype)
+        else:
+            s, y, stats = ops.add_layer_norm(x, res, weight, bias, eps, out_dtype)
         ctx.save_for_backward(s, weight, stats)
         ctx.set_materialize_grads(False)
         ctx.res_dtype = None if res is None else res.dtype
-        ctx.bias_dtype = bias.dtype
+        ctx.bias_dtype = None if bias is None else bias.dtype
         return (y,) if res is None else (s, y)
 
     @staticmethod
@@ -690,7 +693,11 @@ class _AddLayerNorm(Function):
             gx, dgamma, dbeta = g_s, None, None
         else:
             skip = None if g_s is None else g_s.to(s.dtype).contiguous()
-            gx, dgamma, dbeta = ops.add_layer_norm_backward(g_y.contiguous(), s, stats, weight, skip)
+            if ctx.bias_dtype is None:
+                gx, dgamma = ops.add_rms_norm_backward(g_y.contiguous(), s, stats, weight, skip)
+                dbeta = None
+            else:
+                gx, dgamma, dbeta = ops.add_layer_norm_backward(g_y.contiguous(), s, stats, weight, skip)
         need = ctx.needs_input_grad
         return (gx if need[0] else None,
                 gx.to(ctx.res_dtype) if need[1] and gx is not None and ctx.res_dtype is not None else None,
@@ -712,6 +719,23 @@ def _vit_refusal(x: torch.Tensor) -> str:
         or ops.vit_rows_refusal('x', x.contiguous())
 
 
+def _add_norm(what: str, x, res, weight, bias, eps, out_dtype, strict: bool):
+    """What ``add_layer_norm`` and ``add_rms_norm`` (``bias`` None) decide alike: the refusal, ``strict``, the torch route."""
+    y_dtype = out_dtype or (x.dtype if res is None else res.dtype)
+    why = _vit_refusal(x) or ops.ln_pair_refusal(x, y_dtype) \
+        or ('' if res is None or (res.dtype == y_dtype and res.shape == x.shape) else
+            f'res is {res.dtype} {tuple(res.shape)}, not {y_dtype} {tuple(x.shape)}')
+    if why:
+        if strict:
+            raise ValueError(f'{what}: {why}')
+        if bias is None:
+            return add_rms_norm_torch(x, res, weight, eps, out_dtype)
+        return add_layer_norm_torch(x, res, weight, bias, eps, out_dtype)
+    x, res = x.contiguous(), None if res is None else res.contiguous()
+    out = _AddLayerNorm.apply(x, res, weight, bias, float(eps), y_dtype)
+    return (x, out[0]) if res is None else out
+
+
 def add_layer_norm(x: torch.Tensor, res: Optional[torch.Tensor], weight: torch.Tensor, bias: torch.Tensor, eps: float = 1e-6,
                    out_dtype=None, *, strict: bool = False):
     """``(s, y)`` with ``s = x + res`` (``x`` itself where ``res`` is None) in x's dtype and ``y = layer_norm(s, weight, bias, eps)``
@@ -719,17 +743,25 @@ def add_layer_norm(x: torch.Tensor, res: Optional[torch.Tensor], weight: torch.T
     dtypes, gradients to x, res, weight and bias.  fp32 x with a bf16 / fp16 res and y is the autocast case.  A CPU tensor, float64
     or a dtype combination the kernels do not read computes the same definition in torch - or, with ``strict`` (a module that
     has reported the fused route), raises with the reason."""
-    y_dtype = out_dtype or (x.dtype if res is None else res.dtype)
-    why = _vit_refusal(x) or ops.ln_pair_refusal(x, y_dtype) \
-        or ('' if res is None or (res.dtype == y_dtype and res.shape == x.shape) else
-            f'res is {res.dtype} {tuple(res.shape)}, not {y_dtype} {tuple(x.shape)}')
-    if why:
-        if strict:
-            raise ValueError(f'add_layer_norm: {why}')
-        return add_layer_norm_torch(x, res, weight, bias, eps, out_dtype)
-    x, res = x.contiguous(), None if res is None else res.contiguous()
-    out = _AddLayerNorm.apply(x, res, weight, bias, float(eps), y_dtype)
-    return (x, out[0]) if res is None else out
+    return _add_norm('add_layer_norm', x, res, weight, bias, eps, out_dtype, strict)
+
+
+def add_rms_norm_torch(x: torch.Tensor, res: Optional[torch.Tensor], weight: torch.Tensor, eps: float = 1e-5, out_dtype=None):
+    """The same definition in torch, ``x = x + branch`` and the lines of transformers' ``LlamaRMSNorm`` with its one difference
+    removed: the normalised rows stay fp32 through the product with ``weight`` and are rounded once (for an fp32 or float64
+    stream, which is what the reference trains with, the two coincide).  CPU tensors, float64, ``fused=False``."""
+    s = x if res is None else x + res
+    h = s if s.dtype == torch.float64 else s.to(torch.float32)
+    y = (h * torch.rsqrt(h.pow(2).mean(-1, keepdim=True) + eps)) * weight.to(h.dtype)
+    return s, y.to(out_dtype or s.dtype)
+
+
+def add_rms_norm(x: torch.Tensor, res: Optional[torch.Tensor], weight: torch.Tensor, eps: float = 1e-5, out_dtype=None, *,
+                 strict: bool = False):
+    """``(s, y)`` with ``s = x + res`` (``x`` itself where ``res`` is None) in x's dtype and ``y = s / sqrt(mean(s^2) + eps) * weight``
+    in ``out_dtype`` (default: res's dtype, else x's): the RMS mode of ``add_layer_norm``, one launch, fp32 arithmetic rounded once,
+    gradients to x, res and weight.  The routes, the autocast rows and ``strict`` are ``add_layer_norm``'s."""
+    return _add_norm('add_rms_norm', x, res, weight, None, eps, out_dtype, strict)
 
 
 ROW_ACTS_TORCH = {'gelu': torch.nn.functional.gelu, 'tanh': torch.tanh}
@@ -769,3 +801,37 @@ def row_bias_act(x: torch.Tensor, bias: torch.Tensor, act='gelu', *, strict: boo
             raise ValueError(f'row_bias_act: {why}')
         return row_bias_act_torch(x, bias, act)
     return _RowBiasAct.apply(x.contiguous(), bias, act)
+
+
+class _SwiGLU(Function):
+    """vqhip_row_bias_act_fwd / _bwd with act = VQHIP_ROW_ACT_SWIGLU; saves the INPUT (the backward recomputes the sigmoid)."""
+
+    @staticmethod
+    def forward(ctx, x):
+        ctx.save_for_backward(x)
+        return ops.swiglu(x)
+
+    @staticmethod
+    @once_differentiable
+    def backward(ctx, g):
+        x, = ctx.saved_tensors
+        return ops.swiglu_backward(g.contiguous(), x)
+
+
+def swiglu_torch(gate_up: torch.Tensor) -> torch.Tensor:
+    """The same definition in torch: ``act_fn(gate_proj(x)) * up_proj(x)`` of transformers' ``LlamaMLP`` on the two halves."""
+    gate, up = gate_up.chunk(2, dim=-1)
+    return torch.nn.functional.silu(gate) * up
+
+
+def swiglu(gate_up: torch.Tensor, *, strict: bool = False) -> torch.Tensor:
+    """``silu(gate) * up`` of rows [..., 2 F] = (gate | up), [..., F] in the rows' dtype: one launch, fp32 arithmetic rounded once (no
+    bf16 intermediate), and a backward that writes both halves of the gradient in one launch from the saved input.  A CPU tensor,
+    float64 or rows the kernels do not read compute the same definition in torch - or, with ``strict``, raise with the reason."""
+    why = ('' if gate_up.is_cuda else f'the rows are on device {gate_up.device}, not on a GPU') \
+        or ops.float_dtype_refusal('the rows are', gate_up) or ops.swiglu_refusal('x', gate_up.contiguous())
+    if why:
+        if strict:
+            raise ValueError(f'swiglu: {why}')
+        return swiglu_torch(gate_up)
+    return _SwiGLU.apply(gate_up.contiguous())

@@ -1374,13 +1374,10 @@ def ln_pair_refusal(x: torch.Tensor, y_dtype) -> str:
     return '' if ok else f'x is {x.dtype} and the other side {y_dtype}: need one float dtype, or float32 x with bfloat16 or float16'
 
 
-@_on_tensor_device
-def add_layer_norm(x: torch.Tensor, res: Optional[torch.Tensor], weight: torch.Tensor, bias: torch.Tensor, eps: float = 1e-6,
-                   out_dtype=None):
-    """vqhip_add_layer_norm_fwd: ``(s, y, stats)`` with ``s = x + res`` in x's dtype (``x`` itself where ``res`` is None),
-    ``y = layer_norm(s) * weight + bias`` in ``out_dtype`` (default: res's dtype, else x's) and ``stats`` [R, 2] fp32 (each row's
-    mean and 1 / sqrt(var + eps)).  Rows [..., D] read in place; fp32 x with a bf16 / fp16 res and y is the autocast case.  One launch."""
-    xr = _vit_rows('add_layer_norm', 'x', x)
+def _add_norm(what: str, x, res, weight, bias, eps, out_dtype):
+    """vqhip_add_layer_norm_fwd in either mode: ``bias`` None is the RMS mode (beta == NULL).  What both ops decide alike: the row
+    view, the dtype table, res's shape and dtype, the parameter vectors."""
+    xr = _vit_rows(what, 'x', x)
     out_dtype = out_dtype or (x.dtype if res is None else res.dtype)
     why = ln_pair_refusal(x, out_dtype)
     rr = None
@@ -1389,13 +1386,13 @@ def add_layer_norm(x: torch.Tensor, res: Optional[torch.Tensor], weight: torch.T
                f'res is {res.dtype} {tuple(res.shape)}, not {out_dtype} {tuple(x.shape)}') or vit_rows_refusal('res', res)
         _require_cuda(res)
     R, D = xr.shape
-    if not why and (weight.numel() != D or bias.numel() != D):
-        why = f'weight and bias have {weight.numel()} and {bias.numel()} elements, not D={D}'
-    _refuse('add_layer_norm', why)
+    if not why and (weight.numel() != D or (bias is not None and bias.numel() != D)):
+        why = f'weight and bias have {weight.numel()} and {D if bias is None else bias.numel()} elements, not D={D}'
+    _refuse(what, why)
     _require_cuda(weight, bias)
     if res is not None:
         rr = row_view(res, 'res')[0]
-    w, b = _fp32_vector(weight), _fp32_vector(bias)
+    w, b = _fp32_vector(weight), None if bias is None else _fp32_vector(bias)
     s = x if res is None else torch.empty_like(xr).view(x.shape)
     y = torch.empty(x.shape, dtype=out_dtype, device=x.device)
     stats = torch.empty(R, 2, dtype=torch.float32, device=x.device)
@@ -1406,12 +1403,27 @@ def add_layer_norm(x: torch.Tensor, res: Optional[torch.Tensor], weight: torch.T
 
 
 @_on_tensor_device
-def add_layer_norm_backward(g: torch.Tensor, s: torch.Tensor, stats: torch.Tensor, weight: torch.Tensor,
-                            g_skip: Optional[torch.Tensor] = None):
-    """vqhip_add_layer_norm_bwd: ``(gx, dgamma, dbeta)`` from the gradient ``g`` arriving at y, the saved sum ``s`` and the
-    forward's ``stats``; ``g_skip``, the gradient arriving at s itself, is added in the same pass.  ``gx`` in s's dtype (it is the
-    gradient of x and, cast, of res), ``dgamma`` and ``dbeta`` fp32 [D] from a fixed-order two-stage sum."""
-    sr = _vit_rows('add_layer_norm_backward', 's', s)
+def add_layer_norm(x: torch.Tensor, res: Optional[torch.Tensor], weight: torch.Tensor, bias: torch.Tensor, eps: float = 1e-6,
+                   out_dtype=None):
+    """vqhip_add_layer_norm_fwd: ``(s, y, stats)`` with ``s = x + res`` in x's dtype (``x`` itself where ``res`` is None),
+    ``y = layer_norm(s) * weight + bias`` in ``out_dtype`` (default: res's dtype, else x's) and ``stats`` [R, 2] fp32 (each row's
+    mean and 1 / sqrt(var + eps)).  Rows [..., D] read in place; fp32 x with a bf16 / fp16 res and y is the autocast case.  One launch."""
+    if bias is None:
+        raise ValueError('add_layer_norm: bias is required (add_rms_norm is the op without one)')
+    return _add_norm('add_layer_norm', x, res, weight, bias, eps, out_dtype)
+
+
+@_on_tensor_device
+def add_rms_norm(x: torch.Tensor, res: Optional[torch.Tensor], weight: torch.Tensor, eps: float = 1e-5, out_dtype=None):
+    """vqhip_add_layer_norm_fwd with beta == NULL: ``(s, y, stats)`` with ``s = x + res`` in x's dtype (``x`` itself where ``res``
+    is None), ``y = s / sqrt(mean(s^2) + eps) * weight`` in ``out_dtype``, computed in fp32 and rounded once, and ``stats`` [R, 2]
+    fp32 (0 and each row's 1 / sqrt(mean(s^2) + eps)).  Everything else as ``add_layer_norm``.  One launch."""
+    return _add_norm('add_rms_norm', x, res, weight, None, eps, out_dtype)
+
+
+def _add_norm_backward(what: str, g, s, stats, weight, g_skip, rms: bool):
+    """vqhip_add_layer_norm_bwd in either mode: ``rms`` passes dbeta == NULL and returns None for it."""
+    sr = _vit_rows(what, 's', s)
     R, D = sr.shape
     why = ln_pair_refusal(s, g.dtype) or ('' if g.shape == s.shape else f'g is {tuple(g.shape)}, s {tuple(s.shape)}') \
         or vit_rows_refusal('g', g)
@@ -1422,7 +1434,7 @@ def add_layer_norm_backward(g: torch.Tensor, s: torch.Tensor, stats: torch.Tenso
         why = f'stats must be the contiguous fp32 [{R}, 2] of the forward'
     if not why and weight.numel() != D:
         why = f'weight has {weight.numel()} elements, not D={D}'
-    _refuse('add_layer_norm_backward', why)
+    _refuse(what, why)
     _require_cuda(g, g_skip, stats, weight)
     w = _fp32_vector(weight)
     gr = row_view(g, 'g')[0]
@@ -1431,11 +1443,28 @@ def add_layer_norm_backward(g: torch.Tensor, s: torch.Tensor, stats: torch.Tenso
     slabs = _lib.lib().vqhip_add_layer_norm_slabs(R, D)
     ws = torch.empty(2 * slabs * D, dtype=torch.float32, device=s.device)
     dgamma = torch.empty(D, dtype=torch.float32, device=s.device)
-    dbeta = torch.empty(D, dtype=torch.float32, device=s.device)
+    dbeta = None if rms else torch.empty(D, dtype=torch.float32, device=s.device)
     check(_lib.lib().vqhip_add_layer_norm_bwd(_ptr(gr), FLOAT_DTYPES[g.dtype], _ptr(sr), FLOAT_DTYPES[s.dtype], _ptr(kr), R, D, _ptr(w),
                                               _ptr(stats), _ptr(gx), _ptr(dgamma), _ptr(dbeta), _ptr(ws), ws.numel() * 4, _stream()),
           'vqhip_add_layer_norm_bwd')
     return gx, dgamma, dbeta
+
+
+@_on_tensor_device
+def add_layer_norm_backward(g: torch.Tensor, s: torch.Tensor, stats: torch.Tensor, weight: torch.Tensor,
+                            g_skip: Optional[torch.Tensor] = None):
+    """vqhip_add_layer_norm_bwd: ``(gx, dgamma, dbeta)`` from the gradient ``g`` arriving at y, the saved sum ``s`` and the
+    forward's ``stats``; ``g_skip``, the gradient arriving at s itself, is added in the same pass.  ``gx`` in s's dtype (it is the
+    gradient of x and, cast, of res), ``dgamma`` and ``dbeta`` fp32 [D] from a fixed-order two-stage sum."""
+    return _add_norm_backward('add_layer_norm_backward', g, s, stats, weight, g_skip, False)
+
+
+@_on_tensor_device
+def add_rms_norm_backward(g: torch.Tensor, s: torch.Tensor, stats: torch.Tensor, weight: torch.Tensor,
+                          g_skip: Optional[torch.Tensor] = None):
+    """vqhip_add_layer_norm_bwd with dbeta == NULL: ``(gx, dgamma)`` of ``add_rms_norm`` from ITS ``stats`` (the pairing of the two
+    modes is held here: the library sees one call at a time)."""
+    return _add_norm_backward('add_rms_norm_backward', g, s, stats, weight, g_skip, True)[:2]
 
 
 def _row_act_head(what: str, x: torch.Tensor, bias: torch.Tensor, act):
@@ -1478,6 +1507,57 @@ def row_bias_act_backward(g: torch.Tensor, x: torch.Tensor, bias: torch.Tensor, 
     check(_lib.lib().vqhip_row_bias_act_bwd(_ptr(gr), _ptr(xr), FLOAT_DTYPES[x.dtype], R, D, _ptr(b), ROW_ACTS[act], _ptr(gx), _ptr(dbias),
                                             _ptr(ws), 0 if ws is None else ws.numel() * 4, _stream()), 'vqhip_row_bias_act_bwd')
     return gx, dbias
+
+
+def swiglu_refusal(name: str, t: torch.Tensor) -> str:
+    """Why the SwiGLU mode of vqhip_row_bias_act_* would refuse ``t`` [..., 2 F] = (gate | up) ('' if it would not): the clauses of
+    ``vit_rows_refusal`` with D read as the output width F and the element count as R 2 F.  Rows must be dense: no copy is made here."""
+    rows = row_view(t, name)
+    if isinstance(rows, str):
+        return rows
+    rows, stride = rows
+    R, W2 = rows.shape
+    F = W2 // 2
+    return ('' if R >= 1 and W2 >= 1 else f'{name} {tuple(t.shape)} is empty') \
+        or ('' if W2 % 2 == 0 else f'{name} has {W2} columns: (gate | up) needs an even number') \
+        or ('' if stride == W2 else f'the rows of {name} are not dense (row stride {stride}, 2 F={W2})') \
+        or ('' if F <= _lib.VIT_MAX_D else f'F={F} is beyond {_lib.VIT_MAX_D}') \
+        or ('' if R <= _lib.VIT_MAX_R else f'R={R} rows are beyond 2^24') \
+        or ('' if R * W2 < (1 << 31) else f'{R * W2} elements are outside 1 .. 2^31-1')
+
+
+def _swiglu_rows(what: str, x: torch.Tensor):
+    _require_cuda(x)
+    _refuse(what, swiglu_refusal('x', x))
+    return row_view(x, 'x')[0]
+
+
+@_on_tensor_device
+def swiglu(x: torch.Tensor) -> torch.Tensor:
+    """vqhip_row_bias_act_fwd with act = VQHIP_ROW_ACT_SWIGLU: ``silu(x[..., :F]) * x[..., F:]`` of rows [..., 2 F] read in place,
+    [..., F] in x's dtype.  One launch."""
+    xr = _swiglu_rows('swiglu', x)
+    R, F = xr.shape[0], xr.shape[1] // 2
+    y = torch.empty(x.shape[:-1] + (F,), dtype=x.dtype, device=x.device)
+    check(_lib.lib().vqhip_row_bias_act_fwd(_ptr(xr), FLOAT_DTYPES[x.dtype], R, F, None, _lib.ROW_ACT_SWIGLU, _ptr(y), _stream()),
+          'vqhip_row_bias_act_fwd')
+    return y
+
+
+@_on_tensor_device
+def swiglu_backward(g: torch.Tensor, x: torch.Tensor) -> torch.Tensor:
+    """vqhip_row_bias_act_bwd with act = VQHIP_ROW_ACT_SWIGLU: ``gx`` [..., 2 F] in x's dtype, both halves in one launch, from the
+    incoming gradient ``g`` [..., F] and the SAVED INPUT ``x`` (the sigmoid is recomputed; y is not kept)."""
+    xr = _swiglu_rows('swiglu_backward', x)
+    R, F = xr.shape[0], xr.shape[1] // 2
+    _refuse('swiglu_backward', ('' if g.shape == x.shape[:-1] + (F,) and g.dtype == x.dtype else
+                                f'g is {g.dtype} {tuple(g.shape)}, x {x.dtype} {tuple(x.shape)}') or vit_rows_refusal('g', g))
+    _require_cuda(g)
+    gr = row_view(g, 'g')[0]
+    gx = torch.empty_like(xr).view(x.shape)
+    check(_lib.lib().vqhip_row_bias_act_bwd(_ptr(gr), _ptr(xr), FLOAT_DTYPES[x.dtype], R, F, None, _lib.ROW_ACT_SWIGLU, _ptr(gx), None,
+                                            None, 0, _stream()), 'vqhip_row_bias_act_bwd')
+    return gx
 
 
 # ---- fused reconstruction metrics (validation: vq/runners/metrics/loss.py over vq/tasks/image_reconstruction/losses.py) -----

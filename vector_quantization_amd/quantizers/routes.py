@@ -612,6 +612,42 @@ def vit_why(module, x: torch.Tensor) -> Route:
     return Route('torch', why) if why else Route('fused')
 
 
+# ---- the row ops of LlamaTransformer (vector_quantization_amd/transformers.py) ----------------------------------------------------
+
+def llama_why(module, tokens: torch.Tensor, kv_cache=None, attention_mask=None) -> Route:
+    """The residual adds, RMSNorms and the gated activation of ``LlamaTransformer``: the walk over transformers' submodules on the HIP
+    kernels of ``functional.add_rms_norm`` / ``swiglu`` (``fused``), or the reference's call of ``LlamaForCausalLM`` itself
+    (``torch``), with the first clause that refused the walk: ``fused=False`` on the module, a class that overrides ``_walk``, an
+    ``attention_mask`` (the walk passes none: the attention core is causal by itself), ``mlp_bias`` or ``attention_bias`` set (the
+    gated kernel takes no bias; the walk is held to the shipped configuration), a ``hidden_act`` other than ``silu``, tied
+    embeddings, an attention implementation other than ``sdpa`` (only there is ``attention_mask=None`` causal), several tokens behind
+    a cache that is not empty (transformers builds a mask for them), a hidden or intermediate size beyond the kernels' rows, CPU
+    tokens, float64 (or any dtype the kernels do not read) parameters.  A site whose own activation the kernels refuse after that
+    raises with the reason: nothing falls back to torch behind a ``last_route`` that says ``fused``.  No shape is sent to
+    ``torch`` for speed: profiles/llama_transformer.txt has the measurements."""
+    from .. import transformers as vq_transformers
+    why = '' if getattr(module, 'fused', True) else 'fused=False'
+    why = why or own(module, vq_transformers.LlamaTransformer, '_walk')
+    why = why or ('' if attention_mask is None else 'an attention_mask is given: the walk passes none')
+    lm = module._transformer
+    config = lm.config
+    if not why:
+        why = ('mlp_bias=True: the gated kernel takes no bias' if getattr(config, 'mlp_bias', False) else '') \
+            or ('attention_bias=True' if getattr(config, 'attention_bias', False) else '') \
+            or ('' if config.hidden_act == 'silu' else f'hidden_act={config.hidden_act!r} is not \'silu\'') \
+            or ('the embeddings are tied' if getattr(config, 'tie_word_embeddings', False)
+                or lm.lm_head.weight is lm.model.embed_tokens.weight else '') \
+            or ('' if config._attn_implementation == 'sdpa' else
+                f'attention implementation {config._attn_implementation!r}: only sdpa is causal without a mask')
+    if not why and kv_cache is not None and tokens.dim() == 2 and tokens.shape[1] > 1 and kv_cache.get_seq_length() > 0:
+        why = f'{tokens.shape[1]} tokens behind a cache of {kv_cache.get_seq_length()}: transformers builds a mask for them'
+    width = max(config.hidden_size, config.intermediate_size)
+    why = why or ('' if width <= ops._lib.VIT_MAX_D else f'rows of {width} values are beyond {ops._lib.VIT_MAX_D}')
+    why = why or ('' if tokens.is_cuda else f'the tokens are on device {tokens.device}, not on a GPU') \
+        or ops.float_dtype_refusal('the parameters are', lm.model.embed_tokens.weight)
+    return Route('torch', why) if why else Route('fused')
+
+
 # ---- MultinomialAnchor of a CVQ-VAE update (vector_quantization_amd/quantizers/anchors.py) ----------------------------------------
 
 def multinomial_anchor_why(anchor, d, x: torch.Tensor) -> Route:

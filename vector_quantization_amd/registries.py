@@ -101,6 +101,10 @@ class VQSMSamplerRegistry(VQModelRegistry):
         return sampler
 
 
+class VQSMTransformerRegistry(VQModelRegistry):
+    """The transformers of stage 2 (vq/tasks/sequence_modeling/models/registries.py:17): transformers.py."""
+
+
 class AnchorRegistry(Registry):
     pass
 
