@@ -22,7 +22,9 @@ for plumbing.  This module therefore
 What stays defined-by-SURVEY (un-vendored todd arithmetic — three things, kept together in ``_ToddArithmetic``):
 ``todd.utils.ema(a,b,γ)=a·γ+b·(1−γ)``, ``todd.utils.EMA`` (default γ=0.99, first call with ``None`` state returns
 ``b``), and ``todd.models.losses.MSELoss(norm=)`` (mean-reduced, weight 1; ``norm=True`` L2-normalises both
-arguments along dim 1).  Everything else that computes is the reference's or ATen's.
+arguments along dim 1).  ``load_networks()`` (the networks, the discriminator and the GAN losses) adds a fourth, defined by how
+the reference's losses and configs use it: ``todd.models.losses.BaseLoss._reduce`` (``reduction`` none / mean / sum, then a
+constant ``weight``).  Everything else that computes is the reference's or ATen's.
 
 Nothing here travels to the GPU box as behaviour: /root/reference does not exist there; only the generated
 ``tests/golden/*.npz`` do.  The product package never imports this module.
@@ -78,6 +80,21 @@ class _ToddArithmetic:
         if norm:
             pred, target = F.normalize(pred), F.normalize(target)
         return F.mse_loss(pred, target)
+
+    @staticmethod
+    def reduce(loss, reduction: str, weight: float):
+        """``todd.models.losses.BaseLoss._reduce``: defined by how the reference's own losses use it - ``reduction`` is one of
+        'none' | 'mean' | 'sum' over every element (vq/tasks/image_reconstruction/losses.py:55,66 build the element-wise loss with
+        ``reduction='none'`` and hand it to ``_reduce``), default 'mean'; then the constant ``weight`` multiplies the result
+        (configs/llamagen/vqgan.py:25-26 pass ``weight=0.5``), default 1.  The product states the same in
+        ``image_losses.BaseReconstructLoss``; todd's scheduled weights are not restated."""
+        if reduction == 'mean':
+            loss = loss.mean()
+        elif reduction == 'sum':
+            loss = loss.sum()
+        else:
+            assert reduction == 'none', reduction
+        return loss * weight
 
 
 def _install_todd() -> types.ModuleType:
@@ -228,8 +245,12 @@ def _install_todd() -> types.ModuleType:
         pass
 
     class BaseLoss(BuildPreHookMixin, nn.Module):          # VQGANLoss.build_pre_hook calls super() through it (losses.py:107)
-        def __init__(self, *args, **kwargs):
+        def __init__(self, *args, reduction: str = 'mean', weight: float = 1.0, **kwargs):
             super().__init__()
+            self._standin_reduction, self._standin_weight = reduction, weight
+
+        def _reduce(self, loss):
+            return _ToddArithmetic.reduce(loss, self._standin_reduction, self._standin_weight)
 
     class MSELoss(BaseLoss):
         def __init__(self, *args, norm: bool = False, **kwargs):
@@ -299,6 +320,9 @@ def _install_todd() -> types.ModuleType:
         (configs/vqgan/runner.py:123)."""
         return eval('__o' + attr, {'__o': obj})     # noqa: S307 — build-container test infrastructure, fixed strings
 
+    NormRegistry = _registry('NormRegistry')
+    NormRegistry.register_('LN')(nn.LayerNorm)           # vqkd/autoencoder.py:94,153 builds dict(type='LN', eps=1e-06)
+
     known = {
         'todd': dict(Config=Config, Registry=Registry, RegistryMeta=RegistryMeta, Store=Store, logger=_Logger()),
         'todd.bases': {},
@@ -307,7 +331,7 @@ def _install_todd() -> types.ModuleType:
         'todd.registries': dict(InitRegistry=InitRegistry, ModelRegistry=_registry('ModelRegistry'),
                                 DatasetRegistry=_registry('DatasetRegistry'),
                                 RunnerRegistry=_registry('RunnerRegistry'), TaskRegistry=_registry('TaskRegistry')),
-        'todd.models': dict(LossRegistry=_registry('LossRegistry')),
+        'todd.models': dict(LossRegistry=_registry('LossRegistry'), NormRegistry=NormRegistry),
         'todd.models.losses': dict(BaseLoss=BaseLoss, MSELoss=MSELoss),
         'todd.patches': {},
         'todd.patches.torch': dict(ModuleDict=ModuleDict, ModuleList=ModuleList, Sequential=Sequential,
@@ -385,6 +409,9 @@ _PACKAGES = {
                          ('star', 'quantizers'), ('star', 'utils')],
     'vq.algorithms.vq.callbacks': [('star', 'normalize'), ('star', 'update')],   # callbacks/__init__.py:1-2
     'vq.algorithms.vqgan': [('star', 'quantizer')],                              # vqgan/__init__.py:4
+    'vq.algorithms.vqgan.discriminators': [('star', 'base'), ('star', 'patchgan')],          # discriminators/__init__.py:1-2
+    'vq.algorithms.vqgan.losses': [('star', 'discriminator'), ('star', 'generator'),         # losses/__init__.py:1-3
+                                   ('star', 'registries')],
     'vq.algorithms.vqkd': [('pkg', 'quantizers')],                               # vqkd/__init__.py:1
     'vq.algorithms.vqkd.quantizers': [('star', 'base'), ('star', 'callbacks')],  # quantizers/__init__.py:1-2
     'vq.algorithms.cvqvae': [('star', 'anchors'), ('star', 'quantizer_callback'), ('star', 'registries')],
@@ -394,6 +421,7 @@ _PACKAGES = {
 # Packages the model-level file (image_tokenization/models/base.py) imports for type annotations only (datasets,
 # encoders, runners): inert placeholder modules, nothing of theirs is ever executed.
 _INERT = ('vq.datasets', 'vq.models.autoencoders', 'vq.runners')
+_LIVE: set = set()          # names of _INERT that load_networks() has since imported from the reference's own file
 
 
 class _InertModule(types.ModuleType):
@@ -414,7 +442,7 @@ class _RefFinder(importlib.abc.MetaPathFinder, importlib.abc.Loader):
         if fullname != 'vq' and not fullname.startswith('vq.'):
             return None
         rel = os.path.join(REFERENCE_ROOT, *fullname.split('.'))
-        if fullname in _INERT:
+        if fullname in _INERT and fullname not in _LIVE:
             return importlib.machinery.ModuleSpec(fullname, self, is_package=True)
         if fullname in _PACKAGES:
             spec = importlib.machinery.ModuleSpec(fullname, self, is_package=True)
@@ -425,14 +453,14 @@ class _RefFinder(importlib.abc.MetaPathFinder, importlib.abc.Loader):
         raise ReferenceUnavailable(f'{fullname} is outside the quantizer path loaded by oracle/ref_import.py')
 
     def create_module(self, spec):
-        if spec.name in _INERT:
+        if spec.name in _INERT and spec.name not in _LIVE:
             m = _InertModule(spec.name)
             m.__path__ = []
             return m
         return None
 
     def exec_module(self, module):
-        if module.__name__ in _INERT:
+        if isinstance(module, _InertModule):
             return
         for kind, name in _PACKAGES[module.__name__]:
             sub = importlib.import_module(f'{module.__name__}.{name}')
@@ -513,6 +541,39 @@ def load_runners() -> types.SimpleNamespace:
                                  files=['vq/tasks/image_tokenization/runners/callbacks.py',
                                         'vq/tasks/image_tokenization/runners/metrics.py',
                                         'vq/tasks/image_tokenization/runners/tokenizer.py', 'tools/tokenize_llamagen.py'])
+
+
+@functools.lru_cache(1)
+def load_networks() -> types.SimpleNamespace:
+    """The networks either side of the quantizer, the discriminator and the GAN losses, from the reference's own files:
+    ``VQGANEncoder`` / ``VQGANDecoder`` (vq/algorithms/vqgan/autoencoder.py), ``VQKDEncoder`` / ``VQKDDecoder``
+    (vq/algorithms/vqkd/autoencoder.py), ``PatchGANDiscriminator`` (vq/algorithms/vqgan/discriminators/{base,patchgan}.py) and the
+    four losses of vq/algorithms/vqgan/losses/{registries,generator,discriminator}.py.  ``vq/models/autoencoders.py`` stays inert for
+    ``load()`` (the quantizer fixtures are generated in a process that never calls this function) and is executed from its own file
+    here.  ``einops`` is the installed package.  ``StyleGAN2Discriminator`` (discriminators/__init__.py:3) needs ``mmcv.ops`` and is
+    left out."""
+    ref = load()
+    name = 'vq.models.autoencoders'
+    _LIVE.add(name)
+    sys.modules.pop(name, None)
+    bases = importlib.import_module(name)
+    models = sys.modules['vq.models']
+    models.autoencoders = bases
+    for n in bases.__all__:                                                       # vq/models/__init__.py:1
+        setattr(models, n, getattr(bases, n))
+    mods = {n: importlib.import_module(n) for n in (
+        'vq.algorithms.vqgan.autoencoder', 'vq.algorithms.vqkd.autoencoder', 'vq.algorithms.vqgan.discriminators',
+        'vq.algorithms.vqgan.losses')}
+    ns = types.SimpleNamespace(todd=ref.todd, Config=ref.todd.Config, modules=mods, files={})
+    for m in mods.values():
+        for n in getattr(m, '__all__', None) or [k for k, v in vars(m).items() if isinstance(v, type)]:
+            setattr(ns, n, getattr(m, n))
+    for n in ('vq.models.autoencoders', 'vq.algorithms.vqgan.autoencoder', 'vq.algorithms.vqkd.autoencoder',
+              'vq.algorithms.vqgan.registries', 'vq.algorithms.vqgan.discriminators.base',
+              'vq.algorithms.vqgan.discriminators.patchgan', 'vq.algorithms.vqgan.losses.registries',
+              'vq.algorithms.vqgan.losses.generator', 'vq.algorithms.vqgan.losses.discriminator'):
+        ns.files[n] = os.path.relpath(sys.modules[n].__file__, REFERENCE_ROOT)
+    return ns
 
 
 if __name__ == '__main__':
