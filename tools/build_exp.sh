@@ -1,11 +1,13 @@
 #!/bin/bash
 # Experiment builds of libvqhip: tools/build_exp.sh <name> [-DMACRO=value ...]  ->  build/exp/libvqhip_<name>.so
 # (git-ignored, but they travel to the GPU box; select one with VQHIP_LIB=build/exp/libvqhip_<name>.so)
+# The same build as the shipped library (csrc/build.sh and its list of units), with the flags added to every compile and objects
+# of its own under build/exp/obj_<name>/; a name built again with other flags is recompiled.
 set -euo pipefail
 ROOT="$(cd "$(dirname "${BASH_SOURCE[0]}")/.." && pwd)"
 name=$1; shift
-mkdir -p "$ROOT/build/exp"
-/opt/rocm/bin/hipcc --offload-arch=gfx950 -O3 -std=c++17 -fPIC -shared -ffp-contract=off -Wno-unused-function \
-    -I"$ROOT/include" -I"$ROOT/vector_quantization_amd/csrc" "$@" "$ROOT/vector_quantization_amd/csrc/vqhip.hip" \
-    -o "$ROOT/build/exp/libvqhip_$name.so"
+flags=""
+if (( $# )); then flags="$(printf '%q ' "$@")"; fi      # each flag stays one word, spaces and quotes included
+VQ_LIB_OUT="$ROOT/build/exp/libvqhip_$name.so" VQ_OBJ_DIR="$ROOT/build/exp/obj_$name" VQ_EXTRA_FLAGS="$flags" \
+    bash "$ROOT/vector_quantization_amd/csrc/build.sh"
 echo "built build/exp/libvqhip_$name.so ($*)"

@@ -1,5 +1,6 @@
 #!/usr/bin/env python3
-"""LDS-DMA hygiene of a libvqhip device assembly (VQ_KEEP_TEMPS=1 bash vector_quantization_amd/csrc/build.sh -> build/asm/*gfx950.s).
+"""LDS-DMA hygiene of a libvqhip device assembly (VQ_KEEP_TEMPS=1 bash vector_quantization_amd/csrc/build.sh -> build/asm/*gfx950.s,
+one listing per translation unit; all are read).
 A kernel that fills LDS with global_load_lds / buffer_load ... lds and hands the tile to other waves must have drained vmcnt
 before the s_barrier: __syncthreads() does not promise that (a release fence owes nothing to outstanding loads; hipcc emits the
 s_waitcnt vmcnt(0) only where something else needs it).  Per kernel with LDS-DMA: every s_barrier, whether the straight-line code
@@ -7,9 +8,9 @@ in front of it (back to the previous barrier, label or branch) holds an s_waitcn
 that stretch.  A barrier marked `?` starts a basic block: what reaches it has to be read in the listing.
 usage: isa_dma_barriers.py [asm file] [name filter]"""
 import glob, re, sys
-f = sys.argv[1] if len(sys.argv) > 1 and sys.argv[1].endswith('.s') else glob.glob('build/asm/*gfx950.s')[0]
+files = [sys.argv[1]] if len(sys.argv) > 1 and sys.argv[1].endswith('.s') else sorted(glob.glob('build/asm/*gfx950.s'))
 flt = sys.argv[-1] if len(sys.argv) > 1 and not sys.argv[-1].endswith('.s') else ''
-s = open(f).read()
+s = '\n'.join(open(f).read() for f in files)     # one listing per translation unit: all of them
 for m in re.finditer(r'\n(_Z\w+|\w+_kernel\w*):[^\n]*\n(.*?)\.Lfunc_end', s, re.S):
     name, body = m.group(1), m.group(2)
     if flt and flt not in name:

@@ -1,10 +1,10 @@
 #!/usr/bin/env python3
 """Per-kernel resource table of a libvqhip device assembly (VQ_KEEP_TEMPS=1 bash vector_quantization_amd/csrc/build.sh ->
-build/asm/*gfx950.s): VGPRs, spills, scratch, LDS, instruction and MFMA counts.  usage: isa_stats.py [asm file] [name filter]"""
+build/asm/*gfx950.s, one per translation unit; all are read): VGPRs, spills, scratch, LDS, instruction and MFMA counts.  usage: isa_stats.py [asm file] [name filter]"""
 import glob, re, sys
-f = sys.argv[1] if len(sys.argv) > 1 and sys.argv[1].endswith('.s') else glob.glob('build/asm/*gfx950.s')[0]
+files = [sys.argv[1]] if len(sys.argv) > 1 and sys.argv[1].endswith('.s') else sorted(glob.glob('build/asm/*gfx950.s'))
 flt = sys.argv[-1] if len(sys.argv) > 1 and not sys.argv[-1].endswith('.s') else ''
-s = open(f).read()
+s = '\n'.join(open(f).read() for f in files)     # one listing per translation unit: all of them
 meta = {}
 for m in re.finditer(r'\.name:\s+(\S+)\n(.*?)\.wavefront_size', s, re.S):
     b = m.group(2)

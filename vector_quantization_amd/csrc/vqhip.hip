@@ -1,48 +1,33 @@
-// libvqhip — host entry points (C ABI in include/vqhip.h).  gfx950 only.
+// libvqhip — host entry points (C ABI in include/vqhip.h) of the quantizer core, with FSQ and the pooled code features (which
+// share FSQ's constants).  gfx950 only.  The other op families have a translation unit each (csrc/Makefile).
 #include "vqhip.h"
 
 #include <hip/hip_runtime.h>
 #include <stdio.h>
 #include <string.h>
 
+#include "vqhip_host.h"
 #include "vqhip_kernels.h"
+#include "vqhip_prepare_kernels.h"
+#include "vqhip_proposal_kernels.h"
+#include "vqhip_refine_kernels.h"
+#include "vqhip_proposal32_kernels.h"
+#include "vqhip_exact_kernels.h"
+#include "vqhip_stream_kernels.h"
+#include "vqhip_update_kernels.h"
+#include "vqhip_sort_kernels.h"
+#include "vqhip_aux_kernels.h"
+#include "vqhip_exchange_kernels.h"
+#include "vqhip_step_kernels.h"
+#include "vqhip_pool_kernels.h"
 #include "vqhip_fsq_kernels.h"
-#include "vqhip_entropy_kernels.h"
-#include "vqhip_col_multinomial_kernels.h"
-#include "vqhip_sample_kernels.h"
-#include "vqhip_token_ce_kernels.h"
-#include "vqhip_cosine_embed_kernels.h"
-#include "vqhip_lpips_kernels.h"
-#include "vqhip_stylegan2_kernels.h"
-#include "vqhip_group_norm_kernels.h"
-#include "vqhip_vit_kernels.h"
-#include "vqhip_image_metrics_kernels.h"
-
-static thread_local char g_err[256] = "";
-
-static int fail(int code, const char *what, const char *detail = "") {
-    snprintf(g_err, sizeof(g_err), "%s%s%s", what, detail[0] ? ": " : "", detail);
-    return code;
-}
-
-#define VQ_CHECK_LAUNCH(name)                                            \
-    do {                                                                 \
-        hipError_t err__ = hipGetLastError();                            \
-        if (err__ != hipSuccess) return fail(VQHIP_ELAUNCH, name, hipGetErrorString(err__)); \
-    } while (0)
-
-#define VQ_HIP(call)                                                     \
-    do {                                                                 \
-        hipError_t err__ = (call);                                       \
-        if (err__ != hipSuccess) return fail(VQHIP_ELAUNCH, #call, hipGetErrorString(err__)); \
-    } while (0)
 
 // ---- optional per-launch timing of the proposal kernel (bench.py roofline) -------------------------------
 // Events are recorded on the caller's stream right around the coarse_kernel launch; vqhip_profile_collect
 // synchronises on them.  Disabled (zero overhead) unless vqhip_profile_enable(1) was called.
-// Process-wide state is limited to this block and the tuning knobs below; all of it is safe to touch from several host
-// threads (each with its own stream): the profiling list is mutex-protected (the mutex is taken only while profiling is
-// on), the knobs and the per-device attribute cache are atomics.
+// This unit's process-wide state is limited to this block, the tuning knobs below and the per-kernel LdsCache of a launch helper;
+// all of it is safe to touch from several host threads (each with its own stream): the profiling list is mutex-protected (the mutex
+// is taken only while profiling is on), the knobs and the attribute caches (vqhip_host.h) are atomics.
 #include <atomic>
 #include <mutex>
 #include <type_traits>
@@ -69,59 +54,6 @@ static void prof_end(long slot, hipStream_t s) {
     if (slot < 0) return;
     std::lock_guard<std::mutex> lock(g_prof_mu);
     if ((size_t)slot < g_prof_events.size()) (void)hipEventRecord(g_prof_events[slot].second, s);
-}
-
-// hipFuncSetAttribute(MaxDynamicSharedMemorySize) is per device: remember what was set for (kernel, device).
-// Devices beyond the cache simply set the attribute on every call.
-#define VQ_MAX_DEVICES 64
-typedef std::atomic<size_t> LdsCache[VQ_MAX_DEVICES];
-static int ensure_dyn_lds(const void *kern, size_t bytes, LdsCache &set) {
-    int dev = 0;
-    VQ_HIP(hipGetDevice(&dev));
-    const bool cached = dev >= 0 && dev < VQ_MAX_DEVICES;
-    if (!cached || bytes > set[dev].load(std::memory_order_acquire)) {
-        VQ_HIP(hipFuncSetAttribute(kern, hipFuncAttributeMaxDynamicSharedMemorySize, (int)bytes));
-        if (cached) {                                   // keep the maximum (another thread may have raised it meanwhile)
-            size_t cur = set[dev].load(std::memory_order_relaxed);
-            while (cur < bytes && !set[dev].compare_exchange_weak(cur, bytes, std::memory_order_release)) {}
-        }
-    }
-    return VQHIP_OK;
-}
-
-// caller-owned buffers carry their size: an undersized workspace or image is refused here instead of becoming silent
-// device-memory corruption inside a kernel
-#define VQ_NEED(what, have, need)                                                                         \
-    do {                                                                                                  \
-        const int64_t need__ = (need);                                                                    \
-        if ((have) < need__) {                                                                            \
-            char msg__[160];                                                                              \
-            snprintf(msg__, sizeof(msg__), "%lld bytes given, %lld needed", (long long)(have), (long long)need__); \
-            return fail(VQHIP_EINVAL, what, msg__);                                                       \
-        }                                                                                                 \
-    } while (0)
-
-// a refusal with a fixed text ("entry point: what"), and what most entry points refuse
-#define VQ_REQUIRE(cond, text) do { if (!(cond)) return fail(VQHIP_EINVAL, text); } while (0)
-static inline bool vq_public_metric(int m) { return m == VQHIP_METRIC_L2 || m == VQHIP_METRIC_COS || m == VQHIP_METRIC_COS_BF16; }
-static inline bool vq_row_dtype(int t) { return t == VQHIP_DTYPE_F32 || t == VQHIP_DTYPE_BF16; }
-static inline bool vq_float_dtype(int t) { return vq_row_dtype(t) || t == VQHIP_DTYPE_F16; }       // what the activation ops read
-static inline bool vq_dense_layout(int l) { return l == VQHIP_LAYOUT_ROWS || l == VQHIP_LAYOUT_MAP; }
-static inline bool vq_fits_i31(int64_t N, int64_t K) { return N < (1ll << 31) && K < (1ll << 31); }
-
-static inline int waves_grid(int64_t rows, int waves_per_block) {
-    return (int)((rows + waves_per_block - 1) / waves_per_block);
-}
-
-// A float dtype that vq_float_dtype has let through, as a template argument: `fn` is a generic lambda, `decltype(its parameter)
-// ::value` the constant.  Two dtypes nest two calls.  Anything but F32 and BF16 goes to F16.
-template <class Fn>
-static int vq_with_dtype(int dtype, Fn &&fn) {
-    switch (dtype) {
-    case VQHIP_DTYPE_F32: return fn(std::integral_constant<int, VQHIP_DTYPE_F32>{});
-    case VQHIP_DTYPE_BF16: return fn(std::integral_constant<int, VQHIP_DTYPE_BF16>{});
-    default: return fn(std::integral_constant<int, VQHIP_DTYPE_F16>{});
-    }
 }
 
 // ---- proposal-pass dispatch ------------------------------------------------------------------------
@@ -505,296 +437,7 @@ static int launch_hist(const IdxT *idx, int64_t N, int64_t K, int32_t *hist, voi
     return VQHIP_OK;
 }
 
-// ---- fused token sampler: the launch (vqhip_sample_kernels.h) -----------------------------------------------------------
-static LdsCache g_sample_lds[3];
-
-template <int DT>
-static int launch_sample(const VqSampleArgs &a, hipStream_t s) {
-    if (a.V <= VQ_SAMPLE_RESIDENT_MAX) {
-        const size_t lds = (size_t)a.V * sizeof(unsigned int);
-        if (lds > 32768)                                                         // beyond the default budget next to the static part
-            if (int rc = ensure_dyn_lds((const void *)sample_tokens_kernel<DT, true>, lds, g_sample_lds[DT == VQHIP_DTYPE_F32 ? 0 : (DT == VQHIP_DTYPE_BF16 ? 1 : 2)])) return rc;
-        sample_tokens_kernel<DT, true><<<(unsigned)a.Ro, VQ_SAMPLE_THREADS, lds, s>>>(a);
-    } else {
-        sample_tokens_kernel<DT, false><<<(unsigned)a.Ro, VQ_SAMPLE_THREADS, 0, s>>>(a);
-    }
-    VQ_CHECK_LAUNCH("sample_tokens_kernel");
-    return VQHIP_OK;
-}
-
-// ---- fused token cross-entropy: the launches (vqhip_token_ce_kernels.h) ---------------------------------------------------
-template <int DT, bool I64>
-static int launch_token_ce_fwd(const VqCeArgs &a, float *loss, float *lse, int32_t *hit, float *out, hipStream_t s) {
-    token_ce_fwd_kernel<DT, I64><<<(unsigned)a.R, VQ_CE_THREADS, 0, s>>>(a, loss, lse, hit);
-    VQ_CHECK_LAUNCH("token_ce_fwd_kernel");
-    token_ce_reduce_kernel<I64><<<1, VQ_CE_THREADS, 0, s>>>(a, loss, hit, out);
-    VQ_CHECK_LAUNCH("token_ce_reduce_kernel");
-    return VQHIP_OK;
-}
-
-template <int DT, bool I64>
-static int launch_token_ce_bwd(const VqCeArgs &a, const float *lse, const float *g, int g_per_row, const float *wsum, void *grad,
-                               int cols, int64_t row_stride_out, hipStream_t s) {
-    token_ce_bwd_kernel<DT, I64><<<(unsigned)a.R, VQ_CE_THREADS, 0, s>>>(a, lse, g, g_per_row, wsum, grad, cols, row_stride_out);
-    VQ_CHECK_LAUNCH("token_ce_bwd_kernel");
-    return VQHIP_OK;
-}
-
-// ---- fused CosineEmbeddingLoss: the launches (vqhip_cosine_embed_kernels.h) -----------------------------------------------
-template <int DP, int DT>
-static int launch_cosine_embed_fwd(const VqCoseArgs &a, int layout, float *loss, float *stats, float *out, hipStream_t s) {
-    if (layout == VQHIP_LAYOUT_ROWS) {
-        cosine_embed_rows_fwd_kernel<DP, DT><<<(unsigned)((a.R + VQ_COSE_WAVES - 1) / VQ_COSE_WAVES), VQ_COSE_THREADS, 0, s>>>(a, loss, stats);
-        VQ_CHECK_LAUNCH("cosine_embed_rows_fwd_kernel");
-    } else {
-        cosine_embed_map_fwd_kernel<DP, DT><<<(unsigned)((a.R + VQ_COSE_MAP_POS - 1) / VQ_COSE_MAP_POS), VQ_COSE_THREADS, 0, s>>>(a, loss, stats);
-        VQ_CHECK_LAUNCH("cosine_embed_map_fwd_kernel");
-    }
-    cosine_embed_reduce_kernel<<<1, VQ_COSE_THREADS, 0, s>>>(loss, a.R, out);
-    VQ_CHECK_LAUNCH("cosine_embed_reduce_kernel");
-    return VQHIP_OK;
-}
-
-template <int DP, int DT>
-static int launch_cosine_embed_bwd(const VqCoseArgs &a, int layout, const float *stats, const float *g, int g_per_row, int mean,
-                                   void *grad, int64_t grad_stride, hipStream_t s) {
-    if (layout == VQHIP_LAYOUT_ROWS) {
-        cosine_embed_rows_bwd_kernel<DP, DT><<<(unsigned)((a.R + VQ_COSE_WAVES - 1) / VQ_COSE_WAVES), VQ_COSE_THREADS, 0, s>>>(
-            a, stats, g, g_per_row, mean, grad, grad_stride);
-        VQ_CHECK_LAUNCH("cosine_embed_rows_bwd_kernel");
-    } else {
-        cosine_embed_map_bwd_kernel<DP, DT><<<(unsigned)((a.R + VQ_COSE_MAP_POS - 1) / VQ_COSE_MAP_POS), VQ_COSE_THREADS, 0, s>>>(
-            a, stats, g, g_per_row, mean, grad);
-        VQ_CHECK_LAUNCH("cosine_embed_map_bwd_kernel");
-    }
-    return VQHIP_OK;
-}
-
-// ---- fused LPIPS tail: the launches (vqhip_lpips_kernels.h) ----------------------------------------------------------------
-static unsigned lpips_grid(const VqLpipsArgs &a, int layout) {
-    return layout == VQHIP_LAYOUT_ROWS ? (unsigned)((a.B * a.P + VQ_LPIPS_ROWS - 1) / VQ_LPIPS_ROWS) : (unsigned)(a.B * a.tiles);
-}
-
-template <int DP, int DT>
-static int launch_lpips_fwd(const VqLpipsArgs &a, int layout, float *stats, float *value, int accumulate, hipStream_t s) {
-    if (layout == VQHIP_LAYOUT_ROWS) {
-        lpips_rows_fwd_kernel<DP, DT><<<lpips_grid(a, layout), VQ_LPIPS_THREADS, 0, s>>>(a, stats);
-        VQ_CHECK_LAUNCH("lpips_rows_fwd_kernel");
-    } else {
-        lpips_map_fwd_kernel<DP, DT><<<lpips_grid(a, layout), VQ_LPIPS_THREADS, 0, s>>>(a, stats);
-        VQ_CHECK_LAUNCH("lpips_map_fwd_kernel");
-    }
-    lpips_reduce_kernel<<<(unsigned)a.B, VQ_LPIPS_THREADS, 0, s>>>(stats, a.P, accumulate, value);
-    VQ_CHECK_LAUNCH("lpips_reduce_kernel");
-    return VQHIP_OK;
-}
-
-template <int DP, int DT>
-static int launch_lpips_bwd(const VqLpipsArgs &a, int layout, const float *stats, const float *g_out, void *grad, hipStream_t s) {
-    if (layout == VQHIP_LAYOUT_ROWS) {
-        lpips_rows_bwd_kernel<DP, DT><<<lpips_grid(a, layout), VQ_LPIPS_THREADS, 0, s>>>(a, stats, g_out, grad);
-        VQ_CHECK_LAUNCH("lpips_rows_bwd_kernel");
-    } else {
-        lpips_map_bwd_kernel<DP, DT><<<lpips_grid(a, layout), VQ_LPIPS_THREADS, 0, s>>>(a, stats, g_out, grad);
-        VQ_CHECK_LAUNCH("lpips_map_bwd_kernel");
-    }
-    return VQHIP_OK;
-}
-
-// ---- StyleGAN2 discriminator ops: the launches (vqhip_stylegan2_kernels.h) ---------------------------------------------------
-template <int DT>
-static int launch_bias_act_fwd(const VqBiasActArgs &a, bool rows, hipStream_t s) {
-    const int64_t pieces = (a.n + SampleElem<DT>::W - 1) / SampleElem<DT>::W;
-    const int64_t blocks = (pieces + VQ_SG2_THREADS - 1) / VQ_SG2_THREADS;
-    const unsigned grid = (unsigned)(blocks < 8192 ? blocks : 8192);
-    if (rows) bias_act_fwd_kernel<DT, true><<<grid, VQ_SG2_THREADS, 0, s>>>(a);
-    else bias_act_fwd_kernel<DT, false><<<grid, VQ_SG2_THREADS, 0, s>>>(a);
-    VQ_CHECK_LAUNCH("bias_act_fwd_kernel");
-    return VQHIP_OK;
-}
-
-static int launch_sg2_reduce(const float *ws, int64_t slabs, int C, float *gbias, hipStream_t s) {
-    sg2_reduce_kernel<<<(unsigned)((C + VQ_SG2_RED - 1) / VQ_SG2_RED), VQ_SG2_THREADS, 0, s>>>(ws, slabs, C, gbias);
-    VQ_CHECK_LAUNCH("sg2_reduce_kernel");
-    return VQHIP_OK;
-}
-
-template <int DT>
-static int launch_bias_act_bwd(const VqBiasActArgs &a, bool rows, int64_t slabs, float *gbias, hipStream_t s) {
-    if (rows) {
-        const int per = 64 * SampleElem<DT>::W;
-        bias_act_bwd_rows_kernel<DT><<<dim3((unsigned)slabs, (unsigned)((a.C + per - 1) / per)), VQ_SG2_THREADS, 0, s>>>(a);
-        VQ_CHECK_LAUNCH("bias_act_bwd_rows_kernel");
-    } else {
-        bias_act_bwd_map_kernel<DT><<<(unsigned)((int64_t)a.B * a.C * a.chunks), VQ_SG2_THREADS, 0, s>>>(a);
-        VQ_CHECK_LAUNCH("bias_act_bwd_map_kernel");
-    }
-    return gbias ? launch_sg2_reduce(a.ws, slabs, a.C, gbias, s) : VQHIP_OK;
-}
-
-template <int DT, bool ROWS, int DOWN, int FUSED>
-static int launch_fir4_one(const VqFirArgs &a, hipStream_t s) {
-    const int64_t grid = (int64_t)a.B * a.cblocks * a.tiles_y * a.tiles_x;
-    fir4_kernel<DT, ROWS, DOWN, FUSED><<<(unsigned)grid, VQ_SG2_THREADS, 0, s>>>(a);
-    VQ_CHECK_LAUNCH("fir4_kernel");
-    return VQHIP_OK;
-}
-
-template <int DT>
-static int launch_fir4(const VqFirArgs &a, bool rows, int down, int fused, hipStream_t s) {
-#define VQ_FIR_CASE(R, D, F) if (rows == R && down == D && fused == F) return launch_fir4_one<DT, R, D, F>(a, s)
-    VQ_FIR_CASE(false, 1, VQ_FIR_NONE); VQ_FIR_CASE(false, 1, VQ_FIR_ACT_IN); VQ_FIR_CASE(false, 1, VQ_FIR_MASK_OUT);
-    VQ_FIR_CASE(false, 2, VQ_FIR_NONE); VQ_FIR_CASE(false, 2, VQ_FIR_ACT_IN);
-    VQ_FIR_CASE(true, 1, VQ_FIR_NONE); VQ_FIR_CASE(true, 1, VQ_FIR_ACT_IN); VQ_FIR_CASE(true, 1, VQ_FIR_MASK_OUT);
-    VQ_FIR_CASE(true, 2, VQ_FIR_NONE); VQ_FIR_CASE(true, 2, VQ_FIR_ACT_IN);
-#undef VQ_FIR_CASE
-    return fail(VQHIP_EINVAL, "fir4", "no kernel of this form");
-}
-
-// the adjoint blur; in the fused form (a.x) it masks on the way out and the bias gradient follows from its slabs
-template <int DT>
-static int fir4_bwd_run(const VqFirArgs &a, bool rows, float *gbias, hipStream_t s) {
-    if (int rc = launch_fir4<DT>(a, rows, 1, a.x ? VQ_FIR_MASK_OUT : VQ_FIR_NONE, s)) return rc;
-    return a.x ? launch_sg2_reduce(a.ws, (int64_t)a.B * a.tiles_y * a.tiles_x, a.C, gbias, s) : VQHIP_OK;
-}
-
-// ---- GroupNorm (+ SiLU): the launches (vqhip_group_norm_kernels.h) -------------------------------------------------------------
-template <int DT, bool ROWS, int PW>
-static int launch_gn_one(const VqGnArgs &a, int T, bool bwd, hipStream_t s) {
-    const unsigned grid = (unsigned)(T == 64 ? (a.units + 3) / 4 : a.units);
-    if (T == 64) {
-        if (bwd) gn_bwd_kernel<DT, ROWS, PW, 64><<<grid, VQ_GN_THREADS, 0, s>>>(a);
-        else gn_fwd_kernel<DT, ROWS, PW, 64><<<grid, VQ_GN_THREADS, 0, s>>>(a);
-    } else {
-        if (bwd) gn_bwd_kernel<DT, ROWS, PW, 256><<<grid, VQ_GN_THREADS, 0, s>>>(a);
-        else gn_fwd_kernel<DT, ROWS, PW, 256><<<grid, VQ_GN_THREADS, 0, s>>>(a);
-    }
-    VQ_CHECK_LAUNCH(bwd ? "gn_bwd_kernel" : "gn_fwd_kernel");
-    return VQHIP_OK;
-}
-
-// the piece of the rows layout: the widest of 16 bytes, 8 bytes or one element that divides the channels of a group
-template <int DT>
-static int launch_gn(const VqGnArgs &a, bool rows, int T, bool bwd, hipStream_t s) {
-    constexpr int W = SampleElem<DT>::W;
-    if (!rows) return launch_gn_one<DT, false, W>(a, T, bwd, s);
-    if (a.cpg % W == 0) return launch_gn_one<DT, true, W>(a, T, bwd, s);
-    if (W == 8 && a.cpg % 4 == 0) return launch_gn_one<DT, true, 4>(a, T, bwd, s);
-    return launch_gn_one<DT, true, 1>(a, T, bwd, s);
-}
-
-// one launch where a group is one chunk; else the partials, and behind the launch boundary their combination and the result
-template <int DT>
-static int gn_run(VqGnArgs a, bool rows, int T, bool bwd, int64_t slabs, float *dgamma, float *dbeta, hipStream_t s) {
-    if (a.S == 1) {
-        a.phase = VQ_GN_ALL;
-        if (int rc = launch_gn<DT>(a, rows, T, bwd, s)) return rc;
-    } else {
-        a.phase = VQ_GN_PART;
-        if (int rc = launch_gn<DT>(a, rows, T, bwd, s)) return rc;
-        a.phase = VQ_GN_APPLY;
-        if (int rc = launch_gn<DT>(a, rows, T, bwd, s)) return rc;
-    }
-    if (!bwd) return VQHIP_OK;
-    if (int rc = launch_sg2_reduce(a.ws_dg, slabs, a.C, dgamma, s)) return rc;
-    return launch_sg2_reduce(a.ws_db, slabs, a.C, dbeta, s);
-}
-
-// batch statistics: one launch where a channel is one chunk; else the partials, their combination, the result
-template <int DT, int PW>
-static int launch_bn_one(const VqBnArgs &a, bool rows, bool bwd, unsigned grid, hipStream_t s) {
-    if (rows) {
-        if (bwd) bn_rows_bwd_kernel<DT, PW><<<grid, VQ_GN_THREADS, 0, s>>>(a);
-        else bn_rows_fwd_kernel<DT, PW><<<grid, VQ_GN_THREADS, 0, s>>>(a);
-    } else {
-        if (bwd) bn_map_bwd_kernel<DT, PW><<<grid, VQ_GN_THREADS, 0, s>>>(a);
-        else bn_map_fwd_kernel<DT, PW><<<grid, VQ_GN_THREADS, 0, s>>>(a);
-    }
-    VQ_CHECK_LAUNCH(bwd ? "bn_bwd_kernel" : "bn_fwd_kernel");
-    return VQHIP_OK;
-}
-
-template <int DT>
-static int launch_bn(const VqBnArgs &a, bool rows, int pw, bool bwd, unsigned grid, hipStream_t s) {
-    constexpr int W = SampleElem<DT>::W;
-    if (!rows || pw == W) return launch_bn_one<DT, W>(a, rows, bwd, grid, s);
-    if (W == 8 && pw == 4) return launch_bn_one<DT, 4>(a, rows, bwd, grid, s);
-    return launch_bn_one<DT, 1>(a, rows, bwd, grid, s);
-}
-
-template <int DT>
-static int bn_run(VqBnArgs a, bool rows, int pw, bool bwd, unsigned grid, hipStream_t s) {
-    if (a.S == 1) {
-        a.phase = VQ_GN_ALL;
-        return launch_bn<DT>(a, rows, pw, bwd, grid, s);
-    }
-    a.phase = VQ_GN_PART;
-    if (int rc = launch_bn<DT>(a, rows, pw, bwd, grid, s)) return rc;
-    bn_combine_kernel<<<(unsigned)a.C, VQ_GN_THREADS, 0, s>>>(a, bwd ? 1 : 0);
-    VQ_CHECK_LAUNCH("bn_combine_kernel");
-    a.phase = VQ_GN_APPLY;
-    return launch_bn<DT>(a, rows, pw, bwd, grid, s);
-}
-
-// ---- the row ops of the VQ-KD networks: the launches (vqhip_vit_kernels.h) ---------------------------------------------------------
-template <int XDT, int YDT, int PW, bool RMS>
-static int launch_ln_one(const VqLnArgs &a, bool bwd, hipStream_t s) {
-    if (a.D <= VQ_GN_SMALL) {
-        if (bwd) ln_bwd_kernel<XDT, YDT, PW, 64, RMS><<<(unsigned)((a.R + VQ_LN_SLAB - 1) / VQ_LN_SLAB), VQ_LN_THREADS, 0, s>>>(a);
-        else ln_fwd_kernel<XDT, YDT, PW, 64, RMS><<<(unsigned)((a.R + 3) / 4), VQ_LN_THREADS, 0, s>>>(a);
-    } else {
-        if (bwd) ln_bwd_kernel<XDT, YDT, PW, 256, RMS><<<(unsigned)((a.R + VQ_LN_SLAB - 1) / VQ_LN_SLAB), VQ_LN_THREADS, 0, s>>>(a);
-        else ln_fwd_kernel<XDT, YDT, PW, 256, RMS><<<(unsigned)a.R, VQ_LN_THREADS, 0, s>>>(a);
-    }
-    VQ_CHECK_LAUNCH(bwd ? "ln_bwd_kernel" : "ln_fwd_kernel");
-    return VQHIP_OK;
-}
-
-// the piece: 16 bytes of the narrowest dtype where they divide the row, else four elements, else one
-template <int XDT, int YDT, bool RMS>
-static int launch_ln(const VqLnArgs &a, bool bwd, hipStream_t s) {
-    if constexpr (XDT == YDT || XDT == VQHIP_DTYPE_F32) {
-        if constexpr (XDT != VQHIP_DTYPE_F32)
-            if (a.D % 8 == 0) return launch_ln_one<XDT, YDT, 8, RMS>(a, bwd, s);
-        if (a.D % 4 == 0) return launch_ln_one<XDT, YDT, 4, RMS>(a, bwd, s);
-        return launch_ln_one<XDT, YDT, 1, RMS>(a, bwd, s);
-    } else {
-        return fail(VQHIP_EINVAL, "add_layer_norm", "no kernel of this dtype combination");
-    }
-}
-
-template <int DT>
-static int launch_row_act(const VqRowActArgs &a, int act, bool bwd, int64_t slabs, float *dbias, hipStream_t s) {
-    if (act == VQHIP_ROW_ACT_SWIGLU) {                                          // both directions: the forward's grid over the [R, F] side
-        const int64_t pieces = (a.R * a.D + SampleElem<DT>::W - 1) / SampleElem<DT>::W;
-        const int64_t blocks = (pieces + VQ_SG2_THREADS - 1) / VQ_SG2_THREADS;
-        const unsigned grid = (unsigned)(blocks < 8192 ? blocks : 8192);
-        if (bwd) swiglu_kernel<DT, true><<<grid, VQ_SG2_THREADS, 0, s>>>(a);
-        else swiglu_kernel<DT, false><<<grid, VQ_SG2_THREADS, 0, s>>>(a);
-        VQ_CHECK_LAUNCH("swiglu_kernel");
-        return VQHIP_OK;
-    }
-    if (!bwd) {
-        const int64_t pieces = (a.R * a.D + SampleElem<DT>::W - 1) / SampleElem<DT>::W;
-        const int64_t blocks = (pieces + VQ_SG2_THREADS - 1) / VQ_SG2_THREADS;
-        const unsigned grid = (unsigned)(blocks < 8192 ? blocks : 8192);
-        if (act == VQHIP_ROW_ACT_GELU) row_act_fwd_kernel<DT, VQHIP_ROW_ACT_GELU><<<grid, VQ_SG2_THREADS, 0, s>>>(a);
-        else row_act_fwd_kernel<DT, VQHIP_ROW_ACT_TANH><<<grid, VQ_SG2_THREADS, 0, s>>>(a);
-        VQ_CHECK_LAUNCH("row_act_fwd_kernel");
-        return VQHIP_OK;
-    }
-    const int per = 64 * SampleElem<DT>::W;
-    const dim3 grid((unsigned)slabs, (unsigned)((a.D + per - 1) / per));
-    if (act == VQHIP_ROW_ACT_GELU) row_act_bwd_kernel<DT, VQHIP_ROW_ACT_GELU><<<grid, VQ_SG2_THREADS, 0, s>>>(a);
-    else row_act_bwd_kernel<DT, VQHIP_ROW_ACT_TANH><<<grid, VQ_SG2_THREADS, 0, s>>>(a);
-    VQ_CHECK_LAUNCH("row_act_bwd_kernel");
-    return dbias ? launch_sg2_reduce(a.ws, slabs, a.D, dbias, s) : VQHIP_OK;
-}
-
 extern "C" {
-
-int vqhip_version(void) { return VQHIP_VERSION; }
-const char *vqhip_last_error(void) { return g_err; }
 
 int64_t vqhip_codebook_exact_offset(int64_t K, int D) {
     if (K <= 0 || D <= 0) return -1;
@@ -1528,764 +1171,6 @@ int vqhip_fsq_decode_pool(const vqhip_fsq_t *q, const void *quant, int quant_dty
     return VQHIP_OK;
 }
 
-// ---- fused token sampler (vqhip_sample_kernels.h) ---------------------------------------------------------------------------
-int vqhip_sample_tokens(const void *logits, int dtype, int64_t R, int64_t row_stride, int64_t start, int64_t end, float cfg_alpha,
-                        int cfg, float temperature, int top_k, float top_p, const float *u, int64_t *tokens,
-                        vqhip_sample_cut_t *cut, void *stream) {
-    VQ_REQUIRE(logits && u && tokens, "vqhip_sample_tokens: logits, u and tokens are required");
-    VQ_REQUIRE(vq_float_dtype(dtype), "vqhip_sample_tokens: dtype");
-    VQ_REQUIRE(R >= 1 && R < (1ll << 31), "vqhip_sample_tokens: R must be in 1 .. 2^31 - 1");
-    VQ_REQUIRE(!cfg || R % 2 == 0, "vqhip_sample_tokens: R must be even under CFG");
-    VQ_REQUIRE(start >= 0 && start < end && end <= row_stride, "vqhip_sample_tokens: need 0 <= start < end <= row_stride");
-    VQ_REQUIRE(end - start <= VQ_SAMPLE_MAX_V, "vqhip_sample_tokens: end - start is beyond 2^20");
-    VQ_REQUIRE(temperature - temperature == 0.0f && temperature > 0.0f, "vqhip_sample_tokens: the temperature must be finite and > 0");
-    VQ_REQUIRE(!cfg || cfg_alpha - cfg_alpha == 0.0f, "vqhip_sample_tokens: alpha must be finite");
-    VqSampleArgs a;
-    a.logits = logits; a.row_stride = row_stride; a.start = start;
-    a.V = (int)(end - start);
-    a.Ro = (int)(cfg ? R / 2 : R);
-    a.cfg = cfg ? 1 : 0;
-    a.w_uncond = (float)(1.0 - (double)cfg_alpha); a.w_cond = cfg_alpha;
-    a.temperature = temperature;
-    a.k = top_k <= 0 ? 0 : (top_k < a.V ? top_k : a.V);
-    a.use_top_p = (top_p >= 0.0f && top_p <= 1.0f) ? 1 : 0;
-    a.one_minus_p = 1.0 - (double)top_p;
-    a.u = u; a.tokens = tokens; a.cut = cut;
-    return vq_with_dtype(dtype, [&](auto dt) { return launch_sample<decltype(dt)::value>(a, (hipStream_t)stream); });
-}
-
-// ---- fused token cross-entropy (vqhip_token_ce_kernels.h) -----------------------------------------------------------------
-// what the two entry points refuse alike, and the arguments the kernels share
-static int token_ce_setup(const char *what, const void *logits, int dtype, int64_t R, int64_t row_stride, int64_t start, int64_t end,
-                          const void *targets, int target_dtype, int64_t shift_len, int64_t ignore_index, float eps,
-                          const float *weight, VqCeArgs *a) {
-    if (!logits || !targets) return fail(VQHIP_EINVAL, what, "logits and targets are required");
-    if (!vq_float_dtype(dtype)) return fail(VQHIP_EINVAL, what, "dtype");
-    if (target_dtype != VQHIP_DTYPE_I32 && target_dtype != VQHIP_DTYPE_I64) return fail(VQHIP_EINVAL, what, "target_dtype");
-    if (R < 1 || R >= (1ll << 31)) return fail(VQHIP_EINVAL, what, "R must be in 1 .. 2^31 - 1");
-    if (!(start >= 0 && start < end && end <= row_stride)) return fail(VQHIP_EINVAL, what, "need 0 <= start < end <= row_stride");
-    if (end - start > VQ_CE_MAX_V) return fail(VQHIP_EINVAL, what, "end - start is beyond 2^20");
-    if (!(eps >= 0.0f && eps < 1.0f)) return fail(VQHIP_EINVAL, what, "label_smoothing must be in [0, 1)");
-    if (shift_len < 0 || (shift_len > 0 && R % shift_len != 0)) return fail(VQHIP_EINVAL, what, "shift_len must be 0 or divide R");
-    a->logits = logits; a->row_stride = row_stride; a->start = start;
-    a->V = (int)(end - start);
-    a->R = R;
-    a->targets = targets; a->shift_len = shift_len; a->ignore_index = ignore_index;
-    a->eps = eps; a->one_minus_eps = (float)(1.0 - (double)eps); a->eps_over_v = eps / (float)a->V;
-    a->weight = weight;
-    return VQHIP_OK;
-}
-
-int vqhip_token_ce_fwd(const void *logits, int dtype, int64_t R, int64_t row_stride, int64_t start, int64_t end, const void *targets,
-                       int target_dtype, int64_t shift_len, int64_t ignore_index, float label_smoothing, const float *weight,
-                       float *loss, float *lse, int32_t *hit, float *out, void *stream) {
-    VqCeArgs a;
-    if (int rc = token_ce_setup("vqhip_token_ce_fwd", logits, dtype, R, row_stride, start, end, targets, target_dtype, shift_len,
-                                ignore_index, label_smoothing, weight, &a)) return rc;
-    VQ_REQUIRE(loss && lse && out, "vqhip_token_ce_fwd: loss, lse and out are required");
-    hipStream_t s = (hipStream_t)stream;
-    return vq_with_dtype(dtype, [&](auto dt) {
-        constexpr int DT = decltype(dt)::value;
-        return target_dtype == VQHIP_DTYPE_I64 ? launch_token_ce_fwd<DT, true>(a, loss, lse, hit, out, s)
-                                               : launch_token_ce_fwd<DT, false>(a, loss, lse, hit, out, s);
-    });
-}
-
-int vqhip_token_ce_bwd(const void *logits, int dtype, int64_t R, int64_t row_stride, int64_t start, int64_t end, const void *targets,
-                       int target_dtype, int64_t shift_len, int64_t ignore_index, float label_smoothing, const float *weight,
-                       const float *lse, const float *g, int g_per_row, const float *wsum, void *grad, int64_t cols,
-                       int64_t row_stride_out, void *stream) {
-    VqCeArgs a;
-    if (int rc = token_ce_setup("vqhip_token_ce_bwd", logits, dtype, R, row_stride, start, end, targets, target_dtype, shift_len,
-                                ignore_index, label_smoothing, weight, &a)) return rc;
-    VQ_REQUIRE(lse && g && grad, "vqhip_token_ce_bwd: lse, g and grad are required");
-    VQ_REQUIRE(end <= cols && cols <= row_stride_out && cols < (1ll << 31), "vqhip_token_ce_bwd: need end <= cols <= row_stride_out, cols < 2^31");
-    hipStream_t s = (hipStream_t)stream;
-    return vq_with_dtype(dtype, [&](auto dt) {
-        constexpr int DT = decltype(dt)::value;
-        return target_dtype == VQHIP_DTYPE_I64 ? launch_token_ce_bwd<DT, true>(a, lse, g, g_per_row ? 1 : 0, wsum, grad, (int)cols, row_stride_out, s)
-                                               : launch_token_ce_bwd<DT, false>(a, lse, g, g_per_row ? 1 : 0, wsum, grad, (int)cols, row_stride_out, s);
-    });
-}
-
-// ---- fused CosineEmbeddingLoss (vqhip_cosine_embed_kernels.h) --------------------------------------------------------------
-// what the two entry points refuse alike, and the arguments the kernels share
-static int cosine_embed_setup(const char *what, const void *pred, int pred_dtype, int pred_layout, int64_t pred_row_stride,
-                              const void *target, int target_dtype, int64_t target_row_stride, int64_t B, int64_t P, int64_t C,
-                              VqCoseArgs *a) {
-    if (!pred || !target) return fail(VQHIP_EINVAL, what, "pred and target are required");
-    if (!vq_float_dtype(pred_dtype) || !vq_float_dtype(target_dtype)) return fail(VQHIP_EINVAL, what, "dtype");
-    if (!vq_dense_layout(pred_layout)) return fail(VQHIP_EINVAL, what, "pred_layout");
-    const int64_t cap = 1ll << 31;
-    if (B < 1 || P < 1 || B >= cap || P >= cap || B * P >= cap) return fail(VQHIP_EINVAL, what, "R = B * P must be in 1 .. 2^31 - 1");
-    if (C < 1 || C > VQHIP_COSINE_EMBED_MAX_C) return fail(VQHIP_EINVAL, what, "C must be in 1 .. 2^16");
-    if (target_row_stride < C || (pred_layout == VQHIP_LAYOUT_ROWS && pred_row_stride < C))
-        return fail(VQHIP_EINVAL, what, "a row stride is below C");
-    a->pred = pred; a->target = target;
-    a->pred_stride = pred_row_stride; a->target_stride = target_row_stride;
-    a->R = B * P; a->P = P; a->C = (int)C;
-    return VQHIP_OK;
-}
-
-int vqhip_cosine_embed_fwd(const void *pred, int pred_dtype, int pred_layout, int64_t pred_row_stride, const void *target,
-                           int target_dtype, int64_t target_row_stride, int64_t B, int64_t P, int64_t C, float *loss, float *stats,
-                           float *out, void *stream) {
-    VqCoseArgs a;
-    if (int rc = cosine_embed_setup("vqhip_cosine_embed_fwd", pred, pred_dtype, pred_layout, pred_row_stride, target, target_dtype,
-                                    target_row_stride, B, P, C, &a)) return rc;
-    VQ_REQUIRE(loss && stats && out, "vqhip_cosine_embed_fwd: loss, stats and out are required");
-    return vq_with_dtype(pred_dtype, [&](auto dp) { return vq_with_dtype(target_dtype, [&](auto dt) {
-        return launch_cosine_embed_fwd<decltype(dp)::value, decltype(dt)::value>(a, pred_layout, loss, stats, out, (hipStream_t)stream);
-    }); });
-}
-
-int vqhip_cosine_embed_bwd(const void *pred, int pred_dtype, int pred_layout, int64_t pred_row_stride, const void *target,
-                           int target_dtype, int64_t target_row_stride, int64_t B, int64_t P, int64_t C, const float *stats,
-                           const float *g, int g_per_row, int mean, void *grad, int64_t grad_row_stride, void *stream) {
-    VqCoseArgs a;
-    if (int rc = cosine_embed_setup("vqhip_cosine_embed_bwd", pred, pred_dtype, pred_layout, pred_row_stride, target, target_dtype,
-                                    target_row_stride, B, P, C, &a)) return rc;
-    VQ_REQUIRE(stats && g && grad, "vqhip_cosine_embed_bwd: stats, g and grad are required");
-    VQ_REQUIRE(pred_layout != VQHIP_LAYOUT_ROWS || grad_row_stride >= C, "vqhip_cosine_embed_bwd: the row stride of grad is below C");
-    return vq_with_dtype(pred_dtype, [&](auto dp) { return vq_with_dtype(target_dtype, [&](auto dt) {
-        return launch_cosine_embed_bwd<decltype(dp)::value, decltype(dt)::value>(a, pred_layout, stats, g, g_per_row ? 1 : 0, mean ? 1 : 0, grad,
-                                                                                 grad_row_stride, (hipStream_t)stream);
-    }); });
-}
-
-// ---- fused LPIPS tail (vqhip_lpips_kernels.h) -------------------------------------------------------------------------------
-// what the dropout of the three entry points refuses, and its threshold and scale
-static int lpips_dropout(const char *what, const uint32_t *seed, float p, int64_t layer, VqLpipsArgs *a) {
-    if (layer < 0 || layer > VQHIP_LPIPS_MAX_LAYER) return fail(VQHIP_EINVAL, what, "layer must be in 0 .. 2^16");
-    a->seed = seed; a->layer = (uint32_t)layer; a->thr = 0u; a->scale = 1.0f;
-    if (!seed) return VQHIP_OK;
-    if (!(p >= 0.0f && p < 1.0f)) return fail(VQHIP_EINVAL, what, "p must be in [0, 1)");
-    a->thr = (uint32_t)ceil((double)p * 4294967296.0);                          // p < 1 in fp32: at most 2^32 - 256
-    a->scale = 1.0f / (1.0f - p);
-    return VQHIP_OK;
-}
-
-static int lpips_sizes(const char *what, int64_t B, int64_t C, int64_t P, VqLpipsArgs *a) {
-    const int64_t cap = 1ll << 31;
-    if (B < 1 || P < 1 || B >= cap || P >= cap || B * P >= cap) return fail(VQHIP_EINVAL, what, "B * P must be in 1 .. 2^31 - 1");
-    if (C < 1 || C > VQHIP_LPIPS_MAX_C) return fail(VQHIP_EINVAL, what, "C must be in 1 .. 2^16");
-    a->B = B; a->P = P; a->C = (int)C;
-    a->tiles = (P + VQ_LPIPS_MAP_POS - 1) / VQ_LPIPS_MAP_POS;
-    if (B * a->tiles >= cap) return fail(VQHIP_EINVAL, what, "B * ceil(P / 64) must be below 2^31");
-    return VQHIP_OK;
-}
-
-// what the forward and the backward refuse alike, and the arguments the kernels share
-static int lpips_setup(const char *what, const void *pred, int pred_dtype, const void *target, int target_dtype, int layout, int64_t B,
-                       int64_t C, int64_t P, const float *w, const uint32_t *seed, float p, int64_t layer, VqLpipsArgs *a) {
-    if (!pred || !target || !w) return fail(VQHIP_EINVAL, what, "pred, target and w are required");
-    if (!vq_float_dtype(pred_dtype) || !vq_float_dtype(target_dtype)) return fail(VQHIP_EINVAL, what, "dtype");
-    if (!vq_dense_layout(layout)) return fail(VQHIP_EINVAL, what, "layout");
-    if (int rc = lpips_sizes(what, B, C, P, a)) return rc;
-    if (int rc = lpips_dropout(what, seed, p, layer, a)) return rc;
-    a->pred = pred; a->target = target; a->w = w;
-    return VQHIP_OK;
-}
-
-int vqhip_lpips_fwd(const void *pred, int pred_dtype, const void *target, int target_dtype, int layout, int64_t B, int64_t C,
-                    int64_t P, const float *w, const uint32_t *seed, float p, int64_t layer, float *stats, float *value,
-                    int accumulate, void *stream) {
-    VqLpipsArgs a;
-    if (int rc = lpips_setup("vqhip_lpips_fwd", pred, pred_dtype, target, target_dtype, layout, B, C, P, w, seed, p, layer, &a)) return rc;
-    VQ_REQUIRE(stats && value, "vqhip_lpips_fwd: stats and value are required");
-    return vq_with_dtype(pred_dtype, [&](auto dp) { return vq_with_dtype(target_dtype, [&](auto dt) {
-        return launch_lpips_fwd<decltype(dp)::value, decltype(dt)::value>(a, layout, stats, value, accumulate ? 1 : 0, (hipStream_t)stream);
-    }); });
-}
-
-int vqhip_lpips_bwd(const void *pred, int pred_dtype, const void *target, int target_dtype, int layout, int64_t B, int64_t C,
-                    int64_t P, const float *w, const uint32_t *seed, float p, int64_t layer, const float *stats, const float *g_out,
-                    void *grad, void *stream) {
-    VqLpipsArgs a;
-    if (int rc = lpips_setup("vqhip_lpips_bwd", pred, pred_dtype, target, target_dtype, layout, B, C, P, w, seed, p, layer, &a)) return rc;
-    VQ_REQUIRE(stats && g_out && grad, "vqhip_lpips_bwd: stats, g_out and grad are required");
-    return vq_with_dtype(pred_dtype, [&](auto dp) { return vq_with_dtype(target_dtype, [&](auto dt) {
-        return launch_lpips_bwd<decltype(dp)::value, decltype(dt)::value>(a, layout, stats, g_out, grad, (hipStream_t)stream);
-    }); });
-}
-
-int vqhip_lpips_keep_mask(const uint32_t *seed, float p, int64_t layer, int64_t B, int64_t C, int64_t P, uint8_t *out, void *stream) {
-    const char *what = "vqhip_lpips_keep_mask";
-    VqLpipsArgs a;
-    if (!seed || !out) return fail(VQHIP_EINVAL, what, "seed and out are required");
-    if (int rc = lpips_sizes(what, B, C, P, &a)) return rc;
-    if (int rc = lpips_dropout(what, seed, p, layer, &a)) return rc;
-    const int64_t n = B * C * P;                                                // below 2^47
-    const int64_t blocks = (n + VQ_LPIPS_THREADS - 1) / VQ_LPIPS_THREADS;
-    lpips_keep_mask_kernel<<<(unsigned)(blocks < 65536 ? blocks : 65536), VQ_LPIPS_THREADS, 0, (hipStream_t)stream>>>(seed, a.layer, a.thr, n, out);
-    VQ_CHECK_LAUNCH("lpips_keep_mask_kernel");
-    return VQHIP_OK;
-}
-
-// ---- StyleGAN2 discriminator ops (vqhip_stylegan2_kernels.h) -----------------------------------------------------------------
-// what every entry point of the block refuses alike
-static int sg2_common(const char *what, int dtype, int layout, int64_t B, int64_t C, int64_t P) {
-    if (!vq_float_dtype(dtype)) return fail(VQHIP_EINVAL, what, "dtype");
-    if (!vq_dense_layout(layout)) return fail(VQHIP_EINVAL, what, "layout");
-    const int64_t cap = 1ll << 31;
-    if (B < 1 || C < 1 || P < 1 || B >= cap || P >= cap || C > VQHIP_SG2_MAX_C) return fail(VQHIP_EINVAL, what, "need B, P >= 1 and 1 <= C <= 2^16");
-    if (B * P >= cap || B * P * C >= cap) return fail(VQHIP_EINVAL, what, "B * C * P must be below 2^31");
-    return VQHIP_OK;
-}
-
-// a [B, C] matrix (P == 1) is the same memory in both layouts: it takes the rows kernels
-static inline bool sg2_rows(int layout, int64_t P) { return layout == VQHIP_LAYOUT_ROWS || P == 1; }
-
-int64_t vqhip_bias_act_slabs(int layout, int64_t B, int64_t C, int64_t P) {
-    if (sg2_common("vqhip_bias_act_slabs", VQHIP_DTYPE_F32, layout, B, C, P)) return -1;
-    if (sg2_rows(layout, P)) return (B * P + VQ_SG2_ROWS_SLAB - 1) / VQ_SG2_ROWS_SLAB;
-    return B * ((P + VQ_SG2_MAP_CHUNK - 1) / VQ_SG2_MAP_CHUNK);
-}
-
-int vqhip_bias_act_fwd(const void *x, int dtype, int layout, int64_t B, int64_t C, int64_t P, const float *bias, void *y, void *stream) {
-    if (int rc = sg2_common("vqhip_bias_act_fwd", dtype, layout, B, C, P)) return rc;
-    VQ_REQUIRE(x && bias && y, "vqhip_bias_act_fwd: x, bias and y are required");
-    VqBiasActArgs a = {};
-    a.x = x; a.bias = bias; a.out = y; a.n = B * C * P; a.B = (int)B; a.C = (int)C; a.P = (int)P;
-    return vq_with_dtype(dtype, [&](auto dt) { return launch_bias_act_fwd<decltype(dt)::value>(a, sg2_rows(layout, P), (hipStream_t)stream); });
-}
-
-int vqhip_bias_act_bwd(const void *g, const void *y, int dtype, int layout, int64_t B, int64_t C, int64_t P, void *gx, float *gbias,
-                       float *ws, int64_t ws_bytes, void *stream) {
-    if (int rc = sg2_common("vqhip_bias_act_bwd", dtype, layout, B, C, P)) return rc;
-    VQ_REQUIRE(g && y && gx, "vqhip_bias_act_bwd: g, y and gx are required");
-    VQ_REQUIRE(!gbias || ws, "vqhip_bias_act_bwd: gbias needs the workspace");
-    const int64_t slabs = vqhip_bias_act_slabs(layout, B, C, P);
-    if (gbias) VQ_NEED("vqhip_bias_act_bwd: ws too small", ws_bytes, slabs * C * (int64_t)sizeof(float));
-    VQ_REQUIRE(B * C * ((P + VQ_SG2_MAP_CHUNK - 1) / VQ_SG2_MAP_CHUNK) < (1ll << 31), "vqhip_bias_act_bwd: B * C * ceil(P / 4096) is beyond one launch");
-    VqBiasActArgs a = {};
-    a.x = g; a.y = y; a.out = gx; a.ws = gbias ? ws : nullptr; a.n = B * C * P; a.B = (int)B; a.C = (int)C; a.P = (int)P;
-    a.chunks = (int)((P + VQ_SG2_MAP_CHUNK - 1) / VQ_SG2_MAP_CHUNK);
-    return vq_with_dtype(dtype, [&](auto dt) {
-        return launch_bias_act_bwd<decltype(dt)::value>(a, sg2_rows(layout, P), slabs, gbias, (hipStream_t)stream);
-    });
-}
-
-// the sizes and tiles of a blur: (H, W) the blur's INPUT plane, (OH, OW) its output; `adjoint` walks tiles of the input plane
-static int fir4_setup(const char *what, int dtype, int layout, int64_t B, int64_t C, int64_t H, int64_t W, int down, int py0, int py1,
-                      int px0, int px1, bool adjoint, VqFirArgs *a) {
-    const int64_t cap = 1ll << 31;
-    if (H < 1 || W < 1 || H >= cap || W >= cap || H * W >= cap) return fail(VQHIP_EINVAL, what, "H * W must be in 1 .. 2^31 - 1");
-    if (int rc = sg2_common(what, dtype, layout, B, C, H * W)) return rc;
-    if (down != 1 && down != 2) return fail(VQHIP_EINVAL, what, "down must be 1 or 2");
-    for (int p : {py0, py1, px0, px1})
-        if (p < 0 || p > 3) return fail(VQHIP_EINVAL, what, "every padding must be in 0 .. 3");
-    if (H + py0 + py1 < 4 || W + px0 + px1 < 4) return fail(VQHIP_EINVAL, what, "the padded plane is smaller than the 4 x 4 filter");
-    const int64_t OH = (H + py0 + py1 - 4) / down + 1, OW = (W + px0 + px1 - 4) / down + 1;
-    const bool rows = layout == VQHIP_LAYOUT_ROWS;
-    const int CB = rows ? FirTile<true>::CB : FirTile<false>::CB;
-    const int TOH = rows ? FirTile<true>::TOH : FirTile<false>::TOH, TOW = rows ? FirTile<true>::TOW : FirTile<false>::TOW;
-    a->B = (int)B; a->C = (int)C;
-    if (adjoint) {
-        a->IH = (int)OH; a->IW = (int)OW; a->OH = (int)H; a->OW = (int)W;
-        a->up = down; a->offy = 3 - py0; a->offx = 3 - px0;
-    } else {
-        a->IH = (int)H; a->IW = (int)W; a->OH = (int)OH; a->OW = (int)OW;
-        a->up = 1; a->offy = py0; a->offx = px0;
-    }
-    a->cblocks = (int)((C + CB - 1) / CB);
-    a->tiles_y = (a->OH + TOH - 1) / TOH; a->tiles_x = (a->OW + TOW - 1) / TOW;
-    if (B * a->cblocks * a->tiles_y * a->tiles_x >= cap) return fail(VQHIP_EINVAL, what, "the number of tiles is beyond one launch");
-    return VQHIP_OK;
-}
-
-int64_t vqhip_fir4_slabs(int layout, int64_t B, int64_t C, int64_t H, int64_t W) {
-    VqFirArgs a = {};
-    if (fir4_setup("vqhip_fir4_slabs", VQHIP_DTYPE_F32, layout, B, C, H, W, 1, 2, 2, 2, 2, true, &a)) return -1;
-    return B * a.tiles_y * a.tiles_x;
-}
-
-int vqhip_fir4_fwd(const void *x, int dtype, int layout, int64_t B, int64_t C, int64_t H, int64_t W, int down, int py0, int py1, int px0,
-                   int px1, const float *bias, void *out, void *stream) {
-    VqFirArgs a = {};
-    if (int rc = fir4_setup("vqhip_fir4_fwd", dtype, layout, B, C, H, W, down, py0, py1, px0, px1, false, &a)) return rc;
-    VQ_REQUIRE(x && out, "vqhip_fir4_fwd: x and out are required");
-    a.in = x; a.out = out; a.bias = bias;
-    return vq_with_dtype(dtype, [&](auto dt) {
-        return launch_fir4<decltype(dt)::value>(a, layout == VQHIP_LAYOUT_ROWS, down, bias ? VQ_FIR_ACT_IN : VQ_FIR_NONE, (hipStream_t)stream);
-    });
-}
-
-int vqhip_fir4_bwd(const void *g, int dtype, int layout, int64_t B, int64_t C, int64_t H, int64_t W, int down, int py0, int py1, int px0,
-                   int px1, const void *x, const float *bias, void *gx, float *gbias, float *ws, int64_t ws_bytes, void *stream) {
-    VqFirArgs a = {};
-    if (int rc = fir4_setup("vqhip_fir4_bwd", dtype, layout, B, C, H, W, down, py0, py1, px0, px1, true, &a)) return rc;
-    VQ_REQUIRE(g && gx, "vqhip_fir4_bwd: g and gx are required");
-    VQ_REQUIRE((x != nullptr) == (bias != nullptr), "vqhip_fir4_bwd: the fused form needs x and bias together");
-    VQ_REQUIRE(!x || (gbias && ws), "vqhip_fir4_bwd: the fused form needs gbias and the workspace");
-    if (x) VQ_NEED("vqhip_fir4_bwd: ws too small", ws_bytes, (int64_t)B * a.tiles_y * a.tiles_x * C * (int64_t)sizeof(float));
-    a.in = g; a.out = gx; a.x = x; a.bias = bias; a.ws = ws;
-    return vq_with_dtype(dtype, [&](auto dt) { return fir4_bwd_run<decltype(dt)::value>(a, layout == VQHIP_LAYOUT_ROWS, gbias, (hipStream_t)stream); });
-}
-
-// ---- GroupNorm (+ SiLU) (vqhip_group_norm_kernels.h) ---------------------------------------------------------------------------
-struct VqGnPlan {
-    int64_t n, S, units, slabs, ws_floats;
-    int T;
-    int pw;                                     // batch statistics: the piece (elements); units = workgroups of a launch
-};
-
-// the piece of the rows layout in batch mode: the widest of 16 bytes, 8 bytes or one element that divides C
-static int bn_rows_pw(int dtype, int64_t C) {
-    const int W = dtype == VQHIP_DTYPE_F32 ? 4 : 8;
-    return C % W == 0 ? W : (W == 8 && C % 4 == 0 ? 4 : 1);
-}
-
-// G == VQHIP_GN_BATCH, behind the clauses every mode shares: a channel over all images
-static int bn_plan(const char *what, int dtype, int layout, int64_t B, int64_t C, int64_t P, VqGnPlan *pl) {
-    const int64_t cap = 1ll << 31;
-    pl->n = B * P;
-    if (pl->n >= cap) return fail(VQHIP_EINVAL, what, "a channel must hold fewer than 2^31 values over the batch");
-    if (pl->n < 2) return fail(VQHIP_EINVAL, what, "batch statistics need more than one value per channel");
-    const bool rows = layout == VQHIP_LAYOUT_ROWS;
-    pl->pw = rows ? bn_rows_pw(dtype, C) : (dtype == VQHIP_DTYPE_F32 ? 4 : 8);
-    const int64_t chunk = rows ? 1024 / pl->pw : VQ_GN_CHUNK;
-    const int64_t chunk_ws = rows ? 1024 / bn_rows_pw(VQHIP_DTYPE_BF16, C) : VQ_GN_CHUNK;      // the workspace serves every dtype
-    pl->S = (pl->n + chunk - 1) / chunk;
-    const int64_t S_ws = (pl->n + chunk_ws - 1) / chunk_ws;
-    if (C * S_ws >= cap) return fail(VQHIP_EINVAL, what, "C * S is beyond one launch");
-    pl->units = (rows ? (C + VQ_BN_LX * pl->pw - 1) / (VQ_BN_LX * pl->pw) : C) * pl->S;
-    pl->slabs = 0; pl->T = VQ_GN_THREADS;
-    pl->ws_floats = 2 * C + 2 * C * S_ws;
-    return VQHIP_OK;
-}
-
-// what the three entry points refuse alike; on success the launch shape
-static int gn_plan(const char *what, int dtype, int layout, int64_t B, int64_t C, int64_t P, int64_t G, VqGnPlan *pl) {
-    if (!vq_float_dtype(dtype)) return fail(VQHIP_EINVAL, what, "dtype");
-    if (!vq_dense_layout(layout)) return fail(VQHIP_EINVAL, what, "layout");
-    if (B < 1 || C < 1 || P < 1 || (G < 1 && G != VQHIP_GN_BATCH)) return fail(VQHIP_EINVAL, what, "B, C and P must be positive, G positive or VQHIP_GN_BATCH");
-    if (G != VQHIP_GN_BATCH && C % G != 0) return fail(VQHIP_EINVAL, what, "C must be a multiple of G");
-    const int64_t cap = 1ll << 31;
-    if (B >= cap || C >= cap || P >= cap) return fail(VQHIP_EINVAL, what, "B, C and P must be below 2^31");
-    if (B * C > INT64_MAX / P / 8) return fail(VQHIP_EINVAL, what, "B * C * P overflows");     // (8: bytes and the workspace's floats)
-    pl->pw = 0;
-    if (G == VQHIP_GN_BATCH) return bn_plan(what, dtype, layout, B, C, P, pl);
-    pl->n = (C / G) * P;
-    if (pl->n >= cap) return fail(VQHIP_EINVAL, what, "a group must hold fewer than 2^31 values");
-    pl->T = pl->n <= VQ_GN_SMALL ? 64 : 256;
-    pl->S = pl->T == 64 ? 1 : (pl->n + VQ_GN_CHUNK - 1) / VQ_GN_CHUNK;
-    pl->units = B * G * pl->S;
-    if (pl->units >= cap) return fail(VQHIP_EINVAL, what, "B * G * ceil(n / 8192) is beyond one launch");
-    pl->slabs = B * pl->S;
-    pl->ws_floats = 2 * pl->units + 2 * pl->slabs * C;
-    return VQHIP_OK;
-}
-
-int64_t vqhip_group_norm_ws_bytes(int layout, int64_t B, int64_t C, int64_t P, int64_t G) {
-    VqGnPlan pl;
-    if (gn_plan("vqhip_group_norm_ws_bytes", VQHIP_DTYPE_BF16, layout, B, C, P, G, &pl)) return -1;   // (batch mode: the dtype of the most chunks)
-    return pl.ws_floats * (int64_t)sizeof(float);
-}
-
-static void bn_fill(VqBnArgs *a, const VqGnPlan &pl, int layout, int64_t B, int64_t C, int64_t P, float *ws) {
-    a->n = (uint32_t)pl.n; a->chunk = layout == VQHIP_LAYOUT_ROWS ? 1024u / (uint32_t)pl.pw : (uint32_t)VQ_GN_CHUNK;
-    a->B = (int)B; a->C = (int)C; a->P = (int)P; a->S = (int)pl.S;
-    a->mv = ws; a->part = ws + 2 * C;
-}
-
-static void gn_fill(VqGnArgs *a, const VqGnPlan &pl, int64_t B, int64_t C, int64_t P, int64_t G, float *ws) {
-    a->units = pl.units; a->n = (uint32_t)pl.n;
-    a->B = (int)B; a->C = (int)C; a->P = (int)P; a->G = (int)G; a->cpg = (int)(C / G); a->S = (int)pl.S;
-    a->ws_grp = ws; a->ws_dg = ws + 2 * pl.units; a->ws_db = a->ws_dg + pl.slabs * C;
-}
-
-int vqhip_group_norm_fwd(const void *x, int dtype, int layout, int64_t B, int64_t C, int64_t P, int64_t G, const float *gamma,
-                         const float *beta, float eps, int act, void *y, float *stats, float *ws, int64_t ws_bytes, void *stream) {
-    VqGnPlan pl;
-    if (int rc = gn_plan("vqhip_group_norm_fwd", dtype, layout, B, C, P, G, &pl)) return rc;
-    VQ_REQUIRE(act == 0 || act == 1 || (act == VQHIP_GN_ACT_LEAKY && G == VQHIP_GN_BATCH),
-               "vqhip_group_norm_fwd: act must be 0 (none) or 1 (SiLU), with batch statistics also 2 (LeakyReLU)");
-    VQ_REQUIRE(eps >= 0.0f && eps < INFINITY, "vqhip_group_norm_fwd: eps must be finite and not negative");
-    VQ_REQUIRE(x && gamma && beta && y && stats && ws, "vqhip_group_norm_fwd: x, gamma, beta, y, stats and ws are required");
-    VQ_NEED("vqhip_group_norm_fwd: ws too small", ws_bytes, pl.ws_floats * (int64_t)sizeof(float));
-    if (G == VQHIP_GN_BATCH) {
-        VqBnArgs a = {};
-        bn_fill(&a, pl, layout, B, C, P, ws);
-        a.x = x; a.out = y; a.gamma = gamma; a.beta = beta; a.stats = stats; a.eps = eps; a.act = act;
-        return vq_with_dtype(dtype, [&](auto dt) {
-            return bn_run<decltype(dt)::value>(a, layout == VQHIP_LAYOUT_ROWS, pl.pw, false, (unsigned)pl.units, (hipStream_t)stream);
-        });
-    }
-    VqGnArgs a = {};
-    gn_fill(&a, pl, B, C, P, G, ws);
-    a.x = x; a.out = y; a.gamma = gamma; a.beta = beta; a.stats = stats; a.eps = eps; a.act = act;
-    return vq_with_dtype(dtype, [&](auto dt) {
-        return gn_run<decltype(dt)::value>(a, layout == VQHIP_LAYOUT_ROWS, pl.T, false, pl.slabs, nullptr, nullptr, (hipStream_t)stream);
-    });
-}
-
-int vqhip_group_norm_bwd(const void *g, const void *x, int dtype, int layout, int64_t B, int64_t C, int64_t P, int64_t G,
-                         const float *gamma, const float *beta, const float *stats, int act, void *gx, float *dgamma, float *dbeta,
-                         float *ws, int64_t ws_bytes, void *stream) {
-    VqGnPlan pl;
-    if (int rc = gn_plan("vqhip_group_norm_bwd", dtype, layout, B, C, P, G, &pl)) return rc;
-    VQ_REQUIRE(act == 0 || act == 1 || (act == VQHIP_GN_ACT_LEAKY && G == VQHIP_GN_BATCH),
-               "vqhip_group_norm_bwd: act must be 0 (none) or 1 (SiLU), with batch statistics also 2 (LeakyReLU)");
-    VQ_REQUIRE(g && x && gamma && beta && stats && gx && dgamma && dbeta && ws,
-               "vqhip_group_norm_bwd: g, x, gamma, beta, stats, gx, dgamma, dbeta and ws are required");
-    VQ_NEED("vqhip_group_norm_bwd: ws too small", ws_bytes, pl.ws_floats * (int64_t)sizeof(float));
-    if (G == VQHIP_GN_BATCH) {
-        VqBnArgs a = {};
-        bn_fill(&a, pl, layout, B, C, P, ws);
-        a.x = x; a.g = g; a.out = gx; a.gamma = gamma; a.beta = beta; a.stats = const_cast<float *>(stats); a.act = act;
-        a.dgamma = dgamma; a.dbeta = dbeta;
-        return vq_with_dtype(dtype, [&](auto dt) {
-            return bn_run<decltype(dt)::value>(a, layout == VQHIP_LAYOUT_ROWS, pl.pw, true, (unsigned)pl.units, (hipStream_t)stream);
-        });
-    }
-    VqGnArgs a = {};
-    gn_fill(&a, pl, B, C, P, G, ws);
-    a.x = x; a.g = g; a.out = gx; a.gamma = gamma; a.beta = beta; a.stats = const_cast<float *>(stats); a.act = act;
-    return vq_with_dtype(dtype, [&](auto dt) {
-        return gn_run<decltype(dt)::value>(a, layout == VQHIP_LAYOUT_ROWS, pl.T, true, pl.slabs, dgamma, dbeta, (hipStream_t)stream);
-    });
-}
-
-// ---- the row ops of the VQ-KD networks (vqhip_vit_kernels.h) ---------------------------------------------------------------------
-// what the six entry points refuse alike about the rows
-static int vit_rows(const char *what, int64_t R, int64_t D) {
-    if (R < 1 || R > VQHIP_VIT_MAX_R || D < 1 || D > VQHIP_VIT_MAX_D) return fail(VQHIP_EINVAL, what, "need 1 <= R <= 2^24 and 1 <= D <= 8192");
-    if (R > ((1ll << 31) - 1) / D) return fail(VQHIP_EINVAL, what, "R * D must be below 2^31");
-    return VQHIP_OK;
-}
-
-// (x, y): the same float dtype, or fp32 x with a 16-bit y (autocast); res, where given, in y's dtype
-static inline bool vit_ln_pair(int x_dtype, int y_dtype) {
-    return vq_float_dtype(x_dtype) && vq_float_dtype(y_dtype) && (x_dtype == y_dtype || x_dtype == VQHIP_DTYPE_F32);
-}
-
-int64_t vqhip_add_layer_norm_slabs(int64_t R, int64_t D) {
-    if (vit_rows("vqhip_add_layer_norm_slabs", R, D)) return -1;
-    return (R + VQ_LN_SLAB - 1) / VQ_LN_SLAB;
-}
-
-int vqhip_add_layer_norm_fwd(const void *x, int x_dtype, const void *res, int res_dtype, int64_t R, int64_t D, const float *gamma,
-                             const float *beta, float eps, void *sum_out, void *y, int y_dtype, float *stats, void *stream) {
-    if (int rc = vit_rows("vqhip_add_layer_norm_fwd", R, D)) return rc;
-    VQ_REQUIRE(vit_ln_pair(x_dtype, y_dtype), "vqhip_add_layer_norm_fwd: (x, y) must be one float dtype, or fp32 x with a bf16 or fp16 y");
-    VQ_REQUIRE(!res || res_dtype == y_dtype, "vqhip_add_layer_norm_fwd: res must have y's dtype");
-    VQ_REQUIRE(eps >= 0.0f && eps < INFINITY, "vqhip_add_layer_norm_fwd: eps must be finite and not negative");
-    VQ_REQUIRE(x && gamma && y && stats, "vqhip_add_layer_norm_fwd: x, gamma, y and stats are required (beta == NULL: RMS mode)");
-    VQ_REQUIRE(!res || sum_out, "vqhip_add_layer_norm_fwd: res needs sum_out");
-    VqLnArgs a = {};
-    a.x = x; a.res = res; a.sum_out = sum_out; a.out = y; a.gamma = gamma; a.beta = beta; a.stats = stats; a.R = R; a.D = (int)D; a.eps = eps;
-    return vq_with_dtype(x_dtype, [&](auto dx) { return vq_with_dtype(y_dtype, [&](auto dy) {
-        if (!beta) return launch_ln<decltype(dx)::value, decltype(dy)::value, true>(a, false, (hipStream_t)stream);
-        return launch_ln<decltype(dx)::value, decltype(dy)::value, false>(a, false, (hipStream_t)stream);
-    }); });
-}
-
-int vqhip_add_layer_norm_bwd(const void *g, int g_dtype, const void *s, int s_dtype, const void *g_skip, int64_t R, int64_t D,
-                             const float *gamma, const float *stats, void *gx, float *dgamma, float *dbeta, float *ws, int64_t ws_bytes,
-                             void *stream) {
-    if (int rc = vit_rows("vqhip_add_layer_norm_bwd", R, D)) return rc;
-    VQ_REQUIRE(vit_ln_pair(s_dtype, g_dtype), "vqhip_add_layer_norm_bwd: (s, g) must be one float dtype, or fp32 s with a bf16 or fp16 g");
-    VQ_REQUIRE(g && s && gamma && stats && gx && dgamma && ws,
-               "vqhip_add_layer_norm_bwd: g, s, gamma, stats, gx, dgamma and ws are required (dbeta == NULL: RMS mode)");
-    const int64_t slabs = (R + VQ_LN_SLAB - 1) / VQ_LN_SLAB;
-    VQ_NEED("vqhip_add_layer_norm_bwd: ws too small", ws_bytes, 2 * slabs * D * (int64_t)sizeof(float));
-    VqLnArgs a = {};
-    a.x = s; a.res = g_skip; a.g = g; a.out = gx; a.gamma = gamma; a.stats = const_cast<float *>(stats); a.R = R; a.D = (int)D;
-    a.ws_dg = ws; a.ws_db = ws + slabs * D;                                     // (RMS mode leaves the second half alone)
-    const hipStream_t st = (hipStream_t)stream;
-    if (int rc = vq_with_dtype(s_dtype, [&](auto dx) { return vq_with_dtype(g_dtype, [&](auto dy) {
-            if (!dbeta) return launch_ln<decltype(dx)::value, decltype(dy)::value, true>(a, true, st);
-            return launch_ln<decltype(dx)::value, decltype(dy)::value, false>(a, true, st);
-        }); })) return rc;
-    if (int rc = launch_sg2_reduce(a.ws_dg, slabs, a.D, dgamma, st)) return rc;
-    return dbeta ? launch_sg2_reduce(a.ws_db, slabs, a.D, dbeta, st) : VQHIP_OK;
-}
-
-// what act == VQHIP_ROW_ACT_SWIGLU refuses on top of vit_rows: x is [R, 2 D] and there is no bias
-static int swiglu_rows(const char *what, int64_t R, int64_t D, const void *bias, const void *dbias, const void *ws) {
-    if (R > ((1ll << 31) - 1) / (2 * D)) return fail(VQHIP_EINVAL, what, "SwiGLU: R * 2 D must be below 2^31");
-    if (bias || dbias || ws) return fail(VQHIP_EINVAL, what, "SwiGLU has no bias: bias, dbias and ws must be NULL");
-    return VQHIP_OK;
-}
-
-int64_t vqhip_row_bias_act_slabs(int64_t R, int64_t D) {
-    if (vit_rows("vqhip_row_bias_act_slabs", R, D)) return -1;
-    return (R + VQ_SG2_ROWS_SLAB - 1) / VQ_SG2_ROWS_SLAB;
-}
-
-int vqhip_row_bias_act_fwd(const void *x, int dtype, int64_t R, int64_t D, const float *bias, int act, void *y, void *stream) {
-    if (int rc = vit_rows("vqhip_row_bias_act_fwd", R, D)) return rc;
-    VQ_REQUIRE(vq_float_dtype(dtype), "vqhip_row_bias_act_fwd: dtype");
-    VQ_REQUIRE(act == VQHIP_ROW_ACT_GELU || act == VQHIP_ROW_ACT_TANH || act == VQHIP_ROW_ACT_SWIGLU,
-               "vqhip_row_bias_act_fwd: act must be 0 (GELU), 1 (tanh) or 3 (SwiGLU)");
-    if (act == VQHIP_ROW_ACT_SWIGLU) {
-        if (int rc = swiglu_rows("vqhip_row_bias_act_fwd", R, D, bias, nullptr, nullptr)) return rc;
-        VQ_REQUIRE(x && y, "vqhip_row_bias_act_fwd: x and y are required");
-    } else {
-        VQ_REQUIRE(x && bias && y, "vqhip_row_bias_act_fwd: x, bias and y are required");
-    }
-    VqRowActArgs a = {};
-    a.x = x; a.bias = bias; a.out = y; a.R = R; a.D = (int)D;
-    return vq_with_dtype(dtype, [&](auto dt) { return launch_row_act<decltype(dt)::value>(a, act, false, 0, nullptr, (hipStream_t)stream); });
-}
-
-int vqhip_row_bias_act_bwd(const void *g, const void *x, int dtype, int64_t R, int64_t D, const float *bias, int act, void *gx,
-                           float *dbias, float *ws, int64_t ws_bytes, void *stream) {
-    if (int rc = vit_rows("vqhip_row_bias_act_bwd", R, D)) return rc;
-    VQ_REQUIRE(vq_float_dtype(dtype), "vqhip_row_bias_act_bwd: dtype");
-    VQ_REQUIRE(act == VQHIP_ROW_ACT_GELU || act == VQHIP_ROW_ACT_TANH || act == VQHIP_ROW_ACT_SWIGLU,
-               "vqhip_row_bias_act_bwd: act must be 0 (GELU), 1 (tanh) or 3 (SwiGLU)");
-    if (act == VQHIP_ROW_ACT_SWIGLU) {
-        if (int rc = swiglu_rows("vqhip_row_bias_act_bwd", R, D, bias, dbias, ws)) return rc;
-        VQ_REQUIRE(g && x && gx, "vqhip_row_bias_act_bwd: g, x and gx are required");
-    } else {
-        VQ_REQUIRE(g && x && bias && gx, "vqhip_row_bias_act_bwd: g, x, bias and gx are required");
-    }
-    VQ_REQUIRE(!dbias || ws, "vqhip_row_bias_act_bwd: dbias needs the workspace");
-    const int64_t slabs = (R + VQ_SG2_ROWS_SLAB - 1) / VQ_SG2_ROWS_SLAB;
-    if (dbias) VQ_NEED("vqhip_row_bias_act_bwd: ws too small", ws_bytes, slabs * D * (int64_t)sizeof(float));
-    VqRowActArgs a = {};
-    a.x = x; a.g = g; a.bias = bias; a.out = gx; a.ws = dbias ? ws : nullptr; a.R = R; a.D = (int)D;
-    return vq_with_dtype(dtype, [&](auto dt) { return launch_row_act<decltype(dt)::value>(a, act, true, slabs, dbias, (hipStream_t)stream); });
-}
-
-// ---- fused reconstruction metrics (vqhip_image_metrics_kernels.h) ---------------------------------------------------------
-// what both entry points refuse; on success the number of workgroups of the first launch and the tiles along each axis
-static int image_metrics_grid(const char *what, int64_t B, int64_t C, int64_t H, int64_t W, int64_t *groups, int64_t *tiles_x, int64_t *tiles_y) {
-    if (B < 1 || C < 1 || H < 1 || W < 1 || H > (1ll << 30) || W > (1ll << 30)) return fail(VQHIP_EINVAL, what, "need B, C >= 1 and 1 <= H, W <= 2^30");
-    *tiles_x = (W + VQ_IM_T - 1) / VQ_IM_T;
-    *tiles_y = (H + VQ_IM_T - 1) / VQ_IM_T;
-    const int64_t tiles = *tiles_x * *tiles_y;                                 // below 2^50
-    const int64_t cap = 1ll << 31;
-    if (tiles >= cap || C >= cap || B >= cap || tiles * C >= cap || tiles * C * B >= cap) return fail(VQHIP_EINVAL, what, "B * C * tiles must be below 2^31");
-    // C * H * W <= 1024 * tiles * C < 2^41: no overflow; below 2^37 the divisors 255 n and 65025 n are exact doubles
-    if (C * H * W >= (1ll << 37)) return fail(VQHIP_EINVAL, what, "C * H * W must be below 2^37");
-    *groups = tiles * C * B;
-    return VQHIP_OK;
-}
-
-int64_t vqhip_image_metrics_workspace_bytes(int64_t B, int64_t C, int64_t H, int64_t W) {
-    int64_t groups, tx, ty;
-    if (image_metrics_grid("vqhip_image_metrics_workspace_bytes", B, C, H, W, &groups, &tx, &ty)) return 0;
-    return groups * VQ_IM_SLOT * (int64_t)sizeof(long long);
-}
-
-static int image_metrics_side(const char *what, const void *p, int dtype, int layout, int64_t C, int64_t H, int64_t W, VqImSide *s) {
-    if (!p) return fail(VQHIP_EINVAL, what, "pred and image are required");
-    if (!vq_float_dtype(dtype) && dtype != VQHIP_DTYPE_U8) return fail(VQHIP_EINVAL, what, "dtype");
-    if (layout != VQHIP_IMAGE_NCHW && layout != VQHIP_IMAGE_NHWC) return fail(VQHIP_EINVAL, what, "layout");
-    s->p = p; s->dtype = dtype; s->sb = C * H * W;
-    if (layout == VQHIP_IMAGE_NCHW) { s->sc = H * W; s->sy = W; s->sx = 1; }
-    else { s->sc = 1; s->sy = W * C; s->sx = C; }
-    return VQHIP_OK;
-}
-
-int vqhip_image_metrics(const void *pred, int pred_dtype, int pred_layout, const void *image, int image_dtype, int image_layout,
-                        int64_t B, int64_t C, int64_t H, int64_t W, int want_ssim, double c1, double c2, void *ws, int64_t ws_bytes,
-                        double *values64, float *values32, int64_t *sums, void *stream) {
-    const char *what = "vqhip_image_metrics";
-    int64_t groups, tiles_x, tiles_y;
-    if (int rc = image_metrics_grid(what, B, C, H, W, &groups, &tiles_x, &tiles_y)) return rc;
-    VqImArgs a;
-    if (int rc = image_metrics_side(what, pred, pred_dtype, pred_layout, C, H, W, &a.a)) return rc;
-    if (int rc = image_metrics_side(what, image, image_dtype, image_layout, C, H, W, &a.b)) return rc;
-    VQ_REQUIRE(ws && values64 && values32 && sums, "vqhip_image_metrics: ws, values64, values32 and sums are required");
-    int64_t windows = 0;
-    if (want_ssim) {
-        VQ_REQUIRE(H >= 7 && W >= 7, "vqhip_image_metrics: SSIM needs H >= 7 and W >= 7 (a 7 x 7 window)");
-        windows = C * (H - 6) * (W - 6);                                       // C, H, W checked above: no overflow
-        VQ_REQUIRE(windows <= VQHIP_IMAGE_SSIM_MAX_WINDOWS, "vqhip_image_metrics: C * (H - 6) * (W - 6) is beyond 2^22 windows");
-        VQ_REQUIRE(c1 > 0.0 && c2 > 0.0, "vqhip_image_metrics: c1 and c2 must be positive");
-    }
-    VQ_NEED("vqhip_image_metrics: ws too small", ws_bytes, groups * VQ_IM_SLOT * (int64_t)sizeof(long long));
-    a.C = (int)C; a.H = (int)H; a.W = (int)W; a.tiles_x = (int)tiles_x; a.tiles_y = (int)tiles_y;
-    a.want_ssim = want_ssim ? 1 : 0; a.c1 = c1; a.c2 = c2;
-    hipStream_t s = (hipStream_t)stream;
-    image_metrics_tile_kernel<<<(unsigned)groups, VQ_IM_THREADS, 0, s>>>(a, (long long *)ws);
-    VQ_CHECK_LAUNCH("image_metrics_tile_kernel");
-    image_metrics_finish_kernel<<<1, VQ_IM_THREADS, 0, s>>>((const long long *)ws, B, groups / B, (double)(C * H * W), (double)windows,
-                                                            a.want_ssim, values64, values32, (long long *)sums);
-    VQ_CHECK_LAUNCH("image_metrics_finish_kernel");
-    return VQHIP_OK;
-}
-
-// ---- EntropyLoss on row blocks of the distance matrix (vqhip_entropy_kernels.h) ----------------------------------------
-static int entropy_check(const char *what, int64_t R, int64_t K, float T) {
-    // the kernels index a row with int and step by up to VQ_ENT_COLS past K before they stop; R * K elements are addressed in int64
-    if (R <= 0 || K <= 0 || R >= (1ll << 31) || K > (1ll << 31) - 2 * VQ_ENT_COLS) return fail(VQHIP_EINVAL, what, "R must be in 1 .. 2^31 - 1, K in 1 .. 2^31 - 2048");
-    if (!(T == T) || T == 0.0f || T - T != 0.0f) return fail(VQHIP_EINVAL, what, "the temperature must be finite and non-zero");
-    return VQHIP_OK;
-}
-
-int64_t vqhip_entropy_workspace_bytes(int64_t R, int64_t K) {
-    if (R <= 0 || K <= 0) return 0;
-    return ((R + VQ_ENT_CHUNK - 1) / VQ_ENT_CHUNK) * K * (int64_t)sizeof(double);
-}
-
-// column sums of the tile (MODE 0: of p, MODE 1: of its values) added into acc[K], chunk by chunk
-static int entropy_colsums(int mode, const float *tile, int64_t R, int64_t K, float T, const float *lse, double *acc, int init,
-                           void *ws, hipStream_t s) {
-    const int nchunks = (int)((R + VQ_ENT_CHUNK - 1) / VQ_ENT_CHUNK);
-    const dim3 grid((unsigned)((K + VQ_ENT_COLS - 1) / VQ_ENT_COLS), (unsigned)(nchunks < 65535 ? nchunks : 65535));
-#define VQ_ENT_COL(MODE, VEC) entropy_colsum_kernel<MODE, VEC><<<grid, 256, 0, s>>>(tile, (int)R, (int)K, T, lse, (double *)ws)
-    if (K % 4 == 0) { if (mode == 0) VQ_ENT_COL(0, true); else VQ_ENT_COL(1, true); }
-    else { if (mode == 0) VQ_ENT_COL(0, false); else VQ_ENT_COL(1, false); }
-#undef VQ_ENT_COL
-    VQ_CHECK_LAUNCH("entropy_colsum_kernel");
-    int rgrid = (int)((K + 255) / 256); rgrid = rgrid > 4096 ? 4096 : rgrid;
-    entropy_colreduce_kernel<<<rgrid, 256, 0, s>>>((const double *)ws, nchunks, (int)K, acc, init);
-    VQ_CHECK_LAUNCH("entropy_colreduce_kernel");
-    return VQHIP_OK;
-}
-
-int vqhip_entropy_rows(const float *tile, int64_t R, int64_t K, float temperature, float *lse, float *spa, double *qacc,
-                       int init, void *ws, int64_t ws_bytes, void *stream) {
-    const char *what = "vqhip_entropy_rows";
-    if (int rc = entropy_check(what, R, K, temperature)) return rc;
-    if (!tile || !lse || !spa || !qacc || !ws) return fail(VQHIP_EINVAL, what, "null pointer");
-    if ((uintptr_t)tile % 16) return fail(VQHIP_EINVAL, what, "the tile must be 16-byte aligned");
-    VQ_NEED("vqhip_entropy_rows: ws too small", ws_bytes, vqhip_entropy_workspace_bytes(R, K));
-    hipStream_t s = (hipStream_t)stream;
-    int grid = waves_grid(R, 4); grid = grid > 8192 ? 8192 : grid;
-    if (K % 4 == 0) entropy_rows_kernel<true><<<grid, 256, 0, s>>>(tile, (int)R, (int)K, temperature, lse, spa);
-    else entropy_rows_kernel<false><<<grid, 256, 0, s>>>(tile, (int)R, (int)K, temperature, lse, spa);
-    VQ_CHECK_LAUNCH("entropy_rows_kernel");
-    return entropy_colsums(0, tile, R, K, temperature, lse, qacc, init, ws, s);
-}
-
-int vqhip_entropy_finish(const float *lse, const float *spa, const double *qacc, int64_t N, int64_t K, float *q, float *c,
-                         float *loss, void *stream) {
-    const char *what = "vqhip_entropy_finish";
-    if (int rc = entropy_check(what, N, K, 1.0f)) return rc;
-    if (!lse || !spa || !qacc || !q || !c || !loss) return fail(VQHIP_EINVAL, what, "null pointer");
-    entropy_finish_kernel<<<1, 256, 0, (hipStream_t)stream>>>(lse, spa, qacc, (int)N, (int)K, q, c, loss);
-    VQ_CHECK_LAUNCH("entropy_finish_kernel");
-    return VQHIP_OK;
-}
-
-int vqhip_entropy_grad(float *tile, int64_t R, int64_t K, float temperature, const float *lse, const float *spa,
-                       const float *c, float inv_nt, const float *upstream, int metric, float *rowsum, double *colacc,
-                       int init, void *ws, int64_t ws_bytes, void *stream) {
-    const char *what = "vqhip_entropy_grad";
-    if (int rc = entropy_check(what, R, K, temperature)) return rc;
-    if (metric != VQHIP_METRIC_L2 && metric != VQHIP_METRIC_COS) return fail(VQHIP_EINVAL, what, "metric (L2 or COS)");
-    if (!tile || !lse || !spa || !c || !rowsum) return fail(VQHIP_EINVAL, what, "null pointer");
-    if ((uintptr_t)tile % 16) return fail(VQHIP_EINVAL, what, "the tile must be 16-byte aligned");
-    if (!(inv_nt == inv_nt) || inv_nt - inv_nt != 0.0f) return fail(VQHIP_EINVAL, what, "inv_nt must be finite");
-    const bool l2 = metric == VQHIP_METRIC_L2;
-    if (l2) {
-        if (!colacc || !ws) return fail(VQHIP_EINVAL, what, "L2 needs colacc and ws");
-        VQ_NEED("vqhip_entropy_grad: ws too small", ws_bytes, vqhip_entropy_workspace_bytes(R, K));
-    }
-    hipStream_t s = (hipStream_t)stream;
-    int grid = waves_grid(R, 4); grid = grid > 8192 ? 8192 : grid;
-    const int r = (int)R, k = (int)K;
-#define VQ_ENT_GRAD(VEC, L2) entropy_grad_kernel<VEC, L2><<<grid, 256, 0, s>>>(tile, r, k, temperature, lse, spa, c, inv_nt, upstream, rowsum)
-    if (K % 4 == 0) { if (l2) VQ_ENT_GRAD(true, true); else VQ_ENT_GRAD(true, false); }
-    else { if (l2) VQ_ENT_GRAD(false, true); else VQ_ENT_GRAD(false, false); }
-#undef VQ_ENT_GRAD
-    VQ_CHECK_LAUNCH("entropy_grad_kernel");
-    if (!l2) return VQHIP_OK;
-    return entropy_colsums(1, tile, R, K, temperature, lse, colacc, init, ws, s);
-}
-
-// ---- fused MultinomialAnchor on row blocks of the distance matrix (vqhip_col_multinomial_kernels.h) -----------------------
-struct VqColMultiWs {
-    float *colmax;       // [K] running column maximum; NaN = bad column
-    int32_t *sel;        // [K] the block that holds the column's crossing, -1 = none
-    cm_u64 *resid;       // [K] the target inside that block
-    cm_u64 *mass;        // [blocks, K] column masses per block
-    int64_t blocks, total;
-};
-
-// what every entry point refuses, and the carve of `ws` (ws may be null: sizes only)
-static int col_multinomial_setup(const char *what, int64_t N, int64_t K, int64_t R, void *ws, VqColMultiWs *w) {
-    if (N < 1 || N > VQHIP_COL_MULTINOMIAL_MAX_N) return fail(VQHIP_EINVAL, what, "N must be in 1 .. 2^20");
-    if (K < 1 || K >= (1ll << 31)) return fail(VQHIP_EINVAL, what, "K must be in 1 .. 2^31 - 1");
-    if (R < 1 || R > N) return fail(VQHIP_EINVAL, what, "block_rows must be in 1 .. N");
-    auto up = [](int64_t b) { return (b + 255) / 256 * 256; };
-    char *c = (char *)ws;
-    w->blocks = (N + R - 1) / R;                                                 // <= 2^20: blocks * K * 8 < 2^54
-    int64_t off = 0;
-    w->colmax = (float *)(c + off); off += up(K * 4);
-    w->sel = (int32_t *)(c + off); off += up(K * 4);
-    w->resid = (cm_u64 *)(c + off); off += up(K * 8);
-    w->mass = (cm_u64 *)(c + off); off += up(w->blocks * K * 8);
-    w->total = off;
-    return VQHIP_OK;
-}
-
-int64_t vqhip_col_multinomial_workspace_bytes(int64_t N, int64_t K, int64_t block_rows) {
-    VqColMultiWs w;
-    if (col_multinomial_setup("vqhip_col_multinomial_workspace_bytes", N, K, block_rows, nullptr, &w)) return 0;
-    return w.total;
-}
-
-// the checks of a call that takes a block: rows [r0, r0 + *r) with *r = min(block_rows, N - r0)
-static int col_multinomial_block(const char *what, const float *tile, int64_t r0, int64_t N, int64_t K, int64_t R, void *ws,
-                                 int64_t ws_bytes, VqColMultiWs *w, int64_t *r) {
-    if (int rc = col_multinomial_setup(what, N, K, R, ws, w)) return rc;
-    if (!tile || !ws) return fail(VQHIP_EINVAL, what, "null pointer");
-    if (r0 < 0 || r0 >= N || r0 % R != 0) return fail(VQHIP_EINVAL, what, "r0 must be a multiple of block_rows below N");
-    if (ws_bytes < w->total) {
-        char msg[160];
-        snprintf(msg, sizeof(msg), "ws too small: %lld bytes given, %lld needed", (long long)ws_bytes, (long long)w->total);
-        return fail(VQHIP_EINVAL, what, msg);
-    }
-    *r = N - r0 < R ? N - r0 : R;
-    return VQHIP_OK;
-}
-
-int vqhip_col_multinomial_max(const float *tile, int64_t r0, int64_t N, int64_t K, int64_t block_rows, void *ws, int64_t ws_bytes,
-                              void *stream) {
-    VqColMultiWs w;
-    int64_t r;
-    if (int rc = col_multinomial_block("vqhip_col_multinomial_max", tile, r0, N, K, block_rows, ws, ws_bytes, &w, &r)) return rc;
-    const unsigned grid = (unsigned)((K + VQ_CM_COLS - 1) / VQ_CM_COLS);
-    col_multinomial_max_kernel<<<grid, VQ_CM_COLS * VQ_CM_WAVES, 0, (hipStream_t)stream>>>(tile, (int)r, K, w.colmax, r0 == 0 ? 1 : 0);
-    VQ_CHECK_LAUNCH("col_multinomial_max_kernel");
-    return VQHIP_OK;
-}
-
-int vqhip_col_multinomial_mass(const float *tile, int64_t r0, int64_t N, int64_t K, int64_t block_rows, void *ws, int64_t ws_bytes,
-                               void *stream) {
-    VqColMultiWs w;
-    int64_t r;
-    if (int rc = col_multinomial_block("vqhip_col_multinomial_mass", tile, r0, N, K, block_rows, ws, ws_bytes, &w, &r)) return rc;
-    const unsigned grid = (unsigned)((K + VQ_CM_COLS - 1) / VQ_CM_COLS);
-    col_multinomial_mass_kernel<<<grid, VQ_CM_COLS * VQ_CM_WAVES, 0, (hipStream_t)stream>>>(tile, (int)r, K, w.colmax,
-                                                                                           w.mass + (r0 / block_rows) * K);
-    VQ_CHECK_LAUNCH("col_multinomial_mass_kernel");
-    return VQHIP_OK;
-}
-
-int vqhip_col_multinomial_pick(const float *u, int64_t N, int64_t K, int64_t block_rows, void *ws, int64_t ws_bytes, int64_t *col_idx,
-                               void *stream) {
-    const char *what = "vqhip_col_multinomial_pick";
-    VqColMultiWs w;
-    if (int rc = col_multinomial_setup(what, N, K, block_rows, ws, &w)) return rc;
-    if (!u || !ws || !col_idx) return fail(VQHIP_EINVAL, what, "null pointer");
-    VQ_NEED("vqhip_col_multinomial_pick: ws too small", ws_bytes, w.total);
-    col_multinomial_pick_kernel<<<(unsigned)((K + 255) / 256), 256, 0, (hipStream_t)stream>>>(w.mass, (int)w.blocks, K, w.colmax, u, w.sel,
-                                                                                              w.resid, col_idx);
-    VQ_CHECK_LAUNCH("col_multinomial_pick_kernel");
-    return VQHIP_OK;
-}
-
-int vqhip_col_multinomial_resolve(const float *tile, int64_t r0, int64_t N, int64_t K, int64_t block_rows, void *ws, int64_t ws_bytes,
-                                  int64_t *col_idx, void *stream) {
-    const char *what = "vqhip_col_multinomial_resolve";
-    VqColMultiWs w;
-    int64_t r;
-    if (int rc = col_multinomial_block(what, tile, r0, N, K, block_rows, ws, ws_bytes, &w, &r)) return rc;
-    if (!col_idx) return fail(VQHIP_EINVAL, what, "null pointer");
-    col_multinomial_resolve_kernel<<<(unsigned)((K + 63) / 64), 64, 0, (hipStream_t)stream>>>(tile, (int)r, K, (int)(r0 / block_rows), r0,
-                                                                                              w.colmax, w.sel, w.resid, col_idx);
-    VQ_CHECK_LAUNCH("col_multinomial_resolve_kernel");
-    return VQHIP_OK;
-}
-
 int vqhip_scatter_add_rows(const float *src, const int64_t *idx, int64_t N, int64_t K, int D, float *dst, void *stream) {
     if (!src || !idx || !dst || N < 0 || K <= 0 || D <= 0) return fail(VQHIP_EINVAL, "vqhip_scatter_add_rows: bad argument");
     if (N == 0) return VQHIP_OK;
@@ -2882,99 +1767,6 @@ int vqhip_set_tuning(int key, int value) {
     return VQHIP_OK;
 }
 
-// ---- the packed all-reduce on the caller's stream (RCCL resolved at run time; include/vqhip.h) -----------------------
-// libvqhip never links librccl: a process that already holds one (PyTorch-ROCm's) must not get a second copy, and a
-// caller without RCCL must still be able to load the library.  The handful of symbols are looked up once.
-#include <dlfcn.h>
-struct VqRcclId { char bytes[VQHIP_RCCL_ID_BYTES]; };      // ncclUniqueId (rccl.h: 128 opaque bytes), passed by value
-namespace {
-struct RcclApi {
-    void *handle = nullptr;
-    int (*get_unique_id)(void *) = nullptr;
-    int (*comm_init_rank)(void **, int, VqRcclId, int) = nullptr;
-    int (*comm_destroy)(void *) = nullptr;
-    int (*all_reduce)(const void *, void *, size_t, int, int, void *, hipStream_t) = nullptr;
-    const char *(*error_string)(int) = nullptr;
-};
-}  // namespace
-static RcclApi g_rccl;
-static std::mutex g_rccl_mu;
-static const int kNcclFloat32 = 7, kNcclInt64 = 4, kNcclSum = 0, kNcclMin = 3;        // rccl.h: ncclFloat32 = 7, ncclInt64 = 4, ncclSum = 0, ncclMin = 3
-
-static int rccl_fail(const char *what, int rc) {
-    return fail(VQHIP_ERCCL, what, g_rccl.error_string ? g_rccl.error_string(rc) : "RCCL error");
-}
-
-int vqhip_rccl_load(const char *path) {
-    std::lock_guard<std::mutex> lock(g_rccl_mu);
-    if (g_rccl.handle) return VQHIP_OK;
-    void *h = nullptr;
-    if (path && path[0]) {
-        h = dlopen(path, RTLD_NOW | RTLD_GLOBAL);
-        if (!h) return fail(VQHIP_ERCCL, "vqhip_rccl_load: librccl.so not loadable", dlerror());
-    } else {
-        // without a path: ONLY the copy the process already has (RTLD_NOLOAD).  Falling back to the loader's search path could map
-        // a second RCCL (say /opt/rocm's next to PyTorch's) into the process — two copies must never coexist; a caller whose
-        // copy was loaded under another name passes its path
-        const char *names[] = {"librccl.so", "librccl.so.1"};
-        for (const char *n : names)
-            if (!h) h = dlopen(n, RTLD_NOW | RTLD_NOLOAD);
-        if (!h) return fail(VQHIP_ERCCL, "vqhip_rccl_load: no librccl.so is mapped into this process under that name; pass the path of the copy the application uses");
-    }
-    RcclApi api;
-    api.handle = h;
-    api.get_unique_id = (decltype(api.get_unique_id))dlsym(h, "ncclGetUniqueId");
-    api.comm_init_rank = (decltype(api.comm_init_rank))dlsym(h, "ncclCommInitRank");
-    api.comm_destroy = (decltype(api.comm_destroy))dlsym(h, "ncclCommDestroy");
-    api.all_reduce = (decltype(api.all_reduce))dlsym(h, "ncclAllReduce");
-    api.error_string = (decltype(api.error_string))dlsym(h, "ncclGetErrorString");
-    if (!api.get_unique_id || !api.comm_init_rank || !api.comm_destroy || !api.all_reduce || !api.error_string)
-        return fail(VQHIP_ERCCL, "vqhip_rccl_load: librccl.so lacks an nccl* symbol");
-    g_rccl = api;
-    return VQHIP_OK;
-}
-
-int vqhip_rccl_unique_id(void *id_host) {
-    if (!id_host) return fail(VQHIP_EINVAL, "vqhip_rccl_unique_id: null buffer");
-    if (!g_rccl.handle) return fail(VQHIP_ERCCL, "vqhip_rccl_unique_id: call vqhip_rccl_load first");
-    static_assert(sizeof(VqRcclId) == 128, "ncclUniqueId is 128 bytes (rccl.h: NCCL_UNIQUE_ID_BYTES)");
-    const int rc = g_rccl.get_unique_id(id_host);
-    return rc == 0 ? VQHIP_OK : rccl_fail("ncclGetUniqueId", rc);
-}
-
-int vqhip_rccl_comm_init(void **comm, int nranks, const void *id_host, int rank) {
-    if (!comm || !id_host || nranks < 1 || rank < 0 || rank >= nranks) return fail(VQHIP_EINVAL, "vqhip_rccl_comm_init: bad argument");
-    if (!g_rccl.handle) return fail(VQHIP_ERCCL, "vqhip_rccl_comm_init: call vqhip_rccl_load first");
-    VqRcclId id;
-    memcpy(id.bytes, id_host, sizeof(id.bytes));
-    *comm = nullptr;
-    const int rc = g_rccl.comm_init_rank(comm, nranks, id, rank);
-    return rc == 0 ? VQHIP_OK : rccl_fail("ncclCommInitRank", rc);
-}
-
-int vqhip_rccl_comm_destroy(void *comm) {
-    if (!comm) return VQHIP_OK;
-    if (!g_rccl.handle) return fail(VQHIP_ERCCL, "vqhip_rccl_comm_destroy: RCCL not loaded");
-    const int rc = g_rccl.comm_destroy(comm);
-    return rc == 0 ? VQHIP_OK : rccl_fail("ncclCommDestroy", rc);
-}
-
-int vqhip_allreduce_packed(float *buf, int64_t floats, void *comm, void *stream) {
-    if (!buf || !comm || floats < 0) return fail(VQHIP_EINVAL, "vqhip_allreduce_packed: bad argument");
-    if (!g_rccl.handle) return fail(VQHIP_ERCCL, "vqhip_allreduce_packed: RCCL not loaded");
-    if (floats == 0) return VQHIP_OK;
-    const int rc = g_rccl.all_reduce(buf, buf, (size_t)floats, kNcclFloat32, kNcclSum, comm, (hipStream_t)stream);
-    return rc == 0 ? VQHIP_OK : rccl_fail("ncclAllReduce", rc);
-}
-
-int vqhip_allreduce_min_i64(int64_t *buf, int64_t n, void *comm, void *stream) {
-    if (!buf || !comm || n < 0) return fail(VQHIP_EINVAL, "vqhip_allreduce_min_i64: bad argument");
-    if (!g_rccl.handle) return fail(VQHIP_ERCCL, "vqhip_allreduce_min_i64: RCCL not loaded");
-    if (n == 0) return VQHIP_OK;
-    const int rc = g_rccl.all_reduce(buf, buf, (size_t)n, kNcclInt64, kNcclMin, comm, (hipStream_t)stream);
-    return rc == 0 ? VQHIP_OK : rccl_fail("ncclAllReduce", rc);
-}
-
 int vqhip_profile_enable(int on) {
     std::lock_guard<std::mutex> lock(g_prof_mu);
     g_prof_on = on != 0;
@@ -2999,5 +1791,3 @@ int vqhip_profile_collect(double *ms_sum, int64_t *launches) {
 }
 
 }  // extern "C"
-
-

@@ -1,5 +1,8 @@
-// libvqhip device kernels, unit 8 of 8: transposes, codebook metrics, verification aids.  Included by vqhip_kernels.h.
+// libvqhip device kernels, unit 8: transposes, codebook metrics, verification aids.  A unit of the core: vqhip.hip lists them.
 #pragma once
+#include "vqhip_kernels.h"
+#include "vqhip_proposal_kernels.h"
+#include "vqhip_refine_kernels.h"
 // ------------------------------------------------------------------------------------------------
 // callers of the path: BCHW <-> (BHW)C rearrangement and codebook metrics
 // ------------------------------------------------------------------------------------------------

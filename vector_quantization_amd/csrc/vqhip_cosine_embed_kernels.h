@@ -46,8 +46,7 @@
 #include <stdint.h>
 
 #include "vqhip.h"
-#include "vqhip_sample_kernels.h"               // SampleElem: the exact conversion to fp32
-#include "vqhip_token_ce_kernels.h"             // ce_round: nearest even into the output dtype
+#include "vqhip_elem.h"                         // SampleElem: the exact conversion to fp32; ce_round: nearest even into the output dtype
 
 #define VQ_COSE_THREADS 256
 #define VQ_COSE_WAVES (VQ_COSE_THREADS / 64)

@@ -1,6 +1,8 @@
-// libvqhip device kernels, unit 5 of 8: the all-fp32 MFMA pass over whole batches (argmin_exact, col_argmin fallback, distance).
-// Included by vqhip_kernels.h.
+// libvqhip device kernels, unit 5: the all-fp32 MFMA pass over whole batches (argmin_exact, col_argmin fallback, distance).
+// A unit of the core: vqhip.hip lists them.
 #pragma once
+#include "vqhip_kernels.h"
+#include "vqhip_refine_kernels.h"
 // ------------------------------------------------------------------------------------------------
 // exact fp32 MFMA pass (v_mfma_f32_32x32x2_f32 == k-ordered fmaf chain)
 // ------------------------------------------------------------------------------------------------

@@ -3,6 +3,9 @@
 // that consumes it.  gfx950 only.  Reference: vq/algorithms/cvqvae/quantizer_callback.py:85-103, anchors.py:50-67,83-84,
 // vq/algorithms/vq/utils.py:26-52, vq/algorithms/vqkd/quantizers/callbacks.py:44-71.
 #pragma once
+#include "vqhip_kernels.h"
+#include "vqhip_refine_kernels.h"
+#include "vqhip_update_kernels.h"
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 

@@ -16,6 +16,7 @@
 // z rows) go out through the same LDS tile.
 // ------------------------------------------------------------------------------------------------
 #pragma once
+#include "vqhip_kernels.h"
 #define VQ_FSQ_MAX_C 16
 #define VQ_FSQ_TILE 256
 

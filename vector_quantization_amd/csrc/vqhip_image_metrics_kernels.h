@@ -26,7 +26,7 @@
 #include <stdint.h>
 
 #include "vqhip.h"
-#include "vqhip_token_ce_kernels.h"             // SampleElem (exact conversion to fp32), ce_round (nearest even into bf16 / fp16)
+#include "vqhip_elem.h"                         // SampleElem (exact conversion to fp32), ce_round (nearest even into bf16 / fp16)
 
 #define VQ_IM_T VQHIP_IMAGE_METRICS_TILE
 #define VQ_IM_HALO 6

@@ -9,6 +9,7 @@
 
 #include <type_traits>
 
+#include "vqhip.h"
 #include "vqhip_layout.h"
 
 typedef _Float16 half8 __attribute__((ext_vector_type(8)));
@@ -278,16 +279,5 @@ __device__ __forceinline__ void cb_stats_publish(const VqCbStats *st) {
     }
 }
 
-// ---- the units (one translation unit: vqhip.hip includes this header) ----
-#include "vqhip_prepare_kernels.h"
-#include "vqhip_proposal_kernels.h"
-#include "vqhip_refine_kernels.h"
-#include "vqhip_proposal32_kernels.h"
-#include "vqhip_exact_kernels.h"
-#include "vqhip_stream_kernels.h"
-#include "vqhip_update_kernels.h"
-#include "vqhip_sort_kernels.h"
-#include "vqhip_aux_kernels.h"
-#include "vqhip_exchange_kernels.h"
-#include "vqhip_step_kernels.h"
-#include "vqhip_pool_kernels.h"
+// (the units of the core include this header and each other as they need; vqhip.hip, the one translation unit that launches
+// their kernels, lists them)

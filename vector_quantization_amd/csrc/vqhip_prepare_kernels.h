@@ -1,6 +1,7 @@
-// libvqhip device kernels, unit 2 of 8: row norms / F.normalize, codebook image (cb_stats, cb_image), token image (x_prep,
-// pre_kernel; NCHW-direct form).  Included by vqhip_kernels.h.
+// libvqhip device kernels, unit 2: row norms / F.normalize, codebook image (cb_stats, cb_image), token image (x_prep,
+// pre_kernel; NCHW-direct form).  A unit of the core: vqhip.hip lists them.
 #pragma once
+#include "vqhip_kernels.h"
 // ------------------------------------------------------------------------------------------------
 // row kernels: oracle-order |v|^2 and F.normalize
 // ------------------------------------------------------------------------------------------------

@@ -1,4 +1,4 @@
-// libvqhip device kernels, unit 3b: the proposal pass for D <= 16 on v_mfma_f32_32x32x16_f16.  Included by vqhip_kernels.h.
+// libvqhip device kernels, unit 3b: the proposal pass for D <= 16 on v_mfma_f32_32x32x16_f16.  A unit of the core: vqhip.hip lists them.
 //
 // Why a second form.  At D <= 32 the proposal pass is bound by the vector instructions that look at the scores and by MFMA
 // ISSUE, not by the matrix pipe (profiles/r03_d32_epilogue_shares.txt).  With D <= 16 one 32x32x16 instruction
@@ -17,6 +17,9 @@
 // hence the very scores of the stream; the second pass (16x16x32) re-derives scores under the same bound, which is all the
 // margin argument needs of it.
 #pragma once
+#include "vqhip_kernels.h"
+#include "vqhip_proposal_kernels.h"
+#include "vqhip_refine_kernels.h"
 
 // maximum of the 16 accumulator elements of one (token tile, code tile) in eight instructions, ordered behind the fake inputs
 // after[] (results of the MFMAs of the CURRENT tile: >= TT 32-cycle MFMAs after the producers; see tile_max8)

@@ -1,6 +1,7 @@
-// libvqhip device kernels, unit 3 of 8: the fp16-MFMA proposal pass (coarse_kernel) with its record merge and, optionally,
-// the decision stage.  Included by vqhip_kernels.h.
+// libvqhip device kernels, unit 3: the fp16-MFMA proposal pass (coarse_kernel) with its record merge and, optionally,
+// the decision stage.  A unit of the core: vqhip.hip lists them.
 #pragma once
+#include "vqhip_kernels.h"
 // ------------------------------------------------------------------------------------------------
 // fp16 MFMA proposal pass
 // ------------------------------------------------------------------------------------------------

@@ -1,6 +1,8 @@
-// libvqhip device kernels, unit 4 of 8: the row margin, the decision stage, the second proposal pass (rescan_kernel), the exact
-// fp32 re-rank and the last-resort whole-codebook pass for listed rows.  Included by vqhip_kernels.h.
+// libvqhip device kernels, unit 4: the row margin, the decision stage, the second proposal pass (rescan_kernel), the exact
+// fp32 re-rank and the last-resort whole-codebook pass for listed rows.  A unit of the core: vqhip.hip lists them.
 #pragma once
+#include "vqhip_kernels.h"
+#include "vqhip_proposal_kernels.h"
 // ------------------------------------------------------------------------------------------------
 // exact scalar evaluation (refine)
 // ------------------------------------------------------------------------------------------------

@@ -23,6 +23,7 @@
 #include <stdint.h>
 
 #include "vqhip.h"
+#include "vqhip_elem.h"                         // SampleElem: the exact conversion to fp32
 
 #define VQ_SAMPLE_THREADS 512
 #define VQ_SAMPLE_WAVES (VQ_SAMPLE_THREADS / 64)
@@ -67,27 +68,6 @@ __device__ __forceinline__ unsigned int sample_key(float a) {
 __device__ __forceinline__ float sample_unkey(unsigned int k) {
     return __uint_as_float((k & 0x80000000u) ? (k ^ 0x80000000u) : ~k);
 }
-
-template <int DT> struct SampleElem;
-template <> struct SampleElem<VQHIP_DTYPE_F32> {
-    typedef float raw;
-    static constexpr int W = 4;
-    static __device__ __forceinline__ float f32(raw v) { return v; }
-};
-template <> struct SampleElem<VQHIP_DTYPE_BF16> {
-    typedef uint16_t raw;
-    static constexpr int W = 8;
-    static __device__ __forceinline__ float f32(raw v) { return __uint_as_float(((uint32_t)v) << 16); }
-};
-template <> struct SampleElem<VQHIP_DTYPE_F16> {
-    typedef uint16_t raw;
-    static constexpr int W = 8;
-    static __device__ __forceinline__ float f32(raw v) {
-        _Float16 h;
-        __builtin_memcpy(&h, &v, 2);
-        return (float)h;
-    }
-};
 
 // the row as one workgroup sees it
 template <int DT, bool RESIDENT>

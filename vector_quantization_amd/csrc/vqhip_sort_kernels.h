@@ -1,5 +1,6 @@
-// libvqhip device kernels, unit 7 of 8: deterministic (ordered) codebook-side sums.  Included by vqhip_kernels.h.
+// libvqhip device kernels, unit 7: deterministic (ordered) codebook-side sums.  A unit of the core: vqhip.hip lists them.
 #pragma once
+#include "vqhip_kernels.h"
 // ------------------------------------------------------------------------------------------------
 // deterministic codebook-side sums: tokens ordered by code (stable), then one sequential sum per code
 // ------------------------------------------------------------------------------------------------

@@ -1,6 +1,7 @@
 // libvqhip device kernels, unit 5b: the all-fp32 MFMA pass over whole batches, streamed form (round 6).
-// Included by vqhip_kernels.h behind vqhip_exact_kernels.h (whose epilogue rules — l2_skip's monotone sqrt, dist_key — it shares).
+// A unit of the core (vqhip.hip lists them); builds on vqhip_exact_kernels.h (whose epilogue rules — l2_skip's monotone sqrt, dist_key — it shares).
 #pragma once
+#include "vqhip_kernels.h"
 // ------------------------------------------------------------------------------------------------
 // exact_stream_kernel: exact_tiled_kernel's work item (128 rows x 256 codes, the same k-ordered chains of
 // v_mfma_f32_32x32x2_f32 per (row, code), the same epilogue) with BOTH operands read from LDS at the MFMA that consumes them.

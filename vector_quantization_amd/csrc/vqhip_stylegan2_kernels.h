@@ -41,15 +41,12 @@
 #include <stdint.h>
 
 #include "vqhip.h"
-#include "vqhip_sample_kernels.h"               // SampleElem: the exact conversion to fp32
-#include "vqhip_token_ce_kernels.h"             // ce_round: nearest even into the output dtype
+#include "vqhip_elem.h"                         // SampleElem: the exact conversion to fp32; ce_round: nearest even into the output dtype
+#include "vqhip_slab_reduce.h"                  // VQ_SG2_THREADS, VQ_SG2_ROWS_SLAB, sg2_reduce_kernel: the second stage of the bias gradient
 
-#define VQ_SG2_THREADS 256
 #define VQ_SG2_SLOPE 0.2f
 #define VQ_SG2_SCALE 1.41421356237309515f
 #define VQ_SG2_MAP_CHUNK 4096                   // positions of a plane per workgroup of bias_act_bwd_map_kernel
-#define VQ_SG2_ROWS_SLAB 256                    // rows per workgroup of bias_act_bwd_rows_kernel
-#define VQ_SG2_RED 16                           // channels and slab groups per workgroup of sg2_reduce_kernel
 
 struct VqBiasActArgs {
     const void *x;                              // forward: the input; backward: the incoming gradient g
@@ -203,26 +200,6 @@ __global__ __launch_bounds__(VQ_SG2_THREADS) void bias_act_bwd_rows_kernel(VqBia
     if (group != 0 || cnt == 0 || !a.ws) return;
     for (int e = 0; e < cnt; ++e)
         a.ws[(int64_t)blockIdx.x * a.C + c0 + e] = (red[0][lane][e] + red[1][lane][e]) + (red[2][lane][e] + red[3][lane][e]);
-}
-
-// second stage: gbias[c] = sum_s ws[s C + c] in a fixed order
-__global__ __launch_bounds__(VQ_SG2_THREADS) void sg2_reduce_kernel(const float *__restrict__ ws, int64_t S, int C, float *__restrict__ gbias) {
-    __shared__ float red[VQ_SG2_RED][VQ_SG2_RED];
-    const int cl = threadIdx.x % VQ_SG2_RED, sg = threadIdx.x / VQ_SG2_RED;
-    const int c = (int)blockIdx.x * VQ_SG2_RED + cl;
-    float acc = 0.0f;
-    if (c < C) {
-#pragma unroll 4
-        for (int64_t s = sg; s < S; s += VQ_SG2_RED) acc = acc + ws[s * C + c];
-    }
-    red[sg][cl] = acc;
-    __syncthreads();
-#pragma unroll
-    for (int stride = VQ_SG2_RED / 2; stride >= 1; stride >>= 1) {
-        if (sg < stride) red[sg][cl] = red[sg][cl] + red[sg + stride][cl];
-        __syncthreads();
-    }
-    if (sg == 0 && c < C) gbias[c] = red[0][cl];
 }
 
 // ---- FIR -------------------------------------------------------------------------------------------------------------------

@@ -37,7 +37,7 @@
 #include <stdint.h>
 
 #include "vqhip.h"
-#include "vqhip_sample_kernels.h"               // SampleElem: the exact conversion to fp32
+#include "vqhip_elem.h"                         // SampleElem: the exact conversion to fp32; ce_round: nearest even into the output dtype
 
 #define VQ_CE_THREADS 256
 #define VQ_CE_WAVES (VQ_CE_THREADS / 64)
@@ -206,20 +206,6 @@ __global__ __launch_bounds__(VQ_CE_THREADS) void token_ce_reduce_kernel(VqCeArgs
     out[1] = Wt;
     out[2] = (float)((wh[0] + wh[1]) + (wh[2] + wh[3]));
     out[3] = L / Wt;
-}
-
-template <int DT> __device__ __forceinline__ typename SampleElem<DT>::raw ce_round(float v);
-template <> __device__ __forceinline__ float ce_round<VQHIP_DTYPE_F32>(float v) { return v; }
-template <> __device__ __forceinline__ uint16_t ce_round<VQHIP_DTYPE_BF16>(float v) {
-    const uint32_t b = __float_as_uint(v);
-    if (v != v) return (uint16_t)0x7FC0u;
-    return (uint16_t)((b + 0x7FFFu + ((b >> 16) & 1u)) >> 16);                  // round to nearest even (inf stays inf)
-}
-template <> __device__ __forceinline__ uint16_t ce_round<VQHIP_DTYPE_F16>(float v) {
-    const _Float16 h = (_Float16)v;                                             // v_cvt_f16_f32: round to nearest even
-    uint16_t u;
-    __builtin_memcpy(&u, &h, 2);
-    return u;
 }
 
 template <int DT, bool I64>

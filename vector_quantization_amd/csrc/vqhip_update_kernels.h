@@ -1,6 +1,7 @@
-// libvqhip device kernels, unit 6 of 8: gather / STE / loss (token-major and NCHW-map forms), histogram, scatter-add, VQ-KD and
-// CVQ-VAE updates, elementwise autograd pieces, fused backward.  Included by vqhip_kernels.h.
+// libvqhip device kernels, unit 6: gather / STE / loss (token-major and NCHW-map forms), histogram, scatter-add, VQ-KD and
+// CVQ-VAE updates, elementwise autograd pieces, fused backward.  A unit of the core: vqhip.hip lists them.
 #pragma once
+#include "vqhip_kernels.h"
 // ------------------------------------------------------------------------------------------------
 // decode / STE / loss partial sums, histogram, scatter-add, gathers, codebook updates
 // ------------------------------------------------------------------------------------------------
