@@ -78,7 +78,7 @@ static int launch_coarse_cfg(const char *ximg, int64_t N, const char *frag, int6
     if (int rc = ensure_dyn_lds((const void *)kern, LDS, lds_set)) return rc;
     const int64_t ntiles = (N + 15) / 16;
     const int64_t ntb = (ntiles + tpb - 1) / tpb;
-    const int grid = (int)(ntb * nslices);
+    const int grid = (int)(ntb * (XD == 2 ? 1 : nslices));     // XD == 2: one workgroup takes both slices of its token block
     const long slot = prof_begin(s);
     kern<<<grid, WAVES * 64, LDS, s>>>(ximg, N, frag, nstages, nslices, rec, Np, cbst, xh2, rho2, Dp, metric, dec, pad_stage, tpb);
     prof_end(slot, s);
@@ -152,7 +152,9 @@ static int balanced_tiles_per_block(int64_t N, int full) {
 // the D = 256 form with 64 tokens per wave, rows as the caller holds them, the decision stage in its own launch.  Evaluated
 // once per pipeline run, by whoever prepares the token side (encode_fused_front, else argmin_pipeline): VqTokenSide carries the
 // answer to the proposal launch and the second pass (which reads the rows instead).
-// The form never decides in-kernel: it needs at least two slices (one slice, forced by key 2 included, decides in-kernel).
+// The two-workgroup form (XD = 1) never decides in-kernel — its statistics are written by slice 0's workgroup and a decision in
+// the same launch would read them through the kernel's __restrict__ parameters — so it needs at least two slices: one slice forced
+// by key 2 keeps the token image (below), and launch_coarse never gives the form fewer than two whatever the knob says by then.
 static bool vq_xdirect(int64_t N, int64_t K, int D, int x_dtype, int metric, const int *n_dev) {
     if (D != 256 || n_dev != nullptr || vq_cb_layout(K, D).nstages < 2 || g_tune_slices.load() == 1) return false;
     // bf16 rows only: a piece of 8 latents has the fragment's own 16 bytes and is converted in place.  fp32 rows (twice the
@@ -166,7 +168,19 @@ static bool vq_xdirect(int64_t N, int64_t K, int D, int x_dtype, int metric, con
 // the token side argmin_pipeline finds in its workspace: none (it runs x_prep_kernel itself), the token image, or (vq_xdirect) the housekeeping only
 enum VqTokenSide { VQ_TOKENS_UNPREPARED, VQ_TOKENS_IMAGE, VQ_TOKENS_ROWS };
 
-static int pick_slices(int64_t ntb, int64_t nstages, int min_slices = 2) {
+static int pick_slices(int64_t ntb, int64_t nstages, int min_slices = 2);
+// ... and whether ONE workgroup per token block streams both slices and decides (coarse_kernel<..., XD = 2>): where
+// the slice count is the default's two — never a count forced through key 2 — and the workgroups, half as many and twice as long,
+// fill no more rounds of the chip's 256 CUs than the two-workgroup form's: 129..256 token blocks, 385..512, and every count
+// from 1024 on a multiple of 256 away (the headline's 1024 make exactly four rounds instead of eight half rounds).
+static bool vq_one_workgroup(int64_t N, int64_t nstages) {
+    if (g_tune_slices.load() > 0) return false;
+    const int64_t ntb = (N + 511) / 512;
+    if (nstages < 2 || pick_slices(ntb, nstages) != 2) return false;
+    return 2 * ((ntb + 255) / 256) <= (2 * ntb + 255) / 256;
+}
+
+static int pick_slices(int64_t ntb, int64_t nstages, int min_slices) {
     if (const int forced = g_tune_slices.load(); forced > 0) { int ns = forced; while (ns > 1 && ns > nstages) ns >>= 1; return ns; }
     // Enough slices to put a workgroup on every CU, no more: fewer, longer workgroups amortise their prologue and
     // record write-back, re-read the token image fewer times and write fewer records.  (Rows whose candidates cannot
@@ -258,7 +272,24 @@ static int launch_coarse(const char *ximg, int64_t N, const VqCbLayout &L, const
                 if (small32) VQ_CFG(2, VQ_D32_SMALL_TT, VQ_D32_SMALL_W, VQ_TPS_D32, VQ_NBUF_D32, true) else VQ_CFG(2, 4, 8, VQ_TPS_D32, VQ_NBUF_D32, true)
         case 4: if (small) VQ_CFG(4, 2, 8, 4, 4, true) else VQ_CFG(4, 4, 8, 4, 4, true)
         case 8: if (small) VQ_CFG(8, 2, 8, 4, 4, true) else VQ_CFG(8, 4, 8, 4, 4, true)
-        case 16: if (xd && !small16) VQ_CFG(16, 4, 8, VQ_TPS16, 4, false, false, false, 1)
+        case 16: if (xd && !small16) {
+                     // no token image (vq_xdirect): ONE workgroup per token block that decides in-kernel (vq_one_workgroup), else
+                     // a workgroup per slice — at least two, the decision left to refine_decide_kernel
+                     const int tpb = 8 * 4;
+                     VqDecideOut dsel = dec;
+                     if (L.nstages >= 2 && vq_one_workgroup(N, L.nstages)) {
+                         *nslices_out = 2;
+                         *fused_decide_out = 1;
+                         return launch_coarse_cfg<16, 4, 8, VQ_TPS16, 4, false, false, false, 2>(ximg, N, frag, L.nstages, 2, rec, Np, cbst, xh2, rho2, L.Dp, metric, dsel, pad_stage, tpb, s);
+                     }
+                     if (L.nstages < 2) return fail(VQHIP_EINVAL, "vqhip_argmin: the row-direct proposal form needs two stages");
+                     int ns = pick_slices((N + tpb * 16 - 1) / (tpb * 16), L.nstages, 2);
+                     ns = ns < 2 ? 2 : ns;
+                     *nslices_out = ns;
+                     dsel.idx = nullptr;
+                     *fused_decide_out = 0;
+                     return launch_coarse_cfg<16, 4, 8, VQ_TPS16, 4, false, false, false, 1>(ximg, N, frag, L.nstages, ns, rec, Np, cbst, xh2, rho2, L.Dp, metric, dsel, pad_stage, tpb, s);
+                 }
                  if (small16) VQ_CFG(16, 2, 8, VQ_TPS16, 4) else VQ_CFG(16, 4, 8, VQ_TPS16, 4)
         // large D: the token fragments of a wave must stay in registers for the whole stream
         case 32: VQ_CFG(32, 2, 8, 2)

@@ -79,6 +79,12 @@ __device__ __forceinline__ int tile_row16(int e, int lane) { return 16 * (e >> 2
 // computes them (same fma chains, same folding order: bit-identical statistics) — and slice 0 writes the statistics.  The
 // 268 MB fp16 token image of the headline batch is then neither written nor read: pre_kernel's token side (85 us of HBM time
 // at 524 288 x 256 bf16) is gone, for a prologue that converts what it loaded anyway.
+// XD == 2: the same prologue, and ONE workgroup per token block streams the two codebook slices as two consecutive halves of one
+// stream (grid = token blocks; nslices == 2 names the records).  At the first stage of half 1 a wave retires the last tile of
+// half 0, merges and writes its slice-0 records exactly as the end of a slice does, resets its trackers and goes on: the ring
+// never drains, and the stage boundaries, operands and MFMA sequence per accumulator are those of the two workgroups, so every
+// record is bitwise theirs.  The workgroup then decides its own tokens (no ticket): one prologue per token block instead of two,
+// and no decision launch behind the kernel.
 template <int NSTEP, int TT, int WAVES, int TPS, int NBUF = 2, bool FILTER = false, bool NOAUX = false,
           bool GROUPS = false, int XD = 0>
 __global__ __launch_bounds__(WAVES * 64, (FILTER && NSTEP <= 2) ? (GROUPS ? 4 : VQ_D32_PLAIN_OCC) : WAVES / 4) void coarse_kernel(
@@ -121,9 +127,11 @@ __global__ __launch_bounds__(WAVES * 64, (FILTER && NSTEP <= 2) ? (GROUPS ? 4 : 
     //  measured slower, -4.6 % at configs[2], -14 % at small N: profiles/r02_ab_streamk.txt; removed.)
     const bool wave_active = wave * TT < tpb;
     cb_stats_publish(cbst);
-    const int sl = blockIdx.x % nslices;
-    const int64_t tb = blockIdx.x / nslices;
-    const int64_t st0 = (nstages * sl) / nslices, st1 = (nstages * (sl + 1)) / nslices;
+    constexpr bool ONEWG = XD == 2;                      // both slices by this workgroup, one after the other
+    const int sl = ONEWG ? 0 : blockIdx.x % nslices;     // (ONEWG: the slice whose records leave first)
+    const int64_t tb = ONEWG ? blockIdx.x : blockIdx.x / nslices;
+    const int64_t st0 = ONEWG ? 0 : (nstages * sl) / nslices, st1 = ONEWG ? nstages : (nstages * (sl + 1)) / nslices;
+    [[maybe_unused]] const int64_t mid = nstages / 2;    // ONEWG: half 0 is [0, mid), as slice 0 of two is
   // A loop that runs once.  It is what is left of the stream-K segment loop, and it stays because of what hipcc makes of the
   // kernel with it: without it the D = 1024 instantiation comes out with another schedule (165 instead of 193 VGPRs, the A
   // fragments fetched less far ahead) and runs 21 % slower (1.075 -> 1.301 ms at 65 536 x 8192, same-device A/B), every other
@@ -142,7 +150,7 @@ __global__ __launch_bounds__(WAVES * 64, (FILTER && NSTEP <= 2) ? (GROUPS ? 4 : 
             for (int s = 0; s < NS32; ++s) xf[t][s] = *(const half8 *)(src + s * VQ_CHUNK_BYTES);
         }
     } else {
-        static_assert(XD == 1 && !FILTER && !GROUPS && !NOAUX && (NSTEP % 4) == 0, "token side in the prologue: bf16 rows, plain D % 64 == 0 forms");
+        static_assert((XD == 1 || XD == 2) && !FILTER && !GROUPS && !NOAUX && (NSTEP % 4) == 0, "token side in the prologue: bf16 rows, plain D % 64 == 0 forms");
         const int q4 = lane >> 4, r16 = lane & 15;           // the fragment's own layout: token r16 of the tile, dims 32 s + 8 q4 .. + 8
         constexpr int Dr = NS32 * 32;
         // bf16 rows: a piece of 8 latents is 16 bytes, exactly the fragment's size — ALL the wave's pieces are requested into the
@@ -288,7 +296,7 @@ __global__ __launch_bounds__(WAVES * 64, (FILTER && NSTEP <= 2) ? (GROUPS ? 4 : 
 #ifndef VQ_LAG_MIN_STAGES
 #define VQ_LAG_MIN_STAGES 48     // slices shorter than this run without the lag (one iteration less)
 #endif
-    const int lag = (NBUF >= 4 && wave >= WAVES / 2 && st1 - st0 >= VQ_LAG_MIN_STAGES) ? 1 : 0;
+    const int lag = (NBUF >= 4 && wave >= WAVES / 2 && (ONEWG ? mid : st1 - st0) >= VQ_LAG_MIN_STAGES) ? 1 : 0;   // (ONEWG: as its slices would decide)
     if (st0 < st1) issue_stage(st0, 0);
     if (AHEAD >= 2 && st0 + 1 < st1) issue_stage(st0 + 1, 1);
     vq_dma_barrier();  // drains the LDS-DMA (vmcnt(0)) and makes it visible to every wave
@@ -306,10 +314,45 @@ __global__ __launch_bounds__(WAVES * 64, (FILTER && NSTEP <= 2) ? (GROUPS ? 4 : 
         for (int t = 0; t < TT; ++t) accA[1][t] = f32x4{-3.0e38f, -3.0e38f, -3.0e38f, -3.0e38f};
     }
 
-    for (int64_t it = st0; it < st1 + ((NBUF >= 4 && st1 - st0 >= VQ_LAG_MIN_STAGES) ? 1 : 0); ++it) {
+    for (int64_t it = st0; it < st1 + ((NBUF >= 4 && (ONEWG ? mid : st1 - st0) >= VQ_LAG_MIN_STAGES) ? 1 : 0); ++it) {
         if (it + AHEAD < st1) issue_stage(it + AHEAD, (int)((it + AHEAD - st0) % NBUF));
         const int64_t st = it - lag;
         if (st < st0 || st >= st1 || !wave_active) { vq_dma_barrier(); continue; }
+        if constexpr (ONEWG) {
+            // Half 0 ends in front of this stage: what the end of a slice does below — the last tile's epilogue (it sits in
+            // accB), the merge of the four lanes of a token, the record of slice 0 — then the trackers start over as slice 1's
+            // do.  The ring is not touched: stage st is in its buffer, st + 1 and st + 2 are on their way.
+            if (st == mid) {
+                // (the lane index through an opaque copy: nothing in here is computed ahead of the loop and kept in registers across it)
+                int hl = lane;
+                asm volatile("" : "+v"(hl));
+#pragma unroll
+                for (int t = 0; t < TT; ++t) {
+                    const uint32_t old = __float_as_uint(b1[t]);
+#pragma unroll
+                    for (int e = 0; e < NE; ++e) {
+                        float v = __uint_as_float((__float_as_uint(accB[e >> 2][t][e & 3]) & 0xFFFFFFF0u) | (uint32_t)e);
+                        b2[t] = __builtin_amdgcn_fmed3f(b1[t], b2[t], v);
+                        b1[t] = vmax(b1[t], v);
+                    }
+                    t1[t] = (__float_as_uint(b1[t]) != old) ? (uint32_t)(mid * TPS - 1) : t1[t];
+                    Top2 r; r.v1 = r.v2 = r.v3 = -INFINITY; r.c1 = r.c2 = 0xFFFFFFFFu;
+                    if (b1[t] > -INFINITY) top_insert(r, b1[t], t1[t] * 32u + (uint32_t)tile_row16((int)(__float_as_uint(b1[t]) & 7u), hl));
+                    r.v3 = fmaxf(r.v3, b2[t]);
+                    top_merge_lane(r, 16);
+                    top_merge_lane(r, 32);
+                    const int64_t tokn = (tb * tpb + wave * TT + t) * 16 + (hl & 15);
+                    if (hl < 16 && tokn < N && wave * TT + t < tpb) {
+                        float *rp = rec + tokn;
+                        rp[0] = r.v1; rp[Np] = __uint_as_float(r.c1); rp[2 * Np] = r.v2;
+                        rp[3 * Np] = __uint_as_float(r.c2); rp[4 * Np] = r.v3;
+                    }
+                    b1[t] = -INFINITY; b2[t] = -INFINITY; t1[t] = 0;
+#pragma unroll
+                    for (int c = 0; c < 2; ++c) accB[c][t] = f32x4{-3.0e38f, -3.0e38f, -3.0e38f, -3.0e38f};
+                }
+            }
+        }
         const int buf = (int)((st - st0) % NBUF);
         const char *base = lds + buf * STAGE_BYTES;
         const char *aux = base + TPS * NSTEP * VQ_CHUNK_BYTES;
@@ -624,8 +667,8 @@ __global__ __launch_bounds__(WAVES * 64, (FILTER && NSTEP <= 2) ? (GROUPS ? 4 : 
         top_merge_lane(r, 32);
         const int64_t tokn = (tb * tpb + wave * TT + t) * 16 + (lane & 15);
         if (lane < 16 && tokn < N && wave * TT + t < tpb) {
-            float *rp = rec + (int64_t)sl * VQ_REC_FIELDS * Np + tokn;
-            if (dec.idx != nullptr && nslices > 1) {
+            float *rp = rec + (int64_t)(ONEWG ? 1 : sl) * VQ_REC_FIELDS * Np + tokn;
+            if (!ONEWG && dec.idx != nullptr && nslices > 1) {
                 // read by ANOTHER workgroup of this launch (the one that draws the block's last ticket): agent-scope stores, which go
                 // past this XCD's L2 on their own — no write-back of the whole L2 (the release fence) in front of the ticket
                 __hip_atomic_store(rp, r.v1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
@@ -644,7 +687,19 @@ __global__ __launch_bounds__(WAVES * 64, (FILTER && NSTEP <= 2) ? (GROUPS ? 4 : 
     // Arrival counter per token block (MI355X guide, Guideline 16): every wave drains its record stores, the workgroup
     // meets, one lane releases at agent scope and takes a ticket; the workgroup that draws the last ticket of the block
     // (nslices of them) acquires and merges the records of all slices — one launch less on the critical path.
-    if (dec.idx != nullptr) {
+    // XD == 1 never decides in here: slice 0's workgroup has just written the statistics, and xh2 / rho2 promise (__restrict__)
+    // that nobody in this launch writes what they read; launch_coarse hands that form no dec.idx.
+    if constexpr (ONEWG) {
+        // both records of every token of the block are this workgroup's own: no ticket.  The statistics come from this
+        // workgroup's prologue and are read through the pointers they were written through, not through xh2 / rho2.
+        asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+        __syncthreads();                                 // records and statistics have left every wave; the stage ring is free
+        int *wcount = (int *)lds, *wbase = wcount + 3 * 16;
+        int64_t n = tb * (int64_t)(tpb * 16) + threadIdx.x;
+        const bool oob = (int)threadIdx.x >= tpb * 16 || n >= N;
+        if (n >= N) n = N - 1;
+        decide_rows<true>(n, oob, cbst, Dp, metric, 2, rec, dec.xh2_w, dec.rho2_w, Np, dec, wcount, wbase);
+    } else if (XD != 1 && dec.idx != nullptr) {
         int *flags = (int *)lds;                         // the stage ring is free now (first barrier below)
         asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
         __syncthreads();
