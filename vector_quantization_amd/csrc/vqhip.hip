@@ -1,26 +1,21 @@
-// libvqhip — host entry points (C ABI in include/vqhip.h) of the quantizer core, with FSQ and the pooled code features (which
-// share FSQ's constants).  gfx950 only.  The other op families have a translation unit each (csrc/Makefile).
+// libvqhip — host entry points (C ABI in include/vqhip.h) of the proposal pipeline: the dispatch of the proposal pass, the
+// decision, second pass and re-rank behind it (argmin_pipeline), the codebook image and the encode / argmin / column-pass
+// entry points, with the tuning knobs and the proposal kernel's profiling.  gfx950 only.  The rest of the quantizer core has a
+// translation unit per concern — vqhip_exact.hip (the all-fp32 pass), vqhip_decode.hip, vqhip_fsq.hip, vqhip_update.hip,
+// vqhip_step.hip — as the other op families have (csrc/Makefile); vqhip_core.h declares what crosses between them.
 #include "vqhip.h"
 
 #include <hip/hip_runtime.h>
 #include <stdio.h>
 #include <string.h>
 
-#include "vqhip_host.h"
-#include "vqhip_kernels.h"
+#include "vqhip_core.h"
 #include "vqhip_prepare_kernels.h"
 #include "vqhip_proposal_kernels.h"
 #include "vqhip_refine_kernels.h"
 #include "vqhip_proposal32_kernels.h"
-#include "vqhip_exact_kernels.h"
-#include "vqhip_stream_kernels.h"
-#include "vqhip_update_kernels.h"
-#include "vqhip_sort_kernels.h"
 #include "vqhip_aux_kernels.h"
-#include "vqhip_exchange_kernels.h"
-#include "vqhip_step_kernels.h"
-#include "vqhip_pool_kernels.h"
-#include "vqhip_fsq_kernels.h"
+#include "vqhip_stream_kernels.h"
 
 // ---- optional per-launch timing of the proposal kernel (bench.py roofline) -------------------------------
 // Events are recorded on the caller's stream right around the coarse_kernel launch; vqhip_profile_collect
@@ -326,172 +321,31 @@ static int resident_grid(int per_cu) {
     return n * per_cu;
 }
 
-// The all-fp32 MFMA pass over a whole batch.  Streamed form (exact_stream_kernel, both operands from LDS, two workgroups per CU,
-// contiguous spans of work items) wherever rows and codes move as whole 16-byte pieces; the register form
-// (exact_tiled_kernel) for the other D and on request (vqhip_set_tuning key 18 = 0, A/B: the results are identical).
+// The streamed form of the all-fp32 pass over a whole batch (run_exact_tiled in vqhip_exact.hip decides when), launched from
+// this unit: vqhip_core.h says why.
 template <int MODE>
-static int run_exact_tiled(const void *x, int x_dtype, const float *e, const float *en, const float *xn, int64_t N, int64_t K,
-                           int D, int metric, u64 *keys, float *dout, hipStream_t s) {
-    const int bf = x_dtype == VQHIP_DTYPE_F32 ? 0 : 1;
-    const int64_t items = ((N + 127) / 128) * ((K + 255) / 256);
-    if (g_tune_stream.load() && D % (bf ? 8 : 4) == 0 && items < (int64_t)1 << 31) {
-        static LdsCache ssets[2];
-        const int lds = vq_xs_lds_bytes(bf);
-        const void *kern = bf ? (const void *)exact_stream_kernel<1, MODE> : (const void *)exact_stream_kernel<0, MODE>;
-        if (int rc = ensure_dyn_lds(kern, lds, ssets[bf])) return rc;
-        const int cap = resident_grid(2);
-        const int grid = (int)(items < cap ? items : cap);
-        if (bf) exact_stream_kernel<1, MODE><<<grid, 256, lds, s>>>(x, e, en, xn, N, K, D, metric, keys, dout);
-        else exact_stream_kernel<0, MODE><<<grid, 256, lds, s>>>(x, e, en, xn, N, K, D, metric, keys, dout);
-        VQ_CHECK_LAUNCH("exact_stream_kernel");
-        return VQHIP_OK;
-    }
-    constexpr int LDS = 2 * 32 * 128 * 4 + 8 * 32 * 4;      // two staged tiles + the |e|^2 of an item's 256 codes
-    static LdsCache sets[4];
-    const void *kerns[4] = {(const void *)exact_tiled_kernel<0, MODE, false>, (const void *)exact_tiled_kernel<1, MODE, false>,
-                            (const void *)exact_tiled_kernel<0, MODE, true>, (const void *)exact_tiled_kernel<1, MODE, true>};
-    const int v4 = (D % 4 == 0) ? 2 : 0;
-    if (int rc = ensure_dyn_lds(kerns[v4 + bf], LDS, sets[v4 + bf])) return rc;
-    int grid = (int)(items < 1024 ? items : 1024);
-#define VQ_TILED(DT, V4) exact_tiled_kernel<DT, MODE, V4><<<grid, 256, LDS, s>>>(x, e, en, xn, N, K, D, metric, keys, dout)
-    if (v4) { if (bf) VQ_TILED(1, true); else VQ_TILED(0, true); }
-    else { if (bf) VQ_TILED(1, false); else VQ_TILED(0, false); }
-#undef VQ_TILED
-    VQ_CHECK_LAUNCH("exact_tiled_kernel");
+int run_exact_stream(const void *x, int bf, const float *e, const float *en, const float *xn, int64_t N, int64_t K, int D, int metric,
+                     u64 *keys, float *dout, int64_t items, hipStream_t s) {
+    static LdsCache ssets[2];
+    const int lds = vq_xs_lds_bytes(bf);
+    const void *kern = bf ? (const void *)exact_stream_kernel<1, MODE> : (const void *)exact_stream_kernel<0, MODE>;
+    if (int rc = ensure_dyn_lds(kern, lds, ssets[bf])) return rc;
+    const int cap = resident_grid(2);
+    const int grid = (int)(items < cap ? items : cap);
+    if (bf) exact_stream_kernel<1, MODE><<<grid, 256, lds, s>>>(x, e, en, xn, N, K, D, metric, keys, dout);
+    else exact_stream_kernel<0, MODE><<<grid, 256, lds, s>>>(x, e, en, xn, N, K, D, metric, keys, dout);
+    VQ_CHECK_LAUNCH("exact_stream_kernel");
     return VQHIP_OK;
 }
-
-// The fp32-only route over a whole batch, in an encode workspace: the oracle-order norms of both sides under L2, then
-// run_exact_tiled<MODE>.  MODE 0: the keys are armed in front and turned into idx / dmin / hist behind; MODE 2 (`dout`) has none.
-template <int MODE>
-static int exact_whole(const void *x, int x_dtype, const float *e, int64_t N, int64_t K, int D, int metric, const VqWsView &V,
-                       int64_t *idx, float *dmin, int32_t *hist, float *dout, hipStream_t s) {
-    constexpr bool keyed = MODE != 2;
-    const bool l2 = metric == VQHIP_METRIC_L2;
-    if (l2) if (int rc = vqhip_row_sqnorm(e, VQHIP_DTYPE_F32, K, D, V.en, s)) return rc;
-    if constexpr (keyed) { fill_u64_kernel<<<256, 256, 0, s>>>(V.keys, N, ~0ull); VQ_CHECK_LAUNCH("fill_u64_kernel"); }
-    if (l2) if (int rc = vqhip_row_sqnorm(x, x_dtype, N, D, V.xn_whole, s)) return rc;
-    if (int rc = run_exact_tiled<MODE>(x, x_dtype, e, V.en, V.xn_whole, N, K, D, metric, keyed ? V.keys : nullptr, dout, s)) return rc;
-    if constexpr (keyed) { finalize_kernel<<<256, 256, 0, s>>>(V.keys, nullptr, nullptr, N, idx, dmin, hist); VQ_CHECK_LAUNCH("finalize_kernel"); }
-    return VQHIP_OK;
-}
-
-// The few-rows (VALU) form of exact_kernel stages its operands in dynamic LDS: a 64 KiB ring + 64 D bytes.  The request applies to
-// the LAUNCH, i.e. also when the device-side count picks the MFMA form: at D > 512 (96 KiB) that would leave the MFMA form one
-// workgroup per CU, and a part with less LDS per workgroup than asked for would refuse the launch — so the form is offered only
-// where the request stays within 96 KiB and within what the device grants a workgroup.
-static int exact_few_max(int D) {
-    if (D > 512 || D > VQ_FEW_MAX_D) return 0;
-    static std::atomic<int> lds_limit{-1};
-    int lim = lds_limit.load(std::memory_order_relaxed);
-    if (lim < 0) {
-        int dev = 0, v = 0;
-        if (hipGetDevice(&dev) != hipSuccess || hipDeviceGetAttribute(&v, hipDeviceAttributeMaxSharedMemoryPerBlock, dev) != hipSuccess) v = 65536;
-        lim = v;
-        lds_limit.store(lim);
-    }
-    return vq_few_lds_bytes(D) <= lim ? VQ_EXACT_FEW_MAX : 0;
-}
-
-static int run_exact_rows(const void *x, int x_dtype, const float *e, const float *en, const float *xn, int64_t N, int64_t K, int D,
-                          int metric, const int *row_list, const int *nrows_dev, u64 *keys, int *ticket, int64_t *idx,
-                          int32_t *hist, hipStream_t s) {
-    // last-resort path of vqhip_argmin: a few listed rows against the whole codebook (small work items); the workgroup
-    // that finishes last turns the keys into indices (ticket: zeroed by x_prep_kernel with the other counters)
-    const int64_t ncb = (K + 63) / 64;           // work items of the few-rows form per 16 listed rows
-    const int grid = (int)(ncb < 256 ? 256 : (ncb > 1024 ? 1024 : ncb));
-    if (D % 4) return fail(VQHIP_EINVAL, "exact_kernel: D % 4 != 0 (the proposal route has D % 8 == 0)");
-    const int few_max = exact_few_max(D);
-    const int lds = few_max ? vq_few_lds_bytes(D) : 0;
-    static LdsCache sets[2];
-    const int bf = x_dtype == VQHIP_DTYPE_F32 ? 0 : 1;
-    if (int rc = ensure_dyn_lds(bf ? (const void *)exact_kernel<1> : (const void *)exact_kernel<0>, lds, sets[bf])) return rc;
-    if (!bf)
-        exact_kernel<0><<<grid, 256, lds, s>>>(x, e, en, xn, N, K, D, metric, row_list, nrows_dev, keys, ticket, idx, hist, few_max);
-    else
-        exact_kernel<1><<<grid, 256, lds, s>>>(x, e, en, xn, N, K, D, metric, row_list, nrows_dev, keys, ticket, idx, hist, few_max);
-    VQ_CHECK_LAUNCH("exact_kernel");
-    return VQHIP_OK;
-}
-
-template <int MODE>
-static int run_segsum(const void *src, int x_dtype, const float *e, const int64_t *idx, const int32_t *order,
-                      const int32_t *offsets, int64_t N, int64_t K, int D, const float *g_cb, float *dst, void *ws,
-                      hipStream_t s) {
-    float *partial = (float *)ws;
-    const int64_t nranges = (N + VQ_SEG_RANGE - 1) / VQ_SEG_RANGE;
-    int grid = (int)((nranges + 3) / 4); grid = grid < 1 ? 1 : (grid > 4096 ? 4096 : grid);
-    if (x_dtype == VQHIP_DTYPE_F32) segsum_rows_kernel<MODE, 0><<<grid, 256, 0, s>>>(src, e, idx, order, offsets, N, (int)K, D, g_cb, dst, partial);
-    else segsum_rows_kernel<MODE, 1><<<grid, 256, 0, s>>>(src, e, idx, order, offsets, N, (int)K, D, g_cb, dst, partial);
-    VQ_CHECK_LAUNCH("segsum_rows_kernel");
-    int fgrid = (int)((K + 3) / 4); fgrid = fgrid > 2048 ? 2048 : fgrid;
-    segsum_fixup_kernel<<<fgrid, 256, 0, s>>>(offsets, (int)K, D, partial, dst);
-    VQ_CHECK_LAUNCH("segsum_fixup_kernel");
-    return VQHIP_OK;
-}
-
-// rows of at most 32 elements take L = 8, 16 or 32 lanes each: 64 / L rows per wave
-static inline int vq_small_lanes(int D) { return D <= 8 ? 8 : (D <= 16 ? 16 : 32); }
-
-// |v|^2 / F.normalize for rows of at most 32 elements (row_small_kernel)
-template <bool NORMALIZE>
-static int launch_row_small(const void *v, int dtype, int64_t R, int D, float eps, float *out, hipStream_t s) {
-    const int L = vq_small_lanes(D);
-    const int grid = waves_grid((R + 64 / L - 1) / (64 / L), 4);
-#define VQ_ROW_SMALL(DT, LL) row_small_kernel<DT, LL, NORMALIZE><<<grid, 256, 0, s>>>(v, R, D, eps, out)
-    if (dtype == VQHIP_DTYPE_F32) { if (L == 8) VQ_ROW_SMALL(0, 8); else if (L == 16) VQ_ROW_SMALL(0, 16); else VQ_ROW_SMALL(0, 32); }
-    else { if (L == 8) VQ_ROW_SMALL(1, 8); else if (L == 16) VQ_ROW_SMALL(1, 16); else VQ_ROW_SMALL(1, 32); }
-#undef VQ_ROW_SMALL
-    VQ_CHECK_LAUNCH("row_small_kernel");
-    return VQHIP_OK;
-}
-
-// hist[K] += bincount(idx) for int64 (hist_kernel, hist_lds_kernel) or int32 tokens (their _i32 twins)
-template <typename IdxT>
-static int launch_hist(const IdxT *idx, int64_t N, int64_t K, int32_t *hist, void *stream) {
-    constexpr bool i64 = sizeof(IdxT) == 8;
-    VQ_REQUIRE(idx && hist && N >= 0 && K > 0, i64 ? "vqhip_hist: bad argument" : "vqhip_hist_i32: bad argument");
-    if (N == 0) return VQHIP_OK;
-    hipStream_t s = (hipStream_t)stream;
-    if (K <= 32768 && N >= 16384) {            // enough tokens per block that the K-bin flush pays: at most 256 blocks, >= 2048 tokens each
-        static LdsCache lds_set;
-        if (int rc = ensure_dyn_lds(i64 ? (const void *)hist_lds_kernel : (const void *)hist_i32_lds_kernel, (size_t)K * 4, lds_set)) return rc;
-        int grid = (int)((N + 2047) / 2048); grid = grid > 256 ? 256 : grid;
-        if constexpr (i64) hist_lds_kernel<<<grid, 1024, (size_t)K * 4, s>>>(idx, N, (int)K, hist);
-        else hist_i32_lds_kernel<<<grid, 1024, (size_t)K * 4, s>>>(idx, N, (int)K, hist);
-    } else {
-        int grid = (int)((N + 255) / 256); grid = grid > 2048 ? 2048 : grid;
-        if constexpr (i64) hist_kernel<<<grid, 256, 0, s>>>(idx, N, K, hist);
-        else hist_i32_kernel<<<grid, 256, 0, s>>>(idx, N, K, hist);
-    }
-    VQ_CHECK_LAUNCH(i64 ? "hist_kernel" : "hist_i32_kernel");
-    return VQHIP_OK;
-}
+template int run_exact_stream<0>(const void *, int, const float *, const float *, const float *, int64_t, int64_t, int, int, u64 *, float *, int64_t, hipStream_t);
+template int run_exact_stream<1>(const void *, int, const float *, const float *, const float *, int64_t, int64_t, int, int, u64 *, float *, int64_t, hipStream_t);
+template int run_exact_stream<2>(const void *, int, const float *, const float *, const float *, int64_t, int64_t, int, int, u64 *, float *, int64_t, hipStream_t);
 
 extern "C" {
 
 int64_t vqhip_codebook_exact_offset(int64_t K, int D) {
     if (K <= 0 || D <= 0) return -1;
     return vq_cb_layout(K, D).off_eexact;
-}
-
-// front of the VQ-KD / NormalizeCallback forwards (vqhip_step_kernels.h): the L-lanes-per-row form at D <= 32
-static int launch_vqkd_front(const float *w_in, float *w_mid, int64_t K, const void *x, int x_dtype, float *xn, int64_t N, int D, float eps,
-                             float *zero, int64_t nzero, int w_passes, hipStream_t s) {
-    if (D <= 32) {
-        const int L = vq_small_lanes(D), rpb = 4 * (64 / L);
-        const int kblocks = (int)((K + rpb - 1) / rpb), xblocks = (int)((N + rpb - 1) / rpb);
-#define VQ_FRONT_SMALL(DT, LL) vqkd_front_small_kernel<DT, LL><<<kblocks + xblocks, 256, 0, s>>>(w_in, w_mid, K, x, xn, N, D, eps, kblocks, zero, nzero, w_passes)
-        if (x_dtype == VQHIP_DTYPE_F32) { if (L == 8) VQ_FRONT_SMALL(0, 8); else if (L == 16) VQ_FRONT_SMALL(0, 16); else VQ_FRONT_SMALL(0, 32); }
-        else { if (L == 8) VQ_FRONT_SMALL(1, 8); else if (L == 16) VQ_FRONT_SMALL(1, 16); else VQ_FRONT_SMALL(1, 32); }
-#undef VQ_FRONT_SMALL
-    } else {
-        const int kblocks = (int)((K + 3) / 4), xblocks = (int)((N + 3) / 4);
-        if (x_dtype == VQHIP_DTYPE_F32) vqkd_front_kernel<0><<<kblocks + xblocks, 256, 0, s>>>(w_in, w_mid, K, x, xn, N, D, eps, kblocks, zero, nzero, w_passes);
-        else vqkd_front_kernel<1><<<kblocks + xblocks, 256, 0, s>>>(w_in, w_mid, K, x, xn, N, D, eps, kblocks, zero, nzero, w_passes);
-    }
-    VQ_CHECK_LAUNCH("vqkd_front_kernel");
-    return VQHIP_OK;
 }
 
 int64_t vqhip_codebook_bytes(int64_t K, int D) {
@@ -502,30 +356,6 @@ int64_t vqhip_codebook_bytes(int64_t K, int D) {
 int64_t vqhip_workspace_bytes(int64_t N, int64_t K, int D) {
     if (N < 0 || K <= 0 || D <= 0) return 0;
     return vq_ws_layout(N > 0 ? N : 1, K, D).total;
-}
-
-int vqhip_row_sqnorm(const void *v, int dtype, int64_t R, int D, float *out, void *stream) {
-    if (!v || !out || D <= 0 || R < 0) return fail(VQHIP_EINVAL, "vqhip_row_sqnorm: bad argument");
-    if (R == 0) return VQHIP_OK;
-    hipStream_t s = (hipStream_t)stream;
-    if (D <= 32 && (dtype == VQHIP_DTYPE_F32 || dtype == VQHIP_DTYPE_BF16)) return launch_row_small<false>(v, dtype, R, D, 0.0f, out, s);
-    if (dtype == VQHIP_DTYPE_F32) row_sqnorm_kernel<0><<<waves_grid(R, 4), 256, 0, s>>>(v, R, D, out);
-    else if (dtype == VQHIP_DTYPE_BF16) row_sqnorm_kernel<1><<<waves_grid(R, 4), 256, 0, s>>>(v, R, D, out);
-    else return fail(VQHIP_EINVAL, "vqhip_row_sqnorm: dtype");
-    VQ_CHECK_LAUNCH("row_sqnorm_kernel");
-    return VQHIP_OK;
-}
-
-int vqhip_normalize_rows(const void *v, int dtype, int64_t R, int D, float eps, float *out, void *stream) {
-    if (!v || !out || D <= 0 || R < 0) return fail(VQHIP_EINVAL, "vqhip_normalize_rows: bad argument");
-    if (R == 0) return VQHIP_OK;
-    hipStream_t s = (hipStream_t)stream;
-    if (D <= 32 && (dtype == VQHIP_DTYPE_F32 || dtype == VQHIP_DTYPE_BF16)) return launch_row_small<true>(v, dtype, R, D, eps, out, s);
-    if (dtype == VQHIP_DTYPE_F32) normalize_rows_kernel<0><<<waves_grid(R, 4), 256, 0, s>>>(v, R, D, eps, out);
-    else if (dtype == VQHIP_DTYPE_BF16) normalize_rows_kernel<1><<<waves_grid(R, 4), 256, 0, s>>>(v, R, D, eps, out);
-    else return fail(VQHIP_EINVAL, "vqhip_normalize_rows: dtype");
-    VQ_CHECK_LAUNCH("normalize_rows_kernel");
-    return VQHIP_OK;
 }
 
 // metric may carry the internal words (VQ_METRIC_DOT, VQ_METRIC_SWAP)
@@ -646,8 +476,7 @@ static int argmin_pipeline(const void *x, int x_dtype, const float *e_exact, con
     }
     // last resort: whole-codebook fp32 pass (non-finite data, overflowing candidate lists)
     if (const int force = g_tune_force_exact.load()) {
-        force_exact_rows_kernel<<<1, 1024, 0, s>>>((int)(force < N ? force : N), V.exact_list, V.counters, V.keys);
-        VQ_CHECK_LAUNCH("force_exact_rows_kernel");
+        if (int frc = force_exact_rows((int)(force < N ? force : N), V.exact_list, V.counters, V.keys, s)) return frc;
     }
     return run_exact_rows(x, x_dtype, e_exact, en, V.xn, N, K, D, metric, V.exact_list, V.counters + 2, V.keys, V.counters + 3, idx, hist, s);
 }
@@ -790,23 +619,6 @@ int vqhip_argmin(const void *x, int x_dtype, const float *e, const void *cb, int
     return argmin_pipeline(x, x_dtype, e_exact, cb, N, K, D, metric, idx, hist, ws, stream);
 }
 
-int vqhip_argmin_exact(const void *x, int x_dtype, const float *e, int64_t N, int64_t K, int D, int metric, int64_t *idx,
-                       float *dmin, int32_t *hist, void *ws, int64_t ws_bytes, void *stream) {
-    if (N == 0) return VQHIP_OK;
-    if (!x || !e || !idx || !ws || N < 0 || K <= 0 || D <= 0) return fail(VQHIP_EINVAL, "vqhip_argmin_exact: bad argument");
-    VQ_REQUIRE(vq_row_dtype(x_dtype), "vqhip_argmin_exact: x_dtype");
-    VQ_REQUIRE(vq_fits_i31(N, K), "vqhip_argmin_exact: N or K too large");
-    VQ_NEED("vqhip_argmin_exact: ws too small", ws_bytes, vqhip_workspace_bytes(N, K, D));
-    return exact_whole<0>(x, x_dtype, e, N, K, D, metric, vq_ws_view(ws, vq_ws_layout(N, K, D)), idx, dmin, hist, nullptr, (hipStream_t)stream);
-}
-
-// The column pass, roles swapped: the codebook rows are the "rows", the N latents are the "codes"; the same proposal + exact
-// re-rank pipeline then returns for every code its nearest latent.  Its metric word: the exact finishing keeps the reference's
-// operand order, (chain + |x_n|^2) + |e_k|^2 = (chain + code norm) + row norm (VQ_METRIC_SWAP); cosine uses the operands as
-// given (both normalised by the caller): VQ_METRIC_DOT.
-static inline int vq_swapped_metric(int metric) {
-    return (metric == VQHIP_METRIC_L2) ? (VQHIP_METRIC_L2 | VQ_METRIC_SWAP) : (VQ_METRIC_DOT | (metric & VQ_METRIC_BF16));
-}
 // the latents as the fp32 rows an image is made from: themselves, or (bf16) their copy in `copy`
 static int latents_as_f32(const void *x, int x_dtype, int64_t N, int D, float *copy, hipStream_t s, const float **rows) {
     *rows = (const float *)x;
@@ -847,17 +659,7 @@ int vqhip_col_argmin(const void *x, int x_dtype, const float *e, int64_t N, int6
         return argmin_pipeline(e, VQHIP_DTYPE_F32, codes, img, K, N, D, m, col_idx, nullptr, pipe_ws, stream, tokens);
     }
     // D without a proposal image: the fp32-only route with one key per code
-    const VqWsView V = vq_ws_view(ws, vq_ws_layout(N, K, D));
-    if (metric == VQHIP_METRIC_L2) {
-        if (int rc = vqhip_row_sqnorm(e, VQHIP_DTYPE_F32, K, D, V.en, stream)) return rc;
-        if (int rc = vqhip_row_sqnorm(x, x_dtype, N, D, V.xn_whole, stream)) return rc;
-    }
-    fill_u64_kernel<<<256, 256, 0, s>>>(V.keys, K, ~0ull);
-    VQ_CHECK_LAUNCH("fill_u64_kernel");
-    if (int rc = run_exact_tiled<1>(x, x_dtype, e, V.en, V.xn_whole, N, K, D, metric, V.keys, nullptr, s)) return rc;
-    finalize_kernel<<<256, 256, 0, s>>>(V.keys, nullptr, nullptr, K, col_idx, nullptr, nullptr);
-    VQ_CHECK_LAUNCH("finalize_kernel");
-    return VQHIP_OK;
+    return exact_whole_cols(x, x_dtype, e, N, K, D, metric, vq_ws_view(ws, vq_ws_layout(N, K, D)), col_idx, s);
 }
 
 // ---- the column pass over a SHORT list, directly in fp32 ----------------------------------------------------------------
@@ -875,34 +677,6 @@ static bool col_direct_ok(int x_dtype, int metric, int64_t cap, int64_t N, int64
     if (x_dtype != VQHIP_DTYPE_F32) return false;        // the pass reads the tokens as fp32 rows, whatever the metric
     if (((cap + 31) / 32) * ((N + 127) / 128) * (int64_t)D > VQ_COL_DIRECT_MAX_WORK) return false;
     return ws_bytes >= vq_col_direct_layout(N, K).total;
-}
-// x: the tokens [N, D] as the exact definition consumes them (fp32), e: the codebook rows [K, D] likewise; tok_norm / row_norm:
-// oracle-order |x_n|^2 [N] / |e_k|^2 [K] where a caller has them already (L2 only; nullable: computed here)
-static int col_rows_direct(const void *x, const float *e, const int32_t *rows, const int32_t *count, int64_t cap, int64_t N,
-                           int64_t K, int D, int metric, int64_t *col_idx, char *ws, const float *tok_norm, const float *row_norm,
-                           hipStream_t s) {
-    const VqColDirectLayout C = vq_col_direct_layout(N, K);
-    u64 *keys = (u64 *)ws;
-    int *ticket = (int *)(ws + C.off_ticket);
-    float *tok_ws = (float *)(ws + C.off_tok_norm), *row_ws = (float *)(ws + C.off_row_norm);
-    col_direct_init_kernel<<<(int)((cap + 255) / 256), 256, 0, s>>>(rows, count, cap, keys, ticket);
-    VQ_CHECK_LAUNCH("col_direct_init_kernel");
-    const int m = vq_swapped_metric(metric);
-    if (metric == VQHIP_METRIC_L2) {
-        if (!tok_norm) { if (int rc = vqhip_row_sqnorm(x, VQHIP_DTYPE_F32, N, D, tok_ws, s)) return rc; tok_norm = tok_ws; }
-        if (!row_norm) { if (int rc = vqhip_row_sqnorm(e, VQHIP_DTYPE_F32, K, D, row_ws, s)) return rc; row_norm = row_ws; }
-    }
-    const int64_t ncb = (N + 63) / 64;
-    const int grid = (int)(ncb < 256 ? 256 : (ncb > 1024 ? 1024 : ncb));
-    const int few_max = exact_few_max(D);
-    const int lds = few_max ? vq_few_lds_bytes(D) : 0;
-    static LdsCache lds_set;
-    if (int rc = ensure_dyn_lds((const void *)exact_kernel<0>, lds, lds_set)) return rc;
-    // roles swapped: the listed codebook rows are the "rows", the tokens the "codes"
-    exact_kernel<0><<<grid, 256, lds, s>>>(e, (const float *)x, tok_norm, row_norm, K, N, D, m, (const int *)rows, (const int *)count, keys, ticket,
-                                           col_idx, nullptr, few_max, 1);
-    VQ_CHECK_LAUNCH("exact_kernel (direct column pass)");
-    return VQHIP_OK;
 }
 
 int64_t vqhip_col_rows_workspace_bytes(int64_t N, int64_t cap, int D) {
@@ -947,819 +721,9 @@ int vqhip_col_argmin_rows(const void *x, int x_dtype, const float *e, const int3
     return argmin_pipeline(esub, VQHIP_DTYPE_F32, codes, img, cap, N, D, m, col_idx, nullptr, pipe_ws, stream, tokens, count);
 }
 
-int vqhip_distance(const void *x, int x_dtype, const float *e, int64_t N, int64_t K, int D, int metric, float *d, void *ws,
-                   int64_t ws_bytes, void *stream) {
-    if (!x || !e || !d || !ws || N <= 0 || K <= 0 || D <= 0) return fail(VQHIP_EINVAL, "vqhip_distance: bad argument");
-    VQ_NEED("vqhip_distance: ws too small", ws_bytes, vqhip_workspace_bytes(N, K, D));
-    VQ_REQUIRE(vq_row_dtype(x_dtype), "vqhip_distance: x_dtype");
-    VQ_REQUIRE(vq_public_metric(metric), "vqhip_distance: metric");
-    return exact_whole<2>(x, x_dtype, e, N, K, D, metric, vq_ws_view(ws, vq_ws_layout(N, K, D)), nullptr, nullptr, nullptr, d, (hipStream_t)stream);
-}
-
-static int gather_ste_impl(const void *x, int x_dtype, const float *e, const int64_t *idx, int64_t N, int D, float *z,
-                           float *z_ste, double *sse, float *mse, void *stream, float beta = 0.0f);
-
-int vqhip_gather_ste_loss(const void *x, int x_dtype, const float *e, const int64_t *idx, int64_t N, int D, float *z,
-                          float *z_ste, double *sse, void *stream) {
-    if (!x || !e || !idx || N < 0 || D <= 0) return fail(VQHIP_EINVAL, "vqhip_gather_ste_loss: bad argument");
-    return gather_ste_impl(x, x_dtype, e, idx, N, D, z, z_ste, sse, nullptr, stream);
-}
-
-int vqhip_gather_ste_mse(const void *x, int x_dtype, const float *e, const int64_t *idx, int64_t N, int D, float *z,
-                         float *z_ste, float *mse, float beta, void *scratch16, void *stream) {
-    if (!x || !e || !idx || !mse || !scratch16 || N <= 0 || D <= 0) return fail(VQHIP_EINVAL, "vqhip_gather_ste_mse: bad argument");
-    return gather_ste_impl(x, x_dtype, e, idx, N, D, z, z_ste, (double *)scratch16, mse, stream, beta);
-}
-
-int vqhip_gather_ste_map(const void *x_rows, int x_dtype, const float *e, const int64_t *idx, int64_t B, int64_t HW, int D,
-                         float *out_map, float *mse, float beta, void *scratch16, void *stream) {
-    const int64_t N = B * HW;
-    if (!e || !idx || !out_map || B <= 0 || HW <= 0 || D <= 0 || (x_rows && (!mse || !scratch16)))
-        return fail(VQHIP_EINVAL, "vqhip_gather_ste_map: bad argument");
-    hipStream_t s = (hipStream_t)stream;
-    double *sse = x_rows ? (double *)scratch16 : nullptr;
-    VQ_REQUIRE(!x_rows || vq_row_dtype(x_dtype), "vqhip_gather_ste_map: x_dtype");
-    if (HW % 256 == 0 && D % 32 == 0) {
-        // images of a multiple of 256 positions: whole 1 KiB channel rows per wave-store (gather_ste_map256_kernel)
-        const int64_t nt = N / 256;
-        int csplit = 1;                                     // share the channels while that still leaves whole chunks and the grid is short
-        while (nt * csplit < 512 && (D / 32) % (csplit * 2) == 0) csplit *= 2;
-        const int64_t items = nt * csplit;
-        const int grid256 = (int)(items < 1024 ? items : 1024);
-        constexpr int LDS = 2 * 32 * 256 * 4;
-        static LdsCache sets[2];
-        const int bf = (x_rows && x_dtype == VQHIP_DTYPE_BF16) ? 1 : 0;
-        if (int rc = ensure_dyn_lds(bf ? (const void *)gather_ste_map256_kernel<1> : (const void *)gather_ste_map256_kernel<0>, LDS, sets[bf])) return rc;
-        if (!bf) gather_ste_map256_kernel<0><<<grid256, 512, LDS, s>>>(x_rows, e, idx, N, D, HW, csplit, out_map, sse, mse, beta);
-        else gather_ste_map256_kernel<1><<<grid256, 512, LDS, s>>>(x_rows, e, idx, N, D, HW, csplit, out_map, sse, mse, beta);
-        VQ_CHECK_LAUNCH("gather_ste_map256_kernel");
-        return VQHIP_OK;
-    }
-    int64_t ntiles = (N + 63) / 64;
-    const int grid = (int)(ntiles < 2048 ? ntiles : 2048);
-    if (!x_rows || x_dtype == VQHIP_DTYPE_F32) gather_ste_map_kernel<0><<<grid, 256, 0, s>>>(x_rows, e, idx, N, D, HW, out_map, sse, mse, beta);
-    else if (x_dtype == VQHIP_DTYPE_BF16) gather_ste_map_kernel<1><<<grid, 256, 0, s>>>(x_rows, e, idx, N, D, HW, out_map, sse, mse, beta);
-    else return fail(VQHIP_EINVAL, "vqhip_gather_ste_map: x_dtype");
-    VQ_CHECK_LAUNCH("gather_ste_map_kernel");
-    return VQHIP_OK;
-}
-
-static int gather_ste_impl(const void *x, int x_dtype, const float *e, const int64_t *idx, int64_t N, int D, float *z,
-                           float *z_ste, double *sse, float *mse, void *stream, float beta) {
-    if (N == 0) return VQHIP_OK;
-    hipStream_t s = (hipStream_t)stream;
-    // outputs beyond the Infinity Cache (256 MiB) are streamed: non-temporal accesses and twice the waves in flight
-    const int64_t out_bytes = (int64_t)N * D * 4 * ((z ? 1 : 0) + (z_ste ? 1 : 0));
-    const bool streamed = out_bytes > (192ll << 20);
-    int cap = streamed ? 512 : 256;                                    // blocks of 16 waves
-    int grid = (int)((N + 15) / 16);
-    grid = grid > cap ? cap : grid;
-#define VQ_GATHER(DT, NT) gather_ste_loss_kernel<DT, NT><<<grid, 1024, 0, s>>>(x, e, idx, N, D, z, z_ste, sse, mse, beta)
-    if (x_dtype == VQHIP_DTYPE_F32) { if (streamed) VQ_GATHER(0, 1); else VQ_GATHER(0, 0); }
-    else if (x_dtype == VQHIP_DTYPE_BF16) { if (streamed) VQ_GATHER(1, 1); else VQ_GATHER(1, 0); }
-    else return fail(VQHIP_EINVAL, "vqhip_gather_ste_loss: x_dtype");
-#undef VQ_GATHER
-    VQ_CHECK_LAUNCH("gather_ste_loss_kernel");
-    return VQHIP_OK;
-}
-
-int vqhip_hist(const int64_t *idx, int64_t N, int64_t K, int32_t *hist, void *stream) { return launch_hist(idx, N, K, hist, stream); }
-int vqhip_hist_i32(const int32_t *idx, int64_t N, int64_t K, int32_t *hist, void *stream) { return launch_hist(idx, N, K, hist, stream); }
-
-// ---- FiniteScalarQuantizer ----------------------------------------------------------------------------------------------
-// Validates the caller's constants and the shape, and turns them into the kernels' by-value argument.  Every refusal names
-// the entry point (`what`).
-static int fsq_setup(const char *what, const vqhip_fsq_t *q, int layout, int64_t N, int64_t HW, VqFsqConsts *k, int *grid) {
-    char msg[160];
-    if (!q) return fail(VQHIP_EINVAL, what, "null constants");
-    if (q->struct_bytes != (int64_t)sizeof(vqhip_fsq_t)) return fail(VQHIP_EINVAL, what, "struct_bytes != sizeof(vqhip_fsq_t)");
-    if (q->C < 1 || q->C > VQHIP_FSQ_MAX_C) {
-        snprintf(msg, sizeof(msg), "C = %d outside 1..%d", q->C, VQHIP_FSQ_MAX_C);
-        return fail(VQHIP_EINVAL, what, msg);
-    }
-    if (layout != VQHIP_LAYOUT_ROWS && layout != VQHIP_LAYOUT_MAP) return fail(VQHIP_EINVAL, what, "unknown layout");
-    if (N < 0 || N >= (1ll << 31)) return fail(VQHIP_EINVAL, what, "N outside 0 .. 2^31 - 1");
-    if (layout == VQHIP_LAYOUT_MAP && (HW < 1 || HW >= (1ll << 31) || N % HW != 0))
-        return fail(VQHIP_EINVAL, what, "the map needs HW >= 1 and N % HW == 0");
-    memset(k, 0, sizeof(*k));
-    k->C = q->C;
-    int64_t cum = 1;
-    for (int i = 0; i < q->C; ++i) {
-        const int L = q->levels[i];
-        if (L < 3) {
-            snprintf(msg, sizeof(msg), "level %d of channel %d < 3 (2 gives NaN, 1 divides by zero)", L, i);
-            return fail(VQHIP_EINVAL, what, msg);
-        }
-        if (cum * L > (1ll << 24)) return fail(VQHIP_EINVAL, what, "prod(levels) > 2^24 (the fp32 digit sum would not be exact)");
-        k->level[i] = L;
-        k->cum[i] = (int)cum;
-        k->cumf[i] = (float)cum;
-        k->half[i] = (float)(L / 2);
-        k->rhalf[i] = ((L / 2) & (L / 2 - 1)) == 0 ? 1.0f / (float)(L / 2) : 0.f;
-        k->odd[i] = (float)((L - 1) % 2);
-        k->shift[i] = q->shift[i];
-        k->scale[i] = q->scale[i];
-        cum *= L;
-    }
-    k->K = (int)cum;
-    *grid = (int)((N + VQ_FSQ_TILE - 1) / VQ_FSQ_TILE);
-    return VQHIP_OK;
-}
-
-static inline int fsq_aligned(const void *p, int flag) { return ((uintptr_t)p % 16 == 0) ? flag : 0; }
-
-int vqhip_fsq_encode(const vqhip_fsq_t *q, const void *x, int x_dtype, int layout, int64_t N, int64_t HW, int32_t *quant,
-                     float *z, int z_rows, void *x_rows, int32_t *hist, void *stream) {
-    const char *what = "vqhip_fsq_encode";
-    VqFsqConsts k;
-    int grid = 0;
-    if (int rc = fsq_setup(what, q, layout, N, HW, &k, &grid)) return rc;
-    if (!x || !quant) return fail(VQHIP_EINVAL, what, "x and quant are required");
-    if (!vq_row_dtype(x_dtype)) return fail(VQHIP_EINVAL, what, "x_dtype");
-    if (x_rows && layout != VQHIP_LAYOUT_MAP) return fail(VQHIP_EINVAL, what, "x_rows is a by-product of the map layout");
-    if (N == 0) return VQHIP_OK;
-    const int vec = fsq_aligned(x, VQ_FSQ_VEC_X) | fsq_aligned(z, VQ_FSQ_VEC_Z) | fsq_aligned(x_rows, VQ_FSQ_VEC_ROWS);
-    hipStream_t s = (hipStream_t)stream;
-    const int n = (int)N, hw = (int)(layout == VQHIP_LAYOUT_MAP ? HW : 0);
-#define VQ_FSQ_ENC(DT, MAP) fsq_encode_kernel<DT, MAP><<<grid, VQ_FSQ_TILE, 0, s>>>(k, x, n, hw, quant, z, z_rows, x_rows, hist, vec)
-    if (layout == VQHIP_LAYOUT_ROWS) { if (x_dtype == VQHIP_DTYPE_F32) VQ_FSQ_ENC(0, false); else VQ_FSQ_ENC(1, false); }
-    else { if (x_dtype == VQHIP_DTYPE_F32) VQ_FSQ_ENC(0, true); else VQ_FSQ_ENC(1, true); }
-#undef VQ_FSQ_ENC
-    VQ_CHECK_LAUNCH("fsq_encode_kernel");
-    return VQHIP_OK;
-}
-
-int vqhip_fsq_backward(const vqhip_fsq_t *q, const void *x, int x_dtype, int layout, int64_t N, int64_t HW, const float *g,
-                       void *grad_x, void *stream) {
-    const char *what = "vqhip_fsq_backward";
-    VqFsqConsts k;
-    int grid = 0;
-    if (int rc = fsq_setup(what, q, layout, N, HW, &k, &grid)) return rc;
-    if (!x || !g || !grad_x) return fail(VQHIP_EINVAL, what, "x, g and grad_x are required");
-    if (!vq_row_dtype(x_dtype)) return fail(VQHIP_EINVAL, what, "x_dtype");
-    if (N == 0) return VQHIP_OK;
-    const int vec = fsq_aligned(x, VQ_FSQ_VEC_X) | fsq_aligned(grad_x, VQ_FSQ_VEC_Z) | fsq_aligned(g, VQ_FSQ_VEC_G);
-    hipStream_t s = (hipStream_t)stream;
-    const int n = (int)N, hw = (int)(layout == VQHIP_LAYOUT_MAP ? HW : 0);
-#define VQ_FSQ_BWD(DT, MAP) fsq_backward_kernel<DT, MAP><<<grid, VQ_FSQ_TILE, 0, s>>>(k, x, g, n, hw, grad_x, vec)
-    if (layout == VQHIP_LAYOUT_ROWS) { if (x_dtype == VQHIP_DTYPE_F32) VQ_FSQ_BWD(0, false); else VQ_FSQ_BWD(1, false); }
-    else { if (x_dtype == VQHIP_DTYPE_F32) VQ_FSQ_BWD(0, true); else VQ_FSQ_BWD(1, true); }
-#undef VQ_FSQ_BWD
-    VQ_CHECK_LAUNCH("fsq_backward_kernel");
-    return VQHIP_OK;
-}
-
-int vqhip_fsq_decode(const vqhip_fsq_t *q, const void *quant, int quant_dtype, int layout, int64_t N, int64_t HW, float *z,
-                     void *stream) {
-    const char *what = "vqhip_fsq_decode";
-    VqFsqConsts k;
-    int grid = 0;
-    if (int rc = fsq_setup(what, q, layout, N, HW, &k, &grid)) return rc;
-    if (!quant || !z) return fail(VQHIP_EINVAL, what, "quant and z are required");
-    if (quant_dtype != VQHIP_DTYPE_I32 && quant_dtype != VQHIP_DTYPE_I64) return fail(VQHIP_EINVAL, what, "quant_dtype");
-    if (N == 0) return VQHIP_OK;
-    const int vec = fsq_aligned(z, VQ_FSQ_VEC_Z);
-    hipStream_t s = (hipStream_t)stream;
-    const int n = (int)N, hw = (int)(layout == VQHIP_LAYOUT_MAP ? HW : 0);
-#define VQ_FSQ_DEC(I64, MAP) fsq_decode_kernel<I64, MAP><<<grid, VQ_FSQ_TILE, 0, s>>>(k, quant, n, hw, z, vec)
-    if (layout == VQHIP_LAYOUT_ROWS) { if (quant_dtype == VQHIP_DTYPE_I64) VQ_FSQ_DEC(true, false); else VQ_FSQ_DEC(false, false); }
-    else { if (quant_dtype == VQHIP_DTYPE_I64) VQ_FSQ_DEC(true, true); else VQ_FSQ_DEC(false, true); }
-#undef VQ_FSQ_DEC
-    VQ_CHECK_LAUNCH("fsq_decode_kernel");
-    return VQHIP_OK;
-}
-
-// ---- pooled code features (vqhip_pool_kernels.h) -----------------------------------------------------------------------
-// what the three entry points refuse alike: B, HW >= 1 and B * HW < 2^31 (tokens are counted in 32 bits), a token dtype
-static int pool_check(const char *what, int quant_dtype, int64_t B, int64_t HW) {
-    if (B < 1 || HW < 1) return fail(VQHIP_EINVAL, what, "B and HW must be >= 1");
-    if (B >= (1ll << 31) || HW >= (1ll << 31) || !vq_fits_i31(B * HW, 0)) return fail(VQHIP_EINVAL, what, "B * HW must be below 2^31");
-    if (quant_dtype != VQHIP_DTYPE_I32 && quant_dtype != VQHIP_DTYPE_I64) return fail(VQHIP_EINVAL, what, "quant_dtype");
-    return VQHIP_OK;
-}
-
-static inline int pool_log2_ceil(int64_t v, int cap_log2) {
-    int l = 0;
-    while (l < cap_log2 && (1ll << l) < v) ++l;
-    return l;
-}
-
-int vqhip_decode_pool(const float *e, int64_t K, int D, const void *quant, int quant_dtype, int64_t B, int64_t HW, float *out,
-                      void *stream) {
-    const char *what = "vqhip_decode_pool";
-    VQ_REQUIRE(e && quant && out, "vqhip_decode_pool: e, quant and out are required");
-    VQ_REQUIRE(K >= 1 && D >= 1, "vqhip_decode_pool: K and D must be >= 1");
-    if (int rc = pool_check(what, quant_dtype, B, HW)) return rc;
-    // 16-byte columns where every row and the output row start aligned; else channel by channel
-    const bool vec = D % 4 == 0 && (uintptr_t)e % 16 == 0 && (uintptr_t)out % 16 == 0;
-    const int64_t cols = vec ? D / 4 : D;
-    const int cw_log2 = pool_log2_ceil(cols, 6);
-    const int64_t nchunks = (cols + (1ll << cw_log2) - 1) >> cw_log2;
-    const int group_threads = VQ_POOL_PARTIALS << cw_log2;
-    const int block = group_threads > 256 ? group_threads : 256;
-    const int64_t per_block = block / group_threads;
-    const int64_t grid = (B * nchunks + per_block - 1) / per_block;          // (B < 2^31, nchunks < 2^31: no overflow)
-    VQ_REQUIRE(grid < (1ll << 31), "vqhip_decode_pool: B * ceil(D / 256) is beyond one launch");
-    hipStream_t s = (hipStream_t)stream;
-#define VQ_POOL(I64, VEC) decode_pool_kernel<I64, VEC><<<(unsigned)grid, block, 0, s>>>(e, K, D, quant, B, (int)HW, cw_log2, (int)nchunks, out)
-    if (quant_dtype == VQHIP_DTYPE_I64) { if (vec) VQ_POOL(true, true); else VQ_POOL(true, false); }
-    else { if (vec) VQ_POOL(false, true); else VQ_POOL(false, false); }
-#undef VQ_POOL
-    VQ_CHECK_LAUNCH("decode_pool_kernel");
-    return VQHIP_OK;
-}
-
-int vqhip_decode_pool_bwd(const float *g, const void *quant, int quant_dtype, int64_t B, int64_t HW, int64_t K, int D,
-                          float *grad_e, void *stream) {
-    const char *what = "vqhip_decode_pool_bwd";
-    VQ_REQUIRE(g && quant && grad_e, "vqhip_decode_pool_bwd: g, quant and grad_e are required");
-    VQ_REQUIRE(K >= 1 && D >= 1, "vqhip_decode_pool_bwd: K and D must be >= 1");
-    if (int rc = pool_check(what, quant_dtype, B, HW)) return rc;
-    const int64_t N = B * HW;
-    const int lp_log2 = pool_log2_ceil(D, 6);
-    const int64_t grid = ((N << lp_log2) + 255) / 256;                       // N < 2^31, at most 64 lanes each
-    VQ_REQUIRE(grid < (1ll << 31), "vqhip_decode_pool_bwd: B * HW is beyond one launch");
-    hipStream_t s = (hipStream_t)stream;
-    if (quant_dtype == VQHIP_DTYPE_I64) decode_pool_bwd_kernel<true><<<(unsigned)grid, 256, 0, s>>>(g, quant, N, (int)HW, K, D, lp_log2, grad_e);
-    else decode_pool_bwd_kernel<false><<<(unsigned)grid, 256, 0, s>>>(g, quant, N, (int)HW, K, D, lp_log2, grad_e);
-    VQ_CHECK_LAUNCH("decode_pool_bwd_kernel");
-    return VQHIP_OK;
-}
-
-int vqhip_fsq_decode_pool(const vqhip_fsq_t *q, const void *quant, int quant_dtype, int64_t B, int64_t HW, float *out, void *stream) {
-    const char *what = "vqhip_fsq_decode_pool";
-    VQ_REQUIRE(q && quant && out, "vqhip_fsq_decode_pool: q, quant and out are required");
-    if (int rc = pool_check(what, quant_dtype, B, HW)) return rc;
-    VqFsqConsts k;
-    int unused = 0;
-    if (int rc = fsq_setup(what, q, VQHIP_LAYOUT_MAP, B * HW, HW, &k, &unused)) return rc;
-    const int64_t grid = (B * k.C * VQ_POOL_PARTIALS + 255) / 256;           // B < 2^31, C <= 16
-    VQ_REQUIRE(grid < (1ll << 31), "vqhip_fsq_decode_pool: B is beyond one launch");
-    hipStream_t s = (hipStream_t)stream;
-    if (quant_dtype == VQHIP_DTYPE_I64) fsq_decode_pool_kernel<true><<<(unsigned)grid, 256, 0, s>>>(k, quant, B, (int)HW, out);
-    else fsq_decode_pool_kernel<false><<<(unsigned)grid, 256, 0, s>>>(k, quant, B, (int)HW, out);
-    VQ_CHECK_LAUNCH("fsq_decode_pool_kernel");
-    return VQHIP_OK;
-}
-
-int vqhip_scatter_add_rows(const float *src, const int64_t *idx, int64_t N, int64_t K, int D, float *dst, void *stream) {
-    if (!src || !idx || !dst || N < 0 || K <= 0 || D <= 0) return fail(VQHIP_EINVAL, "vqhip_scatter_add_rows: bad argument");
-    if (N == 0) return VQHIP_OK;
-    scatter_add_rows_kernel<<<waves_grid(N, 4), 256, 0, (hipStream_t)stream>>>(src, idx, N, K, D, dst);
-    VQ_CHECK_LAUNCH("scatter_add_rows_kernel");
-    return VQHIP_OK;
-}
-
-int vqhip_gather_rows(const void *x, int x_dtype, const int64_t *row_idx, int64_t K, int D, float *out, void *stream) {
-    if (!x || !row_idx || !out || K < 0 || D <= 0) return fail(VQHIP_EINVAL, "vqhip_gather_rows: bad argument");
-    if (K == 0) return VQHIP_OK;
-    hipStream_t s = (hipStream_t)stream;
-    if (x_dtype == VQHIP_DTYPE_F32) gather_rows_kernel<0><<<waves_grid(K, 4), 256, 0, s>>>(x, row_idx, K, D, out);
-    else if (x_dtype == VQHIP_DTYPE_BF16) gather_rows_kernel<1><<<waves_grid(K, 4), 256, 0, s>>>(x, row_idx, K, D, out);
-    else return fail(VQHIP_EINVAL, "vqhip_gather_rows: x_dtype");
-    VQ_CHECK_LAUNCH("gather_rows_kernel");
-    return VQHIP_OK;
-}
-
-int vqhip_vqkd_update(float *w, const int64_t *hist, const float *sums, int64_t K, int D, float decay, int centroid_only,
-                      void *stream) {
-    if (!w || !hist || !sums || K <= 0 || D <= 0) return fail(VQHIP_EINVAL, "vqhip_vqkd_update: bad argument");
-    vqkd_update_kernel<<<waves_grid(K, 4), 256, 0, (hipStream_t)stream>>>(w, hist, sums, K, D, decay, centroid_only);
-    VQ_CHECK_LAUNCH("vqkd_update_kernel");
-    return VQHIP_OK;
-}
-
-int vqhip_cvq_update(float *w, float *p, const int64_t *hist, int64_t numel, const int64_t *numel_dev, const float *anchors,
-                     int64_t K, int D, float ema_decay, float eps, int stage, void *stream) {
-    if (!w || !p || K <= 0 || D <= 0 || stage < 1 || stage > 3 || ((stage & 1) && (!hist || (numel <= 0 && !numel_dev))) ||
-        ((stage & 2) && !anchors)) return fail(VQHIP_EINVAL, "vqhip_cvq_update: bad argument");
-    cvq_update_kernel<<<waves_grid(K, 4), 256, 0, (hipStream_t)stream>>>(w, p, hist, numel, numel_dev, anchors, K, D, ema_decay, eps, stage);
-    VQ_CHECK_LAUNCH("cvq_update_kernel");
-    return VQHIP_OK;
-}
-
-int vqhip_cvq_step(const float *w_in, float *w_out, const float *p_in, float *p_out, const int32_t *hist, int64_t numel,
-                   const void *x, int x_dtype, const int64_t *col_idx, int64_t K, int D, float ema_decay, float eps,
-                   void *stream) {
-    if (!w_in || !w_out || !p_in || !p_out || !hist || !x || !col_idx || K <= 0 || D <= 0 || numel <= 0)
-        return fail(VQHIP_EINVAL, "vqhip_cvq_step: bad argument");
-    hipStream_t s = (hipStream_t)stream;
-    if (x_dtype == VQHIP_DTYPE_F32) cvq_step_kernel<0><<<waves_grid(K, 4), 256, 0, s>>>(w_in, w_out, p_in, p_out, hist, numel, x, col_idx, K, D, ema_decay, eps);
-    else if (x_dtype == VQHIP_DTYPE_BF16) cvq_step_kernel<1><<<waves_grid(K, 4), 256, 0, s>>>(w_in, w_out, p_in, p_out, hist, numel, x, col_idx, K, D, ema_decay, eps);
-    else return fail(VQHIP_EINVAL, "vqhip_cvq_step: x_dtype");
-    VQ_CHECK_LAUNCH("cvq_step_kernel");
-    return VQHIP_OK;
-}
-
-int vqhip_cvq_decay(const float *p, int64_t K, float ema_decay, float eps, float *decay, void *stream) {
-    if (!p || !decay || K <= 0) return fail(VQHIP_EINVAL, "vqhip_cvq_decay: bad argument");
-    cvq_decay_kernel<<<(int)((K + 255) / 256), 256, 0, (hipStream_t)stream>>>(p, K, ema_decay, eps, decay);
-    VQ_CHECK_LAUNCH("cvq_decay_kernel");
-    return VQHIP_OK;
-}
-
-int vqhip_cvq_update_rows(float *w, const float *p, const int64_t *rows, const float *anchors_sub, int64_t M, int64_t K, int D,
-                          float ema_decay, float eps, void *stream) {
-    if (!w || !p || K <= 0 || D <= 0 || M < 0 || (M > 0 && (!rows || !anchors_sub)))
-        return fail(VQHIP_EINVAL, "vqhip_cvq_update_rows: bad argument");
-    if (M == 0) return VQHIP_OK;
-    cvq_update_rows_kernel<<<waves_grid(M, 4), 256, 0, (hipStream_t)stream>>>(w, p, rows, anchors_sub, M, K, D, ema_decay, eps);
-    VQ_CHECK_LAUNCH("cvq_update_rows_kernel");
-    return VQHIP_OK;
-}
-
-int vqhip_cvq_rows(const float *p, int64_t K, float ema_decay, float eps, int32_t *rows, int32_t *slot, int32_t *count,
-                   void *stream) {
-    if (!p || !rows || !slot || !count || K <= 0 || K >= (1ll << 31)) return fail(VQHIP_EINVAL, "vqhip_cvq_rows: bad argument");
-    cvq_rows_kernel<<<1, 1024, 0, (hipStream_t)stream>>>(p, K, ema_decay, eps, rows, slot, count);
-    VQ_CHECK_LAUNCH("cvq_rows_kernel");
-    return VQHIP_OK;
-}
-
-int64_t vqhip_pack_floats(int64_t K, int64_t M, int D) {
-    if (K <= 0 || M < 0 || D <= 0) return 0;
-    return VQ_PACK_HEADER(K) + M * (int64_t)D;
-}
-
-int vqhip_pack_counts(const void *hist, int hist_is_int64, int64_t numel, int64_t K, float *packed, void *stream) {
-    if (!hist || !packed || K <= 0 || numel < 0) return fail(VQHIP_EINVAL, "vqhip_pack_counts: bad argument");
-    const int grid = (int)((K + 255) / 256);
-    if (hist_is_int64) pack_counts_kernel<1><<<grid, 256, 0, (hipStream_t)stream>>>(hist, numel, K, packed);
-    else pack_counts_kernel<0><<<grid, 256, 0, (hipStream_t)stream>>>(hist, numel, K, packed);
-    VQ_CHECK_LAUNCH("pack_counts_kernel");
-    return VQHIP_OK;
-}
-
-int vqhip_unpack_counts(const float *packed, int64_t K, int64_t *out, void *stream) {
-    if (!packed || !out || K <= 0) return fail(VQHIP_EINVAL, "vqhip_unpack_counts: bad argument");
-    unpack_counts_kernel<<<(int)((K + 255) / 256), 256, 0, (hipStream_t)stream>>>(packed, K, out);
-    VQ_CHECK_LAUNCH("unpack_counts_kernel");
-    return VQHIP_OK;
-}
-
-int vqhip_cvq_pack(const int32_t *hist, int64_t numel, const void *x, int x_dtype, const int64_t *col_idx, const int32_t *count,
-                   int64_t cap, int64_t K, int D, float *packed, void *stream) {
-    if (!hist || !packed || K <= 0 || D <= 0 || numel <= 0 || cap < 0 || cap > K || (cap > 0 && (!x || !col_idx || !count)))
-        return fail(VQHIP_EINVAL, "vqhip_cvq_pack: bad argument");
-    hipStream_t s = (hipStream_t)stream;
-    const int hb = (int)((K + 255) / 256);
-    const int grid = hb + waves_grid(cap, 4);
-    if (x_dtype == VQHIP_DTYPE_BF16) cvq_pack_kernel<1><<<grid, 256, 0, s>>>(hist, numel, x, col_idx, count, cap, K, D, packed, hb);
-    else if (x_dtype == VQHIP_DTYPE_F32) cvq_pack_kernel<0><<<grid, 256, 0, s>>>(hist, numel, x, col_idx, count, cap, K, D, packed, hb);
-    else return fail(VQHIP_EINVAL, "vqhip_cvq_pack: x_dtype");
-    VQ_CHECK_LAUNCH("cvq_pack_kernel");
-    return VQHIP_OK;
-}
-
-int vqhip_cvq_apply(const float *w_in, float *w_out, const float *p_in, float *p_out, const int32_t *hist, int64_t numel,
-                    const void *x, int x_dtype, const int64_t *col_idx, const float *packed, int world, const int32_t *slot,
-                    int64_t cap, int64_t K, int D, float ema_decay, float eps, void *stream) {
-    if (!w_in || !w_out || !p_in || !p_out || !slot || K <= 0 || D <= 0 || cap < 0 || cap > K) return fail(VQHIP_EINVAL, "vqhip_cvq_apply: bad argument");
-    hipStream_t s = (hipStream_t)stream;
-    if (packed != nullptr) {
-        if (world < 1 || world > VQ_PACK_MAX_WORLD) return fail(VQHIP_EINVAL, "vqhip_cvq_apply: world must be in [1, 256] (exact fp32 count sums)");
-        cvq_apply_kernel<0, true><<<waves_grid(K, 4), 256, 0, s>>>(w_in, w_out, p_in, p_out, nullptr, 0, nullptr, nullptr, packed, world, slot, (int)cap, K, D, ema_decay, eps);
-    } else {
-        if (!hist || numel <= 0) return fail(VQHIP_EINVAL, "vqhip_cvq_apply: the one-rank form needs hist and numel");   // (x, col_idx: read for listed codes only)
-        if (x_dtype == VQHIP_DTYPE_F32) cvq_apply_kernel<0, false><<<waves_grid(K, 4), 256, 0, s>>>(w_in, w_out, p_in, p_out, hist, numel, x, col_idx, nullptr, 1, slot, (int)cap, K, D, ema_decay, eps);
-        else if (x_dtype == VQHIP_DTYPE_BF16) cvq_apply_kernel<1, false><<<waves_grid(K, 4), 256, 0, s>>>(w_in, w_out, p_in, p_out, hist, numel, x, col_idx, nullptr, 1, slot, (int)cap, K, D, ema_decay, eps);
-        else return fail(VQHIP_EINVAL, "vqhip_cvq_apply: x_dtype");
-    }
-    VQ_CHECK_LAUNCH("cvq_apply_kernel");
-    return VQHIP_OK;
-}
-
-// ---- NearestAnchor(sync=True) across ranks: keys of the local winners, the masked pack (include/vqhip.h) ---------------
-int vqhip_cvq_col_keys(const void *x, int x_dtype, const float *e, const int32_t *rows, const int32_t *count, int64_t cap,
-                       const int64_t *col_idx, int64_t N, int64_t K, int D, int metric, int rank, int64_t *keys, void *stream) {
-    if (!x || !e || !rows || !count || !col_idx || !keys || N <= 0 || K <= 0 || D <= 0 || cap < 0 || cap > K)
-        return fail(VQHIP_EINVAL, "vqhip_cvq_col_keys: bad argument");
-    if (N > VQHIP_SYNC_MAX_ROWS || rank < 0 || rank >= VQ_PACK_MAX_WORLD)
-        return fail(VQHIP_EINVAL, "vqhip_cvq_col_keys: a key holds 24 bits of row and 8 bits of rank (N <= 2^24, rank < 256)");
-    VQ_REQUIRE(vq_public_metric(metric), "vqhip_cvq_col_keys: metric");
-    if (cap == 0) return VQHIP_OK;
-    hipStream_t s = (hipStream_t)stream;
-    const int grid = (int)((cap + 63) / 64);
-    if (x_dtype == VQHIP_DTYPE_F32) cvq_col_keys_kernel<0><<<grid, 64, 0, s>>>(x, e, rows, count, cap, col_idx, D, metric, rank, keys);
-    else if (x_dtype == VQHIP_DTYPE_BF16) cvq_col_keys_kernel<1><<<grid, 64, 0, s>>>(x, e, rows, count, cap, col_idx, D, metric, rank, keys);
-    else return fail(VQHIP_EINVAL, "vqhip_cvq_col_keys: x_dtype");
-    VQ_CHECK_LAUNCH("cvq_col_keys_kernel");
-    return VQHIP_OK;
-}
-
-int vqhip_cvq_pack_sync(const int32_t *hist, int64_t numel, const void *x, int x_dtype, const int64_t *keys, const int32_t *count,
-                        int64_t cap, int rank, int64_t K, int D, float *packed, void *stream) {
-    if (!hist || !packed || K <= 0 || D <= 0 || numel <= 0 || cap < 0 || cap > K || rank < 0 || rank >= VQ_PACK_MAX_WORLD ||
-        (cap > 0 && (!x || !keys || !count)))
-        return fail(VQHIP_EINVAL, "vqhip_cvq_pack_sync: bad argument");
-    hipStream_t s = (hipStream_t)stream;
-    const int hb = (int)((K + 255) / 256);
-    const int grid = hb + waves_grid(cap, 4);
-    if (x_dtype == VQHIP_DTYPE_BF16) cvq_pack_sync_kernel<1><<<grid, 256, 0, s>>>(hist, numel, x, keys, count, cap, rank, K, D, packed, hb);
-    else if (x_dtype == VQHIP_DTYPE_F32) cvq_pack_sync_kernel<0><<<grid, 256, 0, s>>>(hist, numel, x, keys, count, cap, rank, K, D, packed, hb);
-    else return fail(VQHIP_EINVAL, "vqhip_cvq_pack_sync: x_dtype");
-    VQ_CHECK_LAUNCH("cvq_pack_sync_kernel");
-    return VQHIP_OK;
-}
-
-// ---- one host call per training forward (include/vqhip.h) ------------------------------------------------------------
-int64_t vqhip_cvq_forward_ws_bytes(int64_t N, int64_t K, int D, int64_t cap_max) {
-    if (N <= 0 || K <= 0 || D <= 0 || cap_max < 0 || cap_max > K) return 0;
-    return vq_cvq_ws_layout(N, K, D, cap_max).total;
-}
-
-int vqhip_cvq_forward(vqhip_cvq_forward_t *a, void *stream) {
-    if (!a || a->struct_bytes != (int64_t)sizeof(vqhip_cvq_forward_t)) return fail(VQHIP_EINVAL, "vqhip_cvq_forward: struct_bytes != sizeof(vqhip_cvq_forward_t)");
-    const int64_t N = a->N, K = a->K;
-    const int D = a->D, metric = a->metric;
-    VQ_REQUIRE(N > 0 && K > 0 && D > 0 && vq_fits_i31(N, K) && vq_coarse_supported(D), "vqhip_cvq_forward: needs N, K > 0 and D <= 1024, D % 8 == 0");
-    VQ_REQUIRE(vq_public_metric(metric), "vqhip_cvq_forward: metric");
-    VQ_REQUIRE(vq_row_dtype(a->x_dtype), "vqhip_cvq_forward: x_dtype");
-    const bool sync = a->exchange && a->anchor_sync;
-    if (a->phases < 1 || (a->phases > VQHIP_STEP_ALL && !(sync && a->phases == VQHIP_STEP_PACK_SYNC))) return fail(VQHIP_EINVAL, "vqhip_cvq_forward: phases");
-    if (!a->x || !a->w_in || !a->p_in || !a->w_out || !a->p_out || !a->rows || !a->slot || !a->count || !a->cb || !a->idx || !a->hist || !a->ws)
-        return fail(VQHIP_EINVAL, "vqhip_cvq_forward: null pointer");
-    const bool cos = VQ_IS_COS(metric);
-    if (cos && !a->xq) return fail(VQHIP_EINVAL, "vqhip_cvq_forward: the cosine metric needs the xq buffer");
-    if ((a->z_ste || a->mse) && (!a->mse || !a->scratch16)) return fail(VQHIP_EINVAL, "vqhip_cvq_forward: the decode tail needs mse and scratch16");
-    if (a->exchange) {
-        if (!a->packed) return fail(VQHIP_EINVAL, "vqhip_cvq_forward: exchange without a packed buffer");
-        if (a->world < 1 || a->world > VQ_PACK_MAX_WORLD) return fail(VQHIP_EINVAL, "vqhip_cvq_forward: world must be in [1, 256]");
-        if (a->phases == VQHIP_STEP_ALL && !a->comm && a->world > 1)
-            return fail(VQHIP_EINVAL, "vqhip_cvq_forward: VQHIP_STEP_ALL over more than one rank needs a communicator (or issue the collective between the two phases)");
-    }
-    if (sync) {
-        if (!a->keys) return fail(VQHIP_EINVAL, "vqhip_cvq_forward: anchor_sync needs the keys buffer");
-        if (a->rank < 0 || a->rank >= a->world) return fail(VQHIP_EINVAL, "vqhip_cvq_forward: anchor_sync needs this rank's number in [0, world)");
-        if (N > VQHIP_SYNC_MAX_ROWS) return fail(VQHIP_EINVAL, "vqhip_cvq_forward: anchor_sync holds a row in 24 bits (N <= 2^24 per rank)");
-    }
-    hipStream_t s = (hipStream_t)stream;
-    const VqCvqWsLayout C = vq_cvq_ws_layout(N, K, D, 0);       // the column pass is sized once this step's capacity is known
-    VQ_NEED("vqhip_cvq_forward: ws too small", a->ws_bytes, C.total);
-    char *w = (char *)a->ws;
-    int64_t *col_idx = (int64_t *)(w + C.off_col_idx);
-    char *col_ws = w + C.off_col_ws;
-    const int64_t col_ws_have = a->ws_bytes - C.off_col_ws;
-    if (a->phases != VQHIP_STEP_PACK_SYNC && (a->phases & VQHIP_STEP_BEFORE_EXCHANGE)) {
-        if (int rc = vqhip_encode_ex(a->x, a->x_dtype, a->w_in, N, K, D, metric, a->cb, a->cb_bytes, a->idx, a->hist, a->xq, a->ws,
-                                     C.enc_bytes, VQHIP_ENCODE_ZERO_HIST, stream)) return rc;
-        if (!a->list_ready)
-            if (int rc = vqhip_cvq_rows(a->p_in, K, a->ema_decay, a->eps, a->rows, a->slot, a->count, stream)) return rc;
-        if (!a->exchange && a->early_word_host && a->early_seq_dev) {     // one rank: the histogram is final behind the encode
-            cvq_count_next_kernel<false><<<1, 1024, 0, s>>>(a->p_in, a->hist, N, nullptr, K, a->ema_decay, a->eps, a->early_seq_dev, a->early_word_host);
-            VQ_CHECK_LAUNCH("cvq_count_next_kernel");
-        }
-        int64_t cap = a->cap;
-        if (cap < 0) {                   // the count the previous call's prefetch copied out: queued a whole step ago
-            if (!a->count_host) return fail(VQHIP_EINVAL, "vqhip_cvq_forward: cap < 0 needs count_host");
-            if (a->count_event) VQ_HIP(hipEventSynchronize((hipEvent_t)a->count_event));
-            cap = (int64_t)*(volatile const int32_t *)a->count_host;
-        }
-        if (cap < 0 || cap > K) return fail(VQHIP_EINVAL, "vqhip_cvq_forward: capacity outside [0, K]");
-        a->cap_used = cap;
-        a->exchange_floats = a->exchange ? vqhip_pack_floats(K, cap, D) : 0;
-        if (a->exchange) VQ_NEED("vqhip_cvq_forward: packed buffer too small (floats)", a->packed_floats, a->exchange_floats);
-        if (cap > 0) {
-            VQ_NEED("vqhip_cvq_forward: ws too small for the column pass", col_ws_have, vqhip_col_rows_workspace_bytes(N, cap, D));
-            const VqCbLayout L = vq_cb_layout(K, D);
-            const void *rows_x = cos ? (const void *)a->xq : a->x;
-            const float *codes = cos ? (const float *)((const char *)a->cb + L.off_eexact) : a->w_in;
-            if (int rc = vqhip_col_argmin_rows(rows_x, cos ? VQHIP_DTYPE_F32 : a->x_dtype, codes, a->rows, a->count, cap, N, K, D, metric,
-                                               col_idx, col_ws, col_ws_have, stream)) return rc;
-            if (sync)                    // the local winners' keys: the ranks agree on the global winner by a MIN all-reduce
-                if (int rc = vqhip_cvq_col_keys(rows_x, cos ? VQHIP_DTYPE_F32 : a->x_dtype, codes, a->rows, a->count, cap, col_idx, N, K, D, metric,
-                                                a->rank, a->keys, stream)) return rc;
-        }
-        if (a->exchange && !sync)
-            if (int rc = vqhip_cvq_pack(a->hist, N, a->x, a->x_dtype, col_idx, a->count, cap, K, D, a->packed, stream)) return rc;
-    }
-    if (sync && (a->phases == VQHIP_STEP_ALL || a->phases == VQHIP_STEP_PACK_SYNC)) {
-        if (a->cap_used < 0 || a->cap_used > K) return fail(VQHIP_EINVAL, "vqhip_cvq_forward: cap_used (the BEFORE phase writes it)");
-        if (a->phases == VQHIP_STEP_ALL && a->comm && a->cap_used > 0)
-            if (int rc = vqhip_allreduce_min_i64(a->keys, a->cap_used, a->comm, stream)) return rc;
-        if (int rc = vqhip_cvq_pack_sync(a->hist, N, a->x, a->x_dtype, a->keys, a->count, a->cap_used, a->rank, K, D, a->packed, stream)) return rc;
-    }
-    if (a->phases == VQHIP_STEP_ALL && a->exchange && a->comm)
-        if (int rc = vqhip_allreduce_packed(a->packed, a->exchange_floats, a->comm, stream)) return rc;
-    if (a->phases != VQHIP_STEP_PACK_SYNC && (a->phases & VQHIP_STEP_AFTER_EXCHANGE)) {
-        if (a->cap_used < 0 || a->cap_used > K) return fail(VQHIP_EINVAL, "vqhip_cvq_forward: cap_used (the BEFORE phase writes it)");
-        if (a->exchange && a->early_word_host && a->early_seq_dev) {      // the next list's length, right behind the reduced histogram
-            cvq_count_next_kernel<true><<<1, 1024, 0, s>>>(a->p_in, nullptr, 0, a->packed, K, a->ema_decay, a->eps, a->early_seq_dev, a->early_word_host);
-            VQ_CHECK_LAUNCH("cvq_count_next_kernel");
-        }
-        // sync: the packed rows ARE the global winners' latents (every other rank added -0): no averaging (anchors.py:59-63)
-        if (int rc = vqhip_cvq_apply(a->w_in, a->w_out, a->p_in, a->p_out, a->hist, N, a->x, a->x_dtype, col_idx, a->exchange ? a->packed : nullptr,
-                                     sync ? 1 : a->world, a->slot, a->cap_used, K, D, a->ema_decay, a->eps, stream)) return rc;
-        if (a->prefetch) {
-            // the list of the NEXT step; its length also goes straight to the caller's pinned host word (a store of the kernel
-            // itself — pinned host memory is device-visible at its own address — instead of a 4-byte copy launch behind it)
-            cvq_rows_kernel<<<1, 1024, 0, s>>>(a->p_out, K, a->ema_decay, a->eps, a->rows, a->slot, a->count, a->count_host);
-            VQ_CHECK_LAUNCH("cvq_rows_kernel");
-            if (a->count_host && a->count_event) VQ_HIP(hipEventRecord((hipEvent_t)a->count_event, s));
-        }
-        if (a->mse)
-            if (int rc = vqhip_gather_ste_mse(a->x, a->x_dtype, a->w_out, a->idx, N, D, nullptr, a->z_ste, a->mse, a->beta, a->scratch16, stream)) return rc;
-    }
-    return VQHIP_OK;
-}
-
-static inline VqKdWsLayout vqkd_ws_layout(int64_t N, int64_t K, int D) {
-    return vq_kd_ws_layout(N, K, D, vqhip_order_workspace_bytes(N, K), vqhip_segsum_workspace_bytes(N, D));
-}
-
-int64_t vqhip_vqkd_forward_ws_bytes(int64_t N, int64_t K, int D) {
-    if (N <= 0 || K <= 0 || D <= 0) return 0;
-    return vqkd_ws_layout(N, K, D).total;
-}
-
-int vqhip_vqkd_forward(vqhip_vqkd_forward_t *a, void *stream) {
-    if (!a || a->struct_bytes != (int64_t)sizeof(vqhip_vqkd_forward_t)) return fail(VQHIP_EINVAL, "vqhip_vqkd_forward: struct_bytes != sizeof(vqhip_vqkd_forward_t)");
-    const int64_t N = a->N, K = a->K;
-    const int D = a->D;
-    VQ_REQUIRE(N > 0 && K > 0 && D > 0 && vq_fits_i31(N, K) && vq_coarse_supported(D), "vqhip_vqkd_forward: needs N, K > 0 and D <= 1024, D % 8 == 0");
-    if (a->metric != VQHIP_METRIC_COS && a->metric != VQHIP_METRIC_COS_BF16) return fail(VQHIP_EINVAL, "vqhip_vqkd_forward: metric (cosine only)");
-    VQ_REQUIRE(vq_row_dtype(a->x_dtype), "vqhip_vqkd_forward: x_dtype");
-    if (a->phases < 1 || a->phases > VQHIP_STEP_ALL) return fail(VQHIP_EINVAL, "vqhip_vqkd_forward: phases");
-    if (!a->x || !a->w_in || !a->w_mid || !a->w_out || !a->xn || !a->xq || !a->cb || !a->idx || !a->hist || !a->packed || !a->ws)
-        return fail(VQHIP_EINVAL, "vqhip_vqkd_forward: null pointer");
-    if (a->tail && (!a->mse || !a->scratch16)) return fail(VQHIP_EINVAL, "vqhip_vqkd_forward: the tail needs mse and scratch16");
-    if (a->world < 1 || a->world > VQ_PACK_MAX_WORLD) return fail(VQHIP_EINVAL, "vqhip_vqkd_forward: world must be in [1, 256]");
-    if (a->phases == VQHIP_STEP_ALL && a->exchange && !a->comm && a->world > 1)
-        return fail(VQHIP_EINVAL, "vqhip_vqkd_forward: VQHIP_STEP_ALL over more than one rank needs a communicator (or issue the collective between the two phases)");
-    if (a->ordered && (K > 32768 || (D % 4) != 0)) return fail(VQHIP_EINVAL, "vqhip_vqkd_forward: ordered sums need K <= 32768 and D % 4 == 0");
-    const int64_t floats = vqhip_pack_floats(K, K, D);
-    VQ_NEED("vqhip_vqkd_forward: packed buffer too small (floats)", a->packed_floats, floats);
-    const VqKdWsLayout C = vqkd_ws_layout(N, K, D);
-    VQ_NEED("vqhip_vqkd_forward: ws too small", a->ws_bytes, C.total);
-    hipStream_t s = (hipStream_t)stream;
-    char *w = (char *)a->ws;
-    float *payload = a->packed + VQ_PACK_HEADER(K);
-    if (a->phases & VQHIP_STEP_BEFORE_EXCHANGE) {
-        a->exchange_floats = floats;
-        // front: codebook normalised twice, latents normalised, payload zeroed (the atomic sums need it; the ordered sums write every row)
-        int64_t nzero = a->ordered ? 0 : K * (int64_t)D;
-        if (nzero && ((K & 1) || (nzero % 4))) {            // a payload that is not 16-byte aligned / sized: plain memset
-            VQ_HIP(hipMemsetAsync(payload, 0, (size_t)nzero * 4, s));
-            nzero = 0;
-        }
-        if (int rc = launch_vqkd_front(a->w_in, a->w_mid, K, a->x, a->x_dtype, a->xn, N, D, 1e-12f, payload, nzero, 2, s)) return rc;
-        const int xblocks = (int)((N + 3) / 4);             // wave per token: the scatter below
-        if (int rc = vqhip_encode_ex(a->xn, VQHIP_DTYPE_F32, a->w_mid, N, K, D, a->metric, a->cb, a->cb_bytes, a->idx, a->hist, a->xq, a->ws,
-                                     C.enc_bytes, VQHIP_ENCODE_ZERO_HIST, stream)) return rc;
-        const int hb = (int)((K + 255) / 256);
-        if (a->ordered) {
-            int32_t *counts = (int32_t *)(w + C.off_counts), *offsets = (int32_t *)(w + C.off_offsets), *order = (int32_t *)(w + C.off_order);
-            if (int rc = vqhip_token_order(a->idx, N, K, counts, offsets, order, w + C.off_order_ws, vqhip_order_workspace_bytes(N, K), stream)) return rc;
-            const float *x2 = a->xq;                      // F.normalize(xn): the encode's by-product — except under the bf16-autocast
-            if (VQ_IS_BF16(a->metric)) {                  // metric, where xq holds the ROUNDED rows (the operand of that metric)
-                if (int rc = vqhip_normalize_rows(a->xn, VQHIP_DTYPE_F32, N, D, 1e-12f, (float *)(w + C.off_x2), stream)) return rc;
-                x2 = (const float *)(w + C.off_x2);
-            }
-            if (int rc = vqhip_segsum_rows(x2, a->idx, order, offsets, N, K, D, payload, w + C.off_segsum_ws, vqhip_segsum_workspace_bytes(N, D), stream)) return rc;
-            vqkd_scatter_pack_kernel<<<hb, 256, 0, s>>>(a->hist, N, a->xn, a->idx, N, K, D, 1e-12f, a->packed, hb, 0);
-        } else {
-            vqkd_scatter_pack_kernel<<<hb + xblocks, 256, 0, s>>>(a->hist, N, a->xn, a->idx, N, K, D, 1e-12f, a->packed, hb, 1);
-        }
-        VQ_CHECK_LAUNCH("vqkd_scatter_pack_kernel");
-    }
-    if (a->phases == VQHIP_STEP_ALL && a->exchange && a->comm)
-        if (int rc = vqhip_allreduce_packed(a->packed, floats, a->comm, stream)) return rc;
-    if (a->phases & VQHIP_STEP_AFTER_EXCHANGE) {
-        vqkd_update_packed_kernel<<<waves_grid(K, 4), 256, 0, s>>>(a->w_mid, a->w_out, a->packed, K, D, a->ema_decay);
-        VQ_CHECK_LAUNCH("vqkd_update_packed_kernel");
-        if (a->tail) {
-            // per-workgroup partial sums of the loss (<= 256 doubles): the record area of the encode's workspace, free by now
-            double *tail_partials = (double *)vq_ws_view(a->ws, vq_ws_layout(N, K, D)).rec;
-            if (D <= 32) {                                  // L lanes per token (vqhip_step_kernels.h)
-                const int L = vq_small_lanes(D), rpb = 16 * (64 / L);
-                int grid = (int)((N + rpb - 1) / rpb); grid = grid > 256 ? 256 : grid;
-                if (L == 8) vqkd_tail_small_kernel<8><<<grid, 1024, 0, s>>>(a->xn, a->w_out, a->idx, N, D, 1e-12f, a->z_ste, (double *)a->scratch16, a->mse, tail_partials);
-                else if (L == 16) vqkd_tail_small_kernel<16><<<grid, 1024, 0, s>>>(a->xn, a->w_out, a->idx, N, D, 1e-12f, a->z_ste, (double *)a->scratch16, a->mse, tail_partials);
-                else vqkd_tail_small_kernel<32><<<grid, 1024, 0, s>>>(a->xn, a->w_out, a->idx, N, D, 1e-12f, a->z_ste, (double *)a->scratch16, a->mse, tail_partials);
-            } else {
-                int grid = (int)((N + 15) / 16); grid = grid > 256 ? 256 : grid;
-                vqkd_tail_kernel<<<grid, 1024, 0, s>>>(a->xn, a->w_out, a->idx, N, D, 1e-12f, a->z_ste, (double *)a->scratch16, a->mse, tail_partials);
-            }
-            VQ_CHECK_LAUNCH("vqkd_tail_kernel");
-        }
-    }
-    return VQHIP_OK;
-}
-
-int vqhip_vq_forward(vqhip_vq_forward_t *a, void *stream) {
-    if (!a || a->struct_bytes != (int64_t)sizeof(vqhip_vq_forward_t)) return fail(VQHIP_EINVAL, "vqhip_vq_forward: struct_bytes != sizeof(vqhip_vq_forward_t)");
-    const int64_t N = a->N, K = a->K;
-    const int D = a->D;
-    VQ_REQUIRE(N > 0 && K > 0 && D > 0 && vq_fits_i31(N, K), "vqhip_vq_forward: N, K, D");
-    VQ_REQUIRE(vq_public_metric(a->metric), "vqhip_vq_forward: metric");
-    VQ_REQUIRE(vq_row_dtype(a->x_dtype), "vqhip_vq_forward: x_dtype");
-    if (!a->x || !a->w_in || !a->cb || !a->idx || !a->ws || (a->normalize && (!a->w_out || !a->xn))) return fail(VQHIP_EINVAL, "vqhip_vq_forward: null pointer");
-    if (VQ_IS_COS(a->metric) && !a->xq) return fail(VQHIP_EINVAL, "vqhip_vq_forward: the cosine metric needs the xq buffer");
-    if ((a->z_ste || a->mse) && (!a->mse || !a->scratch16)) return fail(VQHIP_EINVAL, "vqhip_vq_forward: the decode tail needs mse and scratch16");
-    VQ_NEED("vqhip_vq_forward: ws too small", a->ws_bytes, vqhip_workspace_bytes(N, K, D));
-    hipStream_t s = (hipStream_t)stream;
-    const void *rows = a->x;
-    int rows_dtype = a->x_dtype;
-    const float *codes = a->w_in;
-    if (a->normalize) {
-        if (int rc = launch_vqkd_front(a->w_in, a->w_out, K, a->x, a->x_dtype, a->xn, N, D, 1e-12f, nullptr, 0, 1, s)) return rc;
-        rows = a->xn; rows_dtype = VQHIP_DTYPE_F32; codes = a->w_out;
-    }
-    if (int rc = vqhip_encode_ex(rows, rows_dtype, codes, N, K, D, a->metric, a->cb, a->cb_bytes, a->idx, a->hist, a->xq, a->ws, a->ws_bytes,
-                                 a->hist ? VQHIP_ENCODE_ZERO_HIST : 0, stream)) return rc;
-    if (a->mse)
-        if (int rc = vqhip_gather_ste_mse(rows, rows_dtype, codes, a->idx, N, D, nullptr, a->z_ste, a->mse, a->beta, a->scratch16, stream)) return rc;
-    return VQHIP_OK;
-}
-
-int vqhip_vqkd_backward(const void *x, int x_dtype, const float *xn, const float *w, const int64_t *idx, int64_t N, int D,
-                        const float *g_zste, const float *g_loss, float *grad_x, void *stream) {
-    if (!x || !xn || !w || !idx || !grad_x || N < 0 || D <= 0) return fail(VQHIP_EINVAL, "vqhip_vqkd_backward: bad argument");
-    if (N == 0) return VQHIP_OK;
-    hipStream_t s = (hipStream_t)stream;
-    VQ_REQUIRE(vq_row_dtype(x_dtype), "vqhip_vqkd_backward: x_dtype");
-    if (D <= 32) {                                          // L lanes per token (vqhip_step_kernels.h)
-        const int L = vq_small_lanes(D), rpb = 4 * (64 / L);
-        int grid = (int)((N + rpb - 1) / rpb); grid = grid > 2048 ? 2048 : grid;
-#define VQ_BWD_SMALL(DT, LL) vqkd_backward_small_kernel<DT, LL><<<grid, 256, 0, s>>>(x, xn, w, idx, N, D, 1e-12f, g_zste, g_loss, grad_x)
-        if (x_dtype == VQHIP_DTYPE_F32) { if (L == 8) VQ_BWD_SMALL(0, 8); else if (L == 16) VQ_BWD_SMALL(0, 16); else VQ_BWD_SMALL(0, 32); }
-        else { if (L == 8) VQ_BWD_SMALL(1, 8); else if (L == 16) VQ_BWD_SMALL(1, 16); else VQ_BWD_SMALL(1, 32); }
-#undef VQ_BWD_SMALL
-        VQ_CHECK_LAUNCH("vqkd_backward_kernel");
-        return VQHIP_OK;
-    }
-    int grid = (int)((N + 3) / 4); grid = grid > 2048 ? 2048 : grid;
-    if (x_dtype == VQHIP_DTYPE_F32) vqkd_backward_kernel<0><<<grid, 256, 0, s>>>(x, xn, w, idx, N, D, 1e-12f, g_zste, g_loss, grad_x);
-    else vqkd_backward_kernel<1><<<grid, 256, 0, s>>>(x, xn, w, idx, N, D, 1e-12f, g_zste, g_loss, grad_x);
-    VQ_CHECK_LAUNCH("vqkd_backward_kernel");
-    return VQHIP_OK;
-}
-
 int vqhip_argmin_stats(const void *ws, int32_t *out, void *stream) {
     if (!ws || !out) return fail(VQHIP_EINVAL, "vqhip_argmin_stats: bad argument");
     VQ_HIP(hipMemcpyAsync(out, ws, 16, hipMemcpyDeviceToDevice, (hipStream_t)stream));
-    return VQHIP_OK;
-}
-
-int vqhip_diff(const void *a, int a_dtype, const void *b, int b_dtype, int64_t n, float scale, const float *scale_dev,
-               float *out, double *sse, void *stream) {
-    if (!a || !b || n < 0 || (!out && !sse)) return fail(VQHIP_EINVAL, "vqhip_diff: bad argument");
-    if (n == 0) return VQHIP_OK;
-    hipStream_t s = (hipStream_t)stream;
-    int grid = (int)((n + 255) / 256); grid = grid > 2048 ? 2048 : grid;
-    if (a_dtype == 0 && b_dtype == 0) diff_kernel<0, 0><<<grid, 256, 0, s>>>(a, b, n, scale, scale_dev, out, sse);
-    else if (a_dtype == 0 && b_dtype == 1) diff_kernel<0, 1><<<grid, 256, 0, s>>>(a, b, n, scale, scale_dev, out, sse);
-    else if (a_dtype == 1 && b_dtype == 0) diff_kernel<1, 0><<<grid, 256, 0, s>>>(a, b, n, scale, scale_dev, out, sse);
-    else if (a_dtype == 1 && b_dtype == 1) diff_kernel<1, 1><<<grid, 256, 0, s>>>(a, b, n, scale, scale_dev, out, sse);
-    else return fail(VQHIP_EINVAL, "vqhip_diff: dtype");
-    VQ_CHECK_LAUNCH("diff_kernel");
-    return VQHIP_OK;
-}
-
-int vqhip_vq_backward(const void *x, int x_dtype, const float *e, const int64_t *idx, int64_t N, int D, const float *g_zste,
-                      const float *g_cb, const float *g_cm, float *grad_x, float *grad_w, void *stream) {
-    return vqhip_vq_backward_ex(x, x_dtype, e, idx, N, D, g_zste, g_cb, g_cm, nullptr, 0.0f, grad_x, grad_w, stream);
-}
-
-int vqhip_vq_backward_ex(const void *x, int x_dtype, const float *e, const int64_t *idx, int64_t N, int D, const float *g_zste,
-                         const float *g_cb, const float *g_cm, const float *g_comb, float beta, float *grad_x, float *grad_w,
-                         void *stream) {
-    if (!x || !e || !idx || N < 0 || D <= 0 || (!grad_x && !grad_w)) return fail(VQHIP_EINVAL, "vqhip_vq_backward: bad argument");
-    if (N == 0) return VQHIP_OK;
-    hipStream_t s = (hipStream_t)stream;
-    int grid = (int)((N + 3) / 4); grid = grid > 2048 ? 2048 : grid;
-    if (x_dtype == VQHIP_DTYPE_F32)
-        vq_backward_kernel<0><<<grid, 256, 0, s>>>(x, e, idx, N, D, g_zste, g_cb, g_cm, grad_x, grad_w, g_comb, beta);
-    else if (x_dtype == VQHIP_DTYPE_BF16)
-        vq_backward_kernel<1><<<grid, 256, 0, s>>>(x, e, idx, N, D, g_zste, g_cb, g_cm, grad_x, grad_w, g_comb, beta);
-    else return fail(VQHIP_EINVAL, "vqhip_vq_backward: x_dtype");
-    VQ_CHECK_LAUNCH("vq_backward_kernel");
-    return VQHIP_OK;
-}
-
-int vqhip_vq_backward_map(const void *x_rows, int x_dtype, const float *e, const int64_t *idx, int64_t B, int64_t HW, int D,
-                          const float *g_map, const float *g_cm, const float *g_comb, float beta, void *grad_map, int grad_dtype,
-                          void *stream) {
-    if (!x_rows || !e || !idx || !grad_map || B <= 0 || HW <= 0 || D <= 0) return fail(VQHIP_EINVAL, "vqhip_vq_backward_map: bad argument");
-    if ((HW % 256) != 0 || (D % 32) != 0) return fail(VQHIP_EINVAL, "vqhip_vq_backward_map: needs HW % 256 == 0 and D % 32 == 0 (transpose and use vqhip_vq_backward_ex)");
-    VQ_REQUIRE(vq_row_dtype(x_dtype) && vq_row_dtype(grad_dtype), "vqhip_vq_backward_map: dtype");
-    const int64_t N = B * HW, nt = N / 256;
-    int csplit = 1;
-    while (nt * csplit < 512 && (D / 32) % (csplit * 2) == 0) csplit *= 2;
-    const int64_t items = nt * csplit;
-    const int grid = (int)(items < 1024 ? items : 1024);
-    constexpr int LDS = 2 * 32 * 256 * 4;
-    static LdsCache sets[4];
-    const int v = (x_dtype == VQHIP_DTYPE_BF16 ? 1 : 0) + (grad_dtype == VQHIP_DTYPE_BF16 ? 2 : 0);
-    const void *kerns[4] = {(const void *)vq_backward_map256_kernel<0, 0>, (const void *)vq_backward_map256_kernel<1, 0>,
-                            (const void *)vq_backward_map256_kernel<0, 1>, (const void *)vq_backward_map256_kernel<1, 1>};
-    if (int rc = ensure_dyn_lds(kerns[v], LDS, sets[v])) return rc;
-    hipStream_t s = (hipStream_t)stream;
-#define VQ_BMAP(DT, ODT) vq_backward_map256_kernel<DT, ODT><<<grid, 512, LDS, s>>>(x_rows, e, idx, N, D, HW, csplit, g_map, g_cm, g_comb, beta, grad_map)
-    if (v == 0) VQ_BMAP(0, 0); else if (v == 1) VQ_BMAP(1, 0); else if (v == 2) VQ_BMAP(0, 1); else VQ_BMAP(1, 1);
-#undef VQ_BMAP
-    VQ_CHECK_LAUNCH("vq_backward_map256_kernel");
-    return VQHIP_OK;
-}
-
-// ---- deterministic (ordered) codebook-side sums -----------------------------------------------------------------
-int64_t vqhip_order_workspace_bytes(int64_t N, int64_t K) {
-    if (N < 0 || K <= 0) return 0;
-    const int64_t nchunks = (N + VQ_SORT_CHUNK - 1) / VQ_SORT_CHUNK;
-    return (nchunks > 0 ? nchunks : 1) * K * 4;
-}
-
-int vqhip_token_order(const int64_t *idx, int64_t N, int64_t K, int32_t *counts, int32_t *offsets, int32_t *order, void *ws,
-                      int64_t ws_bytes, void *stream) {
-    if (!idx || !counts || !offsets || !order || !ws || N < 0 || K <= 0) return fail(VQHIP_EINVAL, "vqhip_token_order: bad argument");
-    VQ_NEED("vqhip_token_order: ws too small", ws_bytes, vqhip_order_workspace_bytes(N, K));
-    if (K > 32768) return fail(VQHIP_EINVAL, "vqhip_token_order: K > 32768 (per-chunk histogram must fit in LDS)");
-    if (N >= (1ll << 31)) return fail(VQHIP_EINVAL, "vqhip_token_order: N too large");
-    const int64_t nchunks = (N + VQ_SORT_CHUNK - 1) / VQ_SORT_CHUNK;
-    if (nchunks * K >= (1ll << 31)) return fail(VQHIP_EINVAL, "vqhip_token_order: N*K too large for the ordered route");
-    hipStream_t s = (hipStream_t)stream;
-    int *blockhist = (int *)ws;
-    const size_t lds = (size_t)K * 4;
-    static LdsCache lds_set;
-    if (int rc = ensure_dyn_lds((const void *)sort_hist_kernel, lds, lds_set)) return rc;
-    if (nchunks > 0) {
-        sort_hist_kernel<<<(int)nchunks, VQ_SORT_CHUNK, lds, s>>>(idx, N, (int)K, blockhist);
-        VQ_CHECK_LAUNCH("sort_hist_kernel");
-    }
-    sort_colscan_kernel<<<(int)((K + 255) / 256), 256, 0, s>>>(blockhist, (int)nchunks, (int)K, counts);
-    VQ_CHECK_LAUNCH("sort_colscan_kernel");
-    sort_offsets_kernel<<<1, 1024, 0, s>>>(counts, (int)K, offsets);
-    VQ_CHECK_LAUNCH("sort_offsets_kernel");
-    if (nchunks > 0) {
-        sort_place_kernel<<<(int)nchunks, VQ_SORT_CHUNK, 0, s>>>(idx, N, (int)K, blockhist, offsets, order);
-        VQ_CHECK_LAUNCH("sort_place_kernel");
-    }
-    return VQHIP_OK;
-}
-
-int64_t vqhip_segsum_workspace_bytes(int64_t N, int D) {
-    if (N < 0 || D <= 0) return 0;
-    return ((N + VQ_SEG_RANGE - 1) / VQ_SEG_RANGE + 1) * 2 * (int64_t)D * 4;
-}
-
-int vqhip_segsum_rows(const float *src, const int64_t *idx, const int32_t *order, const int32_t *offsets, int64_t N, int64_t K,
-                      int D, float *dst, void *ws, int64_t ws_bytes, void *stream) {
-    if (!src || !idx || !order || !offsets || !dst || !ws || N < 0 || K <= 0 || D <= 0 || (D % 4) != 0)
-        return fail(VQHIP_EINVAL, "vqhip_segsum_rows: bad argument (D must be a multiple of 4)");
-    VQ_NEED("vqhip_segsum_rows: ws too small", ws_bytes, vqhip_segsum_workspace_bytes(N, D));
-    return run_segsum<0>(src, VQHIP_DTYPE_F32, nullptr, idx, order, offsets, N, K, D, nullptr, dst, ws, (hipStream_t)stream);
-}
-
-int vqhip_vq_backward_w_ordered(const void *x, int x_dtype, const float *e, const int64_t *idx, const int32_t *order,
-                                const int32_t *offsets, int64_t N, int64_t K, int D, const float *g_cb, float *grad_w, void *ws,
-                                int64_t ws_bytes, void *stream) {
-    if (!x || !e || !idx || !order || !offsets || !grad_w || !ws || N < 0 || K <= 0 || D <= 0 || (D % 4) != 0)
-        return fail(VQHIP_EINVAL, "vqhip_vq_backward_w_ordered: bad argument (D must be a multiple of 4)");
-    VQ_NEED("vqhip_vq_backward_w_ordered: ws too small", ws_bytes, vqhip_segsum_workspace_bytes(N, D));
-    VQ_REQUIRE(vq_row_dtype(x_dtype), "vqhip_vq_backward_w_ordered: x_dtype");
-    return run_segsum<1>(x, x_dtype, e, idx, order, offsets, N, K, D, g_cb, grad_w, ws, (hipStream_t)stream);
-}
-
-int vqhip_ste(const void *x, int x_dtype, const float *z, int64_t n, float *out, void *stream) {
-    if (!x || !z || !out || n < 0) return fail(VQHIP_EINVAL, "vqhip_ste: bad argument");
-    if (n == 0) return VQHIP_OK;
-    hipStream_t s = (hipStream_t)stream;
-    int grid = (int)((n + 255) / 256); grid = grid > 4096 ? 4096 : grid;
-    if (x_dtype == VQHIP_DTYPE_F32) ste_kernel<0><<<grid, 256, 0, s>>>(x, z, n, out);
-    else if (x_dtype == VQHIP_DTYPE_BF16) ste_kernel<1><<<grid, 256, 0, s>>>(x, z, n, out);
-    else return fail(VQHIP_EINVAL, "vqhip_ste: dtype");
-    VQ_CHECK_LAUNCH("ste_kernel");
-    return VQHIP_OK;
-}
-
-int vqhip_normalize_rows_bwd(const void *v, int dtype, const float *g, int64_t R, int D, float eps, float *gv, void *stream) {
-    if (!v || !g || !gv || R < 0 || D <= 0) return fail(VQHIP_EINVAL, "vqhip_normalize_rows_bwd: bad argument");
-    if (R == 0) return VQHIP_OK;
-    hipStream_t s = (hipStream_t)stream;
-    if (dtype == VQHIP_DTYPE_F32) normalize_bwd_kernel<0><<<waves_grid(R, 4), 256, 0, s>>>(v, g, R, D, eps, gv);
-    else if (dtype == VQHIP_DTYPE_BF16) normalize_bwd_kernel<1><<<waves_grid(R, 4), 256, 0, s>>>(v, g, R, D, eps, gv);
-    else return fail(VQHIP_EINVAL, "vqhip_normalize_rows_bwd: dtype");
-    VQ_CHECK_LAUNCH("normalize_bwd_kernel");
-    return VQHIP_OK;
-}
-
-int vqhip_transpose(const void *in, void *out, int elem_bytes, int64_t B, int R, int C, void *stream) {
-    if (!in || !out || B < 0 || R <= 0 || C <= 0 || (elem_bytes != 2 && elem_bytes != 4))
-        return fail(VQHIP_EINVAL, "vqhip_transpose: bad argument");
-    if (B == 0) return VQHIP_OK;
-    if (B > 65535) return fail(VQHIP_EINVAL, "vqhip_transpose: batch too large for one launch");
-    dim3 grid((C + 63) / 64, (R + 63) / 64, (unsigned)B);
-    hipStream_t s = (hipStream_t)stream;
-    if (elem_bytes == 4) transpose_kernel<uint32_t><<<grid, 256, 0, s>>>((const uint32_t *)in, (uint32_t *)out, B, R, C);
-    else transpose_kernel<uint16_t><<<grid, 256, 0, s>>>((const uint16_t *)in, (uint16_t *)out, B, R, C);
-    VQ_CHECK_LAUNCH("transpose_kernel");
-    return VQHIP_OK;
-}
-
-int vqhip_codebook_metrics(const int64_t *counts, int64_t K, double *out, void *stream) {
-    if (!counts || !out || K <= 0) return fail(VQHIP_EINVAL, "vqhip_codebook_metrics: bad argument");
-    codebook_metrics_kernel<<<1, 1024, 0, (hipStream_t)stream>>>(counts, K, out);
-    VQ_CHECK_LAUNCH("codebook_metrics_kernel");
     return VQHIP_OK;
 }
 
@@ -1789,6 +753,10 @@ int vqhip_debug_proposal_scores(const void *x, int x_dtype, const void *cb, int6
     VQ_CHECK_LAUNCH("debug_margin_kernel");
     return VQHIP_OK;
 }
+
+}  // extern "C"
+int vq_tune_stream() { return g_tune_stream.load(); }
+extern "C" {
 
 int vqhip_set_tuning(int key, int value) {
     if (key == 2) g_tune_slices = (value == 1 || value == 2 || value == 4 || value == 8 || value == 16) ? value : 0;

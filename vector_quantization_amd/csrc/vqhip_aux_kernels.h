@@ -1,70 +1,23 @@
-// libvqhip device kernels, unit 8: transposes, codebook metrics, verification aids.  A unit of the core: vqhip.hip lists them.
+// libvqhip device kernels, unit 8: the column pass's copies (bf16 -> fp32, listed rows) and the verification aids.  Owned by vqhip.hip.
 #pragma once
 #include "vqhip_kernels.h"
 #include "vqhip_proposal_kernels.h"
 #include "vqhip_refine_kernels.h"
-// ------------------------------------------------------------------------------------------------
-// callers of the path: BCHW <-> (BHW)C rearrangement and codebook metrics
-// ------------------------------------------------------------------------------------------------
-// 'b c h w -> (b h w) c' (models/base.py:124,140) as a 64x64 LDS-tiled transpose per image: in[b][c][p] -> out[b][p][c]
-// (TO_TOKENS) or the inverse '(b h w) c -> b c h w' (base.py:126).  T = 2-byte or 4-byte element.
-template <typename T>
-__global__ __launch_bounds__(256) void transpose_kernel(const T *__restrict__ in, T *__restrict__ out, int64_t B, int R, int C) {
-    // in: [B][R][C] -> out: [B][C][R]
-    __shared__ T tile[64][65];
-    const int tx = threadIdx.x & 63, ty = threadIdx.x >> 6;     // 64 x 4
-    const int64_t b = blockIdx.z;
-    const int r0 = blockIdx.y * 64, c0 = blockIdx.x * 64;
-    const T *src = in + b * (int64_t)R * C;
-    T *dst = out + b * (int64_t)R * C;
-#pragma unroll
-    for (int i = 0; i < 16; ++i) {
-        const int r = r0 + ty + 4 * i, c = c0 + tx;
-        if (r < R && c < C) tile[ty + 4 * i][tx] = src[(int64_t)r * C + c];
-    }
-    __syncthreads();
-#pragma unroll
-    for (int i = 0; i < 16; ++i) {
-        const int c = c0 + ty + 4 * i, r = r0 + tx;
-        if (r < R && c < C) dst[(int64_t)c * R + r] = tile[tx][ty + 4 * i];
-    }
-}
-
-// CodebookUsageMetric / CodebookPPLMetric summaries (runners/metrics.py:58-73) from the accumulated counts:
-// out[0] = #nonzero / K, out[1] = entropy of counts / sum(counts) in nats.  One block.
-__global__ __launch_bounds__(1024) void codebook_metrics_kernel(const int64_t *counts, int64_t K, double *out) {
-    __shared__ double red[3][16];
-    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-    double tot = 0.0, nz = 0.0;
-    for (int64_t k = threadIdx.x; k < K; k += blockDim.x) { tot += (double)counts[k]; nz += counts[k] != 0 ? 1.0 : 0.0; }
-#pragma unroll
-    for (int off = 32; off >= 1; off >>= 1) { tot += __shfl_xor(tot, off, 64); nz += __shfl_xor(nz, off, 64); }
-    if (lane == 0) { red[0][wave] = tot; red[1][wave] = nz; }
-    __syncthreads();
-    tot = 0.0; nz = 0.0;
-    for (int i = 0; i < (int)(blockDim.x >> 6); ++i) { tot += red[0][i]; nz += red[1][i]; }
-    double ent = 0.0;
-    for (int64_t k = threadIdx.x; k < K; k += blockDim.x) {
-        const double c = (double)counts[k];
-        if (c > 0.0) { const double p = c / tot; ent -= p * log(p); }
-    }
-#pragma unroll
-    for (int off = 32; off >= 1; off >>= 1) ent += __shfl_xor(ent, off, 64);
-    __syncthreads();
-    if (lane == 0) red[2][wave] = ent;
-    __syncthreads();
-    if (threadIdx.x == 0) {
-        double e = 0.0;
-        for (int i = 0; i < (int)(blockDim.x >> 6); ++i) e += red[2][i];
-        out[0] = nz / (double)K;
-        out[1] = tot > 0.0 ? e : 0.0;
-    }
-}
-
 // bf16 -> fp32 copy (the column pass needs the latents as an fp32 "codebook")
 __global__ void bf16_to_f32_kernel(const uint16_t *in, int64_t n, float *out) {
     for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (int64_t)gridDim.x * blockDim.x)
         out[i] = bf16_to_f32(in[i]);
+}
+
+// out[i] = e[rows[i]] for i < count, zeros up to cap (the role-swapped pipeline reads whole 32-row blocks)
+__global__ void gather_listed_rows_kernel(const float *__restrict__ e, const int32_t *__restrict__ rows,
+                                          const int32_t *__restrict__ count, int64_t cap, int D, float *__restrict__ out) {
+    const int64_t i = (int64_t)blockIdx.x * (blockDim.x / 64) + (threadIdx.x >> 6);
+    const int lane = threadIdx.x & 63;
+    if (i >= cap) return;
+    const bool live = i < (int64_t)count[0];
+    const int64_t k = live ? rows[i] : 0;
+    for (int d = lane; d < D; d += 64) out[i * D + d] = live ? e[k * D + d] : 0.0f;
 }
 
 // ------------------------------------------------------------------------------------------------

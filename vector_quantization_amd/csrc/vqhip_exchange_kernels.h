@@ -1,31 +1,13 @@
 // Codebook-update kernels around the ONE exchange step of a training forward: the CVQ-VAE sparse anchor
 // set, the packed all-reduce buffer (code counts as exactly-summable fp32 pairs next to the fp32 payload), and the update
 // that consumes it.  gfx950 only.  Reference: vq/algorithms/cvqvae/quantizer_callback.py:85-103, anchors.py:50-67,83-84,
-// vq/algorithms/vq/utils.py:26-52, vq/algorithms/vqkd/quantizers/callbacks.py:44-71.
+// vq/algorithms/vq/utils.py:26-52, vq/algorithms/vqkd/quantizers/callbacks.py:44-71.  Owned by vqhip_update.hip (the layout of
+// the packed buffer, which the one-call forwards' kernels read too: vqhip_kernels.h).
 #pragma once
 #include "vqhip_kernels.h"
-#include "vqhip_refine_kernels.h"
 #include "vqhip_update_kernels.h"
 #include <hip/hip_runtime.h>
 #include <stdint.h>
-
-// ------------------------------------------------------------------------------------------------
-// Packed exchange buffer (fp32, one SUM all-reduce):
-//   [0, K)       low 16 bits of this rank's code counts        [K, 2K)  the bits above
-//   [2K, 2K+3)   token count in 16-bit pieces                   [2K+3]   zero (keeps the payload 16-byte aligned)
-//   [2K+4, ...)  payload rows [M, D] fp32 (anchors / centroid sums)
-// Every count piece is an integer below 2^16, so sums over up to 256 ranks stay below 2^24 and are EXACT in fp32 in any
-// order — the histogram of vq/algorithms/vq/utils.py:34-35 survives the trip through a float collective bit for bit.
-// ------------------------------------------------------------------------------------------------
-#define VQ_PACK_HEADER(K) (2 * (int64_t)(K) + 4)
-#define VQ_PACK_MAX_WORLD 256
-
-__device__ __forceinline__ int64_t unpack_count(const float *packed, int64_t K, int64_t k) {
-    return (int64_t)packed[K + k] * 65536 + (int64_t)packed[k];
-}
-__device__ __forceinline__ int64_t unpack_numel(const float *packed, int64_t K) {
-    return ((int64_t)packed[2 * K + 2] * 65536 + (int64_t)packed[2 * K + 1]) * 65536 + (int64_t)packed[2 * K];
-}
 
 // header from an int32 (HT = 0) or int64 (HT = 1) histogram
 template <int HT>
@@ -176,17 +158,6 @@ __global__ __launch_bounds__(1024) void cvq_count_next_kernel(const float *__res
         __hip_atomic_store(word_host, ((unsigned long long)(uint32_t)seq << 32) | (unsigned long long)(uint32_t)total, __ATOMIC_RELAXED,
                            __HIP_MEMORY_SCOPE_SYSTEM);
     }
-}
-
-// out[i] = e[rows[i]] for i < count, zeros up to cap (the role-swapped pipeline reads whole 32-row blocks)
-__global__ void gather_listed_rows_kernel(const float *__restrict__ e, const int32_t *__restrict__ rows,
-                                          const int32_t *__restrict__ count, int64_t cap, int D, float *__restrict__ out) {
-    const int64_t i = (int64_t)blockIdx.x * (blockDim.x / 64) + (threadIdx.x >> 6);
-    const int lane = threadIdx.x & 63;
-    if (i >= cap) return;
-    const bool live = i < (int64_t)count[0];
-    const int64_t k = live ? rows[i] : 0;
-    for (int d = lane; d < D; d += 64) out[i * D + d] = live ? e[k * D + d] : 0.0f;
 }
 
 // Packed buffer of one rank for the CVQ-VAE exchange: header from the epilogue histogram, payload row i = the anchor

@@ -13,7 +13,7 @@
 // starts aligned when the tensor does), and each lane reads its own row from LDS — lanes never stride C elements through
 // global memory.  MAP: the NCHW-contiguous map [B, C, HW] with N = B*HW; lane n reads x[b, i, p] (b = n / HW, p = n % HW),
 // i.e. neighbouring lanes touch neighbouring words of one channel row.  Token-major by-products of the map form (x_rows,
-// z rows) go out through the same LDS tile.
+// z rows) go out through the same LDS tile.  Owned by vqhip_fsq.hip.
 // ------------------------------------------------------------------------------------------------
 #pragma once
 #include "vqhip_kernels.h"
@@ -264,28 +264,4 @@ __global__ __launch_bounds__(VQ_FSQ_TILE) void fsq_decode_kernel(VqFsqConsts q, 
         __syncthreads();
         fsq_tile_out(z + (int64_t)n0 * C, tf, rows * C, vec & VQ_FSQ_VEC_Z);
     }
-}
-
-// hist[K] += bincount(idx) for int32 tokens; the out-of-range rule of hist_kernel (only 0 <= k < K is counted)
-__global__ void hist_i32_kernel(const int32_t *__restrict__ idx, int64_t N, int64_t K, int32_t *__restrict__ hist) {
-    for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < N; i += (int64_t)gridDim.x * blockDim.x) {
-        const int32_t k = idx[i];
-        if (k >= 0 && k < K) atomicAdd(&hist[k], 1);
-    }
-}
-
-// K <= 32768: block-private bins in LDS, flushed with lane-contiguous atomics (as hist_lds_kernel)
-__global__ __launch_bounds__(1024) void hist_i32_lds_kernel(const int32_t *__restrict__ idx, int64_t N, int K,
-                                                            int32_t *__restrict__ hist) {
-    extern __shared__ __attribute__((aligned(16))) char lds[];
-    int *h = (int *)lds;
-    for (int k = threadIdx.x; k < K; k += 1024) h[k] = 0;
-    __syncthreads();
-    for (int64_t i = (int64_t)blockIdx.x * 1024 + threadIdx.x; i < N; i += (int64_t)gridDim.x * 1024) {
-        const int32_t k = idx[i];
-        if (k >= 0 && k < K) atomicAdd(&h[k], 1);
-    }
-    __syncthreads();
-    for (int k = threadIdx.x; k < K; k += 1024)
-        if (h[k]) atomicAdd(&hist[k], h[k]);
 }

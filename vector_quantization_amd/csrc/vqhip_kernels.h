@@ -279,5 +279,68 @@ __device__ __forceinline__ void cb_stats_publish(const VqCbStats *st) {
     }
 }
 
-// (the units of the core include this header and each other as they need; vqhip.hip, the one translation unit that launches
-// their kernels, lists them)
+// ------------------------------------------------------------------------------------------------
+// exact scalar evaluation (refine)
+// ------------------------------------------------------------------------------------------------
+template <int DT>
+__device__ float sqnorm_thread(const void *x, int64_t off, int D) {   // oracle order, one thread
+    float p[64];
+#pragma unroll
+    for (int j = 0; j < 64; ++j) p[j] = 0.0f;
+    for (int base = 0; base < D; base += 64) {
+#pragma unroll
+        for (int j = 0; j < 64; ++j)
+            if (base + j < D) { float a = load_elem<DT>(x, off + base + j); p[j] = fmaf(a, a, p[j]); }
+    }
+#pragma unroll
+    for (int off2 = 32; off2 >= 1; off2 >>= 1)
+#pragma unroll
+        for (int j = 0; j < 32; ++j)
+            if (j < off2) p[j] = p[j] + p[j + off2];
+    return p[0];
+}
+
+template <int DT>
+__device__ float oracle_distance(const void *x, int64_t xoff, const float *erow, int D, int metric, float xn, float en) {
+    float c = 0.0f;
+    if (VQ_IS_L2(metric)) {
+        for (int d = 0; d < D; ++d) c = fmaf(-2.0f * load_elem<DT>(x, xoff + d), erow[d], c);
+        float t = (c + xn) + en;
+        t = (t < 0.0f) ? 0.0f : t;
+        return sqrtf(t);
+    }
+    for (int d = 0; d < D; ++d) c = fmaf(load_elem<DT>(x, xoff + d), erow[d], c);
+    return cos_distance(c, metric);
+}
+
+// torch.argmin order on (distance, index): NaN first, then smaller distance, then smaller index
+__device__ __forceinline__ u64 dist_key(float d, uint32_t k) {
+    if (isnan(d)) return (u64)k;
+    if (d == 0.0f) d = 0.0f;                 // -0 and +0 tie (lowest index wins), as in torch.argmin
+    uint32_t b = __float_as_uint(d);
+    // distances are >= 0 for L2; COS distances may be slightly negative: make the map monotone for both signs
+    b = (b & 0x80000000u) ? ~b : (b | 0x80000000u);
+    return ((u64)b + 1ull) << 32 | (u64)k;      // b+1 <= 2^32 : fits in the upper 33 bits
+}
+
+// ------------------------------------------------------------------------------------------------
+// Packed exchange buffer (fp32, one SUM all-reduce):
+//   [0, K)       low 16 bits of this rank's code counts        [K, 2K)  the bits above
+//   [2K, 2K+3)   token count in 16-bit pieces                   [2K+3]   zero (keeps the payload 16-byte aligned)
+//   [2K+4, ...)  payload rows [M, D] fp32 (anchors / centroid sums)
+// Every count piece is an integer below 2^16, so sums over up to 256 ranks stay below 2^24 and are EXACT in fp32 in any
+// order — the histogram of vq/algorithms/vq/utils.py:34-35 survives the trip through a float collective bit for bit.
+// ------------------------------------------------------------------------------------------------
+#define VQ_PACK_HEADER(K) (2 * (int64_t)(K) + 4)
+#define VQ_PACK_MAX_WORLD 256
+
+__device__ __forceinline__ int64_t unpack_count(const float *packed, int64_t K, int64_t k) {
+    return (int64_t)packed[K + k] * 65536 + (int64_t)packed[k];
+}
+__device__ __forceinline__ int64_t unpack_numel(const float *packed, int64_t K) {
+    return ((int64_t)packed[2 * K + 2] * 65536 + (int64_t)packed[2 * K + 1]) * 65536 + (int64_t)packed[2 * K];
+}
+
+// (the kernel headers of the core include this header and each other as they need.  Each names the translation unit that owns
+// it — the one unit that includes it and launches its kernels; what two units need of the device side is a template or
+// __forceinline__ and lives here)

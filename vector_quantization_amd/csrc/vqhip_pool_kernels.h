@@ -14,7 +14,7 @@
 // front of the dependent adds, with the next batch's tokens already requested.  The eight partials of a column meet in LDS.
 // ------------------------------------------------------------------------------------------------
 #pragma once
-#include "vqhip_fsq_kernels.h"      // VqFsqConsts, VQ_FSQ_MAX_C
+#include "vqhip_fsq_kernels.h"      // VqFsqConsts, VQ_FSQ_MAX_C (owned by vqhip_fsq.hip, like this header)
 
 #define VQ_POOL_PARTIALS 8
 #define VQ_POOL_UNROLL 8

@@ -1,4 +1,4 @@
-// libvqhip device kernels, unit 3b: the proposal pass for D <= 16 on v_mfma_f32_32x32x16_f16.  A unit of the core: vqhip.hip lists them.
+// libvqhip device kernels, unit 3b: the proposal pass for D <= 16 on v_mfma_f32_32x32x16_f16.  Owned by vqhip.hip.
 //
 // Why a second form.  At D <= 32 the proposal pass is bound by the vector instructions that look at the scores and by MFMA
 // ISSUE, not by the matrix pipe (profiles/r03_d32_epilogue_shares.txt).  With D <= 16 one 32x32x16 instruction

@@ -1,5 +1,5 @@
 // libvqhip device kernels, unit 3: the fp16-MFMA proposal pass (coarse_kernel) with its record merge and, optionally,
-// the decision stage.  A unit of the core: vqhip.hip lists them.
+// the decision stage.  Owned by vqhip.hip.
 #pragma once
 #include "vqhip_kernels.h"
 // ------------------------------------------------------------------------------------------------

@@ -1,52 +1,8 @@
 // libvqhip device kernels, unit 4: the row margin, the decision stage, the second proposal pass (rescan_kernel), the exact
-// fp32 re-rank and the last-resort whole-codebook pass for listed rows.  A unit of the core: vqhip.hip lists them.
+// fp32 re-rank.  Owned by vqhip.hip (the exact scalar evaluation the re-rank shares with other units: vqhip_kernels.h).
 #pragma once
 #include "vqhip_kernels.h"
 #include "vqhip_proposal_kernels.h"
-// ------------------------------------------------------------------------------------------------
-// exact scalar evaluation (refine)
-// ------------------------------------------------------------------------------------------------
-template <int DT>
-__device__ float sqnorm_thread(const void *x, int64_t off, int D) {   // oracle order, one thread
-    float p[64];
-#pragma unroll
-    for (int j = 0; j < 64; ++j) p[j] = 0.0f;
-    for (int base = 0; base < D; base += 64) {
-#pragma unroll
-        for (int j = 0; j < 64; ++j)
-            if (base + j < D) { float a = load_elem<DT>(x, off + base + j); p[j] = fmaf(a, a, p[j]); }
-    }
-#pragma unroll
-    for (int off2 = 32; off2 >= 1; off2 >>= 1)
-#pragma unroll
-        for (int j = 0; j < 32; ++j)
-            if (j < off2) p[j] = p[j] + p[j + off2];
-    return p[0];
-}
-
-template <int DT>
-__device__ float oracle_distance(const void *x, int64_t xoff, const float *erow, int D, int metric, float xn, float en) {
-    float c = 0.0f;
-    if (VQ_IS_L2(metric)) {
-        for (int d = 0; d < D; ++d) c = fmaf(-2.0f * load_elem<DT>(x, xoff + d), erow[d], c);
-        float t = (c + xn) + en;
-        t = (t < 0.0f) ? 0.0f : t;
-        return sqrtf(t);
-    }
-    for (int d = 0; d < D; ++d) c = fmaf(load_elem<DT>(x, xoff + d), erow[d], c);
-    return cos_distance(c, metric);
-}
-
-// torch.argmin order on (distance, index): NaN first, then smaller distance, then smaller index
-__device__ __forceinline__ u64 dist_key(float d, uint32_t k) {
-    if (isnan(d)) return (u64)k;
-    if (d == 0.0f) d = 0.0f;                 // -0 and +0 tie (lowest index wins), as in torch.argmin
-    uint32_t b = __float_as_uint(d);
-    // distances are >= 0 for L2; COS distances may be slightly negative: make the map monotone for both signs
-    b = (b & 0x80000000u) ? ~b : (b | 0x80000000u);
-    return ((u64)b + 1ull) << 32 | (u64)k;      // b+1 <= 2^32 : fits in the upper 33 bits
-}
-
 // Rigorous per-row margin (in scaled score units) between the proposal score and the fp32 definition.
 // Returns a negative value when the bound cannot be formed (non-finite data): the row is then flagged.
 // bf16_part (optional): receives the share of the returned margin that is the worst-case width of a bf16 tie bucket

@@ -1,4 +1,4 @@
-// libvqhip device kernels, unit 7: deterministic (ordered) codebook-side sums.  A unit of the core: vqhip.hip lists them.
+// libvqhip device kernels, unit 7: deterministic (ordered) codebook-side sums.  Owned by vqhip_update.hip.
 #pragma once
 #include "vqhip_kernels.h"
 // ------------------------------------------------------------------------------------------------

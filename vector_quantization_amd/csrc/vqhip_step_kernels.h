@@ -3,9 +3,9 @@
 // scattered straight into the packed exchange buffer, the EMA update read straight from it, and the decode / straight-through /
 // normalised-MSE tail with its backward.  gfx950 only.  Reference: vq/algorithms/vq/callbacks/normalize.py:22-29,
 // vq/algorithms/vqkd/quantizers/callbacks.py:44-75,114-129, vq/algorithms/vq/losses.py:37,53-62 (CommitmentLoss, mse norm=True).
+// Owned by vqhip_step.hip.
 #pragma once
 #include "vqhip_kernels.h"
-#include "vqhip_exchange_kernels.h"
 
 // |v|^2 of one row in the oracle's order (lane l sums elements l, l + 64, ... with fma; halving tree) -> 1 / max(|v|, eps) is
 // NOT formed: every consumer divides by the clamped norm like F.normalize does.

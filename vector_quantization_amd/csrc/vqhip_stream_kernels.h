@@ -1,7 +1,9 @@
 // libvqhip device kernels, unit 5b: the all-fp32 MFMA pass over whole batches, streamed form (round 6).
-// A unit of the core (vqhip.hip lists them); builds on vqhip_exact_kernels.h (whose epilogue rules — l2_skip's monotone sqrt, dist_key — it shares).
+// Owned by vqhip.hip (vqhip_core.h, run_exact_stream: why not by vqhip_exact.hip); shares the epilogue of
+// the register form (vqhip_exact_epilogue.h: tiled_epilogue, l2_skip's monotone sqrt; dist_key).
 #pragma once
 #include "vqhip_kernels.h"
+#include "vqhip_exact_epilogue.h"
 // ------------------------------------------------------------------------------------------------
 // exact_stream_kernel: exact_tiled_kernel's work item (128 rows x 256 codes, the same k-ordered chains of
 // v_mfma_f32_32x32x2_f32 per (row, code), the same epilogue) with BOTH operands read from LDS at the MFMA that consumes them.
