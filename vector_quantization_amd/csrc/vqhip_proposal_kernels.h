@@ -2,6 +2,7 @@
 // the decision stage.  Owned by vqhip.hip.
 #pragma once
 #include "vqhip_kernels.h"
+#include "vqhip_top2.h"
 // ------------------------------------------------------------------------------------------------
 // fp16 MFMA proposal pass
 // ------------------------------------------------------------------------------------------------
@@ -49,7 +50,8 @@ __device__ __forceinline__ int tile_row16(int e, int lane) { return 16 * (e >> 2
 // keeps, per lane and token, the best score with its tile / register and the runner-up value.
 // Scores are a_k = se*(xh . eh_k) - se*|e_k|^2/2 (the accumulator is initialised with the aux value).
 // MFMA shape 16x16x32 (the chip holds a higher clock on it than on 32x32x16: +8..11 % measured on this kernel).
-// The epilogue of tile t-1 (3 VALU per element) is spread over the MFMAs of tile t (two accumulator sets ping-pong).
+// The epilogue of tile t-1 (3 VALU per element; 2.25 where a token tile folds through the network of vqhip_top2.h: NET below)
+// is spread over the MFMAs of tile t (two accumulator sets ping-pong).
 //
 // FILTER (small D, where 3 VALU per score against D/8 MFMA cycles per score make the kernel VALU-issue-bound): the 8
 // elements a lane holds per (token tile, code tile) first go through a 4-instruction maximum (v_max3) and ONE compare
@@ -105,6 +107,19 @@ __global__ __launch_bounds__(WAVES * 64, (FILTER && NSTEP <= 2) ? (GROUPS ? 4 : 
     constexpr int NCH = TPS * NSTEP + VQ_AUX_CHUNKS(TPS);   // chunks per stage (2 per k-step and tile, + aux)
     constexpr int STAGE_BYTES = NCH * VQ_CHUNK_BYTES;
     constexpr int NE = 8;                                // accumulator elements per lane, token tile and code tile
+#ifndef VQ_TOP2_NET
+#define VQ_TOP2_NET 1          // 0: the sequential per-score update everywhere (A/B builds)
+#endif
+    // The unfiltered ping-pong forms whose token tile takes four chunks (D = 256 with four token tiles per wave: the headline
+    // kernel and its two siblings) fold the eight scores of a token tile through the max3 / med3 network of vqhip_top2.h, one
+    // step of it per chunk: 18 vector instructions per token tile where the per-score update takes 24, a chain of 4 instead of 16.
+    constexpr bool NET = (VQ_TOP2_NET != 0) && PIPE && !FILTER && NE * TT == 2 * NSTEP;
+    [[maybe_unused]] auto fold_tile = [](float &b1v, float &b2v, const f32x4 &lo, const f32x4 &hi) __attribute__((always_inline)) {
+        float s[NE];
+#pragma unroll
+        for (int e = 0; e < NE; ++e) s[e] = top2_tag(e < 4 ? lo[e & 3] : hi[e & 3], (uint32_t)e);
+        top2_fold8(b1v, b2v, s);
+    };
 #ifndef VQ_SCALAR_WAVE
 #define VQ_SCALAR_WAVE 1
 #endif
@@ -329,8 +344,9 @@ __global__ __launch_bounds__(WAVES * 64, (FILTER && NSTEP <= 2) ? (GROUPS ? 4 : 
 #pragma unroll
                 for (int t = 0; t < TT; ++t) {
                     const uint32_t old = __float_as_uint(b1[t]);
+                    if constexpr (NET) fold_tile(b1[t], b2[t], accB[0][t], accB[1][t]);
 #pragma unroll
-                    for (int e = 0; e < NE; ++e) {
+                    for (int e = 0; !NET && e < NE; ++e) {
                         float v = __uint_as_float((__float_as_uint(accB[e >> 2][t][e & 3]) & 0xFFFFFFF0u) | (uint32_t)e);
                         b2[t] = __builtin_amdgcn_fmed3f(b1[t], b2[t], v);
                         b1[t] = vmax(b1[t], v);
@@ -432,6 +448,7 @@ __global__ __launch_bounds__(WAVES * 64, (FILTER && NSTEP <= 2) ? (GROUPS ? 4 : 
             uint32_t old[TT];
 #pragma unroll
             for (int t = 0; t < TT; ++t) old[t] = __float_as_uint(b1[t]);
+            [[maybe_unused]] Top2Net net;
             // ring slot of chunk ch of tile ti: by its index in the stage (STAGE_PF) or in the tile
             constexpr int RING = PF + 1;
             const int g0 = STAGE_PF ? ti * NSTEP : 0;
@@ -492,7 +509,16 @@ __global__ __launch_bounds__(WAVES * 64, (FILTER && NSTEP <= 2) ? (GROUPS ? 4 : 
                 }
                 // retire NE*TT/NSTEP accumulator elements of the previous tile per chunk step
                 constexpr int TOTAL = NE * TT;
-                constexpr bool RETIRE = PIPE && !FILTER;
+                constexpr bool RETIRE = PIPE && !FILTER && !NET;
+                if constexpr (NET) {
+                    // token tile ch / 4 of the previous code tile, one step of the network per chunk (5 + 5 + 5 + 3 instructions)
+                    const int t = ch >> 2;
+                    auto sc = [&](int e) { return top2_tag(prv[e >> 2][t][e & 3], (uint32_t)e); };
+                    if ((ch & 3) == 0) top2_net_a(net, sc(0), sc(1), sc(2));
+                    else if ((ch & 3) == 1) top2_net_b(net, sc(3), sc(4), sc(5));
+                    else if ((ch & 3) == 2) top2_net_c(net, sc(6), sc(7), b1[t]);
+                    else top2_net_d(net, b1[t], b2[t]);
+                }
 #pragma unroll
                 for (int i = 0; RETIRE && i < (TOTAL + NSTEP - 1) / NSTEP; ++i) {
                     constexpr int EVERY = (NSTEP / TOTAL) > 0 ? NSTEP / TOTAL : 1;   // TOTAL < NSTEP: one element every EVERY chunks
@@ -566,6 +592,8 @@ __global__ __launch_bounds__(WAVES * 64, (FILTER && NSTEP <= 2) ? (GROUPS ? 4 : 
                 for (int e = 1; e < NE; ++e) g = __builtin_amdgcn_fmed3f(g, accB[e >> 2][t][e & 3], INFINITY);   // max, NaN-transparent like v_max
                 b2[t] = __builtin_amdgcn_fmed3f(b1[t], b2[t], g);
                 b1[t] = vmax(b1[t], g);
+            } else if constexpr (NET) {
+                fold_tile(b1[t], b2[t], accB[0][t], accB[1][t]);
             } else {
 #pragma unroll
                 for (int e = 0; e < NE; ++e) {
