@@ -929,6 +929,55 @@ int vqhip_row_bias_act_fwd(const void *x, int dtype, int64_t R, int64_t D, const
 int vqhip_row_bias_act_bwd(const void *g, const void *x, int dtype, int64_t R, int64_t D, const float *bias, int act, void *gx,
                            float *dbias /* [D] or NULL */, float *ws, int64_t ws_bytes, void *stream);
 
+/* ---- static KV cache: the attention step of cached generation (LlamaTransformer with static_cache=True) --------------------
+ * What transformers' LlamaAttention does between its projections and o_proj when one token follows a cache - apply_rotary_pos_emb,
+ * two torch.cat of DynamicCache.update, sdpa, a transpose - as ONE launch on caches allocated once; and the same storage rule for
+ * the L >= 1 tokens of a prompt, whose (MFMA) attention stays with the framework.
+ * INPUT   q, k, v: the new tokens' projections, rows [R, H Dh] with the heads contiguous inside a row (H = Hq for q, Hkv for k
+ *   and v), each with its own row stride in elements (>= H Dh), so the three may be views into one packed [R, (Hq + 2 Hkv) Dh]
+ *   GEMM output; R = B (decode) or B L (append, row r = b L + t).  dtype VQHIP_DTYPE_F32, _BF16 or _F16.  cos, sin: fp32 [L, Dh]
+ *   for the new positions, as LlamaRotaryEmbedding holds them before its cast.  k_cache, v_cache: [B, Hkv, cap, Dh], contiguous,
+ *   in dtype.  seen: the positions already stored, a host integer by value (a captured launch replays the same position).
+ * ROTARY  transformers' rotate_half convention, half = Dh / 2:  x'[i] = x[i] cos[i] - x[i + half] sin[i],
+ *   x'[i + half] = x[i + half] cos[i + half] + x[i] sin[i + half].  fp32 arithmetic on the loaded values, the two products kept
+ *   with their remainders (fma) and summed by a two-sum, so x' is the fp32 nearest to the exact value of the fp32 inputs or its
+ *   neighbour whatever cancels between the products.
+ * STORE   k' is rounded once (nearest even) to dtype and stored at position seen + t; v is copied there bit for bit.  Nothing past
+ *   position seen + L - 1 and nothing of another batch row's cache is written.
+ * vqhip_rope_append  writes q' rounded once to dtype as q_out [B, Hq, L, Dh] (what a causal sdpa reads) beside the store.
+ * vqhip_decode_attention (L = 1)  q' stays fp32.  With n = seen + 1, the step's own key read back as stored (after its rounding, so
+ *   that a later step sees the same value), group G = Hq / Hkv, and query head h reading kv head h / G:
+ *       s_j = scale * dot(q'_h, K[b, h / G, j]),  j = 0 .. n - 1;   p_j = exp(s_j - max_j s_j);
+ *       out[b, h Dh + i] = (sum_j p_j V[b, h / G, j, i]) / (sum_j p_j), rounded once to dtype: rows [B, Hq Dh], dense, the layout
+ *   o_proj reads.  All of it fp32 on the loaded values, as an online softmax (running maximum subtracted) per group of positions,
+ *   the groups merged in a fixed order: no atomics, a row's bits depend on (its own inputs, seen, Dh, G, dtype) alone - not on B,
+ *   on other rows, on cap or on the run.  Positions >= n are never read: whatever they hold (NaN included) cannot reach out.
+ *   One workgroup per (b, kv head) serves the G query heads from one pass over K and V in 16-byte loads; the length is not split
+ *   across workgroups.
+ * LIMITS  each refused with VQHIP_EINVAL before any HIP call, vqhip_last_error naming the clause: Dh a multiple of 8 with
+ *   16 <= Dh <= VQHIP_ATTN_MAX_HEAD_DIM; Hq % Hkv == 0 and Hq / Hkv <= VQHIP_ATTN_MAX_GROUP; 1 <= cap <= VQHIP_ATTN_MAX_LEN;
+ *   0 <= seen and seen + L <= cap; row strides >= H Dh; B, L >= 1, B L and B Hkv < 2^31; scale finite; k_cache and v_cache
+ *   16-byte aligned (they are read 16 bytes at a time: a cache one element off a boundary is refused by name); q, k, v, cos,
+ *   sin and the output are read and written element by element and need the alignment of their element type only.
+ * ERROR   of out against the definition in exact arithmetic on the same stored cache, u = VQHIP_GN_U, A = max_j sum_i |q'_i K_j,i|,
+ *   vmax = max_j |V_j,i|:   S = 17 u scale A  bounds a score (q' 1, product 1, at most 7 + 5 additions, the scale 1 rounding, (1 + u)^17);
+ *   a weight p_j then carries exp(+-S), one expf and at most two roundings per rescale or merge it passes through - at most
+ *   n / 8 + 10 of them (a slot holds every 8th position at least; 5 butterfly levels, 4 waves) at 6 u each with expf within
+ *   VQHIP_VIT_EXP_ULPS ulps - and the roundings of the exponents' arguments, which telescope to u (max - s_j) and weigh at most
+ *   u ln n in the mean:   eta = expm1(S) + (6 (n / 8 + 10) + 10) u;   |out - exact| <= 2 eta / (1 - eta) vmax + u |out|
+ *   + n 2^-126 vmax (weights that underflow) in fp32 before the store, VQHIP_SG2_STORE_U(dtype) on top.  The Python form of this
+ *   bound lives beside the float64 restatement of the tests (tests/decode_attention_ref.py); DESIGN.md §8 has the derivation.
+ * The last parameter of both is the hipStream_t the launch goes to. */
+#define VQHIP_ATTN_MAX_HEAD_DIM 128
+#define VQHIP_ATTN_MAX_GROUP 8
+#define VQHIP_ATTN_MAX_LEN 4096
+int vqhip_decode_attention(const void *q, int64_t q_stride, const void *k, int64_t k_stride, const void *v, int64_t v_stride, int dtype,
+                           const float *cos, const float *sin, void *k_cache, void *v_cache, int64_t seen, int64_t cap, float scale,
+                           int64_t B, int Hq, int Hkv, int Dh, void *out, void *hip_stream);
+int vqhip_rope_append(const void *q, int64_t q_stride, const void *k, int64_t k_stride, const void *v, int64_t v_stride, int dtype,
+                      const float *cos, const float *sin, void *k_cache, void *v_cache, int64_t seen, int64_t cap, int64_t B, int64_t L,
+                      int Hq, int Hkv, int Dh, void *q_out, void *hip_stream);
+
 /* ---- fused reconstruction metrics: L1, MSE, PSNR and SSIM of a validation pass ---------------------------------------------
  * The four numbers of the reference's table per tokenizer (docs/pretrained_models.md:47-51) that come from ImageLossMetric
  * (vq/runners/metrics/loss.py) over L1Loss, MSELoss, PSNRLoss and SSIMLoss (vq/tasks/image_reconstruction/losses.py), each of

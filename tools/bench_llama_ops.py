@@ -6,6 +6,12 @@ backwards) against the torch composition a ``LlamaDecoderLayer`` runs (``residua
 
     python tools/bench_llama_ops.py [--batch 64] [--blocks 5] [--iters 1000] [--module-iters 5] [--skip-module] [--layers 24]
                                     [--generate-batch 32] [--generate-length 65] [--out profiles/llama_transformer.txt]
+    python tools/bench_llama_ops.py --generate-only --generate-length 65,257 --out profiles/llama_decode.txt
+
+Generation has a third route, ``decode``: the same model with ``static_cache=True`` (a ``StaticKVCache`` and one
+``functional.decode_attention`` launch per layer and token), alternating block by block with the other two; its line also carries
+the kernel launches of one single-token step per layer, counted with the profiler.  ``--generate-only`` times generation alone, at
+every length of ``--generate-length`` (a comma-separated list).
 
 Shapes: [B * 257, 1024] (the residual stream) and [B * 257, 2 * 2816] (the gate | up tensor) with B = ``--batch`` images of 256 tokens
 and the class token.  configs/llamagen/ar.py trains with 256 images per rank; the default here is 64, so that the 24 layers' saved
@@ -139,25 +145,69 @@ def module_case(autocast, args):
     return line, nets
 
 
-def generate_case(nets, autocast, args):
-    """Cached generation, one token per step: ``generate`` from a class token to ``generate-length`` tokens, both routes on the same
+def step_launches(net, autocast, batch, static):
+    """Kernel launches of one single-token step behind a cache of 8 positions, counted with the profiler (None without one)."""
+    from vector_quantization_amd.kv_cache import StaticKVCache
+    try:
+        from torch.profiler import ProfilerActivity, profile
+        with torch.no_grad(), torch.autocast('cuda', torch.bfloat16, enabled=autocast):
+            cache = StaticKVCache.for_model(net._transformer.config, batch, 16, torch.bfloat16 if autocast else torch.float32, 'cuda') if static else None
+            token = torch.randint(0, 1000, (batch, 1), device='cuda')
+            for _ in range(8):
+                _, cache, _ = net.inference(token, cache, {})
+            torch.cuda.synchronize()
+            with profile(activities=[ProfilerActivity.CUDA]) as prof:
+                net.inference(token, cache, {})
+                torch.cuda.synchronize()
+        return sum(e.count for e in prof.key_averages() if getattr(e, 'device_type', None) is not None and 'cuda' in str(e.device_type).lower())
+    except Exception as err:                                                    # no profiler on this build: the count is left out
+        print(f'step_launches: {err!r}', file=sys.stderr)
+        return None
+
+
+def generate_case(nets, autocast, args, length=None):
+    """Cached generation, one token per step: ``generate`` from a class token to ``length`` tokens, every route on the same
     uniforms; the figure is microseconds per generated token."""
+    import copy
     from types import SimpleNamespace
+    length = length or args.generate_length[0]
+    if 'decode' not in nets:
+        nets['decode'] = copy.deepcopy(nets['fused'])
+        nets['decode'].static_cache = True
     codebook = SimpleNamespace(start=1000, end=VOCABULARY)
     prompt = torch.randint(0, 1000, (args.generate_batch, 1), device='cuda')
     u = torch.rand(args.generate_batch, device='cuda')
-    new = args.generate_length - 1
+    new = length - 1
     tokens = {}
 
     def run(name):
         with torch.autocast('cuda', torch.bfloat16, enabled=autocast):
-            tokens[name], _ = nets[name].eval().generate(prompt, args.generate_length, codebook, {'sampler': {'u': u}})
+            tokens[name], _ = nets[name].eval().generate(prompt, length, codebook, {'sampler': {'u': u}})
 
     res = alternate({name: (lambda n=name: run(n)) for name in nets}, args.blocks, 1)
-    assert nets['fused'].last_route.name == 'fused' and nets['torch'].last_route.name == 'torch'
+    assert nets['fused'].last_route.name == 'fused' and nets['torch'].last_route.name == 'torch' and nets['decode'].last_route.name == 'decode', \
+        [n.last_route for n in nets.values()]
     res = {name: {k: round(v / new, 1) for k, v in r.items()} for name, r in res.items()}
     same = float((tokens['fused'] == tokens['torch']).float().mean())
-    return dict(case=f'llama_medium_{args.layers}_layers_generate_us_per_token', new_tokens=new, iters=1, equal_token_share=round(same, 4), **res)
+    same_decode = float((tokens['fused'] == tokens['decode']).float().mean())
+    launches = {name: step_launches(nets[name], autocast, args.generate_batch, name == 'decode') for name in ('fused', 'decode')}
+    per_layer = {f'{name}_launches_per_layer_step': None if n is None else round(n / args.layers, 2) for name, n in launches.items()}
+    return dict(case=f'llama_medium_{args.layers}_layers_generate_us_per_token', new_tokens=new, iters=1, equal_token_share=round(same, 4),
+                decode_equal_token_share=round(same_decode, 4), fused_over_decode=round(res['fused']['median_us'] / res['decode']['median_us'], 2),
+                **per_layer, **res)
+
+
+def generate_nets(args):
+    """The two models of ``module_case`` without its training steps."""
+    from vector_quantization_amd.registries import VQSMTransformerRegistry
+    torch.manual_seed(0)
+    config = dict(type='LlamaTransformer', transformer=dict(MEDIUM, num_hidden_layers=args.layers), vocabulary_size=VOCABULARY,
+                  sampler=dict(type='BaseSampler'))
+    nets = {name: VQSMTransformerRegistry.build(dict(config, fused=name == 'fused')).cuda() for name in ('fused', 'torch')}
+    nets['fused'].init_weights(None)
+    torch.nn.init.normal_(nets['fused']._transformer.lm_head.weight, std=0.02)
+    nets['torch'].load_state_dict(nets['fused'].state_dict(), strict=True)
+    return nets
 
 
 def main():
@@ -168,7 +218,8 @@ def main():
     ap.add_argument('--iters', type=int, default=1000)
     ap.add_argument('--module-iters', type=int, default=5)
     ap.add_argument('--generate-batch', type=int, default=32)
-    ap.add_argument('--generate-length', type=int, default=65)
+    ap.add_argument('--generate-length', type=lambda t: [int(v) for v in t.split(',')], default=[65])
+    ap.add_argument('--generate-only', action='store_true')
     ap.add_argument('--layers', type=int, default=MEDIUM['num_hidden_layers'])
     ap.add_argument('--skip-module', action='store_true')
     ap.add_argument('--out', default=None)
@@ -187,14 +238,21 @@ def main():
         print(json.dumps(line), flush=True)
         lines.append(line)
 
-    for autocast in (False, True):
-        emit(norm_case(functional, R, MEDIUM['hidden_size'], autocast, args), [R, MEDIUM['hidden_size']], autocast)
-        emit(swiglu_case(functional, R, MEDIUM['intermediate_size'], autocast, args), [R, 2 * MEDIUM['intermediate_size']], autocast)
-    if not args.skip_module:
+    if args.generate_only:
+        nets = generate_nets(args)
+        for length in args.generate_length:
+            for autocast in (False, True):
+                emit(generate_case(nets, autocast, args, length), [args.generate_batch, 1], autocast, B=args.generate_batch)
+    else:
+        for autocast in (False, True):
+            emit(norm_case(functional, R, MEDIUM['hidden_size'], autocast, args), [R, MEDIUM['hidden_size']], autocast)
+            emit(swiglu_case(functional, R, MEDIUM['intermediate_size'], autocast, args), [R, 2 * MEDIUM['intermediate_size']], autocast)
+    if not args.skip_module and not args.generate_only:
         for autocast in (False, True):
             line, nets = module_case(autocast, args)
             emit(line, [args.batch, 257], autocast)
-            emit(generate_case(nets, autocast, args), [args.generate_batch, 1], autocast, B=args.generate_batch)
+            for length in args.generate_length:
+                emit(generate_case(nets, autocast, args, length), [args.generate_batch, 1], autocast, B=args.generate_batch)
             del nets
             torch.cuda.empty_cache()
     if args.out:

@@ -20,6 +20,7 @@ from .vqkd_autoencoders import VQKDDecoder, VQKDEncoder
 from .gan_losses import NonSaturatingLoss, R1GradientPenalty, VQGANDiscriminatorLoss, VQGANGeneratorLoss
 from .sequence_losses import CausalTokenLoss, LabelSmoothingCrossEntropy, MaskedTokenLoss
 from .transformers import BaseTransformer, HFTransformer, LlamaTransformer
+from .kv_cache import StaticKVCache
 from .utils import EMA, ema
 
 __all__ = [
@@ -30,7 +31,7 @@ __all__ = [
     'BaseDiscriminator', 'PatchGANDiscriminator', 'StyleGAN2Discriminator', 'VQGANGeneratorLoss', 'NonSaturatingLoss',
     'VQGANDiscriminatorLoss', 'R1GradientPenalty', 'VQDiscriminatorRegistry', 'VQGeneratorLossRegistry', 'VQDiscriminatorLossRegistry',
     'BaseEncoder', 'BaseDecoder', 'VQGANEncoder', 'VQGANDecoder', 'VQKDEncoder', 'VQKDDecoder', 'VQEncoderRegistry', 'VQDecoderRegistry',
-    'BaseTransformer', 'HFTransformer', 'LlamaTransformer', 'VQSMSamplerRegistry', 'VQSMTransformerRegistry',
+    'BaseTransformer', 'HFTransformer', 'LlamaTransformer', 'StaticKVCache', 'VQSMSamplerRegistry', 'VQSMTransformerRegistry',
 ]
 __version__ = '0.1.0'
 

@@ -320,6 +320,8 @@ def swiglu_gx_bounds(a, sg, d, s, g, up, gx_gate, gx_up):
             g * swiglu_silu_bound(s) + GN_U * gx_up + swiglu_floor(a, g))
 
 
+ATTN_MAX_HEAD_DIM, ATTN_MAX_GROUP, ATTN_MAX_LEN = 128, 8, 4096      # VQHIP_ATTN_MAX_*: vqhip_decode_attention / vqhip_rope_append
+
 STEP_BEFORE_EXCHANGE, STEP_AFTER_EXCHANGE, STEP_ALL, STEP_PACK_SYNC = 1, 2, 3, 4
 
 

@@ -835,3 +835,102 @@ def swiglu(gate_up: torch.Tensor, *, strict: bool = False) -> torch.Tensor:
             raise ValueError(f'swiglu: {why}')
         return swiglu_torch(gate_up)
     return _SwiGLU.apply(gate_up.contiguous())
+
+
+# ---- the attention step of cached generation behind a kv_cache.StaticKVCache: rotary + append, and one token's attention over
+#      the cache.  Inference ops: no autograd ----
+
+def _rope_torch(x: torch.Tensor, cos: torch.Tensor, sin: torch.Tensor) -> torch.Tensor:
+    """transformers' ``apply_rotary_pos_emb`` on one tensor: ``x * cos + rotate_half(x) * sin``."""
+    half = x.shape[-1] // 2
+    return x * cos + torch.cat((-x[..., half:], x[..., :half]), -1) * sin
+
+
+def _attn_compute_dtype(q: torch.Tensor):
+    return torch.float64 if q.dtype == torch.float64 else torch.float32
+
+
+def rope_append_torch(q: torch.Tensor, k: torch.Tensor, v: torch.Tensor, cos: torch.Tensor, sin: torch.Tensor, cache, layer: int):
+    """The same definition in torch, any device and dtype (float64 computes in float64, everything else in fp32): see ``rope_append``."""
+    kc, vc, seen = cache.layer(layer)
+    B, Hkv, _, Dh = kc.shape
+    L = q.shape[0] // B
+    cache.require_room(L)
+    ct = _attn_compute_dtype(q)
+    cos, sin = cos.reshape(1, L, 1, Dh).to(ct), sin.reshape(1, L, 1, Dh).to(ct)
+    q_rot = _rope_torch(q.reshape(B, L, -1, Dh).to(ct), cos, sin)
+    k_rot = _rope_torch(k.reshape(B, L, Hkv, Dh).to(ct), cos, sin)
+    kc[:, :, seen:seen + L] = k_rot.transpose(1, 2).to(kc.dtype)
+    vc[:, :, seen:seen + L] = v.reshape(B, L, Hkv, Dh).transpose(1, 2).to(vc.dtype)
+    return q_rot.transpose(1, 2).to(q.dtype).contiguous()
+
+
+def decode_attention_torch(q: torch.Tensor, k: torch.Tensor, v: torch.Tensor, cos: torch.Tensor, sin: torch.Tensor, cache, layer: int, *,
+                           scale: Optional[float] = None) -> torch.Tensor:
+    """The same definition in torch, any device and dtype (float64 computes in float64, everything else in fp32): see
+    ``decode_attention``.  The step's own key enters the scores as stored, after its rounding to the cache's dtype."""
+    kc, vc, seen = cache.layer(layer)
+    B, Hkv, _, Dh = kc.shape
+    cache.require_room(1)
+    ct = _attn_compute_dtype(q)
+    cos, sin = cos.reshape(1, 1, Dh).to(ct), sin.reshape(1, 1, Dh).to(ct)
+    q_rot = _rope_torch(q.reshape(B, -1, Dh).to(ct), cos, sin)                  # stays in the compute dtype
+    Hq = q_rot.shape[1]
+    kc[:, :, seen] = _rope_torch(k.reshape(B, Hkv, Dh).to(ct), cos, sin).to(kc.dtype)
+    vc[:, :, seen] = v.reshape(B, Hkv, Dh).to(vc.dtype)
+    keys = kc[:, :, :seen + 1].to(ct).repeat_interleave(Hq // Hkv, dim=1)       # query head h reads kv head h // (Hq // Hkv)
+    values = vc[:, :, :seen + 1].to(ct).repeat_interleave(Hq // Hkv, dim=1)
+    s = torch.einsum('bhd,bhnd->bhn', q_rot, keys) * (Dh ** -0.5 if scale is None else scale)
+    p = torch.exp(s - s.amax(-1, keepdim=True))
+    out = torch.einsum('bhn,bhnd->bhd', p, values) / p.sum(-1, keepdim=True)
+    return out.reshape(B, Hq * Dh).to(q.dtype)
+
+
+def _attention_refusal(what: str, q, k, v, cos, sin, cache, layer: int, L: int) -> str:
+    """Why the kernels would not take this step ('' if they would); inputs that require grad raise here: these ops have no backward."""
+    if torch.is_grad_enabled() and any(t.requires_grad for t in (q, k, v)):
+        raise ValueError(f'{what}: q, k or v requires grad and grad mode is on: an inference op without a backward')
+    kc, vc, seen = cache.layer(layer)
+    return ('' if q.is_cuda else f'q is on device {q.device}, not on a GPU') or ops.float_dtype_refusal('q is', q) \
+        or ('' if kc.device == q.device else f'the cache is on device {kc.device}, q on {q.device}') \
+        or ops.attention_refusal(q, k, v, cos, sin, kc, vc, seen, L)
+
+
+def _fp32_table(t: torch.Tensor, L: int) -> torch.Tensor:
+    """cos or sin as the kernels read it: contiguous fp32 [L, Dh] (no copy where ``LlamaRotaryEmbedding`` returned fp32)."""
+    return t.reshape(L, -1).to(torch.float32).contiguous()
+
+
+def decode_attention(q: torch.Tensor, k: torch.Tensor, v: torch.Tensor, cos: torch.Tensor, sin: torch.Tensor, cache, layer: int, *,
+                     scale: Optional[float] = None, strict: bool = False) -> torch.Tensor:
+    """One generated token's attention step behind ``cache`` (a ``StaticKVCache``), layer ``layer``, in one launch: rotates ``q``
+    [B, Hq Dh] and ``k`` [B, Hkv Dh] by ``cos`` / ``sin`` [Dh] (``rotate_half`` convention, fp32), stores the rounded k' and ``v`` at
+    the cache's position ``seen`` in place, and returns softmax(scale q' K^T) V over positions 0 .. seen with grouped-query heads as
+    rows [B, Hq Dh] in q's dtype - what ``o_proj`` reads.  q, k and v may be views into one packed GEMM output.  The caller
+    advances the cache once per model step.  CPU tensors, float64 and shapes the kernel does not take compute the same definition
+    in torch - or, with ``strict``, raise with the reason.  No autograd."""
+    cos32, sin32 = _fp32_table(cos, 1), _fp32_table(sin, 1)
+    why = _attention_refusal('decode_attention', q, k, v, cos32, sin32, cache, layer, 1)
+    if why:
+        if strict:
+            raise ValueError(f'decode_attention: {why}')
+        return decode_attention_torch(q, k, v, cos, sin, cache, layer, scale=scale)
+    kc, vc, seen = cache.layer(layer)
+    return ops.decode_attention(q, k, v, cos32, sin32, kc, vc, seen, scale)
+
+
+def rope_append(q: torch.Tensor, k: torch.Tensor, v: torch.Tensor, cos: torch.Tensor, sin: torch.Tensor, cache, layer: int, *,
+                strict: bool = False) -> torch.Tensor:
+    """The prefill form of ``decode_attention``'s storage step, for L >= 1 new tokens per batch row in one launch: rows [B L, H Dh]
+    (row b L + t), ``cos`` / ``sin`` [L, Dh].  Stores the rounded k' and ``v`` at positions seen .. seen + L - 1 of the cache in place
+    and returns q' [B, Hq, L, Dh] in q's dtype for a causal sdpa over the cache's first positions.  Routes and ``strict`` as
+    ``decode_attention``."""
+    L = max(q.shape[0] // max(cache.batch, 1), 1)
+    cos32, sin32 = _fp32_table(cos, L), _fp32_table(sin, L)
+    why = _attention_refusal('rope_append', q, k, v, cos32, sin32, cache, layer, L)
+    if why:
+        if strict:
+            raise ValueError(f'rope_append: {why}')
+        return rope_append_torch(q, k, v, cos, sin, cache, layer)
+    kc, vc, seen = cache.layer(layer)
+    return ops.rope_append(q, k, v, cos32, sin32, kc, vc, seen)

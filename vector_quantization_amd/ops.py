@@ -1560,6 +1560,83 @@ def swiglu_backward(g: torch.Tensor, x: torch.Tensor) -> torch.Tensor:
     return gx
 
 
+# ---- static KV cache: rotary + append, and the one-token attention over the cache (LlamaTransformer, static_cache=True) --------
+
+def attention_shape_refusal(Hq: int, Hkv: int, Dh: int) -> str:
+    """Why vqhip_decode_attention / vqhip_rope_append would refuse these head counts and this head dimension ('' if not)."""
+    return ('' if Dh % 8 == 0 and 16 <= Dh <= _lib.ATTN_MAX_HEAD_DIM else
+            f'a head dimension of {Dh} is not a multiple of 8 in 16 .. {_lib.ATTN_MAX_HEAD_DIM}') \
+        or ('' if Hkv >= 1 and Hq >= 1 and Hq % Hkv == 0 else f'{Hq} query heads are not a multiple of {Hkv} key-value heads') \
+        or ('' if Hq // Hkv <= _lib.ATTN_MAX_GROUP else f'{Hq // Hkv} query heads per key-value head are beyond {_lib.ATTN_MAX_GROUP}')
+
+
+def attention_refusal(q: torch.Tensor, k: torch.Tensor, v: torch.Tensor, cos: torch.Tensor, sin: torch.Tensor, k_cache: torch.Tensor,
+                      v_cache: torch.Tensor, seen: int, L: int = 1) -> str:
+    """Why vqhip_decode_attention (``L`` = 1) / vqhip_rope_append would refuse these tensors ('' if they would not): the clauses of
+    their LIMITS that depend on dtypes, shapes, strides and alignment.  q [B L, Hq Dh], k and v [B L, Hkv Dh] are read in place
+    through their row strides (three views into one packed row pass), cos and sin are [L, Dh] (or anything that flattens to it),
+    the caches [B, Hkv, cap, Dh]."""
+    if k_cache.dim() != 4 or v_cache.shape != k_cache.shape:
+        return f'the caches must both be [B, Hkv, cap, Dh], got {tuple(k_cache.shape)} and {tuple(v_cache.shape)}'
+    B, Hkv, cap, Dh = k_cache.shape
+    why = float_dtype_refusal('q is', q)
+    for name, t in (('k', k), ('v', v), ('k_cache', k_cache), ('v_cache', v_cache)):
+        why = why or ('' if t.dtype == q.dtype else f'{name} is {t.dtype}, q {q.dtype}')
+    for name, t in (('q', q), ('k', k), ('v', v)):
+        why = why or ('' if t.dim() == 2 and t.shape[0] == B * L and (t.stride(1) == 1 or t.shape[1] == 1) and
+                      (t.stride(0) >= t.shape[1] or t.shape[0] == 1) else
+                      f'{name} {tuple(t.shape)} with strides {t.stride()} is not {B * L} rows of contiguous heads')
+    if why:
+        return why
+    Hq = q.shape[1] // max(Dh, 1)
+    return ('' if q.shape[1] == Hq * Dh and k.shape[1] == Hkv * Dh and v.shape[1] == Hkv * Dh else
+            f'rows of {q.shape[1]}, {k.shape[1]} and {v.shape[1]} values are not heads of {Dh} for {Hkv} key-value heads') \
+        or attention_shape_refusal(Hq, Hkv, Dh) \
+        or ('' if 1 <= cap <= _lib.ATTN_MAX_LEN else f'a capacity of {cap} is outside 1 .. {_lib.ATTN_MAX_LEN}') \
+        or ('' if seen >= 0 and L >= 1 and seen + L <= cap else f'{L} tokens behind {seen} do not fit a capacity of {cap}') \
+        or ('' if all(t.dtype == torch.float32 and t.numel() == L * Dh and t.is_contiguous() for t in (cos, sin)) else
+            f'cos and sin must be contiguous float32 with {L} x {Dh} elements, got {cos.dtype} {tuple(cos.shape)} and {sin.dtype} {tuple(sin.shape)}') \
+        or ('' if k_cache.is_contiguous() and v_cache.is_contiguous() else 'the caches are not contiguous') \
+        or ('' if k_cache.data_ptr() % 16 == 0 and v_cache.data_ptr() % 16 == 0 else 'the caches are not 16-byte aligned')
+
+
+def _attention_args(what: str, q, k, v, cos, sin, k_cache, v_cache, seen: int, L: int):
+    _require_cuda(q, k, v, cos, sin, k_cache, v_cache)
+    _refuse(what, attention_refusal(q, k, v, cos, sin, k_cache, v_cache, seen, L))
+    B, Hkv, cap, Dh = k_cache.shape
+
+    def stride(t):
+        return max(t.stride(0), t.shape[1])
+    return (_ptr(q), stride(q), _ptr(k), stride(k), _ptr(v), stride(v), FLOAT_DTYPES[q.dtype], _ptr(cos), _ptr(sin), _ptr(k_cache),
+            _ptr(v_cache), int(seen), cap), (B, q.shape[1] // Dh, Hkv, Dh)
+
+
+@_on_tensor_device
+def decode_attention(q: torch.Tensor, k: torch.Tensor, v: torch.Tensor, cos: torch.Tensor, sin: torch.Tensor, k_cache: torch.Tensor,
+                     v_cache: torch.Tensor, seen: int, scale: Optional[float] = None) -> torch.Tensor:
+    """vqhip_decode_attention: one new token per batch row.  Rotates q [B, Hq Dh] and k [B, Hkv Dh] by ``cos`` / ``sin`` (fp32 [Dh]),
+    stores the rounded k' and v at position ``seen`` of the caches [B, Hkv, cap, Dh] (in place) and returns the attention of q'
+    over positions 0 .. seen as rows [B, Hq Dh] in q's dtype - what ``o_proj`` reads.  ``scale`` defaults to Dh ** -0.5.  One launch."""
+    head, (B, Hq, Hkv, Dh) = _attention_args('decode_attention', q, k, v, cos, sin, k_cache, v_cache, seen, 1)
+    out = torch.empty(B, Hq * Dh, dtype=q.dtype, device=q.device)
+    check(_lib.lib().vqhip_decode_attention(*head, float(Dh ** -0.5 if scale is None else scale), B, Hq, Hkv, Dh, _ptr(out), _stream()),
+          'vqhip_decode_attention')
+    return out
+
+
+@_on_tensor_device
+def rope_append(q: torch.Tensor, k: torch.Tensor, v: torch.Tensor, cos: torch.Tensor, sin: torch.Tensor, k_cache: torch.Tensor,
+                v_cache: torch.Tensor, seen: int) -> torch.Tensor:
+    """vqhip_rope_append: L >= 1 new tokens per batch row, rows [B L, H Dh] (row b L + t), ``cos`` / ``sin`` fp32 [L, Dh].  Stores the
+    rounded k' and v at positions seen .. seen + L - 1 of the caches (in place) and returns q' [B, Hq, L, Dh] in q's dtype, the
+    layout a causal sdpa reads.  One launch."""
+    L = max(cos.numel() // max(k_cache.shape[-1], 1), 1) if k_cache.dim() == 4 else 1
+    head, (B, Hq, Hkv, Dh) = _attention_args('rope_append', q, k, v, cos, sin, k_cache, v_cache, seen, L)
+    q_out = torch.empty(B, Hq, L, Dh, dtype=q.dtype, device=q.device)
+    check(_lib.lib().vqhip_rope_append(*head, B, L, Hq, Hkv, Dh, _ptr(q_out), _stream()), 'vqhip_rope_append')
+    return q_out
+
+
 # ---- fused reconstruction metrics (validation: vq/runners/metrics/loss.py over vq/tasks/image_reconstruction/losses.py) -----
 
 IMAGE_METRIC_COLUMNS = ('l1', 'mse', 'psnr', 'ssim')

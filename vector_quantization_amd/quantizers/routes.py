@@ -648,6 +648,44 @@ def llama_why(module, tokens: torch.Tensor, kv_cache=None, attention_mask=None) 
     return Route('torch', why) if why else Route('fused')
 
 
+def llama_decode_why(module, tokens: torch.Tensor, kv_cache=None) -> Route:
+    """Cached generation of ``LlamaTransformer`` behind a ``StaticKVCache``: the walk that calls the attention's own submodules -
+    one packed q/k/v GEMM, ``functional.decode_attention`` (one token) or ``rope_append`` + a causal sdpa (a prompt), ``o_proj`` -
+    (``decode``); or, with the first clause that refused it, the fused walk behind a ``DynamicCache`` (``walk``) where only the
+    attention step is refused, and transformers' own forward (``torch``) where ``llama_why`` refuses the walk itself.  The
+    clauses of ``walk``: a class that overrides ``_walk_static``, a ``rope_type`` other than ``default`` or an
+    ``attention_scaling`` other than 1 (the kernels rotate by cos and sin as they are), a sliding window, a head dimension or
+    a group of query heads beyond the kernels' limits, a capacity beyond theirs, a cache (``kv_cache``, where one is given) of
+    another shape, on another device or of another dtype than the projections produce (the autocast dtype under autocast, else
+    the parameters').  Nothing falls back behind a route that says ``decode``: a step the kernels refuse after that raises."""
+    from .. import transformers as vq_transformers
+    base = llama_why(module, tokens, kv_cache)
+    if base.name != 'fused':
+        return base
+    lm = module._transformer
+    config, rotary = lm.config, lm.model.rotary_emb
+    Hq, Hkv = config.num_attention_heads, config.num_key_value_heads
+    Dh = getattr(config, 'head_dim', None) or config.hidden_size // Hq
+    rope_type = getattr(rotary, 'rope_type', 'default')
+    scaling = getattr(rotary, 'attention_scaling', 1.0)
+    sliding = getattr(config, 'sliding_window', None) or 'sliding_attention' in (getattr(config, 'layer_types', None) or ())
+    why = own(module, vq_transformers.LlamaTransformer, '_walk_static') \
+        or ('' if rope_type == 'default' else f'rope_type={rope_type!r} is not \'default\'') \
+        or ('' if scaling == 1 else f'attention_scaling={scaling} is not 1') \
+        or ('a sliding window is configured' if sliding else '') \
+        or ops.attention_shape_refusal(Hq, Hkv, Dh)
+    if not why and kv_cache is not None:
+        dtype = torch.get_autocast_dtype('cuda') if tokens.is_cuda and torch.is_autocast_enabled() else lm.model.embed_tokens.weight.dtype
+        shape = (config.num_hidden_layers, tokens.shape[0], Hkv, Dh)
+        have = (getattr(kv_cache, 'layers', None), getattr(kv_cache, 'batch', None), getattr(kv_cache, 'kv_heads', None),
+                getattr(kv_cache, 'head_dim', None))
+        why = ('' if have == shape else f'the cache holds (layers, batch, kv heads, head dim) = {have}, the step needs {shape}') \
+            or ('' if kv_cache.capacity <= ops._lib.ATTN_MAX_LEN else f'a capacity of {kv_cache.capacity} is beyond {ops._lib.ATTN_MAX_LEN}') \
+            or ('' if kv_cache.device == tokens.device else f'the cache is on device {kv_cache.device}, the tokens on {tokens.device}') \
+            or ('' if kv_cache.dtype == dtype else f'the cache is {kv_cache.dtype}, the projections produce {dtype}')
+    return Route('walk', why) if why else Route('decode')
+
+
 # ---- MultinomialAnchor of a CVQ-VAE update (vector_quantization_amd/quantizers/anchors.py) ----------------------------------------
 
 def multinomial_anchor_why(anchor, d, x: torch.Tensor) -> Route:

@@ -19,6 +19,13 @@ The GEMMs, the rotary embedding and the attention core stay with the framework. 
   configuration ``routes.llama_why`` names.
 
 ``routes.llama_why`` decides per call; the decision is kept in ``last_route``.
+
+``LlamaTransformer(..., static_cache=True)`` (off by default) generates behind a ``StaticKVCache`` instead of transformers'
+``DynamicCache``: K and V are allocated once for the requested length and ``_walk_static`` calls the attention's own submodules -
+one GEMM against the packed q/k/v weights, ``functional.decode_attention`` (one launch: rotary, append, grouped-query attention over
+the cache, rows as ``o_proj`` reads them) or, for a prompt, ``functional.rope_append`` and a causal sdpa, then ``o_proj``.  The packed
+q/k/v and gate/up weights are built once per ``generate`` call, in the autocast dtype under autocast, and dropped when the loop ends.
+``routes.llama_decode_why`` decides; a step on this route leaves ``Route('decode')`` in ``last_route``.
 """
 from __future__ import annotations
 
@@ -32,12 +39,13 @@ from torch import nn
 from . import functional
 from . import samplers  # noqa: F401  (registers the samplers a config names)
 from .config import BuildPreHookMixin, Config
+from .kv_cache import StaticKVCache
 from .quantizers.memo import get_memo
 from .registries import VQSMSamplerRegistry, VQSMTransformerRegistry
 from .sequence_losses import CausalTokenLoss
 from .vqkd_autoencoders import _autocast_dtype
 
-__all__ = ['BaseTransformer', 'HFTransformer', 'LlamaTransformer']
+__all__ = ['BaseTransformer', 'HFTransformer', 'LlamaTransformer', 'StaticKVCache']
 
 
 class BaseTransformer(BuildPreHookMixin, nn.Module, ABC):
@@ -142,11 +150,16 @@ class HFTransformer(BaseTransformer):
 
 @VQSMTransformerRegistry.register_()
 class LlamaTransformer(HFTransformer):
-    """``LlamaForCausalLM(LlamaConfig(**transformer))``.  ``fused=False`` pins the torch route."""
+    """``LlamaForCausalLM(LlamaConfig(**transformer))``.  ``fused=False`` pins the torch route; ``static_cache=True`` lets
+    ``generate`` run behind a ``StaticKVCache`` where ``routes.llama_decode_why`` allows it (``decode_route`` keeps that decision)."""
 
-    def __init__(self, *args, **kwargs) -> None:
+    decode_route = None
+
+    def __init__(self, *args, static_cache: bool = False, **kwargs) -> None:
         super().__init__(*args, **kwargs)
         self._loss = CausalTokenLoss()
+        self.static_cache = static_cache
+        self._packed = None
 
     @classmethod
     def transformer_build_pre_hook(cls, config: Config, registry, item) -> Config:
@@ -203,12 +216,91 @@ class LlamaTransformer(HFTransformer):
         _, y = self._norm(model.norm, x, pending, torch_ops=torch_ops)
         return lm.lm_head(y)
 
+    # ---- the decode route: the same walk behind a StaticKVCache ------------------------------------------------------------------
+    def _pack(self, dtype=None):
+        """Per layer ``(cat(q_proj, k_proj, v_proj).weight, cat(gate_proj, up_proj).weight)`` in ``dtype`` (None: as they are)."""
+        packed = []
+        for layer in self._transformer.model.layers[:self._transformer.config.num_hidden_layers]:
+            a, mlp = layer.self_attn, layer.mlp
+            qkv = torch.cat((a.q_proj.weight, a.k_proj.weight, a.v_proj.weight))
+            gate_up = torch.cat((mlp.gate_proj.weight, mlp.up_proj.weight))
+            packed.append((qkv.to(dtype), gate_up.to(dtype)) if dtype is not None else (qkv, gate_up))
+        return packed
+
+    def _walk_static(self, tokens: torch.Tensor, kv_cache: StaticKVCache, *, torch_ops: bool = False) -> torch.Tensor:
+        """Logits [B, L, V] of ``tokens`` [B, L] behind the ``StaticKVCache`` (written in place, advanced once).  One token: eight
+        launches per layer - norm, qkv GEMM, attention, ``o_proj``, norm, gate-up GEMM, SwiGLU, ``down_proj``.  ``torch_ops`` puts
+        the ``_torch`` restatements in place of the kernels: the same walk on any device, float64 included."""
+        lm = self._transformer
+        model = lm.model
+        B, L = tokens.shape
+        kv_cache.require_room(L)                                                 # before anything is launched
+        seen = kv_cache.get_seq_length()
+        x = model.embed_tokens(tokens)
+        position_ids = (torch.arange(L, device=x.device) + seen).unsqueeze(0)
+        cos, sin = model.rotary_emb(x, position_ids=position_ids)
+        cos, sin = cos[0], sin[0]                                                # [L, Dh]
+        packed = self._packed or self._pack(_autocast_dtype(x))
+        swiglu = functional.swiglu_torch if torch_ops else (lambda t: functional.swiglu(t, strict=True))
+        decode = functional.decode_attention_torch if torch_ops else (lambda *a, **k: functional.decode_attention(*a, strict=True, **k))
+        append = functional.rope_append_torch if torch_ops else (lambda *a: functional.rope_append(*a, strict=True))
+        Hq, Hkv = model.config.num_attention_heads, kv_cache.kv_heads
+        nq, nk = Hq * kv_cache.head_dim, Hkv * kv_cache.head_dim
+        pending = None
+        for i, layer in enumerate(model.layers[:model.config.num_hidden_layers]):
+            attn, (w_qkv, w_gate_up) = layer.self_attn, packed[i]
+            x, y = self._norm(layer.input_layernorm, x, pending, torch_ops=torch_ops)
+            rows = F.linear(y, w_qkv).view(B * L, nq + 2 * nk)
+            q, k, v = rows[:, :nq], rows[:, nq:nq + nk], rows[:, nq + nk:]      # three views into the packed rows
+            if L == 1:
+                o = decode(q, k, v, cos, sin, kv_cache, i, scale=attn.scaling).view(B, 1, nq)
+            else:
+                q_rot = append(q, k, v, cos, sin, kv_cache, i)
+                kc, vc, _ = kv_cache.layer(i)
+                o = F.scaled_dot_product_attention(q_rot, kc[:, :, :seen + L], vc[:, :, :seen + L], is_causal=True, scale=attn.scaling,
+                                                   enable_gqa=Hq != Hkv).transpose(1, 2).reshape(B, L, nq)
+            x, y = self._norm(layer.post_attention_layernorm, x, attn.o_proj(o), torch_ops=torch_ops)
+            pending = layer.mlp.down_proj(swiglu(F.linear(y, w_gate_up)))
+        _, y = self._norm(model.norm, x, pending, torch_ops=torch_ops)
+        kv_cache.advance(L)
+        return lm.lm_head(y)
+
+    def _generate(self, tokens: torch.Tensor, length: int, codebook, memo):
+        from .quantizers import routes
+        if not self.static_cache:
+            return super()._generate(tokens, length, codebook, memo)
+        self.decode_route = route = routes.llama_decode_why(self, tokens, None)
+        if route.name != 'decode':                                               # today's loop; ``decode_route`` says why
+            return super()._generate(tokens, length, codebook, memo)
+        assert tokens.shape[1] < length
+        dtype = _autocast_dtype(tokens) or self._transformer.model.embed_tokens.weight.dtype
+        kv_cache = StaticKVCache.for_model(self._transformer.config, tokens.shape[0], length, dtype, tokens.device)
+        self._packed = self._pack(_autocast_dtype(tokens))
+        try:
+            token = tokens
+            while tokens.shape[1] < length:
+                logits, kv_cache, memo = self.inference(token, kv_cache, memo)
+                token, memo = self.sample(logits[:, [-1]], codebook, memo)
+                tokens = torch.cat((tokens, token), 1)
+        finally:
+            self._packed = None
+        assert tokens.shape[1] == length
+        return tokens, memo
+
     def _route(self, tokens: torch.Tensor, kv_cache=None, attention_mask=None) -> bool:
         from .quantizers import routes
         self.last_route = route = routes.llama_why(self, tokens, kv_cache, attention_mask)
         return route.name == 'fused'
 
     def _inference(self, tokens: torch.Tensor, kv_cache, memo, attention_mask=None):
+        if isinstance(kv_cache, StaticKVCache):
+            from .quantizers import routes
+            route = routes.llama_decode_why(self, tokens, kv_cache) if attention_mask is None else \
+                routes.Route('torch', 'an attention_mask is given: the walk passes none')
+            self.last_route = self.decode_route = route
+            if route.name != 'decode':                                           # no other route reads a StaticKVCache
+                raise ValueError(f'LlamaTransformer: a StaticKVCache was given, but the decode route is refused: {route.why}')
+            return self._walk_static(tokens, kv_cache), kv_cache, memo
         if self._route(tokens, kv_cache, attention_mask):
             if kv_cache is None:
                 from transformers import DynamicCache
