@@ -937,7 +937,8 @@ int vqhip_row_bias_act_bwd(const void *g, const void *x, int dtype, int64_t R, i
  *   and v), each with its own row stride in elements (>= H Dh), so the three may be views into one packed [R, (Hq + 2 Hkv) Dh]
  *   GEMM output; R = B (decode) or B L (append, row r = b L + t).  dtype VQHIP_DTYPE_F32, _BF16 or _F16.  cos, sin: fp32 [L, Dh]
  *   for the new positions, as LlamaRotaryEmbedding holds them before its cast.  k_cache, v_cache: [B, Hkv, cap, Dh], contiguous,
- *   in dtype.  seen: the positions already stored, a host integer by value (a captured launch replays the same position).
+ *   in dtype.  seen: the positions already stored, a host integer by value (a captured vqhip_decode_attention or
+ *   vqhip_rope_append launch replays the same position; vqhip_decode_attention_at below reads it from device memory instead).
  * ROTARY  transformers' rotate_half convention, half = Dh / 2:  x'[i] = x[i] cos[i] - x[i + half] sin[i],
  *   x'[i + half] = x[i + half] cos[i + half] + x[i] sin[i + half].  fp32 arithmetic on the loaded values, the two products kept
  *   with their remainders (fma) and summed by a two-sum, so x' is the fp32 nearest to the exact value of the fp32 inputs or its
@@ -967,13 +968,33 @@ int vqhip_row_bias_act_bwd(const void *g, const void *x, int dtype, int64_t R, i
  *   u ln n in the mean:   eta = expm1(S) + (6 (n / 8 + 10) + 10) u;   |out - exact| <= 2 eta / (1 - eta) vmax + u |out|
  *   + n 2^-126 vmax (weights that underflow) in fp32 before the store, VQHIP_SG2_STORE_U(dtype) on top.  The Python form of this
  *   bound lives beside the float64 restatement of the tests (tests/decode_attention_ref.py); DESIGN.md §8 has the derivation.
- * The last parameter of both is the hipStream_t the launch goes to. */
+ * vqhip_decode_attention_at  the same step with the position in DEVICE memory, so that one captured launch serves every generated
+ *   token: every workgroup loads s = *pos (int32, 4-byte aligned) once, uses seen = s and row s of cos_table and sin_table, fp32
+ *   [cap, Dh] (row j: the cos, sin of position j).  The kernel body is vqhip_decode_attention's: with *pos == s and the tables' row s
+ *   equal to the cos, sin of the by-value call, every byte written - out, row s of k_cache, row s of v_cache - is the byte that
+ *   vqhip_decode_attention(..., seen = s, ...) writes, and the error bound above holds unchanged.  With s < 0 or s >= cap the launch
+ *   writes nothing at all: out and the caches are left as they are.  LIMITS as above without the seen clause; pos must not be null
+ *   and must be 4-byte aligned.
+ * vqhip_decode_advance  the end of a replayed step, one workgroup: with s = *pos, if 0 <= s and s + 1 < length then
+ *   sequence[r, s + 1] = token[r] as it is (the sampler's -1 for a bad row stays visible), next[r] = token[r] < 0 ? 0 : token[r] (no
+ *   embedding gather of a later replay leaves its table) for r = 0 .. R - 1, and afterwards *pos = s + 1; otherwise nothing is
+ *   written and pos stays where it is.  token [R], next [R], sequence [R, length] are int64 on the device.  Every thread reads pos
+ *   in front of a barrier, thread 0 stores the new count behind the writes with an ordinary store: no atomics.  LIMITS (VQHIP_EINVAL
+ *   before any HIP call): all pointers non-null, token, next and sequence 8-byte and pos 4-byte aligned, 1 <= R < 2^31,
+ *   2 <= length <= VQHIP_ATTN_MAX_LEN.
+ * The last parameter of each is the hipStream_t the launch goes to. */
 #define VQHIP_ATTN_MAX_HEAD_DIM 128
 #define VQHIP_ATTN_MAX_GROUP 8
 #define VQHIP_ATTN_MAX_LEN 4096
 int vqhip_decode_attention(const void *q, int64_t q_stride, const void *k, int64_t k_stride, const void *v, int64_t v_stride, int dtype,
                            const float *cos, const float *sin, void *k_cache, void *v_cache, int64_t seen, int64_t cap, float scale,
                            int64_t B, int Hq, int Hkv, int Dh, void *out, void *hip_stream);
+int vqhip_decode_attention_at(const void *q, int64_t q_stride, const void *k, int64_t k_stride, const void *v, int64_t v_stride, int dtype,
+                              const float *cos_table, const float *sin_table /* fp32 [cap, Dh] */, void *k_cache, void *v_cache,
+                              const int32_t *pos /* device, 4-byte aligned */, int64_t cap, float scale,
+                              int64_t B, int Hq, int Hkv, int Dh, void *out, void *hip_stream);
+int vqhip_decode_advance(const int64_t *token /* [R] */, int64_t *next /* [R] */, int64_t *sequence /* [R, length] */,
+                         int64_t R, int64_t length, int32_t *pos, void *hip_stream);
 int vqhip_rope_append(const void *q, int64_t q_stride, const void *k, int64_t k_stride, const void *v, int64_t v_stride, int dtype,
                       const float *cos, const float *sin, void *k_cache, void *v_cache, int64_t seen, int64_t cap, int64_t B, int64_t L,
                       int Hq, int Hkv, int Dh, void *q_out, void *hip_stream);

@@ -11,7 +11,10 @@ backwards) against the torch composition a ``LlamaDecoderLayer`` runs (``residua
 Generation has a third route, ``decode``: the same model with ``static_cache=True`` (a ``StaticKVCache`` and one
 ``functional.decode_attention`` launch per layer and token), alternating block by block with the other two; its line also carries
 the kernel launches of one single-token step per layer, counted with the profiler.  ``--generate-only`` times generation alone, at
-every length of ``--generate-length`` (a comma-separated list).
+every length of ``--generate-length`` (a comma-separated list).  A fourth route, ``graph``, is the decode route with ``graph=True``:
+the single-token steps replayed from one captured HIP graph (``decode_graph.DecodeGraph``).  Its line carries two figures, both
+against the eager decode route of the same run: ``first_call`` - one ``generate`` that has to capture, timed once, beside one decode
+call timed at the same moment - and the alternating blocks, where the captured graph is reused.
 
 Shapes: [B * 257, 1024] (the residual stream) and [B * 257, 2 * 2816] (the gate | up tensor) with B = ``--batch`` images of 256 tokens
 and the class token.  configs/llamagen/ar.py trains with 256 images per rank; the default here is 64, so that the 24 layers' saved
@@ -174,6 +177,9 @@ def generate_case(nets, autocast, args, length=None):
     if 'decode' not in nets:
         nets['decode'] = copy.deepcopy(nets['fused'])
         nets['decode'].static_cache = True
+    if 'graph' not in nets:
+        nets['graph'] = copy.deepcopy(nets['decode'])
+        nets['graph'].graph = True
     codebook = SimpleNamespace(start=1000, end=VOCABULARY)
     prompt = torch.randint(0, 1000, (args.generate_batch, 1), device='cuda')
     u = torch.rand(args.generate_batch, device='cuda')
@@ -184,17 +190,27 @@ def generate_case(nets, autocast, args, length=None):
         with torch.autocast('cuda', torch.bfloat16, enabled=autocast):
             tokens[name], _ = nets[name].eval().generate(prompt, length, codebook, {'sampler': {'u': u}})
 
+    # the first call of the graph route, capture included, beside a decode call at the same moment (decode warmed by two calls)
+    nets['graph'].graph = False                                                 # (drops a graph an earlier case left)
+    nets['graph'].graph = True
+    run('decode'); run('decode')
+    torch.cuda.synchronize()
+    first = {name: round(block_us(lambda n=name: run(n), 1) / new, 1) for name in ('decode', 'graph')}
+    assert nets['graph']._decode_graph.captures == 1
     res = alternate({name: (lambda n=name: run(n)) for name in nets}, args.blocks, 1)
-    assert nets['fused'].last_route.name == 'fused' and nets['torch'].last_route.name == 'torch' and nets['decode'].last_route.name == 'decode', \
-        [n.last_route for n in nets.values()]
+    assert nets['fused'].last_route.name == 'fused' and nets['torch'].last_route.name == 'torch' and nets['decode'].last_route.name == 'decode' \
+        and nets['graph'].last_route.name == 'graph' and nets['graph']._decode_graph.captures == 1, [n.last_route for n in nets.values()]
     res = {name: {k: round(v / new, 1) for k, v in r.items()} for name, r in res.items()}
     same = float((tokens['fused'] == tokens['torch']).float().mean())
     same_decode = float((tokens['fused'] == tokens['decode']).float().mean())
+    same_graph = float((tokens['decode'] == tokens['graph']).float().mean())
     launches = {name: step_launches(nets[name], autocast, args.generate_batch, name == 'decode') for name in ('fused', 'decode')}
     per_layer = {f'{name}_launches_per_layer_step': None if n is None else round(n / args.layers, 2) for name, n in launches.items()}
     return dict(case=f'llama_medium_{args.layers}_layers_generate_us_per_token', new_tokens=new, iters=1, equal_token_share=round(same, 4),
                 decode_equal_token_share=round(same_decode, 4), fused_over_decode=round(res['fused']['median_us'] / res['decode']['median_us'], 2),
-                **per_layer, **res)
+                graph_equal_token_share_of_decode=round(same_graph, 4),
+                decode_over_graph=round(res['decode']['median_us'] / res['graph']['median_us'], 2),
+                first_call=dict(first, decode_over_graph=round(first['decode'] / first['graph'], 2)), **per_layer, **res)
 
 
 def generate_nets(args):

@@ -1,5 +1,5 @@
 // libvqhip — the attention step of cached generation: rotary embedding + append to a static KV cache, and the one-token
-// attention over it.
+// attention over it, with the position by value or in device memory; the end of a replayed step.
 #include "vqhip.h"
 
 #include <hip/hip_runtime.h>
@@ -8,7 +8,7 @@
 #include "vqhip_host.h"
 #include "vqhip_attn_kernels.h"
 
-// what the two entry points refuse alike (every clause before any HIP call), and the arguments the kernels share
+// what the entry points refuse alike (every clause before any HIP call), and the arguments the kernels share
 static int attn_setup(const char *what, const void *q, int64_t q_stride, const void *k, int64_t k_stride, const void *v, int64_t v_stride,
                       int dtype, const float *cos, const float *sin, void *k_cache, void *v_cache, int64_t seen, int64_t cap,
                       int64_t B, int64_t L, int Hq, int Hkv, int Dh, void *out, VqAttnArgs *a) {
@@ -33,6 +33,7 @@ static int attn_setup(const char *what, const void *q, int64_t q_stride, const v
     a->cos = cos; a->sin = sin;
     a->k_cache = k_cache; a->v_cache = v_cache; a->out = out;
     a->seen = seen; a->cap = cap; a->L = L;
+    a->pos = nullptr; a->table_stride = 0;
     a->scale = 0.0f;
     a->Hq = Hq; a->Hkv = Hkv; a->Dh = Dh; a->G = Hq / Hkv;
     return VQHIP_OK;
@@ -43,6 +44,14 @@ static int launch_decode_attention(const VqAttnArgs &a, int64_t B, hipStream_t s
     decode_attention_kernel<DT, GMAX><<<(unsigned)(B * a.Hkv), VQ_ATTN_THREADS, 0, s>>>(a);
     VQ_CHECK_LAUNCH("decode_attention_kernel");
     return VQHIP_OK;
+}
+
+static int launch_decode(const VqAttnArgs &a, int dtype, int64_t B, hipStream_t s) {
+    return vq_with_dtype(dtype, [&](auto dt) {
+        constexpr int DT = decltype(dt)::value;
+        return a.G == 1 ? launch_decode_attention<DT, 1>(a, B, s) : a.G == 2 ? launch_decode_attention<DT, 2>(a, B, s)
+             : a.G <= 4 ? launch_decode_attention<DT, 4>(a, B, s) : launch_decode_attention<DT, 8>(a, B, s);
+    });
 }
 
 template <int DT>
@@ -62,12 +71,34 @@ int vqhip_decode_attention(const void *q, int64_t q_stride, const void *k, int64
                             B, 1, Hq, Hkv, Dh, out, &a)) return rc;
     VQ_REQUIRE(scale - scale == 0.0f, "vqhip_decode_attention: scale must be finite");
     a.scale = scale;
-    hipStream_t s = (hipStream_t)hip_stream;
-    return vq_with_dtype(dtype, [&](auto dt) {
-        constexpr int DT = decltype(dt)::value;
-        return a.G == 1 ? launch_decode_attention<DT, 1>(a, B, s) : a.G == 2 ? launch_decode_attention<DT, 2>(a, B, s)
-             : a.G <= 4 ? launch_decode_attention<DT, 4>(a, B, s) : launch_decode_attention<DT, 8>(a, B, s);
-    });
+    return launch_decode(a, dtype, B, (hipStream_t)hip_stream);
+}
+
+int vqhip_decode_attention_at(const void *q, int64_t q_stride, const void *k, int64_t k_stride, const void *v, int64_t v_stride, int dtype,
+                              const float *cos_table, const float *sin_table, void *k_cache, void *v_cache, const int32_t *pos, int64_t cap,
+                              float scale, int64_t B, int Hq, int Hkv, int Dh, void *out, void *hip_stream) {
+    VqAttnArgs a;
+    // (seen = 0 with L = 1 passes the seen clause for every cap the cap clause admits: the position is the kernel's to check)
+    if (int rc = attn_setup("vqhip_decode_attention_at", q, q_stride, k, k_stride, v, v_stride, dtype, cos_table, sin_table, k_cache, v_cache,
+                            0, cap, B, 1, Hq, Hkv, Dh, out, &a)) return rc;
+    VQ_REQUIRE(scale - scale == 0.0f, "vqhip_decode_attention_at: scale must be finite");
+    VQ_REQUIRE(pos != nullptr, "vqhip_decode_attention_at: pos is required");
+    VQ_REQUIRE((uintptr_t)pos % 4 == 0, "vqhip_decode_attention_at: pos must be 4-byte aligned");
+    a.scale = scale;
+    a.pos = pos;
+    a.table_stride = Dh;
+    return launch_decode(a, dtype, B, (hipStream_t)hip_stream);
+}
+
+int vqhip_decode_advance(const int64_t *token, int64_t *next, int64_t *sequence, int64_t R, int64_t length, int32_t *pos, void *hip_stream) {
+    VQ_REQUIRE(token && next && sequence && pos, "vqhip_decode_advance: token, next, sequence and pos are required");
+    VQ_REQUIRE(R >= 1 && R < (1ll << 31), "vqhip_decode_advance: R must be in 1 .. 2^31 - 1");
+    VQ_REQUIRE(length >= 2 && length <= VQHIP_ATTN_MAX_LEN, "vqhip_decode_advance: length must be in 2 .. VQHIP_ATTN_MAX_LEN");
+    VQ_REQUIRE(((uintptr_t)token | (uintptr_t)next | (uintptr_t)sequence) % 8 == 0 && (uintptr_t)pos % 4 == 0,
+               "vqhip_decode_advance: token, next and sequence must be 8-byte aligned, pos 4-byte aligned");
+    decode_advance_kernel<<<1, VQ_ATTN_THREADS, 0, (hipStream_t)hip_stream>>>(token, next, sequence, R, length, pos);
+    VQ_CHECK_LAUNCH("decode_advance_kernel");
+    return VQHIP_OK;
 }
 
 int vqhip_rope_append(const void *q, int64_t q_stride, const void *k, int64_t k_stride, const void *v, int64_t v_stride, int dtype,

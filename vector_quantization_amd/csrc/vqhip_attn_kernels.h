@@ -1,5 +1,7 @@
 // The attention step of cached generation (include/vqhip.h, "static KV cache"): rope_append_kernel writes the rotated keys and the
-// values of L new tokens into the caches, decode_attention_kernel does that for one token and attends over the positions stored.
+// values of L new tokens into the caches, decode_attention_kernel does that for one token and attends over the positions stored -
+// at a position passed by value or, for a launch that a captured graph replays, read from device memory (VqAttnArgs::pos), where
+// decode_advance_kernel counts it at the end of a step.
 //
 // decode_attention_kernel: one workgroup of four wave64s per (batch row, kv head); it serves the G = Hq / Hkv query heads of the group
 // from one pass over K and V.  A cache row of Dh elements is C = Dh / E pieces of 16 bytes (E = 4 fp32 or 8 16-bit elements); LP, the
@@ -24,6 +26,8 @@ struct VqAttnArgs {
     void *k_cache, *v_cache;            // [B, Hkv, cap, Dh]
     void *out;                          // decode: [B, Hq * Dh]; append: q' [B, Hq, L, Dh]
     int64_t seen, cap, L;
+    const int32_t *pos;                 // decode only: where not null, the position is *pos and cos, sin are [cap, Dh] tables
+    int64_t table_stride;               // elements between the tables' rows (0 without pos)
     float scale;
     int Hq, Hkv, Dh, G;
 };
@@ -109,6 +113,16 @@ __global__ __launch_bounds__(VQ_ATTN_THREADS) void decode_attention_kernel(VqAtt
     const int64_t b = blockIdx.x / a.Hkv;
     const int kvh = blockIdx.x % a.Hkv;
     const int tid = threadIdx.x, lane = tid & 63, w = tid >> 6;
+    // the position: by value, or loaded once from device memory - the same for every thread of every workgroup, so a position
+    // outside the cache ends the whole launch here, in front of the first store and the first barrier
+    int64_t seen = a.seen;
+    const float *cos = a.cos, *sin = a.sin;
+    if (a.pos) {
+        seen = *a.pos;
+        if (seen < 0 || seen >= a.cap) return;
+        cos += seen * a.table_stride;
+        sin += seen * a.table_stride;
+    }
     raw *kc = (raw *)a.k_cache + ((b * a.Hkv + kvh) * a.cap) * Dh;              // this (b, kv head)'s [cap, Dh]
     raw *vc = (raw *)a.v_cache + ((b * a.Hkv + kvh) * a.cap) * Dh;
 
@@ -119,9 +133,9 @@ __global__ __launch_bounds__(VQ_ATTN_THREADS) void decode_attention_kernel(VqAtt
         const raw *v = (const raw *)a.v + b * a.v_stride + (int64_t)kvh * Dh;
         for (int e = tid; e < (G + 2) * Dh; e += VQ_ATTN_THREADS) {
             const int h = e / Dh, i = e % Dh;
-            if (h < G) qs[h * Dh + i] = rope_elem<DT>(q + h * Dh, a.cos, a.sin, i, half);
-            else if (h == G) kc[a.seen * Dh + i] = ce_round<DT>(rope_elem<DT>(k, a.cos, a.sin, i, half));
-            else vc[a.seen * Dh + i] = v[i];
+            if (h < G) qs[h * Dh + i] = rope_elem<DT>(q + h * Dh, cos, sin, i, half);
+            else if (h == G) kc[seen * Dh + i] = ce_round<DT>(rope_elem<DT>(k, cos, sin, i, half));
+            else vc[seen * Dh + i] = v[i];
         }
     }
     __syncthreads();                                                              // the stores above are read back below: same workgroup
@@ -131,7 +145,7 @@ __global__ __launch_bounds__(VQ_ATTN_THREADS) void decode_attention_kernel(VqAtt
     while (LP < C) LP <<= 1;                                                      // lanes that share a position: 2 .. 32
     const int PP = 64 / LP, c = lane & (LP - 1), p = lane / LP;
     const bool mine = c < C;
-    const int64_t n = a.seen + 1;
+    const int64_t n = seen + 1;
 
     float qf[GMAX][E], acc[GMAX][E], m[GMAX], l[GMAX];
 #pragma unroll
@@ -229,4 +243,20 @@ __global__ __launch_bounds__(VQ_ATTN_THREADS) void decode_attention_kernel(VqAtt
         }
         out[e] = ce_round<DT>(num / den);
     }
+}
+
+// ---- the end of a replayed step: record the sampled tokens, feed them to the next step, count the position -------------------
+// One workgroup.  Every thread reads the position before the barrier and thread 0 stores the new one behind it, so no thread sees
+// the count it is about to become.  At the last column (or a position outside the sequence) nothing is written.
+__global__ __launch_bounds__(VQ_ATTN_THREADS) void decode_advance_kernel(const int64_t *token, int64_t *next, int64_t *sequence, int64_t R,
+                                                                         int64_t length, int32_t *pos) {
+    const int64_t s = *pos;
+    __syncthreads();
+    if (s < 0 || s + 1 >= length) return;
+    for (int64_t r = threadIdx.x; r < R; r += VQ_ATTN_THREADS) {
+        const int64_t t = token[r];
+        sequence[r * length + s + 1] = t;                                         // a bad row's -1 stays visible
+        next[r] = t < 0 ? 0 : t;                                                  // and gathers embedding row 0 in the next step
+    }
+    if (threadIdx.x == 0) *pos = (int32_t)(s + 1);
 }

@@ -870,8 +870,13 @@ def decode_attention_torch(q: torch.Tensor, k: torch.Tensor, v: torch.Tensor, co
     """The same definition in torch, any device and dtype (float64 computes in float64, everything else in fp32): see
     ``decode_attention``.  The step's own key enters the scores as stored, after its rounding to the cache's dtype."""
     kc, vc, seen = cache.layer(layer)
-    B, Hkv, _, Dh = kc.shape
     cache.require_room(1)
+    return _decode_attention_at(q, k, v, cos, sin, kc, vc, seen, scale)
+
+
+def _decode_attention_at(q, k, v, cos, sin, kc, vc, seen: int, scale: Optional[float]) -> torch.Tensor:
+    """``decode_attention_torch`` at position ``seen`` of the caches ``kc``, ``vc``, with that position's ``cos``, ``sin``."""
+    B, Hkv, _, Dh = kc.shape
     ct = _attn_compute_dtype(q)
     cos, sin = cos.reshape(1, 1, Dh).to(ct), sin.reshape(1, 1, Dh).to(ct)
     q_rot = _rope_torch(q.reshape(B, -1, Dh).to(ct), cos, sin)                  # stays in the compute dtype
@@ -886,14 +891,35 @@ def decode_attention_torch(q: torch.Tensor, k: torch.Tensor, v: torch.Tensor, co
     return out.reshape(B, Hq * Dh).to(q.dtype)
 
 
-def _attention_refusal(what: str, q, k, v, cos, sin, cache, layer: int, L: int) -> str:
+def decode_attention_at_torch(q: torch.Tensor, k: torch.Tensor, v: torch.Tensor, cos_table: torch.Tensor, sin_table: torch.Tensor, cache,
+                              layer: int, *, scale: Optional[float] = None) -> torch.Tensor:
+    """``decode_attention_at`` in torch: ``decode_attention_torch`` at the position ``cache.position`` holds, read with ``.item()`` -
+    a host synchronisation, so this serves CPU and float64 tensors (the tests, the ``torch_ops`` walk), never a capture.  A
+    position outside the cache writes nothing and returns zeros."""
+    kc, vc, _ = cache.layer(layer)
+    s = int(cache.position.item())
+    if not 0 <= s < kc.shape[2]:
+        return q.new_zeros(kc.shape[0], q.shape[1])
+    return _decode_attention_at(q, k, v, cos_table[s], sin_table[s], kc, vc, s, scale)
+
+
+def decode_advance_torch(token: torch.Tensor, next_token: torch.Tensor, sequence: torch.Tensor, pos: torch.Tensor) -> None:
+    """``decode_advance`` in torch (``pos`` read with ``.item()``): see there."""
+    s = int(pos.item())
+    if 0 <= s and s + 1 < sequence.shape[1]:
+        sequence[:, s + 1] = token.reshape(-1)
+        next_token.copy_(token.clamp(min=0).reshape(next_token.shape))
+        pos.fill_(s + 1)
+
+
+def _attention_refusal(what: str, q, k, v, cos, sin, cache, layer: int, L: int, tables: bool = False) -> str:
     """Why the kernels would not take this step ('' if they would); inputs that require grad raise here: these ops have no backward."""
     if torch.is_grad_enabled() and any(t.requires_grad for t in (q, k, v)):
         raise ValueError(f'{what}: q, k or v requires grad and grad mode is on: an inference op without a backward')
     kc, vc, seen = cache.layer(layer)
     return ('' if q.is_cuda else f'q is on device {q.device}, not on a GPU') or ops.float_dtype_refusal('q is', q) \
         or ('' if kc.device == q.device else f'the cache is on device {kc.device}, q on {q.device}') \
-        or ops.attention_refusal(q, k, v, cos, sin, kc, vc, seen, L)
+        or ops.attention_refusal(q, k, v, cos, sin, kc, vc, seen, L, tables)
 
 
 def _fp32_table(t: torch.Tensor, L: int) -> torch.Tensor:
@@ -917,6 +943,38 @@ def decode_attention(q: torch.Tensor, k: torch.Tensor, v: torch.Tensor, cos: tor
         return decode_attention_torch(q, k, v, cos, sin, cache, layer, scale=scale)
     kc, vc, seen = cache.layer(layer)
     return ops.decode_attention(q, k, v, cos32, sin32, kc, vc, seen, scale)
+
+
+def decode_attention_at(q: torch.Tensor, k: torch.Tensor, v: torch.Tensor, cos_table: torch.Tensor, sin_table: torch.Tensor, cache,
+                        layer: int, *, scale: Optional[float] = None, strict: bool = False, out: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """``decode_attention`` with the position read on the device: ``cache.position`` (one int32, counted by ``decode_advance``) in
+    place of the host count, and row ``position`` of ``cos_table`` / ``sin_table`` (contiguous fp32 [capacity, Dh]:
+    ``LlamaRotaryEmbedding`` over ``arange(capacity)``, before its cast) in place of one position's cos and sin.  Bit for bit what
+    ``decode_attention`` gives at ``seen == position``, in one launch that a captured graph can replay for every generated
+    token.  A position outside the cache writes nothing - neither the caches nor ``out`` (optional: a dense [B, Hq Dh] tensor to
+    write into).  The host count is not read and not advanced.  Routes and ``strict`` as ``decode_attention``."""
+    why = _attention_refusal('decode_attention_at', q, k, v, cos_table, sin_table, cache, layer, 1, tables=True)
+    if why:
+        if strict:
+            raise ValueError(f'decode_attention_at: {why}')
+        got = decode_attention_at_torch(q, k, v, cos_table, sin_table, cache, layer, scale=scale)
+        return got if out is None else out.copy_(got)
+    kc, vc, _ = cache.layer(layer)
+    return ops.decode_attention_at(q, k, v, cos_table, sin_table, kc, vc, cache.position, scale, out)
+
+
+def decode_advance(token: torch.Tensor, next_token: torch.Tensor, sequence: torch.Tensor, pos: torch.Tensor, *, strict: bool = False) -> None:
+    """The end of a replayed generation step, in one launch: with s = ``pos`` (one int32 on the device) and s + 1 < length, writes
+    the sampled ``token`` (R int64) into column s + 1 of ``sequence`` (int64 [R, length]) as it is - the sampler's -1 for a bad row
+    stays visible -, into ``next_token`` (R int64, the next step's input) with negatives clamped to 0, and counts ``pos`` to s + 1.
+    At the last column, or with a position outside the sequence, nothing is written.  CPU tensors compute the same in torch - or,
+    with ``strict``, raise."""
+    why = '' if all(t.is_cuda for t in (token, next_token, sequence, pos)) else 'a tensor is not on a GPU'
+    if why:
+        if strict:
+            raise ValueError(f'decode_advance: {why}')
+        return decode_advance_torch(token, next_token, sequence, pos)
+    return ops.decode_advance(token, next_token, sequence, pos)
 
 
 def rope_append(q: torch.Tensor, k: torch.Tensor, v: torch.Tensor, cos: torch.Tensor, sin: torch.Tensor, cache, layer: int, *,

@@ -2,7 +2,12 @@
 
 transformers' ``DynamicCache`` grows by ``torch.cat``: every token re-allocates and copies the whole K and V of every layer.  Here a
 layer's K and V are ``[B, Hkv, capacity, Dh]`` from the start; a step writes its position in place (``functional.decode_attention`` /
-``functional.rope_append``) and the cache only counts.  The count is a host integer: nothing here reads the device.
+``functional.rope_append``) and the cache only counts.  The count is a host integer, and it is the authority: ``require_room`` and
+``advance`` are host arithmetic.  A replayed decode step (``decode_graph.DecodeGraph``) cannot read a host integer, so a cache also
+offers ``position``: one int32 on the device, created on first use and set from the host count, which
+``functional.decode_attention_at`` reads and ``functional.decode_advance`` counts on the device.  The host counts one per replay
+it issues, so the two agree by construction; nothing here reads the device back, and a cache that never asks for ``position`` has
+none.
 """
 from __future__ import annotations
 
@@ -22,6 +27,7 @@ class StaticKVCache:
                              f'capacity={capacity}, head_dim={head_dim}')
         self._store = torch.zeros(layers, 2, batch, kv_heads, capacity, head_dim, dtype=dtype, device=device)
         self._seen = 0
+        self._position = None
 
     @classmethod
     def for_model(cls, config, batch: int, capacity: int, dtype, device) -> 'StaticKVCache':
@@ -55,5 +61,19 @@ class StaticKVCache:
         self._seen += n
         return self._seen
 
+    @property
+    def position(self) -> torch.Tensor:
+        """The count as one int32 on the cache's device, for the steps that read it there.  Created on first use from the host
+        count; after host-side steps (a prompt through ``rope_append``, ``reset``) ``sync_position`` sets it again."""
+        if self._position is None:
+            self._position = torch.full((1,), self._seen, dtype=torch.int32, device=self.device)
+        return self._position
+
+    def sync_position(self) -> torch.Tensor:
+        """Sets the device position from the host count (one fill on the current stream) and returns it."""
+        return self.position.fill_(self._seen)
+
     def reset(self) -> None:
         self._seen = 0
+        if self._position is not None:
+            self._position.zero_()

@@ -1571,11 +1571,12 @@ def attention_shape_refusal(Hq: int, Hkv: int, Dh: int) -> str:
 
 
 def attention_refusal(q: torch.Tensor, k: torch.Tensor, v: torch.Tensor, cos: torch.Tensor, sin: torch.Tensor, k_cache: torch.Tensor,
-                      v_cache: torch.Tensor, seen: int, L: int = 1) -> str:
+                      v_cache: torch.Tensor, seen: int, L: int = 1, tables: bool = False) -> str:
     """Why vqhip_decode_attention (``L`` = 1) / vqhip_rope_append would refuse these tensors ('' if they would not): the clauses of
     their LIMITS that depend on dtypes, shapes, strides and alignment.  q [B L, Hq Dh], k and v [B L, Hkv Dh] are read in place
     through their row strides (three views into one packed row pass), cos and sin are [L, Dh] (or anything that flattens to it),
-    the caches [B, Hkv, cap, Dh]."""
+    the caches [B, Hkv, cap, Dh].  ``tables``: vqhip_decode_attention_at - cos and sin are the [cap, Dh] tables and there is no
+    ``seen`` to refuse (the kernel reads the position)."""
     if k_cache.dim() != 4 or v_cache.shape != k_cache.shape:
         return f'the caches must both be [B, Hkv, cap, Dh], got {tuple(k_cache.shape)} and {tuple(v_cache.shape)}'
     B, Hkv, cap, Dh = k_cache.shape
@@ -1593,22 +1594,30 @@ def attention_refusal(q: torch.Tensor, k: torch.Tensor, v: torch.Tensor, cos: to
             f'rows of {q.shape[1]}, {k.shape[1]} and {v.shape[1]} values are not heads of {Dh} for {Hkv} key-value heads') \
         or attention_shape_refusal(Hq, Hkv, Dh) \
         or ('' if 1 <= cap <= _lib.ATTN_MAX_LEN else f'a capacity of {cap} is outside 1 .. {_lib.ATTN_MAX_LEN}') \
-        or ('' if seen >= 0 and L >= 1 and seen + L <= cap else f'{L} tokens behind {seen} do not fit a capacity of {cap}') \
-        or ('' if all(t.dtype == torch.float32 and t.numel() == L * Dh and t.is_contiguous() for t in (cos, sin)) else
-            f'cos and sin must be contiguous float32 with {L} x {Dh} elements, got {cos.dtype} {tuple(cos.shape)} and {sin.dtype} {tuple(sin.shape)}') \
+        or ('' if tables or (seen >= 0 and L >= 1 and seen + L <= cap) else f'{L} tokens behind {seen} do not fit a capacity of {cap}') \
+        or ('' if all(t.dtype == torch.float32 and t.numel() == (cap if tables else L) * Dh and t.is_contiguous() for t in (cos, sin)) else
+            f'cos and sin must be contiguous float32 with {cap if tables else L} x {Dh} elements, got {cos.dtype} {tuple(cos.shape)} and '
+            f'{sin.dtype} {tuple(sin.shape)}') \
         or ('' if k_cache.is_contiguous() and v_cache.is_contiguous() else 'the caches are not contiguous') \
         or ('' if k_cache.data_ptr() % 16 == 0 and v_cache.data_ptr() % 16 == 0 else 'the caches are not 16-byte aligned')
 
 
-def _attention_args(what: str, q, k, v, cos, sin, k_cache, v_cache, seen: int, L: int):
-    _require_cuda(q, k, v, cos, sin, k_cache, v_cache)
-    _refuse(what, attention_refusal(q, k, v, cos, sin, k_cache, v_cache, seen, L))
+def position_refusal(pos: torch.Tensor) -> str:
+    """Why ``pos`` is not the device position of vqhip_decode_attention_at / vqhip_decode_advance ('' if it is): one int32."""
+    return '' if pos.dtype == torch.int32 and pos.numel() == 1 else f'pos must hold one int32, got {pos.dtype} {tuple(pos.shape)}'
+
+
+def _attention_args(what: str, q, k, v, cos, sin, k_cache, v_cache, seen, L: int):
+    """``seen``: the host count, or the int32 device tensor of the position (cos and sin are then the [cap, Dh] tables)."""
+    at = torch.is_tensor(seen)
+    _require_cuda(q, k, v, cos, sin, k_cache, v_cache, seen if at else None)
+    _refuse(what, (position_refusal(seen) if at else '') or attention_refusal(q, k, v, cos, sin, k_cache, v_cache, 0 if at else seen, L, at))
     B, Hkv, cap, Dh = k_cache.shape
 
     def stride(t):
         return max(t.stride(0), t.shape[1])
     return (_ptr(q), stride(q), _ptr(k), stride(k), _ptr(v), stride(v), FLOAT_DTYPES[q.dtype], _ptr(cos), _ptr(sin), _ptr(k_cache),
-            _ptr(v_cache), int(seen), cap), (B, q.shape[1] // Dh, Hkv, Dh)
+            _ptr(v_cache), _ptr(seen) if at else int(seen), cap), (B, q.shape[1] // Dh, Hkv, Dh)
 
 
 @_on_tensor_device
@@ -1622,6 +1631,41 @@ def decode_attention(q: torch.Tensor, k: torch.Tensor, v: torch.Tensor, cos: tor
     check(_lib.lib().vqhip_decode_attention(*head, float(Dh ** -0.5 if scale is None else scale), B, Hq, Hkv, Dh, _ptr(out), _stream()),
           'vqhip_decode_attention')
     return out
+
+
+@_on_tensor_device
+def decode_attention_at(q: torch.Tensor, k: torch.Tensor, v: torch.Tensor, cos_table: torch.Tensor, sin_table: torch.Tensor,
+                        k_cache: torch.Tensor, v_cache: torch.Tensor, pos: torch.Tensor, scale: Optional[float] = None,
+                        out: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """vqhip_decode_attention_at: ``decode_attention`` with the position read from ``pos`` (one int32 on the device) and the rotary
+    rows from ``cos_table`` / ``sin_table`` (fp32 [cap, Dh]), bit for bit - a launch that a captured graph can replay for every
+    generated token.  A position outside 0 .. cap - 1 writes nothing: ``out`` (a dense [B, Hq Dh] tensor to write into; a new one if
+    None) and the caches are left as they are.  One launch."""
+    head, (B, Hq, Hkv, Dh) = _attention_args('decode_attention_at', q, k, v, cos_table, sin_table, k_cache, v_cache, pos, 1)
+    if out is None:
+        out = torch.empty(B, Hq * Dh, dtype=q.dtype, device=q.device)
+    elif out.shape != (B, Hq * Dh) or out.dtype != q.dtype or out.device != q.device or not out.is_contiguous():
+        raise ValueError(f'decode_attention_at: out must be contiguous {q.dtype} {(B, Hq * Dh)} on {q.device}, got {out.dtype} {tuple(out.shape)}')
+    check(_lib.lib().vqhip_decode_attention_at(*head, float(Dh ** -0.5 if scale is None else scale), B, Hq, Hkv, Dh, _ptr(out), _stream()),
+          'vqhip_decode_attention_at')
+    return out
+
+
+@_on_tensor_device
+def decode_advance(token: torch.Tensor, next_token: torch.Tensor, sequence: torch.Tensor, pos: torch.Tensor) -> None:
+    """vqhip_decode_advance: the end of a replayed step.  With s = ``pos`` (one int32 on the device) and s + 1 < length:
+    ``sequence[:, s + 1] = token`` as it is, ``next_token = max(token, 0)`` and ``pos = s + 1``; otherwise nothing.  ``token`` and
+    ``next_token`` hold R int64 each, ``sequence`` is int64 [R, length]; all are written and read in place.  One launch."""
+    _require_cuda(token, next_token, sequence, pos)
+    R = token.numel()
+    _refuse('decode_advance', position_refusal(pos)
+            or ('' if sequence.dim() == 2 and sequence.shape[0] == R and next_token.numel() == R else
+                f'token {tuple(token.shape)}, next {tuple(next_token.shape)} and sequence {tuple(sequence.shape)} are not R, R and [R, length]')
+            or ('' if all(t.dtype == torch.int64 and t.is_contiguous() for t in (token, next_token, sequence)) else
+                'token, next and sequence must be contiguous int64')
+            or ('' if all(t.device == pos.device for t in (token, next_token, sequence)) else 'the tensors are on several devices'))
+    check(_lib.lib().vqhip_decode_advance(_ptr(token), _ptr(next_token), _ptr(sequence), R, sequence.shape[1], _ptr(pos), _stream()),
+          'vqhip_decode_advance')
 
 
 @_on_tensor_device

@@ -20,6 +20,9 @@ shape, dtype, alignment, the probability buffer, the world size, train / eval). 
     group_norm_why        fused | torch
     vit_why               fused | torch
     multinomial_anchor_why  fused | matrix
+    llama_why             fused | torch
+    llama_decode_why      decode | walk | torch
+    llama_graph_why       graph | decode (| what llama_decode_why refuses)
 """
 from __future__ import annotations
 
@@ -684,6 +687,31 @@ def llama_decode_why(module, tokens: torch.Tensor, kv_cache=None) -> Route:
             or ('' if kv_cache.device == tokens.device else f'the cache is on device {kv_cache.device}, the tokens on {tokens.device}') \
             or ('' if kv_cache.dtype == dtype else f'the cache is {kv_cache.dtype}, the projections produce {dtype}')
     return Route('walk', why) if why else Route('decode')
+
+
+def llama_graph_why(module, tokens: torch.Tensor, length: int) -> Route:
+    """``LlamaTransformer.generate`` behind a ``StaticKVCache``: the single-token steps replayed from ONE captured HIP graph
+    (``decode_graph.DecodeGraph``: ``functional.decode_attention_at`` reads the position from device memory) (``graph``); or, with
+    the first clause that refused it, today's eager decode loop (``decode``).  Where ``llama_decode_why`` refuses the decode route
+    itself, its route comes back as it is.  The clauses of ``decode``: ``graph=False`` or ``static_cache=False`` on the module, a
+    class that overrides ``_walk_static``, ``sample`` or ``_generate`` (the captured step restates the first, calls the second and
+    is driven by the third), a sampler whose configuration or arguments ``sampler_why`` sends to its torch route (that one
+    synchronises), fewer than two steps behind the prompt's own draw (the first runs eagerly as the capture's warm-up: there
+    would be nothing to replay), a stream that is already capturing.  No shape is sent to either route for speed:
+    profiles/llama_decode_graph.txt has the measurements."""
+    from .. import transformers as vq_transformers
+    base = llama_decode_why(module, tokens, None)
+    if base.name != 'decode':
+        return base
+    steps = length - tokens.shape[1] - 1
+    sampler = sampler_config(module.sampler) or sampler_arguments(module.sampler)
+    why = ('' if getattr(module, 'graph', False) else 'graph=False') \
+        or ('' if getattr(module, 'static_cache', False) else 'static_cache=False') \
+        or own(module, vq_transformers.LlamaTransformer, '_walk_static', 'sample', '_generate') \
+        or (f'the sampler takes its torch route: {sampler}' if sampler else '') \
+        or ('' if steps >= 2 else f'{max(steps, 0)} steps behind the prompt\'s own draw: nothing to replay') \
+        or ('the stream is already capturing' if torch.is_tensor(tokens) and tokens.is_cuda and torch.cuda.is_current_stream_capturing() else '')
+    return Route('decode', why) if why else Route('graph')
 
 
 # ---- MultinomialAnchor of a CVQ-VAE update (vector_quantization_amd/quantizers/anchors.py) ----------------------------------------

@@ -26,6 +26,12 @@ one GEMM against the packed q/k/v weights, ``functional.decode_attention`` (one 
 the cache, rows as ``o_proj`` reads them) or, for a prompt, ``functional.rope_append`` and a causal sdpa, then ``o_proj``.  The packed
 q/k/v and gate/up weights are built once per ``generate`` call, in the autocast dtype under autocast, and dropped when the loop ends.
 ``routes.llama_decode_why`` decides; a step on this route leaves ``Route('decode')`` in ``last_route``.
+
+``LlamaTransformer(..., static_cache=True, graph=True)`` (off by default) runs the prompt and the first draw as above and then
+hands over to a ``decode_graph.DecodeGraph``: the single-token step - with ``functional.decode_attention_at`` reading the position
+from device memory, ``lm_head``, the sampler and ``functional.decode_advance`` - captured once as a HIP graph and replayed for
+every further token.  ``routes.llama_graph_why`` decides (``graph_route`` keeps the decision); such a call leaves ``Route('graph')``
+in ``last_route``, and the graph is kept on the module for the next call with the same key.
 """
 from __future__ import annotations
 
@@ -151,15 +157,30 @@ class HFTransformer(BaseTransformer):
 @VQSMTransformerRegistry.register_()
 class LlamaTransformer(HFTransformer):
     """``LlamaForCausalLM(LlamaConfig(**transformer))``.  ``fused=False`` pins the torch route; ``static_cache=True`` lets
-    ``generate`` run behind a ``StaticKVCache`` where ``routes.llama_decode_why`` allows it (``decode_route`` keeps that decision)."""
+    ``generate`` run behind a ``StaticKVCache`` where ``routes.llama_decode_why`` allows it (``decode_route`` keeps that decision);
+    ``graph=True`` on top of it replays the single-token steps from one HIP graph where ``routes.llama_graph_why`` allows it
+    (``graph_route`` keeps that decision; setting ``graph = False`` drops the captured graph)."""
 
     decode_route = None
+    graph_route = None
 
-    def __init__(self, *args, static_cache: bool = False, **kwargs) -> None:
+    def __init__(self, *args, static_cache: bool = False, graph: bool = False, **kwargs) -> None:
         super().__init__(*args, **kwargs)
         self._loss = CausalTokenLoss()
         self.static_cache = static_cache
         self._packed = None
+        self._decode_graph = None
+        self._graph = bool(graph)
+
+    @property
+    def graph(self) -> bool:
+        return self._graph
+
+    @graph.setter
+    def graph(self, on: bool) -> None:
+        self._graph = bool(on)
+        if not on:
+            self._decode_graph = None
 
     @classmethod
     def transformer_build_pre_hook(cls, config: Config, registry, item) -> Config:
@@ -265,8 +286,47 @@ class LlamaTransformer(HFTransformer):
         kv_cache.advance(L)
         return lm.lm_head(y)
 
+    def _generate_graph(self, tokens: torch.Tensor, length: int, codebook, memo):
+        """``generate`` on the graph route: the prompt and the first draw on the eager decode route, every further token from the
+        ``DecodeGraph`` (kept for the next call while its key stays).  Returns a clone of the graph's sequence buffer;
+        ``memo['sampler']`` is what the captured sampler call left - its tensors live in the graph's memory and show the LAST
+        replay, also after a later call has replayed again.  A draw of -1 (a row without a finite logit) does not reach an
+        embedding: it is clamped on the device, found by one check behind the loop and raised as ``ValueError``."""
+        from .decode_graph import DecodeGraph
+        from .quantizers import routes
+        assert tokens.shape[1] < length
+        autocast = _autocast_dtype(tokens)
+        dtype = autocast or self._transformer.model.embed_tokens.weight.dtype
+        u = get_memo(memo, 'sampler').get('u')
+        key = DecodeGraph.key_of(self, tokens, length, codebook, dtype, autocast, u is not None)
+        if self._decode_graph is None or self._decode_graph.key != key:
+            self._decode_graph = None                                            # (its memory goes before the next one's comes)
+            self._decode_graph = DecodeGraph(self, tokens.shape[0], length, codebook, device=tokens.device, cache_dtype=dtype,
+                                             autocast=autocast, with_u=u is not None, key=key)
+        graph = self._decode_graph
+        graph.begin(tokens, u)
+        self._packed = graph.packed
+        try:
+            logits, _, memo = self.inference(tokens, graph.cache, memo)
+            token, memo = self.sample(logits[:, [-1]], codebook, memo)
+        finally:
+            self._packed = None
+        sequence = graph.run(token).clone()
+        self.last_route = routes.Route('graph')
+        bad = sequence < 0
+        if bool(bad.any()):
+            column = int(bad.any(0).nonzero()[0])
+            raise ValueError(f'LlamaTransformer.generate: the sampler drew no token for row {int(bad[:, column].nonzero()[0])} at column '
+                             f'{column} (its logits hold NaN, +inf or nothing finite)')
+        memo['sampler'] = dict(graph.memo.get('sampler', {}), **({} if u is None else {'u': u}))
+        return sequence, memo
+
     def _generate(self, tokens: torch.Tensor, length: int, codebook, memo):
         from .quantizers import routes
+        if self._graph:
+            self.graph_route = routes.llama_graph_why(self, tokens, length)
+            if self.graph_route.name == 'graph':
+                return self._generate_graph(tokens, length, codebook, memo)
         if not self.static_cache:
             return super()._generate(tokens, length, codebook, memo)
         self.decode_route = route = routes.llama_decode_why(self, tokens, None)
