@@ -63,7 +63,7 @@ def check_storage(p, before, shape, dtype, L):
     keep = torch.ones(cap, dtype=torch.bool)
     keep[seen:seen + L] = False
     for name in ('kc', 'vc'):
-        a, b = p[name][:, :, keep.cuda()], before[0, 0 if name == 'kc' else 1][:, :, keep.cuda()]
+        a, b = p[name][:, :, keep.to(p[name].device)], before[0, 0 if name == 'kc' else 1][:, :, keep.to(before.device)]
         assert torch.equal(bits(a), bits(b)), f'{name}: a position other than the new ones has changed'
     assert torch.equal(bits(p['store'][1]), bits(before[1])), 'the unrelated cache has changed'
 

@@ -26,7 +26,9 @@ IDS = ['f32', 'bf16', 'f16']
 INT_OF = {8: torch.int64, 4: torch.int32, 2: torch.int16}
 SENTINEL = 777.0
 CAP = 300
-SEENS = (0, 1, 7, 8, 255, 256, 299)            # the edges of the 8-position slots and of the four waves' split
+# the edges of a wave's 8 positions and of a 32-position sweep: the PP = 8 geometry's (Dh = 64 in 16 bits, Dh = 24 in fp32), which
+# the test below does not run - every geometry's own edges are in tests/test_gpu_decode_attention_geometry.py
+SEENS = (0, 1, 7, 8, 255, 256, 299)
 CODEBOOK = SimpleNamespace(start=8, end=48)
 _BASE = {}
 
