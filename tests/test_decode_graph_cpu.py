@@ -12,6 +12,7 @@ import torch
 from vector_quantization_amd import _lib, functional, samplers
 from vector_quantization_amd.decode_graph import DecodeGraph
 from vector_quantization_amd.kv_cache import StaticKVCache
+from vector_quantization_amd.llama_weights import LlamaWeights
 from vector_quantization_amd.quantizers import routes
 from vector_quantization_amd.transformers import LlamaTransformer
 
@@ -140,7 +141,7 @@ def test_the_step_of_the_graph_is_the_walk_behind_a_static_cache(kv_heads):
     tokens = torch.randint(0, 48, (B, length), generator=torch.Generator().manual_seed(2))
     graph = DecodeGraph(m, B, length, CODEBOOK, device='cpu', cache_dtype=F64)
     graph.begin(tokens[:, :1])
-    assert graph.cos.dtype == torch.float32 and graph.cos.shape == (length, 16) and graph.packed[0][0].dtype == F64
+    assert graph.cos.dtype == torch.float32 and graph.cos.shape == (length, 16) and graph.weights('qkv', 0).dtype == F64
     cache = StaticKVCache.for_model(m._transformer.config, B, length, F64, 'cpu')
     for t in range(length):
         graph.token.copy_(tokens[:, t:t + 1])                                    # the fixed sequence in place of the step's own draw
@@ -152,6 +153,33 @@ def test_the_step_of_the_graph_is_the_walk_behind_a_static_cache(kv_heads):
             assert torch.equal(graph.sequence[:, t + 1:t + 2].clamp(min=0), graph.token) and int(graph.token.min()) >= 8
     assert torch.equal(graph.cache._store, cache._store)
     assert copy.deepcopy(graph) is None
+
+
+@torch.no_grad()
+def test_the_graph_form_of_the_weight_set_is_the_eager_one_and_follows_the_parameters_in_place():
+    m = exact64(build_tiny(num_key_value_heads=2))
+    eager = LlamaWeights(m).pack()
+    graph = LlamaWeights(m).allocate('cpu')
+    graph.refresh()
+    keys = graph.entries()
+    assert keys == eager.entries() == [(name, i) for i in range(2) for name in ('qkv', 'gate_up', 'o', 'down')] + [('lm_head', None)]
+    assert all(graph(*key).dtype == F64 and torch.equal(graph(*key), eager(*key)) for key in keys)
+    attn = m._transformer.model.layers[1].self_attn
+    assert eager('o', 1) is attn.o_proj.weight and graph('o', 1) is attn.o_proj.weight       # not cast: the module's own parameter
+    assert eager('qkv', 1).shape == (64 + 2 * 32, 64) and torch.equal(eager('qkv', 1)[64:96], attn.k_proj.weight)
+    cast = LlamaWeights(m, torch.float32).allocate('cpu')                        # under a dtype the single projections are held too
+    cast.refresh()
+    assert set(cast.held) == set(keys) and all(torch.equal(cast(*key), eager(*key).float()) for key in keys)
+    before = {key: cast(*key).data_ptr() for key in keys}
+    stale = cast('qkv', 1).clone()
+    attn.k_proj.weight.mul_(1.5)                                                 # trained in place between two generate calls
+    assert torch.equal(cast('qkv', 1), stale)
+    for form in (graph, cast):
+        form.refresh()
+    now = LlamaWeights(m).pack()
+    assert {key: cast(*key).data_ptr() for key in keys} == before and not torch.equal(cast('qkv', 1), stale)
+    assert all(torch.equal(graph(*key), now(*key)) and torch.equal(cast(*key), now(*key).float()) for key in keys)
+    assert torch.equal(graph('qkv', 1)[64:96], attn.k_proj.weight) and torch.equal(graph('qkv', 1)[:64], eager('qkv', 1)[:64])
 
 
 def test_every_clause_of_llama_graph_why():

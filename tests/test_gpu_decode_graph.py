@@ -257,7 +257,7 @@ def test_generate_under_bf16_autocast_is_as_close_to_float64_as_the_torch_route(
     assert graphed.last_route == routes.Route('graph') and plain.last_route is None
     assert tokens.shape == (4, length) and torch.equal(tokens[:, :1], prompt) and 8 <= int(tokens[:, 1:].min()) and int(tokens.max()) < 48
     graph = graphed._decode_graph
-    assert graph.logits.dtype == torch.bfloat16 and graph.cache.dtype == torch.bfloat16 and graph.cast is not None
+    assert graph.logits.dtype == torch.bfloat16 and graph.cache.dtype == torch.bfloat16 and ('o', 0) in graph.weights.held
     with torch.no_grad():
         full = exact64(base(kv_heads))._transformer(tokens.cpu())['logits']
     # the last step read the token at length - 2 and predicted the one at length - 1

@@ -8,18 +8,19 @@ memory (``StaticKVCache.position``) and ``functional.decode_advance`` counts it 
 
 A ``DecodeGraph`` owns everything a replay reads or writes by pointer: the ``[R, 1]`` input token, the ``[R, length]`` sequence, the
 cache and its position, the ``[capacity, Dh]`` fp32 rotary tables (one ``rotary_emb`` call over ``arange(capacity)``, before its
-cast), the packed q/k/v and gate/up weights, a ``[Ro]`` uniform buffer where the caller gave ``memo['sampler']['u']``, a ``[R, V]``
-buffer with the last step's logits, and the ``torch.cuda.CUDAGraph``.  Under autocast the ``o_proj``, ``down_proj`` and ``lm_head``
-weights are held in the autocast dtype too, so no replay repeats their cast.  ``step`` is the ``L == 1`` branch of
-``LlamaTransformer._walk_static`` followed by ``lm_head``, the sampler and ``decode_advance``, all on one stream: the captured graph
-is a single chain.
+cast), the weight set (``llama_weights.LlamaWeights`` in its allocated form: the packed q/k/v and gate/up weights, and under
+autocast ``o_proj``, ``down_proj`` and ``lm_head`` in the autocast dtype too, so no replay repeats their cast), a ``[Ro]`` uniform
+buffer where the caller gave ``memo['sampler']['u']``, a ``[R, V]`` buffer with the last step's logits, and the
+``torch.cuda.CUDAGraph``.  ``step`` is not a walk of its own: it is ``LlamaTransformer._layers``, the one walk of every route, with
+the attention step of the decode route (``_attend_static``) around ``decode_attention_at`` in place of ``decode_attention``,
+followed by ``lm_head``, the sampler and ``decode_advance``, all on one stream: the captured graph is a single chain.
 
 The first step behind the prompt runs eagerly through ``step`` on a side stream - the warm-up torch asks for in front of a capture,
 and a real step: it advances the position.  The capture itself executes nothing; the remaining steps are ``graph.replay()``, with
 one host ``advance(1)`` of the cache per replay, so the host count and the device position agree by construction.
 
 ``LlamaTransformer(..., static_cache=True, graph=True)`` keeps one ``DecodeGraph`` and reuses it while ``key_of`` gives the same
-key; every ``generate`` call refreshes the packed copies in place (weights trained in place between two calls are seen) and resets
+key; every ``generate`` call refreshes the weight set in place (weights trained in place between two calls are seen) and resets
 the cache, the position and the sequence.
 """
 from __future__ import annotations
@@ -30,22 +31,17 @@ from types import SimpleNamespace
 import torch
 import torch.nn.functional as F
 
-from . import functional
 from .kv_cache import StaticKVCache
+from .llama_weights import LlamaWeights, layers
 
 __all__ = ['DecodeGraph']
-
-
-def _layers(module):
-    lm = module._transformer
-    return lm.model.layers[:lm.config.num_hidden_layers]
 
 
 class DecodeGraph:
     """The replayed decode step of ``module`` (a ``LlamaTransformer``) for ``R`` sequences of ``length`` tokens.
 
     ``begin(prompt, u)`` readies the buffers for one ``generate`` call, the caller runs the prompt through the eager decode route
-    behind ``cache`` with ``packed`` as the module's packed weights, and ``run(token)`` takes over from the first sampled token.
+    behind ``cache`` with ``weights`` as the module's weight set, and ``run(token)`` takes over from the first sampled token.
     ``autocast`` is the autocast dtype (None: off), ``with_u`` whether the sampler draws from the ``u`` buffer (else from torch's
     generator, inside the capture: every replay draws new uniforms)."""
 
@@ -64,14 +60,8 @@ class DecodeGraph:
         self.u = torch.zeros(Ro, dtype=torch.float32, device=device) if with_u else None
         self.memo = {'sampler': {'u': self.u}} if with_u else {}
         self.logits = torch.zeros(R, lm.lm_head.weight.shape[0], dtype=autocast or weight.dtype, device=device)
-
-        def like(*ws):
-            return torch.empty(sum(w.shape[0] for w in ws), ws[0].shape[1], dtype=autocast or ws[0].dtype, device=device)
-        self.packed = [(like(a.q_proj.weight, a.k_proj.weight, a.v_proj.weight), like(m.gate_proj.weight, m.up_proj.weight))
-                       for a, m in ((layer.self_attn, layer.mlp) for layer in _layers(module))]
-        # under autocast a linear would cast its fp32 weight in every replay: these three are held in the autocast dtype as well
-        self.cast = None if autocast is None else \
-            ([(like(layer.self_attn.o_proj.weight), like(layer.mlp.down_proj.weight)) for layer in _layers(module)], like(lm.lm_head.weight))
+        # under autocast a linear would cast its fp32 weight in every replay: there the set holds the single projections as well
+        self.weights = LlamaWeights(module, autocast).allocate(device)
         self.graph = None
         self.captures = 0
 
@@ -84,8 +74,8 @@ class DecodeGraph:
         lm = module._transformer
         model = lm.model
         in_place = [model.embed_tokens.weight, model.norm.weight]
-        for layer in _layers(module):
-            in_place += [layer.input_layernorm.weight, layer.post_attention_layernorm.weight]
+        for layer in layers(module):
+            in_place +=[layer.input_layernorm.weight, layer.post_attention_layernorm.weight]
             if autocast is None:
                 in_place += [layer.self_attn.o_proj.weight, layer.mlp.down_proj.weight]
         if autocast is None:
@@ -97,21 +87,9 @@ class DecodeGraph:
     @torch.no_grad()
     def refresh(self) -> None:
         """The packed (and cast) copies and the rotary tables from the module's parameters as they are now, in place."""
-        lm = self.module._transformer
-        for i, layer in enumerate(_layers(self.module)):
-            a, m = layer.self_attn, layer.mlp
-            for buffer, parts in zip(self.packed[i], ((a.q_proj, a.k_proj, a.v_proj), (m.gate_proj, m.up_proj))):
-                at = 0
-                for part in parts:
-                    buffer[at:at + part.weight.shape[0]].copy_(part.weight)
-                    at += part.weight.shape[0]
-            if self.cast is not None:
-                self.cast[0][i][0].copy_(a.o_proj.weight)
-                self.cast[0][i][1].copy_(m.down_proj.weight)
-        if self.cast is not None:
-            self.cast[1].copy_(lm.lm_head.weight)
+        self.weights.refresh()
         positions = torch.arange(self.length, device=self.cos.device).unsqueeze(0)
-        cos, sin = lm.model.rotary_emb(self.cos, position_ids=positions)        # (an fp32 ``x``: the values before the cast)
+        cos, sin = self.module._transformer.model.rotary_emb(self.cos, position_ids=positions)    # (an fp32 ``x``: the values before the cast)
         self.cos.copy_(cos[0])
         self.sin.copy_(sin[0])
 
@@ -126,35 +104,21 @@ class DecodeGraph:
             self.u.copy_(u.reshape(-1))
 
     def step(self, torch_ops: bool = False) -> None:
-        """One token: the ``L == 1`` branch of ``_walk_static`` at the cache's device position, ``lm_head``, the sampler and
-        ``decode_advance``.  Reads ``token``; leaves ``logits``, the next ``token``, one more column of ``sequence`` and the
-        position counted.  ``torch_ops`` puts the ``_torch`` restatements in place of the kernels (they read the position on the
-        host: any device, float64 included, never a capture)."""
-        module, cache, R = self.module, self.cache, self.R
-        lm = module._transformer
-        model = lm.model
-        swiglu = functional.swiglu_torch if torch_ops else (lambda t: functional.swiglu(t, strict=True))
-        attend = functional.decode_attention_at_torch if torch_ops else \
-            (lambda *a, **k: functional.decode_attention_at(*a, strict=True, **k))
-        nq, nk = model.config.num_attention_heads * cache.head_dim, cache.kv_heads * cache.head_dim
-        x = model.embed_tokens(self.token)
-        pending = None
-        for i, layer in enumerate(_layers(module)):
-            attn, (w_qkv, w_gate_up) = layer.self_attn, self.packed[i]
-            x, y = module._norm(layer.input_layernorm, x, pending, torch_ops=torch_ops)
-            rows = F.linear(y, w_qkv).view(R, nq + 2 * nk)
-            q, k, v = rows[:, :nq], rows[:, nq:nq + nk], rows[:, nq + nk:]      # three views into the packed rows
-            o = attend(q, k, v, self.cos, self.sin, cache, i, scale=attn.scaling).view(R, 1, nq)
-            o = attn.o_proj(o) if self.cast is None else F.linear(o, self.cast[0][i][0])
-            x, y = module._norm(layer.post_attention_layernorm, x, o, torch_ops=torch_ops)
-            h = swiglu(F.linear(y, w_gate_up))
-            pending = layer.mlp.down_proj(h) if self.cast is None else F.linear(h, self.cast[0][i][1])
-        _, y = module._norm(model.norm, x, pending, torch_ops=torch_ops)
-        logits = lm.lm_head(y) if self.cast is None else F.linear(y, self.cast[1])
+        """One token: the module's walk with ``_attend_static`` around ``decode_attention_at`` - the cache's device position -
+        then ``lm_head``, the sampler and ``decode_advance``.  Reads ``token``; leaves ``logits``, the next ``token``, one more
+        column of ``sequence`` and the position counted.  ``torch_ops`` puts the ``_torch`` restatements in place of the kernels
+        (they read the position on the host: any device, float64 included, never a capture)."""
+        module, cache, weights, R = self.module, self.cache, self.weights, self.R
+        attend_at = module._op('decode_attention_at', torch_ops)
+
+        def core(i, scale, q, k, v):
+            return attend_at(q, k, v, self.cos, self.sin, cache, i, scale=scale)
+        x = module._transformer.model.embed_tokens(self.token)
+        y = module._layers(x, weights, module._attend_static(weights, cache, core), torch_ops=torch_ops)
+        logits = F.linear(y, weights('lm_head'))
         self.logits.copy_(logits[:, 0])
         token, self.memo = module.sample(logits, self.codebook, self.memo)
-        advance = functional.decode_advance_torch if torch_ops else (lambda *a: functional.decode_advance(*a, strict=True))
-        advance(token.reshape(R), self.token.view(R), self.sequence, cache.position)
+        module._op('decode_advance', torch_ops)(token.reshape(R), self.token.view(R), self.sequence, cache.position)
 
     def capture(self) -> None:
         """Captures ``step`` on the current device; nothing is executed.  The caller has run ``step`` eagerly on a side stream."""

@@ -31,7 +31,7 @@ from typing import NamedTuple
 import torch
 
 from .. import exchange, ops
-from ..utils import exchanging, get_world_size
+from ..utils import autocast_dtype, exchanging, get_world_size
 # (the three modules, not names out of them: each of them imports this module the same way, so neither side of the cycle reads an
 #  attribute of the other before a call, and any of the four may be imported first)
 from . import callbacks as _cb, scalar_quantizer as _sq, vector_quantizer as _vq
@@ -678,7 +678,7 @@ def llama_decode_why(module, tokens: torch.Tensor, kv_cache=None) -> Route:
         or ('a sliding window is configured' if sliding else '') \
         or ops.attention_shape_refusal(Hq, Hkv, Dh)
     if not why and kv_cache is not None:
-        dtype = torch.get_autocast_dtype('cuda') if tokens.is_cuda and torch.is_autocast_enabled() else lm.model.embed_tokens.weight.dtype
+        dtype = autocast_dtype(tokens) or lm.model.embed_tokens.weight.dtype
         shape = (config.num_hidden_layers, tokens.shape[0], Hkv, Dh)
         have = (getattr(kv_cache, 'layers', None), getattr(kv_cache, 'batch', None), getattr(kv_cache, 'kv_heads', None),
                 getattr(kv_cache, 'head_dim', None))
@@ -694,7 +694,7 @@ def llama_graph_why(module, tokens: torch.Tensor, length: int) -> Route:
     (``decode_graph.DecodeGraph``: ``functional.decode_attention_at`` reads the position from device memory) (``graph``); or, with
     the first clause that refused it, today's eager decode loop (``decode``).  Where ``llama_decode_why`` refuses the decode route
     itself, its route comes back as it is.  The clauses of ``decode``: ``graph=False`` or ``static_cache=False`` on the module, a
-    class that overrides ``_walk_static``, ``sample`` or ``_generate`` (the captured step restates the first, calls the second and
+    class that overrides ``_walk_static``, ``sample`` or ``_generate`` (the captured step stands in for the first, calls the second and
     is driven by the third), a sampler whose configuration or arguments ``sampler_why`` sends to its torch route (that one
     synchronises), fewer than two steps behind the prompt's own draw (the first runs eagerly as the capture's warm-up: there
     would be nothing to replay), a stream that is already capturing.  No shape is sent to either route for speed:

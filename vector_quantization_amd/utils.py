@@ -58,6 +58,15 @@ class _Store:
 Store = _Store()
 
 
+# ---- the dtype a fused norm writes for the ``linear`` behind it (vqkd_autoencoders.py, transformers.py, quantizers/routes.py) ----
+
+def autocast_dtype(x: torch.Tensor):
+    """The dtype a ``linear`` would read ``x`` in: the autocast dtype where autocast is on for x's device, else None (x's own)."""
+    if x.is_cuda and torch.is_autocast_enabled():
+        return torch.get_autocast_dtype('cuda')
+    return None
+
+
 # ---- rank helpers (todd.patches.torch.get_rank / get_world_size) ----
 
 def get_world_size() -> int:

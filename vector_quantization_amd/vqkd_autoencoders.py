@@ -29,20 +29,14 @@ from . import functional
 from .autoencoders import BaseDecoder, BaseEncoder
 from .quantizers.memo import Memo
 from .registries import VQDecoderRegistry, VQEncoderRegistry
+from .utils import autocast_dtype
 
 __all__ = ['Mlp', 'Attention', 'Block', 'PatchEmbed', 'VQKDEncoder', 'VQKDDecoder']
 
 
-def _autocast_dtype(x: torch.Tensor):
-    """The dtype a ``linear`` would read ``x`` in: the autocast dtype where autocast is on for x's device, else None (x's own)."""
-    if x.is_cuda and torch.is_autocast_enabled():
-        return torch.get_autocast_dtype('cuda')
-    return None
-
-
 def _norm(norm: nn.LayerNorm, x: torch.Tensor, pending: Optional[torch.Tensor]):
     """One norm site of the fused route: ``(x + pending, norm(x + pending))`` with the parameters of the ``nn.LayerNorm`` child."""
-    out_dtype = _autocast_dtype(x)
+    out_dtype = autocast_dtype(x)
     if pending is not None and pending.dtype != (out_dtype or x.dtype):
         pending = pending.to(out_dtype or x.dtype)
     return functional.add_layer_norm(x, pending, norm.weight, norm.bias, norm.eps, out_dtype, strict=True)
